@@ -25,9 +25,18 @@ kernels ~10 % slower during roughly steps 4-10 of a run, profiles/r04_g_step_tra
 in the middle of. The timed region is exactly K steps either way; `--settle 0` switches it off.
 
 Output: one JSON line on rank 0. `value` = lattice-node updates of the whole job per second / 1e6
-with all state resident in HBM. `roofline` prices the dominant kernel (k_collide_stream) from HIP
-events recorded on its own stream; `cpu_baseline` times the reference's serial C path (prebuilt
-oracle/_ref library when it travelled, else this repo's CPU restatement) on a bounded sample.
+with all state resident in HBM; `ms_per_step` = wall milliseconds of one timed step.
+
+A plain run does only what that headline needs: set-up, the settle and warm-up steps, the K timed steps, the outputs
+(`--dump-outputs DIR`) and the line. `--full` adds everything else, as one record: the same K steps straight after the
+warm-up (`ms_per_step_unsettled`), the plain-copy yardstick, HIP events around the fused kernel inside the timed region
+(`roofline`, `collide_stream_kernel_ms`), the lattice-mass check, the DEM-only and fluid-only legs, the 200-step leg, the
+reference's own geometry, the fast force kernel and `cpu_baseline`, which times the reference's serial C path (prebuilt
+oracle/_ref library where the build made one, else this repo's CPU restatement) on a bounded sample.
+
+`--dump-outputs DIR` (one GPU, single domain) writes what the last timed step left to a caller, as float64 .npy files:
+the grain kinematics and hydrodynamic forces in full, and a fixed seeded sample of lattice nodes (their distributions and
+obstacle ids). With the same arguments the inputs are the same from run to run, so two builds compare file for file.
 """
 from __future__ import annotations
 
@@ -153,6 +162,63 @@ def cpu_baseline(w, sample_mm, npdem):
     return out
 
 
+DUMP_NODES = 1 << 18       # lattice nodes in the dumped sample: 2 MB of indices, 19 MB of f, 2 MB of obstacle ids
+DUMP_SEED = 20240101
+
+
+def dump_outputs(sim, directory):
+    """What the last timed step left to a caller of renderScene, as float64 .npy files (about 30 MB at 4096^2 / 50k
+    grains): every grain's kinematics (n, 9) and hydrodynamic force (n, 3), and the populations (k, 9) and obstacle ids
+    (k,) of a fixed sample of k lattice nodes (node_index: x * ly + y, drawn with a fixed seed, sorted)."""
+    os.makedirs(directory, exist_ok=True)
+    lx, ly = sim.lx, sim.ly
+    k = min(DUMP_NODES, lx * ly)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(lx * ly, size=k, replace=False))
+    f = np.empty((lx, ly, 9))
+    sim.download_f_into(f)
+    out = {"kinematics": sim.kinematics, "fhf": sim.fhf,
+           "f_sample": f.reshape(lx * ly, 9)[idx], "obst_sample": sim.obst.reshape(-1)[idx],
+           "node_index": idx}
+    del f
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def headline(args, w, sim, lx, ly, ngrains, npdem, elapsed, chain_stats, driver, driver_note, dist_mode):
+    """The result line of every run: the headline figure and the configuration that produced it."""
+    single = args.gpus == 1 and not args.strips
+    out = {
+        "metric": f"MLUPS (D2Q9 collide+stream, coupled LBM-DEM step) on {w['short']}",
+        "value": round(1e-6 * lx * ly * args.steps / elapsed, 1), "unit": "MLUPS", "n_gpus": args.gpus,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": args.precision,
+        "data": w["data"],
+        "config": {"workload": w["name"], "lx": lx, "ly": ly, "grains": int(ngrains), "npDEM": int(npdem),
+                   "step": "1 fluid step + npDEM DEM sub-steps (+ Verlet rebuild every 100 DEM steps)",
+                   "force_kernel": "parity" if args.force_mode == 0 else "fast",
+                   "dem_chain": dict(zip(("launches", "substeps", "tile_slots", "resident"), chain_stats)),
+                   "obst_map": dict(zip(("updated_in_place", "cleared_and_repainted"), sim.obst_stats())),
+                   "fused_launches_reading_one_map": (sim.change_mask_stats()[0] if single else 0),
+                   "settle_steps": args.settle,   # untimed steps of this run before the warm-up (GPU clocks; see --settle)
+                   "driver": driver,
+                   "driver_trial": driver_note if driver else None,
+                   "decomposition": "none" if args.gpus == 1 else (
+                       f"{args.gpus} x-strips, halo 2 rows, grains owned by strips (margin integrated redundantly); per "
+                       f"fluid step and neighbour: f halo rows and grain kinematics (both overlapped with the fluid "
+                       f"step), link-sum tables of the grains on the cut, forces of the margin grains -- point to "
+                       f"point only" if dist_mode else
+                       f"{args.gpus} x-strips; halo exchange overlapped with the interior rows, one bit-exact "
+                       f"all-reduce of the hydrodynamic forces per fluid step; grains replicated (strips narrower "
+                       f"than the margin)")},
+        "dem_steps_per_s": round(args.steps * npdem / elapsed, 1),
+        "dem_chain_recoveries": sim.dem_chain_recoveries(),
+    }
+    if args.precision == "f32":
+        out["metric"] += " -- float build (the reference's -DSINGLE_PRECISION mode), NOT the headline"
+    return out
+
+
 def device_map(world):
     """LBMDEM_BENCH_DEVICES="0,0": the device of every rank, for running several ranks on ONE GPU (the tests do, with
     LBMDEM_RCCL_LIBRARY pointing at tests/rccl_shim -- real RCCL refuses two ranks on one device). Unset: rank k on GPU k."""
@@ -173,8 +239,9 @@ def free_port():
 
 
 def relaunch_under_launcher(args):
-    """`python bench.py --gpus N`, N > 1, started without a launcher (as the driver starts it): replace this process by
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <the same arguments>`."""
+    """`python bench.py --gpus N`, N > 1, started without a launcher (as the driver starts it): run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <the same arguments>` as a fresh child
+    process and exit with its status (this process may already have opened the GPU to count devices)."""
     if device_map(args.gpus) is None:
         import torch
         have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -184,7 +251,9 @@ def relaunch_under_launcher(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    rc = subprocess.run(cmd).returncode
+    raise SystemExit(rc if rc >= 0 else 128 - rc)      # a child killed by signal s: the shell's 128 + s
 
 
 TRIAL_PERIODS = 2
@@ -312,7 +381,17 @@ def main():
                          "own (real50k_ms_per_step; metric workload at one GPU only; 0 = none)")
     ap.add_argument("--strips", action="store_true",
                     help="use the strip-decomposition driver (torch.distributed) even with one rank")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline, in the same record: the unsettled steps, the copy yardstick, "
+                         "the fused kernel's HIP events and roofline, the mass check, the DEM-only / fluid-only / 200-step / "
+                         "real50k / fast-force legs and cpu_baseline (off: set-up, settle, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left to a caller as DIR/<name>.npy (float64): "
+                         "kinematics, fhf, and a fixed seeded sample of lattice nodes (f_sample, obst_sample, their "
+                         "node_index); one GPU, single domain")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.strips):
+        raise SystemExit("--dump-outputs is a one-GPU, single-domain option")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_launcher(args)        # does not return
@@ -359,7 +438,7 @@ def main():
         def sync():
             sim.sync()
         barrier = lambda: None
-        runner = None
+        runner = driver = driver_note = None
         dist_mode = False
     else:
         import torch.distributed as dist
@@ -416,6 +495,8 @@ def main():
             sim.set_dem_chain(args.dem_chain)
         npdem = sim.cfg.npDEM
         dist_mode = isinstance(runner, (strips.DistStripRunner, strips.CCommRunner))
+        driver = ("C (lbmdem_comm_run, RCCL send/recv inside the library)" if isinstance(runner, strips.CCommRunner)
+                  else "torch.distributed (strips.py)")
 
         def run_steps(k):
             runner.render_scene(k * npdem)
@@ -425,45 +506,65 @@ def main():
         barrier = dist.barrier
         reduce_dev = ctl
 
-    # The driver's own protocol first -- its warm-up, then K timed steps straight away -- reported as ms_per_step_unsettled;
-    # then the settle steps and the headline's K timed steps (see --settle for what the difference is).
+    # --full: the driver's own protocol first -- its warm-up, then K timed steps straight away -- reported as
+    # ms_per_step_unsettled. Then, in every run, the settle steps, the W warm-up steps and the headline's K timed steps
+    # (see --settle for what the difference is).
     ms_unsettled = None
     if args.settle > 0:
-        run_steps(args.warmup)
-        sync(); barrier(); sync()
-        t0 = time.perf_counter()
-        run_steps(args.steps)
-        sync(); barrier()
-        ms_unsettled = 1e3 * (time.perf_counter() - t0) / args.steps
-        if world > 1 or args.strips:
-            import torch.distributed as dist
-            tu = torch.tensor([ms_unsettled], dtype=torch.float64, device=reduce_dev)
-            dist.all_reduce(tu, op=dist.ReduceOp.MAX)
-            ms_unsettled = float(tu[0])
+        if args.full:
+            run_steps(args.warmup)
+            sync(); barrier(); sync()
+            t0 = time.perf_counter()
+            run_steps(args.steps)
+            sync(); barrier()
+            ms_unsettled = 1e3 * (time.perf_counter() - t0) / args.steps
+            if world > 1 or args.strips:
+                import torch.distributed as dist
+                tu = torch.tensor([ms_unsettled], dtype=torch.float64, device=reduce_dev)
+                dist.all_reduce(tu, op=dist.ReduceOp.MAX)
+                ms_unsettled = float(tu[0])
         run_steps(args.settle)   # clocks settle; the run simply starts its headline steps later
         sync()
     run_steps(args.warmup)
     sync()
-    # the box's yardstick: a plain copy of 1.2 GB (2.4 GB of traffic, the fused kernel's algorithmic bytes) on the same stream
-    copy_gbs = sim.measure_copy(1200 * 1000 * 1000, 5) if args.precision == "f64" else None
-    # HIP events around the fused kernel, on its stream, inside the timed region -- around every 4th launch (every 8th of a
-    # long run): the two records of a timed launch hold the next dispatch back, ~10 us per coupled step when every launch
-    # is timed (LBMDEM_BENCH_PROFILE=1 does that, =0 times none: the A/B)
-    prof_stride = int(os.environ.get("LBMDEM_BENCH_PROFILE", "8" if args.steps >= 100 else "4"))
-    sim.profile_enable(prof_stride)
+    copy_gbs, prof_stride = None, 0
+    if args.full:
+        # the box's yardstick: a plain copy of 1.2 GB (2.4 GB of traffic, the fused kernel's algorithmic bytes) on the same stream
+        copy_gbs = sim.measure_copy(1200 * 1000 * 1000, 5) if args.precision == "f64" else None
+        # HIP events around the fused kernel, on its stream, inside the timed region -- around every 4th launch (every 8th of a
+        # long run): the two records of a timed launch hold the next dispatch back, ~10 us per coupled step when every launch
+        # is timed (LBMDEM_BENCH_PROFILE=1 does that, =0 times none: the A/B)
+        prof_stride = int(os.environ.get("LBMDEM_BENCH_PROFILE", "8" if args.steps >= 100 else "4"))
+        sim.profile_enable(prof_stride)
     barrier(); sync()
     t0 = time.perf_counter()
     run_steps(args.steps)
     sync(); barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
-    kernel_ms, launches = sim.profile_read()
-    sim.profile_enable(False)
+    kernel_ms, launches = 0.0, 0
+    if args.full:
+        kernel_ms, launches = sim.profile_read()
+        sim.profile_enable(False)
     if world > 1 or args.strips:
         import torch.distributed as dist
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device=reduce_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(t[0]), float(t[1])
+    if args.dump_outputs:      # before the --full legs below, which step this same handle further
+        dump_outputs(sim, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            out = headline(args, w, sim, lx, ly, len(r), npdem, elapsed, sim.dem_chain_stats(), driver, driver_note,
+                           dist_mode)
+            import ctypes
+            ctypes.CDLL(None).fflush(None)      # RCCL prints through C stdio: whatever it buffered comes out BEFORE the line
+            print(json.dumps(out), flush=True)
+        if world > 1 or args.strips:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # the state the timed run left behind must be a lattice (checked here, before the informative legs below: those step the
     # DEM and the fluid SEPARATELY -- 100 periods of sub-steps without a fluid step in between -- which leaves a physically
@@ -574,35 +675,11 @@ def main():
                 traffic_source = ("none: " + os.path.relpath(TRAFFIC_FILE, ROOT) + " was measured on another build of the "
                                   "library (" + f"{tf['traffic_bytes_per_launch'] / 1e9:.3f} GB per launch, "
                                   f"{tf.get('traffic_over_algorithmic', 0):.3f} x algorithmic)")
-        out = {
-            "metric": f"MLUPS (D2Q9 collide+stream, coupled LBM-DEM step) on {w['short']}",
-            "value": round(mlups, 1), "unit": "MLUPS", "n_gpus": args.gpus, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        out = headline(args, w, sim, lx, ly, len(r), npdem, elapsed, chain_stats, driver, driver_note, dist_mode)
+        out.update({
             # the same K steps measured straight after the driver's W warm-up steps, earlier in this run (before --settle)
             "ms_per_step_unsettled": round(ms_unsettled, 4) if ms_unsettled is not None else round(ms_per_step, 4),
             "hbm_copy_gbs": round(copy_gbs, 1) if copy_gbs else None,
-            "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": args.precision,
-            "data": w["data"],
-            "config": {"workload": w["name"], "lx": lx, "ly": ly, "grains": int(len(r)), "npDEM": int(npdem),
-                       "step": "1 fluid step + npDEM DEM sub-steps (+ Verlet rebuild every 100 DEM steps)",
-                       "force_kernel": "parity" if args.force_mode == 0 else "fast",
-                       "dem_chain": dict(zip(("launches", "substeps", "tile_slots", "resident"), chain_stats)),
-                       "obst_map": dict(zip(("updated_in_place", "cleared_and_repainted"), sim.obst_stats())),
-                       "fused_launches_reading_one_map": (sim.change_mask_stats()[0] if world == 1 and not args.strips else 0),
-                       "settle_steps": args.settle,   # untimed steps of this run before the warm-up (GPU clocks; see --settle)
-                       "driver": None if runner is None else ("C (lbmdem_comm_run, RCCL send/recv inside the library)" if
-                                                                isinstance(runner, strips.CCommRunner) else "torch.distributed (strips.py)"),
-                       "driver_trial": None if runner is None else driver_note,
-                       "decomposition": "none" if args.gpus == 1 else (
-                           f"{args.gpus} x-strips, halo 2 rows, grains owned by strips (margin integrated redundantly); per "
-                           f"fluid step and neighbour: f halo rows and grain kinematics (both overlapped with the fluid "
-                           f"step), link-sum tables of the grains on the cut, forces of the margin grains -- point to "
-                           f"point only" if dist_mode else
-                           f"{args.gpus} x-strips; halo exchange overlapped with the interior rows, one bit-exact "
-                           f"all-reduce of the hydrodynamic forces per fluid step; grains replicated (strips narrower "
-                           f"than the margin)")},
-            "dem_steps_per_s": round(args.steps * npdem / elapsed, 1),
             "dem_only_steps_per_s": round(dem_only, 1) if dem_only else None,
             "lbm_step_only_ms": round(lbm_only_ms, 4) if lbm_only_ms else None,
             "lbm_step_only_mlups": round(1e-3 * lx * ly / lbm_only_ms, 1) if lbm_only_ms else None,
@@ -613,7 +690,6 @@ def main():
             "real50k_ms_per_step": round(real_leg["ms_per_step"], 4) if real_leg else None,
             "real50k_mlups": round(1e-3 * lx * ly / real_leg["ms_per_step"], 1) if real_leg else None,
             "real50k_collide_stream_kernel_ms": round(real_leg["kernel_ms"], 4) if real_leg else None,
-            "dem_chain_recoveries": sim.dem_chain_recoveries(),
             "collide_stream_kernel_ms": round(kernel_ms, 4),
             "collide_stream_kernel_mlups": round(1e-6 * rows * ly / (kernel_ms * 1e-3), 1) if kernel_ms > 0 else None,
             "roofline": {"bound": "hbm", "kernel": "k_cs_march (fused reinit+collide+IBB+stream)", "achieved": round(achieved, 1),
@@ -638,9 +714,8 @@ def main():
                                  "not the memory system's ceiling); step_frac / *_200 = the coupled step, and the 200-step leg, priced like frac"},
             "fast_force_mode": fast,
             "total_mass": mass,
-        }
+        })
         if args.precision == "f32":
-            out["metric"] += " -- float build (the reference's -DSINGLE_PRECISION mode), NOT the headline"
             out["roofline"]["note"] = ("achieved = algorithmic 76 B/LUP x lattice nodes per launch / mean HIP-event duration of every `timed_every`-th launch of the timed region; the "
                                        "float build mirrors the reference's mixed float/double arithmetic and gathers the hydrodynamic "
                                        "forces from the lattice (no link-sum table)")

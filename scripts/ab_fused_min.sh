@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 P='import sys,json; d=json.loads(sys.stdin.read()); print(d["collide_stream_kernel_ms"], d["ms_per_step"])'
 rm -f /tmp/ab_*.txt
 for rep in $(seq ${REPS:-6}); do for lib in "$@"; do
-  LBMDEM_HIP_LIBRARY=$PWD/2d-lbm-dem_amd/liblbmdem_hip$lib.so python bench.py --steps ${STEPS:-40} --warmup 5 --settle ${SETTLE:-20} --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$P" >> /tmp/ab_$lib.txt
+  LBMDEM_HIP_LIBRARY=$PWD/2d-lbm-dem_amd/liblbmdem_hip$lib.so python bench.py --full --steps ${STEPS:-40} --warmup 5 --settle ${SETTLE:-20} --no-cpu-baseline 2>/dev/null | tail -1 | python -c "$P" >> /tmp/ab_$lib.txt
 done; done
 for lib in "$@"; do python - "$lib" <<'PY'
 import sys

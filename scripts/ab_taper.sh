@@ -6,9 +6,9 @@ cd $GRAFT_REPO_ROOT
 AB=$PWD/2d-lbm-dem_amd/liblbmdem_hip_ab.so; TR=$PWD/2d-lbm-dem_amd/liblbmdem_hip_ab_trace.so
 P='import sys,json; d=json.loads(sys.stdin.read()); print("ms/step", d["ms_per_step"], "fused_ms", d["collide_stream_kernel_ms"], "frac", d["roofline"]["frac"])'
 for rep in $(seq ${REPS:-2}); do
-  echo "[uniform 32-row segments, compiled] $(LBMDEM_HIP_LIBRARY=$AB LBMDEM_CS_VARIANT=25 python bench.py --steps ${STEPS:-40} --warmup 5 --no-cpu-baseline --workload ${WORKLOAD:-metric} 2>/dev/null | tail -1 | python -c "$P")"
+  echo "[uniform 32-row segments, compiled] $(LBMDEM_HIP_LIBRARY=$AB LBMDEM_CS_VARIANT=25 python bench.py --full --steps ${STEPS:-40} --warmup 5 --no-cpu-baseline --workload ${WORKLOAD:-metric} 2>/dev/null | tail -1 | python -c "$P")"
   for t in "$@"; do
-    echo "[$t] $(env LBMDEM_HIP_LIBRARY=$AB $t python bench.py --steps ${STEPS:-40} --warmup 5 --no-cpu-baseline --workload ${WORKLOAD:-metric} 2>/dev/null | tail -1 | python -c "$P")"
+    echo "[$t] $(env LBMDEM_HIP_LIBRARY=$AB $t python bench.py --full --steps ${STEPS:-40} --warmup 5 --no-cpu-baseline --workload ${WORKLOAD:-metric} 2>/dev/null | tail -1 | python -c "$P")"
   done
 done
 if [ -n "$TRACE" ]; then

@@ -2,10 +2,10 @@
 # the C transport's strip period (8 processes on this GPU through tests/rccl_shim). Output: gpurun_out/r04/.
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG:-r04}; mkdir -p $O
-python bench.py > $O/bench_final.json 2> $O/bench_final.err
-python bench.py --workload real50k --no-cpu-baseline > $O/bench_real50k.json 2>/dev/null
-python bench.py --workload configs4 --no-cpu-baseline > $O/bench_configs4_one_gpu.json 2>/dev/null
-python bench.py --precision f32 > $O/bench_f32.json 2>/dev/null
+python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+python bench.py --full --workload real50k --no-cpu-baseline > $O/bench_real50k.json 2>/dev/null
+python bench.py --full --workload configs4 --no-cpu-baseline > $O/bench_configs4_one_gpu.json 2>/dev/null
+python bench.py --full --precision f32 > $O/bench_f32.json 2>/dev/null
 bash scripts/prof_kernels.sh r04_final > $O/prof_kernels.log 2>&1
 cp $(find gpurun_out/prof_r04_final -name "*kernel_stats*" | head -1) $O/kernel_stats_final.csv 2>/dev/null
 bash scripts/pmc_traffic.sh > $O/pmc_traffic.log 2>&1

@@ -14,7 +14,7 @@ for seg in 32 64 128; do
     LBMDEM_CS_ROWS=$seg LBMDEM_CHUNK=128 bash scripts/pmc_kernel.sh seg$seg k_cs_march "$c" >> $O 2>&1
   done
   echo "[main segments of $seg rows, chunk 128] kernel time" >> $O
-  LBMDEM_CS_ROWS=$seg LBMDEM_CHUNK=128 python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  LBMDEM_CS_ROWS=$seg LBMDEM_CHUNK=128 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('fused kernel ms', d['collide_stream_kernel_ms'], 'step ms', d['ms_per_step'])" >> $O
 done
 cat $O

@@ -4,11 +4,11 @@
 # liblbmdem_hip_ab_{full,NOTAB,NOPASS,NOEVALPASS,NOCOLLIDE,NOREINIT}.so (make AB=1 ABTAG=_X ABFLAGS=-DMARCH_ABL_X; full: none).
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG:-r06}; mkdir -p $O
-python bench.py > $O/bench_final.json 2> $O/bench_final.err
-for k in 1 2 3; do python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O/driver_form_three_runs.jsonl; done
-python bench.py --workload real50k --no-cpu-baseline --real-steps 0 > $O/bench_real50k.json 2>/dev/null
-python bench.py --workload configs4 --no-cpu-baseline > $O/bench_configs4_one_gpu.json 2>/dev/null
-python bench.py --precision f32 --real-steps 0 > $O/bench_f32.json 2>/dev/null
+python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+for k in 1 2 3; do python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 >> $O/driver_form_three_runs.jsonl; done
+python bench.py --full --workload real50k --no-cpu-baseline --real-steps 0 > $O/bench_real50k.json 2>/dev/null
+python bench.py --full --workload configs4 --no-cpu-baseline > $O/bench_configs4_one_gpu.json 2>/dev/null
+python bench.py --full --precision f32 --real-steps 0 > $O/bench_f32.json 2>/dev/null
 bash scripts/prof_kernels.sh r06_final > $O/prof_kernels.log 2>&1
 cp $(find gpurun_out/prof_r06_final -name "*kernel_stats*" | head -1) $O/kernel_stats_final.csv 2>/dev/null
 bash scripts/pmc_traffic.sh > $O/pmc_traffic.log 2>&1

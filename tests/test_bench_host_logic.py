@@ -59,3 +59,41 @@ def test_device_map_and_port_helpers():
         os.environ.pop("LBMDEM_BENCH_DEVICES", None)
     p = bench.free_port()
     assert 1024 < p < 65536
+
+
+def test_dump_outputs_is_a_one_gpu_option():
+    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", "unused"])
+    assert out.returncode != 0 and "--dump-outputs is a one-GPU, single-domain option" in out.stderr
+    assert "Traceback" not in out.stderr
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample(tmp_path):
+    """bench.dump_outputs on a stand-in handle: float64 files, the same node sample every time, within 64 MB even for the
+    largest workload (8192 x 4096, 50 000 grains)"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import importlib
+    bench = importlib.import_module("bench")
+
+    class Sim:
+        lx, ly, n = 300, 200, 7
+        def download_f_into(self, out): out[...] = np.arange(out.size, dtype=np.float64).reshape(out.shape)
+        kinematics = property(lambda self: np.full((self.n, 9), 0.5))
+        fhf = property(lambda self: np.full((self.n, 3), -1.5))
+        obst = property(lambda self: (np.arange(self.lx * self.ly, dtype=np.int32) % 5 - 1).reshape(self.lx, self.ly))
+
+    for d in ("a", "b"):
+        bench.dump_outputs(Sim(), str(tmp_path / d))
+    names = {"kinematics", "fhf", "f_sample", "obst_sample", "node_index"}
+    assert {p.stem for p in (tmp_path / "a").glob("*.npy")} == names
+    for name in names:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b), name
+    idx = np.load(tmp_path / "a" / "node_index.npy").astype(np.int64)
+    k = min(bench.DUMP_NODES, 300 * 200)
+    assert len(idx) == k and np.all(np.diff(idx) > 0)
+    f = np.load(tmp_path / "a" / "f_sample.npy")
+    assert np.array_equal(f, (idx[:, None] * 9 + np.arange(9)).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "obst_sample.npy"), (idx % 5 - 1).astype(np.float64))
+    largest = 8 * (bench.DUMP_NODES * (9 + 1 + 1) + 50000 * (9 + 3))
+    assert largest <= 64 * 2 ** 20

@@ -35,8 +35,8 @@ def test_oracle_dry_steps_reproduce_the_dry_reference_table(po):
 
 
 def test_oracle_dry_steps_equal_the_live_dry_reference(po, tmp_path):
-    if not po.reference_available():
-        pytest.skip("/root/reference is not present here")
+    if po.build_ref(256, 200, dry=True) is None:
+        pytest.skip("build() made no DEM-only reference library here (the reference's sources are not on this machine)")
     import multiprocessing as mp
     r, x1, x2, _ = _inputs()
     sample = tmp_path / "s.data"

@@ -20,7 +20,7 @@ def _last_json(stdout):
 
 
 def test_single_process_line():
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-500:]
     d = _last_json(out.stdout)
@@ -47,7 +47,8 @@ def test_single_process_line():
 
 def test_settle_steps_can_be_switched_off():
     """--settle 0: no untimed steps before the W warm-up steps (the timed region is K steps either way)"""
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--settle", "0", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--settle", "0", "--no-cpu-baseline",
+                          "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-500:]
     d = _last_json(out.stdout)
@@ -72,3 +73,33 @@ def test_plain_python_strips_form_one_rank():
     assert out.returncode == 0, out.stderr[-800:]
     d = _last_json(out.stdout)
     assert d["n_gpus"] == 1 and d["value"] > 1000 and d["config"]["driver"].startswith("C (lbmdem_comm_run")
+
+
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "dem_steps_per_s", "dem_chain_recoveries"}
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line holds the headline and its configuration only (no legs, no kernel events, no baseline);
+    --dump-outputs writes the last timed step's state, and two runs with the same arguments write the same bits"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2",
+                              "--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-800:]
+        line = _last_json(out.stdout)
+        assert set(line) == PLAIN_KEYS and line["steps"] == 5 and line["warmup"] == 2 and line["dtype"] == "f64"
+        assert line["unit"] == "MLUPS" and line["higher_is_better"] is True and line["value"] > 1000
+        assert abs(line["value"] - 1e-3 * 4096 * 4096 / line["ms_per_step"]) < 0.01 * line["value"]
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"kinematics", "fhf", "f_sample", "obst_sample", "node_index"} and set(b) == set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert a["kinematics"].shape == (50000, 9) and a["fhf"].shape == (50000, 3) and a["f_sample"].shape[1] == 9
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+        assert np.all(np.isfinite(a[k])), k
+    # the state moved on from the initial packing, and the sampled lattice holds fluid and grains
+    assert np.abs(a["kinematics"][:, 3:6]).max() > 0 and (a["obst_sample"] >= 0).any() and (a["obst_sample"] < 0).any()

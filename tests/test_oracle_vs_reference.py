@@ -1,14 +1,15 @@
 """CPU: the in-repo oracle against the unmodified reference TU compiled in this container
 (oracle/ref_harness.c -> oracle/_ref/libref_<lx>x<ly>.so), driven live on the reference's own sample
-files. Skipped where neither /root/reference nor a prebuilt reference library exists. One process
-per case: the reference keeps its state in globals."""
+files (copies under tests/golden/ref_samples/). Skipped where build() could not make the reference
+library (the reference's sources are not on that machine). One process per case: the reference keeps
+its state in globals."""
 import multiprocessing as mp
 import os
 
 import numpy as np
 import pytest
 
-REF_BIN = "/root/reference/bin"
+REF_BIN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_samples")   # the reference's bin/
 
 
 def _worker(lx, ly, path, nsteps, q):
