@@ -143,6 +143,11 @@ def _open_library(LIB_PATH):
     L.lbmdem_measure_copy.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_double)]
     L.lbmdem_dem_chain_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_set_lid.argtypes = [C.c_void_p, C.c_double]
+    L.lbmdem_set_vibration.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_vibration.argtypes = [C.c_void_p]
+    L.lbmdem_move_walls.argtypes = [C.c_void_p]
+    L.lbmdem_get_walls.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_vibration_schedule.argtypes = [C.POINTER(Config), C.c_long, C.c_long, C.c_void_p]
     L.lbmdem_force_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -236,6 +241,15 @@ def derive(lx, ly, r, scale=1.0, physics: Physics | None = None, precision="f64"
 
 
 COMM_ID_BYTES = 512
+
+
+def vibration_schedule(cfg: Config, nbsteps0: int, n: int, precision="f64"):
+    """The walls of a vibrating run (the reference's vib = 1, main.c:1700-1705) on sub-steps nbsteps0 .. nbsteps0 + n - 1,
+    starting from cfg's clock and walls: [n][4] = t, Mgx, Mdx, the top wall's amp*freq*cos(freq*t). Host arithmetic only."""
+    L = load_library(precision)
+    out = np.zeros((max(int(n), 0), 4))
+    _chk(L.lbmdem_vibration_schedule(C.byref(cfg), int(nbsteps0), int(n), _vp(out)))
+    return out
 
 
 def comm_unique_id() -> bytes:
@@ -512,6 +526,25 @@ class LbmDem:
     def set_lid(self, uw_h):
         """EXTENSION: the top plate's lid terms the reference has commented out (main.c:1129-1130); lattice units."""
         _chk(self._L.lbmdem_set_lid(self._h, float(uw_h)))
+
+    def set_vibration(self, on=True):
+        """The reference's shaken box (vib = 1, main.c:1700-1705): every renderScene / renderScene_dry moves the left and right
+        walls by amp*sin(freq*t) first (freq, amp of the physics, clock from its t). Single-domain double-precision handles."""
+        _chk(self._L.lbmdem_set_vibration(self._h, 1 if on else 0))
+
+    @property
+    def vibrating(self):
+        return self._L.lbmdem_vibration(self._h) == 1
+
+    def move_walls(self):
+        """renderScene's wall motion alone (main.c:1700-1705), for runs driven phase by phase"""
+        _chk(self._L.lbmdem_move_walls(self._h))
+
+    def walls(self):
+        """{t, Mgx, Mdx, Mby, Mhy} as the next sub-step finds them"""
+        out = np.zeros(5)
+        _chk(self._L.lbmdem_get_walls(self._h, _vp(out)))
+        return dict(zip(("t", "Mgx", "Mdx", "Mby", "Mhy"), (float(v) for v in out)))
 
     def set_force_mode(self, mode):
         _chk(self._L.lbmdem_set_force_mode(self._h, int(mode)))

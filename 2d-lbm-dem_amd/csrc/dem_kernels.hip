@@ -833,7 +833,9 @@ __global__ __launch_bounds__(DEM_THREADS, 4) void k_dem_chain(Kin in, Kin out, c
     if (tid < DEM_GRAINS && mine) {   // the first wavefront holds the tile's grains
       real ds = 0., df1 = 0., dM11 = 0., dM12 = 0., dM21 = 0., dM22 = 0.;
       int dz = 0;
-      walls<false>(me, wf, P, c1, c2, c3, pr, ds, df1, dz, dM11, dM12, dM21, dM22, wh);
+      DemParams Pw = P;   // (a vibrating handle's walls of this sub-step)
+      if (P.vib) { const VibWall w = P.vib[s]; Pw.Mgx = w.Mgx; Pw.Mdx = w.Mdx; Pw.wallT_vel = w.wallT_vel; }
+      walls<false>(me, wf, Pw, c1, c2, c3, pr, ds, df1, dz, dM11, dM12, dM21, dM22, wh);
       // main.c:1511-1515, then the second half kick main.c:1760-1762
       const real mi = sMI[tid], Iti = sMI[DEM_TILE + tid];
       a1 = c1 / mi + sG[tid];

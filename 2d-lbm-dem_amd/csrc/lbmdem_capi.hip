@@ -154,7 +154,7 @@ static int next_paint_epoch(lbmdem_handle* h) {
 
 static int paint_into(lbmdem_handle* h, int* obst) {
   const Kin& K = h->kin[h->kcur];
-  if (h->chain_painted && obst == h->obst[1 - h->ocur]) {
+  if (h->chain_painted && obst == h->obst[1 - h->ocur] && h->chain_paint_Mgx == h->L.Mgx) {
     // the run of sub-steps that ended here has painted the discs at these very positions (k_dem_chain, ChainPaint)
     h->chain_painted = false;
     h->obst_reset_rows = 0;
@@ -167,11 +167,15 @@ static int paint_into(lbmdem_handle* h, int* obst) {
   h->chg_state[b] = 0;   // (this rasterisation keeps no account of what it changes)
   // the pair list tells which discs cannot share a node with another one (plain stores instead of atomics). Not with
   // distributed grains: a rank's list is only right for the grains it integrates
-  const bool list_ok = h->verlet_ok && h->verlet_tracks_positions && !h->dist && !*h->ovf_host &&
+  // (vibrating walls: the side walls push grains further than the list's margin between two rebuilds, and nothing watches
+  // for that on this path -- atomics for everybody, every step)
+  const bool list_ok = h->verlet_ok && h->verlet_tracks_positions && !h->dist && !h->vib && !*h->ovf_host &&
                        *h->moved_host != h->list_generation;   // (a grain has outrun the list: atomics for everybody)
   const int reset_rows = obst == h->obst[1 - h->ocur] ? h->obst_reset_rows : 0;
   const ObstSnap was = h->snap[b][h->snap_cur[b]], now = h->snap[b][1 - h->snap_cur[b]];
-  if (h->obst_update && list_ok && h->snap_ok[b] && reset_rows == 0 && was.xc) {
+  // (not while the walls vibrate: every footprint moves with Mgx, the update's stillness rules assume a disc moves only with
+  // its grain -- DESIGN.md)
+  if (h->obst_update && !h->vib && list_ok && h->snap_ok[b] && reset_rows == 0 && was.xc) {
     // the canvas holds this buffer's last picture: only the nodes whose owner changes are written
     launch_obst_update(obst, h->L, h->n, K.x1, K.x2, h->r, h->rLB, K.v1, K.v2, K.v3, h->xc, h->yc, h->r2, h->rbl0, h->pk,
                        h->fs.touched, h->mincov, h->paint_epoch, h->V.offsets, h->V.nbr, was, now, h->V.xreb, h->V.yreb,
@@ -517,6 +521,9 @@ int lbmdem_destroy(lbmdem_handle* h) {
   for (hipEvent_t e : h->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev1) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev2) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->vib_ev) if (e) (void)hipEventDestroy(e);
+  if (h->vib_host) (void)hipHostFree(h->vib_host);
+  if (h->vib_dev) (void)hipFree(h->vib_dev);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
   return LBMDEM_OK;
@@ -808,14 +815,7 @@ int lbmdem_lbm_step(lbmdem_handle* h) {
 int lbmdem_verlet_rebuild(lbmdem_handle* h) {
   CHECK_H(h);
   // VerletWall moves the right/top DEM walls: main.c:1555-1561
-  lbmdem_config& c = h->cfg;
-  if (h->nbsteps * c.dt < c.phys.dtt) {
-    c.Mdx = 1.e-3 * c.lx / 10;
-    c.Mhy = (1.e-3 * c.ly / 10);
-  } else {
-    c.Mdx = 1.e-3 * c.lx;
-    c.Mhy = 1.e-3 * c.ly;
-  }
+  verlet_wall_reset(h->cfg, h->nbsteps);
   return lbmdem_verlet_build_lists(h);
 }
 
@@ -925,10 +925,50 @@ static void chain_forget_stream(int device, hipStream_t st) {
   if (g_chain_any[device & 63] && g_chain_stream[device & 63] == st) g_chain_any[device & 63] = false;
 }
 
+// one renderScene's wall motion (main.c:1700-1705) on the host's copy of the walls; the fluid kernels take Mgx from L
+static void vib_advance(lbmdem_handle* h) {
+  vib_step(h->cfg);
+  h->L.Mgx = (real)h->cfg.Mgx;
+}
+
+// The walls of the k sub-steps of a launch of k_dem_chain: the first is the current one (its renderScene has moved the walls
+// already), each further one moves them once more. Written into the next slice of the pinned ring and copied on the handle's
+// stream; P->vib points at the device copy. A half of the ring is written again only once the event recorded behind the last
+// launch that read it has completed (one host wait per VIB_HALF sub-steps at most, normally on an event long passed).
+// The handle's walls are not touched: *end receives its config with the walls of the last sub-step, which the caller installs
+// (vib_commit) once the launch is enqueued -- a call that fails before that leaves the walls where they were.
+static int vib_table(lbmdem_handle* h, long k, DemParams* P, lbmdem_config* end) {
+  if (k > VIB_HALF) return fail(LBMDEM_EINVAL, "vibrating walls: a run of %ld sub-steps is longer than the wall table (%d)", k, VIB_HALF);
+  if (h->vib_off + k > VIB_HALF) {
+    HIP_TRY(hipEventRecord(h->vib_ev[h->vib_half], h->stream));
+    h->vib_ev_set[h->vib_half] = true;
+    h->vib_half = 1 - h->vib_half;
+    h->vib_off = 0;
+    if (h->vib_ev_set[h->vib_half]) HIP_TRY(hipEventSynchronize(h->vib_ev[h->vib_half]));
+  }
+  const size_t at = (size_t)h->vib_half * VIB_HALF + h->vib_off;
+  VibWall* w = h->vib_host + at;
+  *end = h->cfg;
+  for (long j = 0; j < k; ++j) {
+    if (j > 0) vib_step(*end);
+    w[j] = vib_wall(*end);
+  }
+  HIP_TRY(hipMemcpyAsync(h->vib_dev + at, w, sizeof(VibWall) * k, hipMemcpyHostToDevice, h->stream));
+  h->vib_off += (int)k;
+  P->vib = h->vib_dev + at;
+  return LBMDEM_OK;
+}
+// the walls vib_table left in `end`, installed in the handle
+static void vib_commit(lbmdem_handle* h, const lbmdem_config& end) {
+  h->cfg.phys.t = end.phys.t; h->cfg.Mgx = end.Mgx; h->cfg.Mdx = end.Mdx;
+  h->L.Mgx = (real)h->cfg.Mgx;
+}
+
 long lbmdem_dem_chain_length(lbmdem_handle* h, long remaining, int fluid) {
   if (h->chain_max < 2 || remaining < 2 || h->diag_always || !h->chain.pub) return 0;
   const lbmdem_config& c = h->cfg;
-  const long cap = remaining < h->chain_max ? remaining : h->chain_max;
+  long cap = remaining < h->chain_max ? remaining : h->chain_max;
+  if (h->vib && cap > VIB_HALF) cap = VIB_HALF;   // (the wall table of one launch)
   long k = 0;
   for (; k < cap; ++k) {
     const long t = h->nbsteps + k;
@@ -960,16 +1000,19 @@ int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid) {
   if (h->dist && CHAIN_FAILED(h)) return fail(LBMDEM_EHIP, CHAIN_FAIL_MSG);
   if (!h->dist && h->run_logged) h->chain_pending.push_back(chain_snapshot(h));   // (the caller has set log_idx / done: see run_steps)
   drop_chain_paint(h);
-  const DemParams P = dem_params(h);
+  DemParams P = dem_params(h);
+  lbmdem_config vib_end;   // (vibrating: the walls of the launch's last sub-step, installed together with nbsteps below)
+  if (h->vib) RC_TRY(vib_table(h, k, &P, &vib_end));
   // A run that ends where the next fluid step begins rasterises the discs itself (the positions are in the tiles' LDS)
   // -- when the canvas is clean already (reset beside the force kernel), the pair list is the one the rasteriser would use,
   // and nothing about the map is pending.
   ChainPaint paint{};
-  if (fluid && h->chain_paint && !h->dist && (h->nbsteps + k) % h->cfg.npDEM == 0 && !h->obst_pending &&
+  // (not while the walls vibrate: the tail's paint trusts the pair list, see paint_into)
+  if (fluid && h->chain_paint && !h->dist && !h->vib && (h->nbsteps + k) % h->cfg.npDEM == 0 && !h->obst_pending &&
       !h->cs_interior_pending && h->verlet_tracks_positions && !*h->ovf_host && h->cfg.x_begin == 0 && h->cfg.x_end == h->cfg.lx) {
     const int b = 1 - h->ocur;
     // in place (the canvas holds the picture its record describes, nobody has touched it) or onto a clean canvas
-    const bool inplace = h->obst_update && h->snap_ok[b] && h->obst_reset_rows == 0 && *h->moved_host != h->list_generation;
+    const bool inplace = h->obst_update && !h->vib && h->snap_ok[b] && h->obst_reset_rows == 0 && *h->moved_host != h->list_generation;
     // (a grain that has outrun the pair list: the tail's "alone according to the list" is not to be trusted -- the stand-alone
     // rasteriser with atomics for everybody paints this step)
     const bool clean = h->obst_reset_rows == h->L.nxl && *h->moved_host != h->list_generation;
@@ -979,6 +1022,7 @@ int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid) {
                          inplace ? h->snap[b][h->snap_cur[b]] : ObstSnap{nullptr, nullptr, nullptr, nullptr},
                          h->snap[b][1 - h->snap_cur[b]], h->r, h->V.xreb, h->V.yreb, (real)(0.5 * h->cfg.phys.distVerlet),
                          h->moved_dev, h->list_generation};
+      h->chain_paint_Mgx = paint.L.Mgx;   // (a fluid step that finds the side wall elsewhere -- walls switched to vibrate -- paints again)
       // ... and, in place, against the picture in the other buffer: the rows in which the two maps of the coming fluid step
       // differ (ObstChange; the bits were cleared beside the last force kernels and nobody has painted this buffer since)
       if (inplace && h->chg[b] && h->chg_on && h->chg_state[b] == 1 && h->snap_ok[1 - b]) {
@@ -1017,6 +1061,7 @@ int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid) {
   HIP_TRY(hipGetLastError());
   h->kcur = 1 - h->kcur;
   h->nbsteps += k;
+  if (h->vib) vib_commit(h, vib_end);
   return LBMDEM_OK;
 }
 
@@ -1133,6 +1178,7 @@ static ChainSnap chain_snapshot(const lbmdem_handle* h) {
   s.substep_seq = h->substep_seq; s.carry_from = h->carry_from;
   s.gathered = h->fs.gathered; s.gathered_next = h->fs.gathered_next;
   s.nbsteps = h->nbsteps; s.Mdx = h->cfg.Mdx; s.Mhy = h->cfg.Mhy;
+  s.Mgx = h->cfg.Mgx; s.t = h->cfg.phys.t;
   return s;
 }
 
@@ -1146,6 +1192,7 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   h->substep_seq = s.substep_seq; h->carry_from = s.carry_from;
   h->fs.gathered = s.gathered; h->fs.gathered_next = s.gathered_next;
   h->nbsteps = s.nbsteps; h->cfg.Mdx = s.Mdx; h->cfg.Mhy = s.Mhy;
+  h->cfg.Mgx = s.Mgx; h->cfg.phys.t = s.t; h->L.Mgx = (real)s.Mgx;
   // what the failed launch may have written on its way: slices of the next map's canvas, and -- by the tiles that did
   // finish -- their discs, in place. The map the next fluid step paints starts from a clean canvas again.
   const int b = 1 - s.ocur;
@@ -1227,6 +1274,7 @@ static int run_steps(lbmdem_handle* h, int fluid, long n, bool logged, bool resu
     }
     int rc = LBMDEM_OK;
     if (!resumed) {
+      if (h->vib) vib_advance(h);                                                                       // main.c:1700-1705
       if (fluid && h->nbsteps % h->cfg.npDEM == 0) rc = lbmdem_lbm_step(h);                           // main.c:1710-1718
       if (rc == LBMDEM_OK && h->nbsteps % h->cfg.phys.updateVerlet == 0) rc = lbmdem_verlet_rebuild(h);  // main.c:1721-1724
       if (rc != LBMDEM_OK) return rc;
@@ -1272,6 +1320,62 @@ int lbmdem_debug_chain_giveup(lbmdem_handle* h, int launch) {
 int lbmdem_set_lid(lbmdem_handle* h, double uw_h) {
   if (!h) return fail(LBMDEM_EINVAL, "null handle");
   h->L.lid6 = uw_h / 6;   // the reference's commented-out expression: -uw_h/6, +uw_h/6
+  return LBMDEM_OK;
+}
+
+// ---- vibrating side walls (the reference's vib == 1, main.c:1700-1705) ----
+
+int lbmdem_vibration_schedule(const lbmdem_config* cfg, long nbsteps0, long n, double* out) {
+  if (!cfg || (n > 0 && !out) || nbsteps0 < 0 || n < 0) return fail(LBMDEM_EINVAL, "bad argument");
+  if (cfg->phys.updateVerlet < 1) return fail(LBMDEM_EINVAL, "updateVerlet < 1");
+  lbmdem_config c = *cfg;
+  for (long k = 0; k < n; ++k) {
+    const long step = nbsteps0 + k;
+    vib_step(c);                                                                 // main.c:1700-1705
+    if (step % c.phys.updateVerlet == 0) verlet_wall_reset(c, step);             // main.c:1721-1724 -> 1555-1561
+    const VibWall w = vib_wall(c);
+    out[4 * k] = c.phys.t; out[4 * k + 1] = w.Mgx; out[4 * k + 2] = w.Mdx; out[4 * k + 3] = w.wallT_vel;
+  }
+  return LBMDEM_OK;
+}
+
+int lbmdem_set_vibration(lbmdem_handle* h, int on) {
+#ifdef LBMDEM_SINGLE_PRECISION
+  (void)on;
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  return fail(LBMDEM_EINVAL, "vibrating walls are not available in the single-precision build of the library");
+#else
+  CHECK_H(h);
+  CHECK_NOT_SPLIT(h);
+  if (h->dist || h->cfg.x_begin != 0 || h->cfg.x_end != h->cfg.lx)
+    return fail(LBMDEM_EINVAL, "vibrating walls are not available on a strip of a decomposition");
+  if (on && !h->vib_host) {
+    HIP_TRY(hipHostMalloc((void**)&h->vib_host, sizeof(VibWall) * 2 * VIB_HALF, hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void**)&h->vib_dev, sizeof(VibWall) * 2 * VIB_HALF));
+    for (int b = 0; b < 2; ++b) HIP_TRY(hipEventCreateWithFlags(&h->vib_ev[b], hipEventDisableTiming));
+  }
+  if ((on != 0) != h->vib) {   // (the in-place map update starts over from a repaint either way)
+    h->snap_ok[0] = h->snap_ok[1] = false;
+    h->chg_state[0] = h->chg_state[1] = 0;
+  }
+  h->vib = on != 0;
+  return LBMDEM_OK;
+#endif
+}
+
+int lbmdem_get_walls(lbmdem_handle* h, double* out5) {
+  CHECK_H(h);
+  if (!out5) return fail(LBMDEM_EINVAL, "null argument");
+  out5[0] = h->cfg.phys.t; out5[1] = h->cfg.Mgx; out5[2] = h->cfg.Mdx; out5[3] = h->cfg.Mby; out5[4] = h->cfg.Mhy;
+  return LBMDEM_OK;
+}
+
+int lbmdem_vibration(lbmdem_handle* h) { return h ? (h->vib ? 1 : 0) : LBMDEM_EINVAL; }
+
+int lbmdem_move_walls(lbmdem_handle* h) {
+  CHECK_H(h);
+  if (!h->vib) return fail(LBMDEM_EINVAL, "lbmdem_move_walls: the walls do not vibrate (lbmdem_set_vibration)");
+  vib_advance(h);
   return LBMDEM_OK;
 }
 

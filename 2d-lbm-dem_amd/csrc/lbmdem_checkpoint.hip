@@ -20,7 +20,8 @@ struct CkptHeader {
   long nbsteps;
   int verlet_ok, nnbr; // symmetric list length
   long plane;          // sanity: nxl * sy of the writer
-  int has_dist, pad;   // a CkptDist section follows the lattice (the writer had its grains distributed over strips)
+  int has_dist;        // a CkptDist section follows the lattice (the writer had its grains distributed over strips)
+  int vib;             // 1: the walls vibrate (lbmdem_set_vibration; t, Mgx, Mdx are in cfg). 0 in every other file
 };
 struct CkptDist {       // follows the lattice when the writer had its grains distributed over strips
   char magic[8];        // "LBMDIST1"
@@ -60,6 +61,7 @@ int lbmdem_checkpoint_save(lbmdem_handle* h, const char* path) try {
   HIP_TRY(hipMemcpy(H.carry, h->ct.carry, sizeof H.carry, hipMemcpyDeviceToHost));
   H.cfg = h->cfg; H.nbsteps = h->nbsteps; H.verlet_ok = h->verlet_ok ? 1 : 0; H.nnbr = off[n]; H.plane = h->L.plane;
   H.has_dist = h->dist ? 1 : 0;
+  H.vib = h->vib ? 1 : 0;
   FILE* fp = fopen(path, "wb");
   if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
   bool ok = wr(fp, &H, sizeof H);
@@ -111,7 +113,7 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
   const lbmdem_config& hc = H.cfg;
   if (hc.nbgrains < 1 || hc.nbgrains > (1 << 28) || hc.lx < 3 || hc.ly < 3 || hc.lx > (1 << 24) || hc.ly > (1 << 24) ||
       hc.x_begin < 0 || hc.x_end > hc.lx || hc.x_begin >= hc.x_end || hc.halo < 0 || hc.halo > hc.lx || hc.npDEM < 1 ||
-      H.nnbr < 0 || H.nbsteps < 0 || H.plane < 1 || (H.has_dist != 0 && H.has_dist != 1))
+      H.nnbr < 0 || H.nbsteps < 0 || H.plane < 1 || (H.has_dist != 0 && H.has_dist != 1) || (H.vib != 0 && H.vib != 1))
     return fail(LBMDEM_EINVAL, "checkpoint '%s': implausible header (grains %d, lattice %d x %d, rows [%d, %d))", path,
                 hc.nbgrains, hc.lx, hc.ly, hc.x_begin, hc.x_end);
   const int n = H.cfg.nbgrains;
@@ -173,6 +175,7 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
   }
   if (!ok) return fail(LBMDEM_EINVAL, "checkpoint '%s' is truncated or from a different decomposition", path);
   h->cfg = cfg;  // wall positions as saved
+  if (H.vib) RC_TRY(lbmdem_set_vibration(h, 1));   // (the clock and the walls go on from cfg)
   h->force_mode = H.force_mode;
   h->L.lid6 = H.lid6;
   h->diag_always = H.diag_always != 0;

@@ -49,6 +49,7 @@ struct ChainSnap {
   int *gathered, *gathered_next;
   long nbsteps;
   double Mdx, Mhy;
+  double Mgx, t;   // a vibrating handle's side wall and clock (lbmdem_set_vibration): with nbsteps, where its schedule stands
 };
 
 struct lbmdem_handle {
@@ -144,6 +145,7 @@ struct lbmdem_handle {
   // next obst_construction has nothing to launch. Dropped (and the canvas marked dirty) by whatever moves a grain first.
   bool chain_painted = false;
   bool chain_paint = true;     // (lbmdem_set_dem_chain: max_substeps < 0 switches only this off, for A/B)
+  real chain_paint_Mgx = 0.;   // the side wall the discs were painted against (vibrating walls move it)
   long chain_paints = 0;
   int dem_tiles_mode = 0;      // how the tiles of k_dem_chain are composed (lbmdem_set_dem_tiles)
   // launches of k_dem_chain that have not been seen to finish, the calls they belong to, and how often one had to be undone
@@ -155,6 +157,16 @@ struct lbmdem_handle {
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
   int force_mode = 0;
+  // vibrating side walls (lbmdem_set_vibration, main.c:1700-1705): cfg.phys.t, cfg.Mgx and cfg.Mdx advance on the host as
+  // sub-steps are issued (vib_advance; with nbsteps they say where the schedule stands); a launch of k_dem_chain reads its sub-steps' walls from a table (DemParams::vib)
+  // copied from a pinned ring on the handle's stream. The ring has two halves; a half is written again only after the event
+  // recorded behind the last launch that read it has completed.
+  bool vib = false;
+  VibWall* vib_host = nullptr;  // pinned [2][VIB_HALF]
+  VibWall* vib_dev = nullptr;   // device [2][VIB_HALF]
+  int vib_half = 0, vib_off = 0;
+  hipEvent_t vib_ev[2] = {nullptr, nullptr};
+  bool vib_ev_set[2] = {false, false};
   // derived scalars
   double fscale12 = 0, fscale3 = 0;
   double* dpartial = nullptr;
@@ -227,12 +239,11 @@ static inline GrainFluidView gview(const lbmdem_handle* h) {
   return GrainFluidView{K.x1, K.x2, K.v1, K.v2, K.v3, h->xc, h->yc, h->r2, h->rbl0, h->pk, h->mincov, h->paint_epoch};
 }
 
-static inline DemParams dem_params(const lbmdem_handle* h) {
-  const lbmdem_config& c = h->cfg;
+static inline DemParams dem_params_of(const lbmdem_config& c) {
   const lbmdem_physics& p = c.phys;
   DemParams P;
-  P.gate = h->chain.gate;
-  P.n = h->n; P.dt = (real)c.dt; P.dt2 = (real)c.dt2;
+  P.gate = nullptr;
+  P.n = c.nbgrains; P.dt = (real)c.dt; P.dt2 = (real)c.dt2;
   P.kg = (real)p.kg; P.nug = (real)p.nug; P.kt = (real)p.kt; P.mu = (real)p.mu; P.murf = (real)p.murf;
   P.km = (real)p.km; P.num = (real)p.num; P.ktm = (real)p.ktm; P.mumb = (real)p.mumb; P.mum = (real)p.mum; P.nugt = (real)p.nugt;
   P.Mgx = (real)c.Mgx; P.Mdx = (real)c.Mdx; P.Mby = (real)c.Mby; P.Mhy = (real)c.Mhy;
@@ -242,7 +253,40 @@ static inline DemParams dem_params(const lbmdem_handle* h) {
   }
   P.xG = (real)c.xG; P.yG = (real)c.yG;
   P.distVerlet = (real)p.distVerlet;
+  P.vib = nullptr;
   return P;
+}
+static inline DemParams dem_params(const lbmdem_handle* h) {
+  DemParams P = dem_params_of(h->cfg);
+  P.gate = h->chain.gate;
+  P.n = h->n;
+  return P;
+}
+
+// ---- vibrating side walls (main.c:1700-1705); host arithmetic, <math.h>'s sin and cos, no contraction ----
+constexpr int VIB_HALF = 1024;   // entries per half of the ring: the longest run of sub-steps a vibrating handle hands to one launch
+// renderScene's first block when vib == 1 (main.c:1700-1705): the clock advances by dt, then the left and the right wall
+// each move by amp times the sine of freq times the new clock
+static inline void vib_step(lbmdem_config& c) {
+#pragma clang fp contract(off)
+  c.phys.t = c.phys.t + c.dt;
+  c.Mgx = c.Mgx + c.phys.amp * sin(c.phys.freq * c.phys.t);
+  c.Mdx = c.Mdx + c.phys.amp * sin(c.phys.freq * c.phys.t);
+}
+// VerletWall's reset of the right and top walls (main.c:1555-1561), at the rebuild of sub-step `nbsteps`
+static inline void verlet_wall_reset(lbmdem_config& c, long nbsteps) {
+  if (nbsteps * c.dt < c.phys.dtt) {
+    c.Mdx = 1.e-3 * c.lx / 10;
+    c.Mhy = (1.e-3 * c.ly / 10);
+  } else {
+    c.Mdx = 1.e-3 * c.lx;
+    c.Mhy = 1.e-3 * c.ly;
+  }
+}
+// the walls a sub-step sees, as dem_params() hands them to the kernels
+static inline VibWall vib_wall(const lbmdem_config& c) {
+  const DemParams P = dem_params_of(c);
+  return VibWall{P.Mgx, P.Mdx, P.wallT_vel};
 }
 
 // shared between the translation units
@@ -253,7 +297,7 @@ LBMDEM_INTERNAL int lbmdem_chain_settle(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {
-  return h->obst_update && !h->dist && h->snap_ok[1 - h->ocur] && h->verlet_ok && h->verlet_tracks_positions &&
+  return h->obst_update && !h->vib && !h->dist && h->snap_ok[1 - h->ocur] && h->verlet_ok && h->verlet_tracks_positions &&
          !*h->ovf_host && h->obst_reset_rows == 0 && *h->moved_host != h->list_generation;
 }
 // the coming ordinary sub-steps that nothing separates (fluid step when `fluid`, list rebuild, film law, table sub-step), at

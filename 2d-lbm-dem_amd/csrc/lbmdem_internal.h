@@ -127,6 +127,13 @@ constexpr int LBMDEM_SPD_MAX = 64;               // larger grains (reduced radiu
 
 #define LBMDEM_GATE(g) do { if ((g) != nullptr && *(g) != 0) return; } while (0)   /* first statement of a gated kernel */
 
+// The walls one sub-step of a vibrating handle sees (lbmdem_set_vibration; main.c:1700-1705 moves Mgx and Mdx, main.c:855
+// reads t): computed on the host with <math.h>'s sin and cos, one entry per sub-step of a launch of k_dem_chain.
+struct VibWall {
+  real Mgx, Mdx;
+  double wallT_vel;
+};
+
 struct DemParams {
   int n;
   const int* gate;                       // the handle's stop word (LatticeView::gate)
@@ -137,6 +144,9 @@ struct DemParams {
   double wallT_vel;                      // amp*freq*cos(freq*t) (main.c:855): cos() makes it a double in either build
   real xG, yG;
   real distVerlet;
+  // k_dem_chain of a vibrating handle: sub-step s of the launch takes Mgx, Mdx and wallT_vel from vib[s] (device memory,
+  // read only). null: the three fields above hold for every sub-step (every other kernel reads only those).
+  const VibWall* vib;
 };
 
 // kinematic state, SoA; two copies ping-pong across DEM sub-steps

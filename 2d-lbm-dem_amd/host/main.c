@@ -10,6 +10,9 @@
  * the reference, which cannot resume) --checkpoint FILE (written at the end) / --restart FILE.
  * --dry: the reference compiled without `#define _FLUIDE_` (main.c:16) -- DEM only: no fluid step and no check_density
  * line (main.c:1709-1719), no VTK frames although nFile still advances (main.c:1767-1772), hydrodynamic forces 0.
+ * --vib [--vib-freq F --vib-amp A]: the reference's shaken box, `vib = 1` (main.c:162-165,1700-1705): the left and right
+ * walls move by amp*sin(freq*t) every DEM step (defaults freq = 5, amp = 4e-4 as main.c:163-164 initialises them); also
+ * with --dry. Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -29,7 +32,7 @@
 /* --gpus N: one process per GPU (forked before anything touches the HIP runtime), x-strips with the grains
  * distributed, neighbour messages over RCCL (lbmdem_comm_*). Rank 0 creates the RCCL id and hands it to the others
  * through a file in a private temporary directory. Rank 0 prints and writes the VTK frames and DEM tables (merged over the ranks); checkpoints are single-GPU. */
-static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0;
+static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0;
 static char g_iddir[256] = "";
 static double g_comm_timeout = 180.;   /* seconds the ranks' transport may take to come up (--comm-timeout, LBMDEM_COMM_TIMEOUT) */
 static int g_devices[64], g_ndevices = 0;   /* --devices */
@@ -68,7 +71,8 @@ static int check_decomposition(int argc, char** argv, int gpus) {
     if (!strcmp(argv[a], "--lx") && a + 1 < argc) lx = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--ly") && a + 1 < argc) ly = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--scale") && a + 1 < argc) scale = atof(argv[++a]);
-    else if (argv[a][0] == '-' && argv[a][1] == '-' && strcmp(argv[a], "--comm") && strcmp(argv[a], "--dry") && a + 1 < argc) ++a;
+    else if (argv[a][0] == '-' && argv[a][1] == '-' && strcmp(argv[a], "--comm") && strcmp(argv[a], "--dry") &&
+             strcmp(argv[a], "--vib") && a + 1 < argc) ++a;
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
   }
   if (!sample) return 0;   /* run() prints the usage line */
@@ -104,6 +108,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[a + 1]);
     if (!strcmp(argv[a], "--comm")) g_use_comm = 1;   /* the RCCL path with a single rank */
     if (!strcmp(argv[a], "--dry")) g_dry = 1;
+    if (!strcmp(argv[a], "--vib")) g_vib = 1;
     if (!strcmp(argv[a], "--comm-timeout") && a + 1 < argc) g_comm_timeout = atof(argv[a + 1]);
     if (!strcmp(argv[a], "--devices") && a + 1 < argc) {
       for (const char* p = argv[a + 1]; *p && g_ndevices < 64;) {
@@ -118,6 +123,7 @@ int main(int argc, char** argv) {
   }
   if (g_ndevices > 0 && g_ndevices < gpus) { fprintf(stderr, "--devices names %d devices for %d ranks\n", g_ndevices, gpus); return EXIT_FAILURE; }
   if (g_dry && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dry is a single-GPU mode (the strips exist for the fluid)\n"); return EXIT_FAILURE; }
+  if (g_vib && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--vib is a single-GPU mode (vibrating walls are not available on strips)\n"); return EXIT_FAILURE; }
   if (gpus <= 1) return run(argc, argv);
   g_world = gpus; g_use_comm = 1;
   { /* every strip must be at least one margin wide (lbmdem_dist_enable would refuse on the ranks whose strip is one
@@ -222,6 +228,7 @@ static int run(int argc, char** argv) {
   long max_steps = -1;
   const char* sample = NULL;
   const char *ckpt_out = NULL, *ckpt_in = NULL;
+  double vib_freq = -1., vib_amp = -1.;   /* --vib-freq, --vib-amp (negative: the reference's initialisers) */
   /* device-resident kernel arguments: ~1.2 us less per launch (the HIP runtime reads this when it
    * initialises, i.e. at the first lbmdem_* call below); an explicit setting of the caller wins */
   setenv("HIP_FORCE_DEV_KERNARG", "1", 0);
@@ -240,11 +247,14 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--devices") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--comm")) {}
     else if (!strcmp(argv[a], "--dry")) {}
+    else if (!strcmp(argv[a], "--vib")) {}
+    else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
+    else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   SAY("Opening file : %s\n", sample);
@@ -267,6 +277,8 @@ static int run(int argc, char** argv) {
   lbmdem_config cfg;
   memset(&cfg, 0, sizeof cfg);
   DIE(lbmdem_physics_defaults(&cfg.phys), "physics_defaults");
+  if (vib_freq >= 0.) cfg.phys.freq = vib_freq;
+  if (vib_amp >= 0.) cfg.phys.amp = vib_amp;
   DIE(lbmdem_derive(&cfg, lx, ly, scale, n, r), "derive");
   cfg.x_begin = 0; cfg.x_end = lx; cfg.halo = 0; cfg.device = device;
   if (g_use_comm) { /* this rank's strip */
@@ -300,6 +312,7 @@ static int run(int argc, char** argv) {
   } else {
     DIE(lbmdem_create(&cfg, r, x1, x2, &h), "create");
   }
+  if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   lbmdem_comm* comm = NULL;
   if (g_use_comm) {
     unsigned char id[LBMDEM_COMM_ID_BYTES];
@@ -346,6 +359,7 @@ static int run(int argc, char** argv) {
       if (g_dry) {   /* renderScene without its `#ifdef _FLUIDE_` block (main.c:1709-1719) */
         DIE(lbmdem_run_dem(h, 1), "run_dem");
       } else if (lbm_now && console_now) {
+        if (lbmdem_vibration(h) == 1) DIE(lbmdem_move_walls(h), "move_walls");   /* main.c:1700-1705 */
         if (comm) DIE(lbmdem_comm_lbm_step(h, comm), "comm_lbm_step"); else DIE(lbmdem_lbm_step(h), "lbm_step");
         double sum = serial_density(h, comm);
         SAY("Iteration Number %ld, Total density in the system %f\n", nbsteps, sum);

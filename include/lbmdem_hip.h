@@ -144,6 +144,30 @@ int lbmdem_run_dem(lbmdem_handle* h, long n_dem_steps);
  * default) -- BASELINE.json configs[1], a lid-driven cavity. Checked against the CPU oracle carrying the same terms. */
 int lbmdem_set_lid(lbmdem_handle* h, double uw_h);
 
+/* The reference's shaken box, `vib = 1` (main.c:162-165). Every renderScene() then starts by advancing the clock t by dt
+ * and moving the left wall Mgx and the right wall Mdx each by amp times the sine of freq times the new t (main.c:1700-1705),
+ * and the fluid step (rasterisation main.c:1009, wall velocity of reinit_obst_density and the IBB main.c:974-980,1172-1216,
+ * torque arm main.c:1296,1320), the Verlet rebuild and the DEM sub-step (the top wall's amp*freq*cos(freq*t), main.c:855)
+ * all use the moved walls. As written there: the rebuild's VerletWall resets Mdx (main.c:1555-1561), discarding its offset,
+ * while Mgx keeps moving away; the lattice-edge walls of the fluid and dx do not move. Same bits as the reference.
+ * lbmdem_set_vibration(h, 1) switches it on (off by default) with freq, amp of cfg.phys and the clock and walls where they
+ * are (cfg.phys.t, cfg.Mgx, cfg.Mdx at create, or as a checkpoint saved them); 0 stops the walls where they are. The walls
+ * move in lbmdem_run and lbmdem_run_dem, once per sub-step, before its fluid step; the separate phases use them as they are.
+ * A checkpoint of a vibrating handle restarts vibrating.
+ * Not available (LBMDEM_EINVAL): on a strip of a decomposition or with distributed grains (lbmdem_dist_enable, the host
+ * driver's --gpus N), and in the single-precision library (liblbmdem_hip_sp.so), which has no checker for this mode. */
+int lbmdem_set_vibration(lbmdem_handle* h, int on);
+int lbmdem_vibration(lbmdem_handle* h);   /* 1 when on, 0 when off */
+/* renderScene's first statement alone (main.c:1700-1705), for callers that run the phases themselves (lbmdem_lbm_step,
+ * lbmdem_verlet_rebuild, lbmdem_dem_substep) instead of lbmdem_run: once per sub-step, before its fluid step */
+int lbmdem_move_walls(lbmdem_handle* h);
+/* walls5 = t, Mgx, Mdx, Mby, Mhy as the next sub-step finds them (before its renderScene moves them) */
+int lbmdem_get_walls(lbmdem_handle* h, double* walls5);
+/* Host only: the walls the reference uses on sub-steps nbsteps0 .. nbsteps0 + n - 1 of a vibrating run that has cfg's clock
+ * and walls before sub-step nbsteps0 -- out[4 k .. 4 k + 3] = t, Mgx, Mdx and the top wall's amp*freq*cos(freq*t), in the
+ * order of renderScene (the move, then the rebuild's reset of Mdx when nbsteps % updateVerlet == 0, with the dtt switch). */
+int lbmdem_vibration_schedule(const lbmdem_config* cfg, long nbsteps0, long n, double* out);
+
 /* hydrodynamic-force summation: 0 = parity (the reference's order of additions, bit-exact); 1 = fast (the same
  * addends reduced across the lanes of a wavefront: differs in the last bits; same speed as parity since round 2,
  * kept for callers that do not need the reference's bits). Default 0. */
