@@ -50,6 +50,27 @@ class Config(C.Structure):
                 ("xG", C.c_double), ("yG", C.c_double), ("phys", Physics)]
 
 
+class SceneEvent(C.Structure):
+    """lbmdem_scene_event"""
+    _fields_ = [("kind", C.c_int), ("nfile", C.c_int), ("step", C.c_long)]
+
+
+_SAY = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
+
+
+class Scene(C.Structure):
+    """lbmdem_scene"""
+    _fields_ = [("dir", C.c_char_p), ("fluid", C.c_int), ("duration", C.c_double), ("say", _SAY), ("user", C.c_void_p)]
+
+
+class SceneResult(C.Structure):
+    """lbmdem_scene_result"""
+    _fields_ = [("steps_done", C.c_long), ("nfile", C.c_int), ("stopped", C.c_int), ("energies8", C.c_double * 8),
+                ("last_density", C.c_double)]
+
+
+SCENE_KINDS = ("CONSOLE_DENSITY", "VTK", "DEM", "STEPS_LINE", "STOP")
+
 _lib = None
 _lib_sp = None
 SP_LIB_PATH = os.path.join(_HERE, "liblbmdem_hip_sp.so")   # `real` = float: the reference's -DSINGLE_PRECISION mode
@@ -148,6 +169,9 @@ def _open_library(LIB_PATH):
     L.lbmdem_move_walls.argtypes = [C.c_void_p]
     L.lbmdem_get_walls.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_vibration_schedule.argtypes = [C.POINTER(Config), C.c_long, C.c_long, C.c_void_p]
+    L.lbmdem_scene_schedule.argtypes = [C.POINTER(Config), C.c_long, C.c_long, C.c_double, C.c_int, C.c_void_p, C.c_long,
+                                        C.POINTER(C.c_long)]
+    L.lbmdem_run_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(Scene), C.POINTER(SceneResult)]
     L.lbmdem_force_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -250,6 +274,19 @@ def vibration_schedule(cfg: Config, nbsteps0: int, n: int, precision="f64"):
     out = np.zeros((max(int(n), 0), 4))
     _chk(L.lbmdem_vibration_schedule(C.byref(cfg), int(nbsteps0), int(n), _vp(out)))
     return out
+
+
+def scene_schedule(cfg: Config, nbsteps0: int, n: int, duration: float = -1.0, fluid: bool = True, precision="f64"):
+    """The events of n calls of renderScene() from step counter nbsteps0 in the reference's main loop (main.c:1697-1777,
+    1880-1890), in order: [(kind, step, nfile)], kind one of SCENE_KINDS -- check_density's line, write_vtk, write_DEM +
+    write_forces, the "steps" line, the stop (first step with step * dt > duration; duration < 0: none). Host arithmetic only."""
+    L = load_library(precision)
+    count = C.c_long(0)
+    _chk(L.lbmdem_scene_schedule(C.byref(cfg), int(nbsteps0), int(n), float(duration), int(bool(fluid)), None, 0, C.byref(count)))
+    ev = (SceneEvent * max(count.value, 1))()
+    _chk(L.lbmdem_scene_schedule(C.byref(cfg), int(nbsteps0), int(n), float(duration), int(bool(fluid)), ev, count.value,
+                                 C.byref(count)))
+    return [(SCENE_KINDS[ev[k].kind], int(ev[k].step), int(ev[k].nfile)) for k in range(count.value)]
 
 
 def comm_unique_id() -> bytes:
@@ -355,6 +392,20 @@ class LbmDem:
     def renderScene(self, n=1):
         """n x renderScene() (main.c:1697-1765)."""
         _chk(self._L.lbmdem_run(self._h, int(n)))
+
+    def run_scene(self, n, outdir=None, fluid=True, duration=-1.0, comm=None):
+        """The reference's main loop (main.c:1879-1890) for n x renderScene(), or fewer when step * dt > duration ends it
+        (duration < 0: never): check_density's console lines, write_vtk / write_DEM / write_forces into `outdir` at the
+        reference's cadences (None: no files), the "steps" lines; the sub-steps between two of those in one call of the run
+        loop. fluid=False: the reference without `#define _FLUIDE_`. -> (console lines, dict(steps_done, nfile, stopped,
+        energies8, last_density)). The header line of stats.data is the caller's."""
+        lines = []
+        say = _SAY(lambda user, line: lines.append(line.decode(errors="replace")))
+        sc = Scene(os.fsencode(outdir) if outdir is not None else None, int(bool(fluid)), float(duration), say, None)
+        res = SceneResult()
+        _chk(self._L.lbmdem_run_scene(self._h, comm._c if comm is not None else None, int(n), C.byref(sc), C.byref(res)))
+        return lines, dict(steps_done=int(res.steps_done), nfile=int(res.nfile), stopped=bool(res.stopped),
+                           energies8=tuple(res.energies8), last_density=float(res.last_density))
 
     def run_dem(self, n=1):
         """n x (Verlet rebuild when due; DEM sub-step) -- renderScene without its fluid step."""

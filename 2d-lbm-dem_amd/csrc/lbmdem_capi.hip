@@ -1259,7 +1259,12 @@ static int run_steps(lbmdem_handle* h, int fluid, long n, bool logged, bool resu
     Scope(lbmdem_handle* h_, bool logged_) : h(h_), was(h_->run_logged) { ++h->in_run; h->run_logged = logged_; }
     ~Scope() { --h->in_run; h->run_logged = was; }
   } scope(h, logged);
-  if (logged) h->runlog.push_back(RunLogEntry{fluid, n});
+  if (logged) {
+    // no launch of k_dem_chain is waiting to be confirmed: nothing refers to the calls before this one (a handle whose
+    // multi-sub-step kernel is off would otherwise keep one entry per call for the whole simulation)
+    if (h->chain_pending.empty()) h->runlog.clear();
+    h->runlog.push_back(RunLogEntry{fluid, n});
+  }
   for (long k = 0; k < n;) {
     size_t cap = CHAIN_PENDING_CAP;
 #ifdef LBMDEM_AB   // (tests: a small cap makes the run loop itself find the failed launch)

@@ -87,6 +87,12 @@ struct lbmdem_comm {
 #define COMM_STALE(c) false
 #endif
 
+int lbmdem_comm_rank_world(lbmdem_comm* c, int* rank, int* world) {
+  if (!c) return fail(LBMDEM_EINVAL, "null communicator");
+  *rank = c->rank; *world = c->world;
+  return LBMDEM_OK;
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 

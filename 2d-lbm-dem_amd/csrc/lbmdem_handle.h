@@ -156,6 +156,8 @@ struct lbmdem_handle {
   long chain_recoveries = 0;
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
+  // KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM of lbmdem_run_scene: its "steps" line prints them (main.c:1885-1889)
+  double scene_energies[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int force_mode = 0;
   // vibrating side walls (lbmdem_set_vibration, main.c:1700-1705): cfg.phys.t, cfg.Mgx and cfg.Mdx advance on the host as
   // sub-steps are issued (vib_advance; with nbsteps they say where the schedule stands); a launch of k_dem_chain reads its sub-steps' walls from a table (DemParams::vib)
@@ -315,3 +317,4 @@ LBMDEM_INTERNAL int lbmdem_dist_unpack_tables_kin_fill(lbmdem_handle* h, const v
                                                        const void* kin_lo, const void* kin_hi);
 LBMDEM_INTERNAL int lbmdem_vtk_place_block(float* fields11, int lx, int ly, int x0, int nx, const float* block11);
 LBMDEM_INTERNAL int lbmdem_dist_enable_caps(lbmdem_handle* h, int M, long cap_g, long cap_t, long cap_l);
+LBMDEM_INTERNAL int lbmdem_comm_rank_world(lbmdem_comm* c, int* rank, int* world);   // for lbmdem_run_scene (lbmdem_scene.hip)

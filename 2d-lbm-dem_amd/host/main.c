@@ -13,9 +13,12 @@
  * --vib [--vib-freq F --vib-amp A]: the reference's shaken box, `vib = 1` (main.c:162-165,1700-1705): the left and right
  * walls move by amp*sin(freq*t) every DEM step (defaults freq = 5, amp = 4e-4 as main.c:163-164 initialises them); also
  * with --dry. Single GPU only.
+ * --run-stats: one more line on stderr at the end, `dem_chain: launches L substeps S recoveries R paints P`: how many
+ * launches of the multi-sub-step DEM kernel covered how many sub-steps, how many had to be undone, how many rasterised.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
+#include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -32,7 +35,7 @@
 /* --gpus N: one process per GPU (forked before anything touches the HIP runtime), x-strips with the grains
  * distributed, neighbour messages over RCCL (lbmdem_comm_*). Rank 0 creates the RCCL id and hands it to the others
  * through a file in a private temporary directory. Rank 0 prints and writes the VTK frames and DEM tables (merged over the ranks); checkpoints are single-GPU. */
-static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0;
+static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_stats = 0;
 static char g_iddir[256] = "";
 static double g_comm_timeout = 180.;   /* seconds the ranks' transport may take to come up (--comm-timeout, LBMDEM_COMM_TIMEOUT) */
 static int g_devices[64], g_ndevices = 0;   /* --devices */
@@ -72,7 +75,7 @@ static int check_decomposition(int argc, char** argv, int gpus) {
     else if (!strcmp(argv[a], "--ly") && a + 1 < argc) ly = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--scale") && a + 1 < argc) scale = atof(argv[++a]);
     else if (argv[a][0] == '-' && argv[a][1] == '-' && strcmp(argv[a], "--comm") && strcmp(argv[a], "--dry") &&
-             strcmp(argv[a], "--vib") && a + 1 < argc) ++a;
+             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && a + 1 < argc) ++a;
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
   }
   if (!sample) return 0;   /* run() prints the usage line */
@@ -109,6 +112,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--comm")) g_use_comm = 1;   /* the RCCL path with a single rank */
     if (!strcmp(argv[a], "--dry")) g_dry = 1;
     if (!strcmp(argv[a], "--vib")) g_vib = 1;
+    if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--comm-timeout") && a + 1 < argc) g_comm_timeout = atof(argv[a + 1]);
     if (!strcmp(argv[a], "--devices") && a + 1 < argc) {
       for (const char* p = argv[a + 1]; *p && g_ndevices < 64;) {
@@ -138,7 +142,12 @@ int main(int argc, char** argv) {
   for (int r = 0; r < gpus; ++r) {
     pids[r] = fork();
     if (pids[r] < 0) { perror("fork"); return EXIT_FAILURE; }
-    if (pids[r] == 0) { g_rank = r; _exit(run(argc, argv)); }
+    if (pids[r] == 0) {   /* (_exit does not flush: into a pipe or a file the end of rank 0's console lines was lost) */
+      g_rank = r;
+      int rc = run(argc, argv);
+      fflush(stdout);
+      _exit(rc);
+    }
   }
   /* the first rank that fails takes the others with it: its peers would otherwise block for ever inside an RCCL call */
   int bad = 0, left = gpus;
@@ -248,13 +257,14 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--comm")) {}
     else if (!strcmp(argv[a], "--dry")) {}
     else if (!strcmp(argv[a], "--vib")) {}
+    else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   SAY("Opening file : %s\n", sample);
@@ -341,59 +351,22 @@ static int run(int argc, char** argv) {
     }
   }
 
-  /* main loop, main.c:1879-1890: advance to the next console cadence (updateVerlet steps) at a time */
+  /* main loop, main.c:1879-1890: the library's (lbmdem_run_scene) -- check_density's lines, write_vtk every stepFilm DEM
+   * steps, write_DEM / write_forces every 4000, the "steps" line every updateVerlet, the stop test after EVERY renderScene().
+   * Between two of those the sub-steps reach the run loop in one piece. With several strips rank 0 prints and writes (the VTK
+   * columns merged over the ranks; the sub-step before a write_DEM run by rank 0 on a full replica). */
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
-  int nFile = (int)(nbsteps / cfg.phys.stepFilm); /* main.c:147 */
-  double energies[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM (main.c:1885-1889) */
-  const int chunk = cfg.phys.updateVerlet;
-  const int stepConsole = 400; /* main.c:140 */
-  int stop = 0;
-  do {
-    long todo = chunk - (nbsteps % chunk);
-    if (max_steps >= 0 && nbsteps + todo > max_steps) todo = max_steps - nbsteps;
-    if (todo <= 0) break;
-    /* check_density cadence (main.c:1715): printed right after the fluid step of such a DEM step */
-    for (long k = 0; k < todo; ++k) {
-      int lbm_now = (nbsteps % cfg.npDEM == 0), console_now = (nbsteps % stepConsole == 0);
-      if (g_dry) {   /* renderScene without its `#ifdef _FLUIDE_` block (main.c:1709-1719) */
-        DIE(lbmdem_run_dem(h, 1), "run_dem");
-      } else if (lbm_now && console_now) {
-        if (lbmdem_vibration(h) == 1) DIE(lbmdem_move_walls(h), "move_walls");   /* main.c:1700-1705 */
-        if (comm) DIE(lbmdem_comm_lbm_step(h, comm), "comm_lbm_step"); else DIE(lbmdem_lbm_step(h), "lbm_step");
-        double sum = serial_density(h, comm);
-        SAY("Iteration Number %ld, Total density in the system %f\n", nbsteps, sum);
-        if (nbsteps % cfg.phys.updateVerlet == 0) DIE(lbmdem_verlet_rebuild(h), "verlet_rebuild");
-        DIE(lbmdem_dem_substep(h), "dem_substep");
-      } else if (comm) {
-        DIE(lbmdem_comm_run(h, comm, 1), "comm_run");
-      } else {
-        DIE(lbmdem_run(h, 1), "run");
-      }
-      ++nbsteps;
-      /* output cadence of renderScene (main.c:1767-1772): write_vtk every stepFilm DEM steps. With several strips
-       * the columns are merged over the ranks and rank 0 writes the same five files */
-      if (nbsteps % cfg.phys.stepFilm == 0) {
-        if (g_dry) {}   /* write_vtk sits inside `#ifdef _FLUIDE_` (main.c:1768-1770); nFile++ does not */
-        else if (comm) DIE(lbmdem_comm_write_vtk(h, comm, ".", nFile), "comm_write_vtk");
-        else DIE(lbmdem_write_vtk(h, ".", nFile), "write_vtk");
-        nFile++;
-      }
-      /* write_DEM and write_forces every stepStrob = 4000 DEM steps (main.c:142,1773-1776). With several strips the
-       * sub-step before was run by rank 0 on a full replica (lbmdem_comm_run): it holds the whole table */
-      if (nbsteps % 4000 == 0 && g_rank == 0) {
-        DIE(lbmdem_write_dem(h, ".", nFile, energies), "write_dem");
-        DIE(lbmdem_write_forces(h, ".", nFile), "write_forces");
-      }
-      /* the reference tests its stop condition after EVERY renderScene() (main.c:1880-1890) */
-      if (nbsteps * cfg.dt > duration) { stop = 1; break; }
-    }
-    if (nbsteps % chunk == 0) {
-      now = time(NULL);
-      SAY("steps %li steps %le KE %le PE %le SE %le WF %le INCE %le SLIP %le RW %le Time %s \n", nbsteps,
-             nbsteps * cfg.dt, energies[0], energies[1], energies[2], energies[4], energies[5], energies[6], energies[7], asctime(localtime(&now)));
-    }
-  } while (!stop && (max_steps < 0 || nbsteps < max_steps));
+  lbmdem_scene scene;
+  memset(&scene, 0, sizeof scene);
+  scene.dir = ".";
+  scene.fluid = !g_dry;   /* --dry: renderScene without its `#ifdef _FLUIDE_` blocks (main.c:1709-1719,1768-1770) */
+  scene.duration = duration;
+  lbmdem_scene_result done;
+  memset(&done, 0, sizeof done);
+  if (max_steps < 0 || max_steps > nbsteps)
+    DIE(lbmdem_run_scene(h, comm, max_steps < 0 ? LONG_MAX : max_steps - nbsteps, &scene, &done), "run_scene");
+  nbsteps += done.steps_done;
   DIE(lbmdem_sync(h), "sync");
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (ckpt_out) {
@@ -415,6 +388,13 @@ static int run(int argc, char** argv) {
     fprintf(stderr, "dem_steps: %ld\n", nbsteps);
     fprintf(stderr, "MLUPS: %.1f  DEM-steps/s: %.1f  (%d GPU%s)\n", 1e-6 * (double)lx * ly * lbm_steps / secs, nbsteps / secs,
             g_world, g_world > 1 ? "s" : "");
+    if (g_run_stats) {   /* how the DEM sub-steps were launched (rank 0's handle) */
+      long launches = 0, substeps = 0, recoveries = 0, paints = 0;
+      DIE(lbmdem_dem_chain_stats(h, &launches, &substeps, NULL, NULL), "dem_chain_stats");
+      DIE(lbmdem_dem_chain_recoveries(h, &recoveries), "dem_chain_recoveries");
+      DIE(lbmdem_dem_chain_paints(h, &paints), "dem_chain_paints");
+      fprintf(stderr, "dem_chain: launches %ld substeps %ld recoveries %ld paints %ld\n", launches, substeps, recoveries, paints);
+    }
   }
   now = time(NULL);
   SAY("End local time and date: %s", asctime(localtime(&now)));

@@ -27,12 +27,14 @@ extern "C" {
 #endif
 
 /* The reference fixes its lattice with the object-like MACROS lx, ly and scale (main.c:24-32; its benchmark passes
- * them as -Dlx= -Dly= -Dscale=, benchmark.xml:85). They would rewrite the member and parameter names below, so they
- * are parked while this header is read and restored at its end: the header can be included anywhere in the reference's
- * main.c (found by compiling the binding of INTEGRATION.md: oracle/make_integration_check.py). */
+ * them as -Dlx= -Dly= -Dscale=, benchmark.xml:85) and its run length with the macro duration (main.c:47). They would
+ * rewrite the member and parameter names below, so they are parked while this header is read and restored at its end:
+ * the header can be included anywhere in the reference's main.c (found by compiling the binding of INTEGRATION.md: oracle/make_integration_check.py). */
 #pragma push_macro("lx")
 #pragma push_macro("ly")
 #pragma push_macro("scale")
+#pragma push_macro("duration")
+#undef duration
 #undef lx
 #undef ly
 #undef scale
@@ -137,6 +139,63 @@ int lbmdem_run(lbmdem_handle* h, long n_dem_steps);
 /* The same without the fluid steps: n x (Verlet rebuild when due; DEM sub-step). For drivers that run the
  * fluid step themselves (strip decomposition: halo exchange and force combine sit between its phases). */
 int lbmdem_run_dem(lbmdem_handle* h, long n_dem_steps);
+
+/* The reference's whole main loop, `do { renderScene(); ... } while (nbsteps * dt <= duration)` (main.c:1879-1890), with
+ * everything that hangs on the step counter besides the step itself. lbmdem_scene_schedule is the single place these
+ * cadences live. With `s` the counter BEFORE a sub-step and s' = s + 1 after it, a sub-step's events in the loop's order:
+ *   LBMDEM_SCENE_CONSOLE_DENSITY  fluid && s % npDEM == 0 && s % 400 == 0 (main.c:1715): the fluid step, then check_density's
+ *                                 line, then the list rebuild if due, then the sub-step                      (step = s)
+ *   LBMDEM_SCENE_VTK              s' % stepFilm == 0 (main.c:1767-1772): write_vtk when `fluid`, with nfile; nFile++ either way
+ *   LBMDEM_SCENE_DEM              s' % 4000 == 0 (main.c:1773-1776): write_DEM, write_forces with the NEW nFile
+ *   LBMDEM_SCENE_STEPS_LINE       s' % updateVerlet == 0 (main.c:1884-1889): the "steps ... KE ... Time" line with the
+ *                                 energies of the last write_DEM
+ *   LBMDEM_SCENE_STOP             the first s' with (double)s' * cfg->dt > duration -- found with that predicate itself, as the
+ *                                 loop evaluates it (main.c:1890), not by a division; a do-while: a run that starts beyond it
+ *                                 still makes one sub-step. duration < 0: no stop. The list ends with this event.
+ * (step = s' for the last four; nfile = the frame counter the event uses, nFile = nbsteps0 / stepFilm at the start as
+ * main.c:147.) Host only, no handle, no device: the events of n calls of renderScene() starting at counter nbsteps0. At most
+ * `cap` of them are written to `out`; *count receives how many there are (cap = 0 to size). */
+#define LBMDEM_SCENE_CONSOLE_DENSITY 0
+#define LBMDEM_SCENE_VTK 1
+#define LBMDEM_SCENE_DEM 2
+#define LBMDEM_SCENE_STEPS_LINE 3
+#define LBMDEM_SCENE_STOP 4
+typedef struct lbmdem_scene_event { int kind; int nfile; long step; } lbmdem_scene_event;
+int lbmdem_scene_schedule(const lbmdem_config* cfg, long nbsteps0, long n, double duration, int fluid,
+                          lbmdem_scene_event* out, long cap, long* count);
+typedef struct lbmdem_comm lbmdem_comm;   /* the RCCL transport of a strip decomposition (lbmdem_comm_*, below) */
+/* The loop itself: n x renderScene() from the handle's step counter, or fewer when the stop condition ends it, with the
+ * console lines and files of that schedule. The sub-steps between two events go to the run loop in ONE call (lbmdem_run;
+ * lbmdem_run_dem when !fluid; lbmdem_comm_run with a communicator), so that runs of ordinary sub-steps are single launches
+ * whose tail rasterises for the next fluid step; a sub-step whose events all follow it is the last of such a stretch. At an
+ * event: CONSOLE_DENSITY = lbmdem_move_walls on a vibrating handle, lbmdem_lbm_step (lbmdem_comm_lbm_step), the serial
+ * chain of lbmdem_total_density_serial (through the ranks in x order), the line, lbmdem_verlet_rebuild if due,
+ * lbmdem_dem_substep; VTK = lbmdem_write_vtk (lbmdem_comm_write_vtk: collective, rank 0 writes); DEM = lbmdem_write_dem +
+ * lbmdem_write_forces on rank 0. The writers and the phase calls settle the handle first like every entry point outside
+ * lbmdem_run / lbmdem_run_dem: a launch of the multi-sub-step kernel that gave up is undone and its sub-steps are repeated
+ * before anything is written or printed. The state after the call is that of lbmdem_run called steps_done times with 1.
+ * Lines: "Iteration Number %ld, Total density in the system %f\n" (main.c:1259) and "steps %li steps %le KE %le PE %le SE
+ * %le WF %le INCE %le SLIP %le RW %le Time %s \n" with asctime (main.c:1885-1889), on rank 0 only, each passed whole to
+ * `say`. The energies of the last write_DEM stay in the handle: a second call prints what the first one's left. The header
+ * line of stats.data is the caller's (the reference writes it in main(), main.c:1867-1877). With a communicator every rank
+ * makes the same call (same n, dir, duration). The single-precision library has no write_DEM / write_forces: there a DEM
+ * event with a directory fails with LBMDEM_EINVAL, by those writers' own refusal (dir = NULL needs none). */
+typedef struct lbmdem_scene {
+  const char* dir;      /* files go here; NULL = write no files (events still happen: nFile still advances) */
+  int fluid;            /* 1: the reference as shipped; 0: without _FLUIDE_ (main.c:16): no fluid step, no density line, no VTK */
+  double duration;      /* main.c:47; < 0: run all n */
+  void (*say)(void* user, const char* line);   /* console lines, one call per line; NULL = stdout */
+  void* user;
+} lbmdem_scene;
+typedef struct lbmdem_scene_result {
+  long steps_done;      /* sub-steps this call made */
+  int nfile;            /* the frame counter after them */
+  int stopped;          /* 1: the stop condition ended the loop */
+  double energies8[8];  /* KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM (lbmdem_write_dem) */
+  double last_density;  /* the last check_density sum of this call (0 when there was none) */
+} lbmdem_scene_result;
+int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm /* NULL: one domain */, long n, const lbmdem_scene* sc,
+                     lbmdem_scene_result* res /* may be NULL */);
 
 /* EXTENSION, not in the reference as it runs: a lid. The reference's top-plate copies carry commented-out moving-wall
  * terms (main.c:1129-1130: f[x][ly-1][3] = f[x-1][ly-2][7]; //-uw_h/6;  f[x][ly-1][5] = f[x+1][ly-2][1]; //+uw_h/6;
@@ -360,7 +419,6 @@ int lbmdem_dist_unpack2(lbmdem_handle* h, int kind, const void* buf_lo, const vo
  * the same over torch.distributed. One process per GPU; rank k talks to ranks k-1 and k+1 only: ncclSend / ncclRecv
  * grouped per message class on side streams (the kinematics and the f halo rows travel while kernels run), no
  * collective on the step path. RCCL is dlopen'ed by the first of these calls. */
-typedef struct lbmdem_comm lbmdem_comm;
 #define LBMDEM_COMM_ID_BYTES 512          /* four RCCL unique ids: one communicator per message class */
 int lbmdem_comm_unique_id(void* id);      /* rank 0 makes it, every rank passes the same bytes to ..._create */
 int lbmdem_comm_create(const void* id, int rank, int world, int device, lbmdem_comm** out);
@@ -435,6 +493,7 @@ const char* lbmdem_version(void);
 /* after every sub-step, grains this rank does not integrate are overwritten with NaN (strip tests: nothing may read them) */
 int lbmdem_dist_set_poison(lbmdem_handle* h, int on);
 
+#pragma pop_macro("duration")
 #pragma pop_macro("scale")
 #pragma pop_macro("ly")
 #pragma pop_macro("lx")
