@@ -69,6 +69,12 @@ class SceneResult(C.Structure):
                 ("last_density", C.c_double)]
 
 
+class ProbeConfig(C.Structure):
+    """lbmdem_probe_config"""
+    _fields_ = [("every", C.c_int), ("capacity", C.c_int), ("pressure_row", C.c_int), ("velocity_row", C.c_int),
+                ("npoints", C.c_int), ("points", C.POINTER(C.c_int)), ("grain_extent", C.c_int)]
+
+
 SCENE_KINDS = ("CONSOLE_DENSITY", "VTK", "DEM", "STEPS_LINE", "STOP")
 
 _lib = None
@@ -172,6 +178,12 @@ def _open_library(LIB_PATH):
     L.lbmdem_scene_schedule.argtypes = [C.POINTER(Config), C.c_long, C.c_long, C.c_double, C.c_int, C.c_void_p, C.c_long,
                                         C.POINTER(C.c_long)]
     L.lbmdem_run_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(Scene), C.POINTER(SceneResult)]
+    L.lbmdem_probe_enable.argtypes = [C.c_void_p, C.POINTER(ProbeConfig)]
+    L.lbmdem_probe_disable.argtypes = [C.c_void_p]
+    L.lbmdem_probe_record_doubles.argtypes = [C.c_void_p]
+    L.lbmdem_probe_record_doubles.restype = C.c_long
+    L.lbmdem_probe_layout.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_probe_read.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.lbmdem_force_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_profile_enable.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_profile_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -596,6 +608,44 @@ class LbmDem:
         out = np.zeros(5)
         _chk(self._L.lbmdem_get_walls(self._h, _vp(out)))
         return dict(zip(("t", "Mgx", "Mdx", "Mby", "Mhy"), (float(v) for v in out)))
+
+    # ---- device-side probes (include/lbmdem_hip.h: lbmdem_probe_*) ----------------------------------------------
+    def probe_enable(self, every=1, capacity=1024, pressure_row=2, velocity_row=True, points=(), grain_extent=True):
+        """Record the reference's uncalled field diagnostics on the device every `every`-th fluid step, right after
+        forces_fluid: the pressure profile of row `pressure_row` (write_densities' pressure_base file, main.c:524-539; None
+        or < 0: off), velocity_profile's row through grain 0 (main.c:1647-1676), `pressures` at the nodes `points` = [(x, y),
+        ...] (main.c:1685-1691), xgrainmax and height (main.c:400-405). The ring holds `capacity` records; samples beyond that
+        are dropped and counted until probe_read() empties it. Whole-lattice double-precision handles."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.int32).reshape(-1, 2))
+        pc = ProbeConfig(int(every), int(capacity), -1 if pressure_row is None else int(pressure_row), int(bool(velocity_row)),
+                         len(pts), pts.ctypes.data_as(C.POINTER(C.c_int)) if len(pts) else None, int(bool(grain_extent)))
+        _chk(self._L.lbmdem_probe_enable(self._h, C.byref(pc)))
+
+    def probe_disable(self):
+        _chk(self._L.lbmdem_probe_disable(self._h))
+
+    def probe_read(self):
+        """The records since the last read, oldest first, as a dict of arrays -- step[n], time[n], clock[n] (a vibrating
+        handle's t), pressure_row[n, lx], velocity_y[n], velocity_row[n, lx], point_pressure[n, npoints], xgrainmax[n],
+        height[n]; fields switched off are absent -- plus `dropped`, the samples that found the ring full. Synchronises;
+        empties the ring."""
+        L = self._L
+        count, dropped = C.c_long(0), C.c_long(0)
+        _chk(L.lbmdem_probe_read(self._h, None, 0, C.byref(count), C.byref(dropped)))
+        rec = int(L.lbmdem_probe_record_doubles(self._h))
+        off = (C.c_long * 6)()
+        _chk(L.lbmdem_probe_layout(self._h, off))
+        buf = np.zeros((max(count.value, 1), rec))
+        _chk(L.lbmdem_probe_read(self._h, _vp(buf), len(buf), C.byref(count), C.byref(dropped)))
+        buf = buf[:count.value]
+        out = dict(step=buf[:, 0].astype(np.int64), time=buf[:, 1].copy(), clock=buf[:, 2].copy(), dropped=int(dropped.value))
+        if off[1] >= 0: out["pressure_row"] = buf[:, off[1]:off[1] + self.lx].copy()
+        if off[2] >= 0: out["velocity_y"] = buf[:, off[2]].astype(np.int64)
+        if off[3] >= 0: out["velocity_row"] = buf[:, off[3]:off[3] + self.lx].copy()
+        if off[4] >= 0: out["point_pressure"] = buf[:, off[4]:(off[5] if off[5] >= 0 else rec)].copy()
+        if off[5] >= 0:
+            out["xgrainmax"], out["height"] = buf[:, off[5]].copy(), buf[:, off[5] + 1].copy()
+        return out
 
     def set_force_mode(self, mode):
         _chk(self._L.lbmdem_set_force_mode(self._h, int(mode)))

@@ -496,6 +496,7 @@ int lbmdem_destroy(lbmdem_handle* h) {
     if (h->obst[b]) (void)hipFree(h->obst[b]);
   }
   if (h->gbuf) (void)hipFree(h->gbuf);
+  lbmdem_probe_release(h);
   for (int b = 0; b < 2; ++b)
     for (int k = 0; k < 2; ++k)
       if (h->snap[b][k].xc) (void)hipFree(h->snap[b][k].xc);
@@ -741,6 +742,7 @@ int lbmdem_forces_fluid(lbmdem_handle* h) {
   } else
     launch_forces_fast(h->f[h->fcur], ob, h->L, gview(h), h->fscale12, h->fscale3, h->fhf, h->owner, h->stream);
   HIP_TRY(hipGetLastError());
+  if (h->probe.on) RC_TRY(lbmdem_probe_sample(h, ob));   // lbmdem_probe_enable: the sample of this fluid step
   return LBMDEM_OK;
 }
 
@@ -1179,6 +1181,7 @@ static ChainSnap chain_snapshot(const lbmdem_handle* h) {
   s.gathered = h->fs.gathered; s.gathered_next = h->fs.gathered_next;
   s.nbsteps = h->nbsteps; s.Mdx = h->cfg.Mdx; s.Mhy = h->cfg.Mhy;
   s.Mgx = h->cfg.Mgx; s.t = h->cfg.phys.t;
+  s.probe_seen = h->probe.seen; s.probe_issued = h->probe.issued;
   return s;
 }
 
@@ -1193,6 +1196,9 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   h->fs.gathered = s.gathered; h->fs.gathered_next = s.gathered_next;
   h->nbsteps = s.nbsteps; h->cfg.Mdx = s.Mdx; h->cfg.Mhy = s.Mhy;
   h->cfg.Mgx = s.Mgx; h->cfg.phys.t = s.t; h->L.Mgx = (real)s.Mgx;
+  // the samples issued behind the failed launch found the stop word: the ring holds what it held (chain_settle_impl sets its
+  // device counters to match), and the fluid steps since are counted again when they are repeated
+  h->probe.seen = s.probe_seen; h->probe.issued = s.probe_issued;
   // what the failed launch may have written on its way: slices of the next map's canvas, and -- by the tiles that did
   // finish -- their discs, in place. The map the next fluid step paints starts from a clean canvas again.
   const int b = 1 - s.ocur;
@@ -1222,6 +1228,7 @@ static int chain_settle_impl(lbmdem_handle* h, bool live, long* rewind) {
   const ChainSnap s = h->chain_pending[i];
   const std::vector<RunLogEntry> log(h->runlog.begin() + s.log_idx, h->runlog.end());
   chain_restore(h, s);
+  RC_TRY(lbmdem_probe_sync_counters(h));
   h->chain_pending.clear();
   // the multi-sub-step kernel stays off for this handle (lbmdem_set_dem_chain switches it back on, with a new census); its
   // lines hold the give-up marks of the tiles

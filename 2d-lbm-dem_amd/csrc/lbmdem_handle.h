@@ -50,6 +50,20 @@ struct ChainSnap {
   long nbsteps;
   double Mdx, Mhy;
   double Mgx, t;   // a vibrating handle's side wall and clock (lbmdem_set_vibration): with nbsteps, where its schedule stands
+  long probe_seen, probe_issued;   // the probe recorder's counts (ProbeState): the ring's write and drop counters follow from them
+};
+
+// The probe recorder (lbmdem_probe_*, lbm_probe.hip). Off unless lbmdem_probe_enable has set it up.
+struct ProbeState {
+  bool on = false;
+  int every = 1, capacity = 0, pressure_row = -1, npoints = 0;
+  long rec = 0;               // doubles per record
+  long off[6] = {0, -1, -1, -1, -1, -1};   // where each field starts in a record (lbmdem_probe_layout)
+  double* ring = nullptr;     // device [capacity][rec]
+  long long* ctr = nullptr;   // device {written, dropped} x 2 (k_probe_sample)
+  int* points = nullptr;      // device [npoints][2]
+  long seen = 0;              // fluid steps since lbmdem_probe_enable (every k-th is sampled)
+  long issued = 0;            // samples launched since the ring was last emptied: min(issued, capacity) are in it, the rest were dropped
 };
 
 struct lbmdem_handle {
@@ -156,6 +170,7 @@ struct lbmdem_handle {
   long chain_recoveries = 0;
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
+  ProbeState probe;
   // KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM of lbmdem_run_scene: its "steps" line prints them (main.c:1885-1889)
   double scene_energies[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int force_mode = 0;
@@ -297,6 +312,11 @@ LBMDEM_INTERNAL int lbmdem_write_vtk_file(const char* path, int nx, int ny, cons
 LBMDEM_INTERNAL int lbmdem_verlet_build_lists(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_chain_settle(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);
+// the probe recorder (lbm_probe.hip): one sample behind the force kernels of a fluid step; the device counters of the ring
+// set to what probe.issued says (after chain_restore has taken it back); its buffers freed
+LBMDEM_INTERNAL int lbmdem_probe_sample(lbmdem_handle* h, const int* obst);
+LBMDEM_INTERNAL int lbmdem_probe_sync_counters(lbmdem_handle* h);
+LBMDEM_INTERNAL void lbmdem_probe_release(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {
   return h->obst_update && !h->vib && !h->dist && h->snap_ok[1 - h->ocur] && h->verlet_ok && h->verlet_tracks_positions &&

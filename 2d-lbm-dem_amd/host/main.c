@@ -15,6 +15,12 @@
  * with --dry. Single GPU only.
  * --run-stats: one more line on stderr at the end, `dem_chain: launches L substeps S recoveries R paints P`: how many
  * launches of the multi-sub-step DEM kernel covered how many sub-steps, how many had to be undone, how many rasterised.
+ * --probes FILE [--probe-every K] [--probe-row Y] [--probe-point X,Y ...]: the device-side probes (lbmdem_probe_*): every K-th
+ * fluid step (default every one) the library records the pressure profile of lattice row Y (default 2, write_densities'
+ * pressure_base row, main.c:522-541), the velocity profile, the pressure at the given nodes, xgrainmax and height; the records
+ * are fetched at every check_density line (where the run synchronises anyway) and at the end. FILE gets one line per record, `step time xgrainmax height` and
+ * the point pressures, and every record its own pressure_base%.6i.dat in the reference's format (main.c:495,532), numbered by
+ * the record. Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -39,6 +45,53 @@ static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_
 static char g_iddir[256] = "";
 static double g_comm_timeout = 180.;   /* seconds the ranks' transport may take to come up (--comm-timeout, LBMDEM_COMM_TIMEOUT) */
 static int g_devices[64], g_ndevices = 0;   /* --devices */
+
+/* --probes: the records the library holds are appended to the file, the ring is emptied */
+static lbmdem_handle* g_probe_handle = NULL;
+static FILE* g_probe_file = NULL;
+static long g_probe_records = 0;
+static int drain_probes(void) {
+  lbmdem_handle* h = g_probe_handle;
+  long count = 0, dropped = 0, off[6];
+  if (lbmdem_probe_read(h, NULL, 0, &count, &dropped) != LBMDEM_OK || lbmdem_probe_layout(h, off) != LBMDEM_OK) return -1;
+  if (count == 0) return 0;
+  const long rec = lbmdem_probe_record_doubles(h);
+  double* buf = (double*)malloc(sizeof(double) * (size_t)rec * (size_t)count);
+  if (!buf || lbmdem_probe_read(h, buf, count, &count, &dropped) != LBMDEM_OK) { free(buf); return -1; }
+  if (dropped > 0) fprintf(stderr, "--probes: %ld samples found the ring full and were dropped\n", dropped);
+  lbmdem_config cfg;
+  if (lbmdem_get_config(h, &cfg) != LBMDEM_OK) { free(buf); return -1; }
+  const long npoints = off[4] < 0 ? 0 : (off[5] < 0 ? rec : off[5]) - off[4];
+  for (long k = 0; k < count; ++k, ++g_probe_records) {
+    const double* R = buf + k * rec;
+    fprintf(g_probe_file, "%ld %le %le %le", (long)R[0], R[1], R[off[5]], R[off[5] + 1]);
+    for (long j = 0; j < npoints; ++j) fprintf(g_probe_file, " %le", R[off[4] + j]);
+    fprintf(g_probe_file, "\n");
+    if (off[1] >= 0) {
+      char name[64];
+      snprintf(name, sizeof name, "pressure_base%.6i.dat", (int)g_probe_records);
+      FILE* fp = fopen(name, "w");
+      if (!fp) { free(buf); return -1; }
+      const double pasxyz = 1. / cfg.lx;   /* main.c:495 */
+      for (int x = 0; x < cfg.lx; ++x) fprintf(fp, "%le %le\n", x * pasxyz, R[off[1] + x]);   /* main.c:532 */
+      fclose(fp);
+    }
+  }
+  fflush(g_probe_file);
+  free(buf);
+  return 0;
+}
+/* The console lines of lbmdem_run_scene, as it prints them itself. The ring is emptied at check_density's line only
+ * (main.c:1259): there the library has just synchronised for the serial density sum, so the read costs no stop of its own;
+ * the "steps" line is printed without one and is left alone. check_density's line comes when s % npDEM == 0 && s % 400 == 0,
+ * i.e. every 400 / gcd(npDEM, 400) fluid steps, 400 at the most: PROBE_RING_RECORDS holds them all for any --probe-every. */
+#define PROBE_RING_RECORDS 512
+static void say_and_drain(void* user, const char* line) {
+  (void)user;
+  fputs(line, stdout);
+  if (strncmp(line, "Iteration Number", 16) != 0) return;
+  if (drain_probes() != 0) { fprintf(stderr, "probe_read: %s\n", lbmdem_last_error()); exit(EXIT_FAILURE); }
+}
 
 static int share_id(unsigned char* id) {
   char path[320], tmp[340];
@@ -105,7 +158,7 @@ static int check_decomposition(int argc, char** argv, int gpus) {
 }
 
 int main(int argc, char** argv) {
-  int gpus = 1;
+  int gpus = 1, probes = 0;
   if (getenv("LBMDEM_COMM_TIMEOUT")) g_comm_timeout = atof(getenv("LBMDEM_COMM_TIMEOUT"));
   for (int a = 1; a < argc; ++a) {
     if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[a + 1]);
@@ -113,6 +166,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--dry")) g_dry = 1;
     if (!strcmp(argv[a], "--vib")) g_vib = 1;
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
+    if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--comm-timeout") && a + 1 < argc) g_comm_timeout = atof(argv[a + 1]);
     if (!strcmp(argv[a], "--devices") && a + 1 < argc) {
       for (const char* p = argv[a + 1]; *p && g_ndevices < 64;) {
@@ -128,6 +182,7 @@ int main(int argc, char** argv) {
   if (g_ndevices > 0 && g_ndevices < gpus) { fprintf(stderr, "--devices names %d devices for %d ranks\n", g_ndevices, gpus); return EXIT_FAILURE; }
   if (g_dry && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dry is a single-GPU mode (the strips exist for the fluid)\n"); return EXIT_FAILURE; }
   if (g_vib && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--vib is a single-GPU mode (vibrating walls are not available on strips)\n"); return EXIT_FAILURE; }
+  if (probes && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--probes is a single-GPU mode (the probes are not available on strips)\n"); return EXIT_FAILURE; }
   if (gpus <= 1) return run(argc, argv);
   g_world = gpus; g_use_comm = 1;
   { /* every strip must be at least one margin wide (lbmdem_dist_enable would refuse on the ranks whose strip is one
@@ -238,6 +293,8 @@ static int run(int argc, char** argv) {
   const char* sample = NULL;
   const char *ckpt_out = NULL, *ckpt_in = NULL;
   double vib_freq = -1., vib_amp = -1.;   /* --vib-freq, --vib-amp (negative: the reference's initialisers) */
+  const char* probe_path = NULL;          /* --probes */
+  int probe_every = 1, probe_row = 2, probe_points[2 * LBMDEM_PROBE_MAX_POINTS], probe_npoints = 0;
   /* device-resident kernel arguments: ~1.2 us less per launch (the HIP runtime reads this when it
    * initialises, i.e. at the first lbmdem_* call below); an explicit setting of the caller wins */
   setenv("HIP_FORCE_DEV_KERNARG", "1", 0);
@@ -260,11 +317,22 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
+    else if (!strcmp(argv[a], "--probes") && a + 1 < argc) probe_path = argv[++a];
+    else if (!strcmp(argv[a], "--probe-every") && a + 1 < argc) probe_every = atoi(argv[++a]);
+    else if (!strcmp(argv[a], "--probe-row") && a + 1 < argc) probe_row = atoi(argv[++a]);
+    else if (!strcmp(argv[a], "--probe-point") && a + 1 < argc) {
+      int px = 0, py = 0;
+      if (probe_npoints >= LBMDEM_PROBE_MAX_POINTS || sscanf(argv[++a], "%d,%d", &px, &py) != 2) {
+        fprintf(stderr, "--probe-point X,Y: a lattice node, at most %d of them\n", LBMDEM_PROBE_MAX_POINTS);
+        return EXIT_FAILURE;
+      }
+      probe_points[2 * probe_npoints] = px; probe_points[2 * probe_npoints + 1] = py; ++probe_npoints;
+    }
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --probes FILE --probe-every K --probe-row Y --probe-point X,Y]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   SAY("Opening file : %s\n", sample);
@@ -364,10 +432,25 @@ static int run(int argc, char** argv) {
   scene.duration = duration;
   lbmdem_scene_result done;
   memset(&done, 0, sizeof done);
+  if (probe_path) {
+    lbmdem_probe_config pc;
+    memset(&pc, 0, sizeof pc);
+    pc.every = probe_every; pc.capacity = PROBE_RING_RECORDS; pc.pressure_row = probe_row; pc.velocity_row = 1;
+    pc.npoints = probe_npoints; pc.points = probe_points; pc.grain_extent = 1;
+    DIE(lbmdem_probe_enable(h, &pc), "probe_enable");
+    g_probe_file = fopen(probe_path, "w");
+    if (!g_probe_file) { perror(probe_path); return EXIT_FAILURE; }
+    g_probe_handle = h;
+    scene.say = say_and_drain;
+  }
   if (max_steps < 0 || max_steps > nbsteps)
     DIE(lbmdem_run_scene(h, comm, max_steps < 0 ? LONG_MAX : max_steps - nbsteps, &scene, &done), "run_scene");
   nbsteps += done.steps_done;
   DIE(lbmdem_sync(h), "sync");
+  if (probe_path) {
+    DIE(drain_probes(), "probe_read");
+    fclose(g_probe_file);
+  }
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (ckpt_out) {
     if (comm) DIE(lbmdem_comm_sync_carries(h, comm), "comm_sync_carries");

@@ -197,6 +197,47 @@ typedef struct lbmdem_scene_result {
 int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm /* NULL: one domain */, long n, const lbmdem_scene* sc,
                      lbmdem_scene_result* res /* may be NULL */);
 
+/* Device-side probes: the field diagnostics the reference has routines for but never calls, recorded
+ * on the device every `every`-th fluid step without the host taking part, and fetched afterwards. A sample is taken right
+ * after forces_fluid of a fluid step (main.c:1710-1718), before that renderScene's list rebuild and DEM sub-step: it sees f
+ * after collision_streaming, obst as obst_construction built it in this step, the grains as the sub-step before left them.
+ * Fluid steps 0, every, 2 every, ... counted from lbmdem_probe_enable are sampled -- in lbmdem_lbm_step, lbmdem_run,
+ * lbmdem_run_scene, and by lbmdem_forces_fluid when the phases are called one by one. One record, all doubles, in this order
+ * (reference arithmetic, same association):
+ *   step, time, clock       the counter s, s * dt, and a vibrating handle's clock t (else 0)
+ *   pressure_row[lx]        row y = pressure_row (the reference uses 2) of write_densities' pressure_base file, main.c:524-539:
+ *                           P = 0.; P += f[x][y][i] for i = 0..8; (1./3.) * rho_moy * (P - 1.) where obst < 0, else 0.0
+ *   velocity_y              the row of velocity_profile, y = (int)((g[0].x2 - Mby) / dx) (main.c:1658), clamped into
+ *                           [0, ly-1] (the reference does not clamp) ...
+ *   velocity_row[lx]        ... and its values, main.c:1660-1672: g[obst].v2 / c on a grain, else u_y / d_loc of the node
+ *   point_pressure[npoints] `pressures` (main.c:1685-1691) at the given nodes: (f0 + ... + f8 - rho_moy) * c_squ where
+ *                           obst == -1, else 0.
+ *   xgrainmax, height       max (x1 + r), max (x2 + r) over the grains (write_DEM, main.c:400-405); 0 if none is positive
+ * lbmdem_probe_layout gives where each of these six starts in a record (-1: switched off). The ring holds `capacity`
+ * records; when it is full further samples are dropped and counted, never overwritten and never waited for, until
+ * lbmdem_probe_read has emptied it. lbmdem_probe_read settles and synchronises the handle, copies the records (oldest
+ * first), reports how many samples were dropped since the last read, and empties the ring; out = NULL only reports the
+ * counts; a buffer of fewer than *count records is refused. Off by default: then nothing is launched or allocated.
+ * LBMDEM_EINVAL: on a strip of a decomposition or with distributed grains (and lbmdem_dist_enable on a probing handle),
+ * in the single-precision library, for a point or pressure_row outside the lattice, for more than
+ * LBMDEM_PROBE_MAX_POINTS points, and when capacity x record size exceeds 1 GiB. Checkpoints do not carry probes: a loaded
+ * handle has none. */
+#define LBMDEM_PROBE_MAX_POINTS 64
+typedef struct lbmdem_probe_config {
+  int every;          /* sample every k-th fluid step, k >= 1 */
+  int capacity;       /* records the device ring holds */
+  int pressure_row;   /* y of the pressure profile (the reference uses 2); < 0: off */
+  int velocity_row;   /* 1: the profile of main.c:1647-1676; 0: off */
+  int npoints;        /* 0..64 */
+  const int* points;  /* npoints x (x, y) */
+  int grain_extent;   /* 1: xgrainmax, height */
+} lbmdem_probe_config;
+int lbmdem_probe_enable(lbmdem_handle* h, const lbmdem_probe_config* pc);   /* allocates; replaces an earlier set-up */
+int lbmdem_probe_disable(lbmdem_handle* h);
+long lbmdem_probe_record_doubles(lbmdem_handle* h);                         /* length of one record */
+int lbmdem_probe_layout(lbmdem_handle* h, long* offsets6);
+int lbmdem_probe_read(lbmdem_handle* h, double* out, long cap_records, long* count, long* dropped);
+
 /* EXTENSION, not in the reference as it runs: a lid. The reference's top-plate copies carry commented-out moving-wall
  * terms (main.c:1129-1130: f[x][ly-1][3] = f[x-1][ly-2][7]; //-uw_h/6;  f[x][ly-1][5] = f[x+1][ly-2][1]; //+uw_h/6;
  * `uw_h` is not even declared). lbmdem_set_lid enables exactly those two terms with uw_h in lattice units (0 = off, the
