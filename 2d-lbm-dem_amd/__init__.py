@@ -147,6 +147,14 @@ def _open_library(LIB_PATH):
     L.lbmdem_download_grain_pressure.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_download_vtk_fields.argtypes = [C.c_void_p] + [C.c_void_p] * 5
     L.lbmdem_write_vtk.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_set_async_output.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_write_vtk_async.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_output_drain.argtypes = [C.c_void_p]
+    L.lbmdem_output_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_vtk_image_bytes.argtypes = [C.c_int, C.c_int]
+    L.lbmdem_vtk_image_bytes.restype = C.c_size_t
+    L.lbmdem_write_vtk_image.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.lbmdem_download_vtk_image.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_set_diagnostics.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_download_grain_table.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_write_dem.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
@@ -227,6 +235,20 @@ def write_vtk_fields(directory, nFile, lx, ly, fields11):
     """the five VTK files of write_vtk (main.c:237-338) from merged lattice-sized fields (LbmDem.vtk_place_owned)"""
     f = np.ascontiguousarray(fields11, dtype=np.float32)
     _chk(load_library().lbmdem_write_vtk_fields(os.fsencode(directory), int(nFile), int(lx), int(ly), _vp(f)))
+
+
+def vtk_image_bytes(lx, ly):
+    """size of a frame image: the five VTK payloads as the files hold them, back to back (44 bytes per node)"""
+    return int(load_library().lbmdem_vtk_image_bytes(int(lx), int(ly)))
+
+
+def write_vtk_image(directory, nFile, lx, ly, image):
+    """the five VTK files of write_vtk from a frame image (LbmDem.vtk_image): big-endian float32, grain_pressure[ly][lx],
+    grain_velocity[ly][lx][3], grain_acceleration[ly][lx][3], fluid_pressure[ly][lx], fluid_velocity[ly][lx][3]. Host only."""
+    buf = np.frombuffer(image, dtype=np.uint8) if not isinstance(image, np.ndarray) else np.ascontiguousarray(image).view(np.uint8).reshape(-1)
+    if buf.size != 44 * max(int(lx), 0) * max(int(ly), 0):
+        raise LbmDemError(-1, f"write_vtk_image: the image of a {lx} x {ly} lattice has {44 * int(lx) * int(ly)} bytes, not {buf.size}")
+    _chk(load_library().lbmdem_write_vtk_image(os.fsencode(directory), int(nFile), int(lx), int(ly), _vp(buf)))
 
 
 def exported_symbols():
@@ -561,6 +583,34 @@ class LbmDem:
     def write_vtk(self, directory=".", nFile=0):
         """write_vtk (main.c:237-338): five binary legacy-VTK files, byte-identical to the reference's."""
         _chk(self._L.lbmdem_write_vtk(self._h, os.fsencode(directory), int(nFile)))
+
+    def set_async_output(self, frames=2):
+        """Frames in the background: `frames` slots (1..4) of device staging + pinned host memory, a copy stream and one writer
+        thread; 0 switches it off again (drains first). While on, run_scene queues its VTK frames instead of writing them."""
+        _chk(self._L.lbmdem_set_async_output(self._h, int(frames)))
+
+    def write_vtk_async(self, directory=".", nFile=0):
+        """write_vtk without the wait: one snapshot kernel on the step stream, then copy and file I/O behind the run's back.
+        Same files byte for byte once output_drain() has returned. Waits for a free slot when all are in flight."""
+        _chk(self._L.lbmdem_write_vtk_async(self._h, os.fsencode(directory), int(nFile)))
+
+    def output_drain(self):
+        """returns when every queued frame is on disk; raises the writer's first failure since the last report"""
+        _chk(self._L.lbmdem_output_drain(self._h))
+
+    def output_stats(self):
+        """dict: frames queued / written / failed, calls that waited for a slot; ms the caller waited for a slot, the writer
+        waited for copies, the writer spent in file I/O, the caller spent in output_drain"""
+        c = np.zeros(4, np.int64); m = np.zeros(4)
+        _chk(self._L.lbmdem_output_stats(self._h, _vp(c), _vp(m)))
+        return dict(queued=int(c[0]), written=int(c[1]), failed=int(c[2]), slot_waits=int(c[3]), ms_slot_wait=float(m[0]),
+                    ms_copy_wait=float(m[1]), ms_io=float(m[2]), ms_drain=float(m[3]))
+
+    def vtk_image(self):
+        """the frame image of the present state (the snapshot kernel alone, synchronously): bytes-like uint8[44 * lx * ly]"""
+        out = np.zeros(44 * self.lx * self.ly, np.uint8)
+        _chk(self._L.lbmdem_download_vtk_image(self._h, _vp(out)))
+        return out
 
     def vtk_fields(self):
         nx = self.cfg.x_end - self.cfg.x_begin

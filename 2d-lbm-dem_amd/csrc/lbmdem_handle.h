@@ -14,7 +14,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <condition_variable>
+#include <deque>
+#include <mutex>
 #include <new>
+#include <thread>
 #include <vector>
 
 #define REF_PI 3.14159265358979 /* main.c:42 */
@@ -64,6 +68,37 @@ struct ProbeState {
   int* points = nullptr;      // device [npoints][2]
   long seen = 0;              // fluid steps since lbmdem_probe_enable (every k-th is sampled)
   long issued = 0;            // samples launched since the ring was last emptied: min(issued, capacity) are in it, the rest were dropped
+};
+
+// Frames written in the background (lbmdem_set_async_output, lbmdem_output.hip). A frame is snapshotted on the handle's
+// stream into its slot's device staging (k_vtk_frame: the image the files hold), copied to the slot's pinned buffer on the
+// copy stream behind an event, and written by the writer thread once the copy's event has completed. A slot is free again
+// when its files are closed: staging and pinned buffer are never overwritten while anything reads them. Does not exist
+// while the feature is off.
+struct AsyncSlot {
+  void* staging = nullptr;   // device, image_bytes
+  void* pinned = nullptr;    // host, image_bytes
+  hipEvent_t snapped = nullptr, copied = nullptr;
+  bool busy = false;         // (under AsyncOut::mu)
+  char dir[4096];
+  int nfile = 0;
+};
+struct AsyncOut {
+  int frames = 0, lx = 0, ly = 0, device = 0;
+  size_t image_bytes = 0;
+  AsyncSlot slot[LBMDEM_ASYNC_MAX_FRAMES];
+  hipStream_t copy_stream = nullptr;
+  std::thread writer;
+  std::mutex mu;
+  std::condition_variable cv_job, cv_free;   // writer: a job or quit; callers: a slot freed / a frame finished
+  std::deque<int> jobs;                      // slots in the order they were queued
+  bool quit = false;
+  int pending = 0;                           // queued and not yet on disk
+  // the first failure of the writer since the last one was reported (the writer never touches the callers' error text)
+  int err_code = 0;
+  char err_msg[4400];
+  long queued = 0, written = 0, failed = 0, slot_waits = 0;
+  double ms_slot_wait = 0, ms_copy_wait = 0, ms_io = 0, ms_drain = 0;
 };
 
 struct lbmdem_handle {
@@ -171,6 +206,7 @@ struct lbmdem_handle {
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
   ProbeState probe;
+  AsyncOut* aout = nullptr;   // null: frames are written synchronously (the default)
   // KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM of lbmdem_run_scene: its "steps" line prints them (main.c:1885-1889)
   double scene_energies[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int force_mode = 0;
@@ -317,6 +353,10 @@ LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_probe_sample(lbmdem_handle* h, const int* obst);
 LBMDEM_INTERNAL int lbmdem_probe_sync_counters(lbmdem_handle* h);
 LBMDEM_INTERNAL void lbmdem_probe_release(lbmdem_handle* h);
+// background frames (lbmdem_output.hip): every queued frame on disk, the writer joined, everything freed (-> off); the
+// writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
+LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);
+LBMDEM_INTERNAL int lbmdem_async_report(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {
   return h->obst_update && !h->vib && !h->dist && h->snap_ok[1 - h->ocur] && h->verlet_ok && h->verlet_tracks_positions &&

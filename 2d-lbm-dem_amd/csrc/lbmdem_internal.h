@@ -305,6 +305,10 @@ void launch_vtk_fields(const real* f, const int* obst, const LatticeView& L, con
                        real rho_moy, float* grain_pressure, float* grain_velocity,
                        float* grain_acceleration, float* fluid_pressure, float* fluid_velocity,
                        hipStream_t st);
+// lbm_frame.hip: the same five fields as one image in file byte order (big-endian float32, the payloads back to back, 44
+// bytes per node), owned rows only
+void launch_vtk_frame(const real* f, const int* obst, const LatticeView& L, const real* gp, const real* v1, const real* v2,
+                      const real* a1, const real* a2, real rho_moy, void* image_be, hipStream_t st);
 
 // dem_kernels.hip
 struct VerletDevice {

@@ -1,8 +1,13 @@
 // lbmdem_output.hip -- the reference's file outputs over the C ABI: write_vtk (main.c:237-338 + visit_writer's binary
 // rectilinear path), write_DEM (main.c:340-438: DEM%06d.dat, stats.data), write_forces (main.c:440-478), the per-grain
-// diagnostics table they print, and the merged-strip forms of the VTK writer.
+// diagnostics table they print, the merged-strip forms of the VTK writer, and the frames written in the background
+// (lbmdem_set_async_output: snapshot kernel, copy stream, writer thread).
 
 #include "lbmdem_handle.h"
+
+#include <chrono>
+#include <errno.h>
+#include <system_error>
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -350,6 +355,303 @@ int lbmdem_write_vtk_fields(const char* dir, int nfile, int lx, int ly, const fl
     const int rc = lbmdem_write_vtk_file(path, lx, ly, names[k], dims[k], data[k]);
     if (rc != LBMDEM_OK) return rc;
   }
+  return LBMDEM_OK;
+}
+
+// ---- frames in the background -------------------------------------------------------------------------------------------
+// The image: the five payloads as the files hold them, back to back (k_vtk_frame, lbm_frame.hip).
+
+static const char* const IMAGE_NAMES[5] = {"grain_pressure", "grain_velocity", "grain_acceleration", "fluid_pressure", "fluid_velocity"};
+static const int IMAGE_DIMS[5] = {1, 3, 3, 1, 3};
+
+// the five files from an image; on failure the text goes to `msg`, not to the thread's error text (the writer thread
+// reports through its job)
+static int write_image_files(const char* dir, int nfile, int nx, int ny, const void* image, char* msg, size_t msglen) try {
+  const size_t cnt = (size_t)nx * ny;
+  const unsigned char* at = static_cast<const unsigned char*>(image);
+  // coordinates: as lbmdem_write_vtk_file
+  const float pas = 1. / nx;
+  std::vector<float> xs(nx), ys(ny);
+  for (int i = 0; i < nx; ++i) xs[i] = i * pas;
+  for (int i = 0; i < ny; ++i) ys[i] = i * pas;
+  const float z = 0.f;
+  for (int k = 0; k < 5; ++k) {
+    char path[4200];
+    snprintf(path, sizeof path, "%s/%s_%.6i.vtk", (dir && *dir) ? dir : ".", IMAGE_NAMES[k], nfile);  // main.c:241-249
+    FILE* fp = fopen(path, "w+");
+    if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing", path); return LBMDEM_EINVAL; }
+    fprintf(fp, "# vtk DataFile Version 2.0\nWritten using VisIt writer\nBINARY\n");
+    fprintf(fp, "DATASET RECTILINEAR_GRID\nDIMENSIONS %d %d 1\n", nx, ny);
+    fprintf(fp, "X_COORDINATES %d float\n", nx); put_be(fp, xs.data(), nx);
+    fprintf(fp, "Y_COORDINATES %d float\n", ny); put_be(fp, ys.data(), ny);
+    fprintf(fp, "Z_COORDINATES 1 float\n"); put_be(fp, &z, 1);
+    fprintf(fp, "CELL_DATA %d\nPOINT_DATA %d\n", (nx - 1) * (ny - 1), nx * ny);
+    if (IMAGE_DIMS[k] == 1) fprintf(fp, "SCALARS %s float\nLOOKUP_TABLE default\n", IMAGE_NAMES[k]);
+    else fprintf(fp, "VECTORS %s float\n", IMAGE_NAMES[k]);
+    const size_t bytes = cnt * 4 * IMAGE_DIMS[k];
+    const bool short_write = fwrite(at, 1, bytes, fp) != bytes;
+    const int err = errno;
+    if (fclose(fp) != 0 || short_write) {
+      snprintf(msg, msglen, "writing '%s' failed: %s", path, strerror(short_write ? err : errno));
+      return LBMDEM_EINVAL;
+    }
+    at += bytes;
+  }
+  return LBMDEM_OK;
+} catch (const std::bad_alloc&) {
+  snprintf(msg, msglen, "host memory allocation failed");
+  return LBMDEM_ENOMEM;
+}
+
+static inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the writer thread: slot by slot in the order they were queued -- wait for the copy, write the files, free the slot
+static void async_writer(AsyncOut* a) {
+  (void)hipSetDevice(a->device);
+  for (;;) {
+    int s;
+    {
+      std::unique_lock<std::mutex> lk(a->mu);
+      a->cv_job.wait(lk, [&] { return a->quit || !a->jobs.empty(); });
+      if (a->jobs.empty()) return;
+      s = a->jobs.front();
+      a->jobs.pop_front();
+    }
+    AsyncSlot& S = a->slot[s];
+    char msg[sizeof a->err_msg];
+    int code = LBMDEM_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipError_t e = hipEventSynchronize(S.copied);
+    const double ms_copy = ms_since(t0);
+    const auto t1 = std::chrono::steady_clock::now();
+    if (e != hipSuccess) {
+      snprintf(msg, sizeof msg, "frame %d: the copy to host memory failed: %s", S.nfile, hipGetErrorString(e));
+      code = LBMDEM_EHIP;
+    } else {
+      code = write_image_files(S.dir, S.nfile, a->lx, a->ly, S.pinned, msg, sizeof msg);
+    }
+    const double ms_io = ms_since(t1);
+    {
+      std::lock_guard<std::mutex> lk(a->mu);
+      a->ms_copy_wait += ms_copy;
+      a->ms_io += ms_io;
+      if (code == LBMDEM_OK) a->written++;
+      else {
+        a->failed++;
+        if (!a->err_code) { a->err_code = code; memcpy(a->err_msg, msg, sizeof msg); }
+      }
+      S.busy = false;
+      a->pending--;
+    }
+    a->cv_free.notify_all();
+  }
+}
+
+static void async_free(AsyncOut* a) {
+  for (AsyncSlot& S : a->slot) {
+    if (S.staging) (void)hipFree(S.staging);
+    if (S.pinned) (void)hipHostFree(S.pinned);
+    if (S.snapped) (void)hipEventDestroy(S.snapped);
+    if (S.copied) (void)hipEventDestroy(S.copied);
+  }
+  if (a->copy_stream) (void)hipStreamDestroy(a->copy_stream);
+  delete a;
+}
+
+void lbmdem_async_release(lbmdem_handle* h) {
+  AsyncOut* a = h->aout;
+  if (!a) return;
+  {
+    std::unique_lock<std::mutex> lk(a->mu);
+    a->cv_free.wait(lk, [&] { return a->pending == 0; });
+    a->quit = true;
+  }
+  a->cv_job.notify_all();
+  if (a->writer.joinable()) a->writer.join();
+  async_free(a);
+  h->aout = nullptr;
+}
+
+int lbmdem_async_report(lbmdem_handle* h) {
+  AsyncOut* a = h->aout;
+  if (!a) return LBMDEM_OK;
+  char msg[sizeof a->err_msg];
+  int code;
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    code = a->err_code;
+    if (code == LBMDEM_OK) return LBMDEM_OK;
+    memcpy(msg, a->err_msg, sizeof msg);
+    a->err_code = LBMDEM_OK;
+  }
+  return fail(code, "background frame writer: %s", msg);
+}
+
+#define CHECK_WHOLE_LATTICE(h, who)                                                                                    \
+  do {                                                                                                                 \
+    const LatticeView& L_ = (h)->L;                                                                                    \
+    if (L_.xo0 != 0 || L_.xo1 != L_.lx || L_.gx0 != 0 || (h)->dist)                                                    \
+      return fail(LBMDEM_EINVAL, who " needs the whole lattice and all grains on this handle (not a strip of a "       \
+                                     "decomposition, no distributed grains): use lbmdem_comm_write_vtk there");        \
+  } while (0)
+
+static void launch_frame(lbmdem_handle* h, void* image_dev) {
+  const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
+  const Kin& K = h->kin[h->kcur];
+  launch_vtk_frame(h->f[h->fcur], ob, h->L, h->gp, K.v1, K.v2, K.a1, K.a2, h->cfg.phys.rho_moy, image_dev, h->stream);
+}
+
+size_t lbmdem_vtk_image_bytes(int lx, int ly) { return (lx > 0 && ly > 0) ? (size_t)44 * lx * ly : 0; }
+
+int lbmdem_write_vtk_image(const char* dir, int nfile, int lx, int ly, const void* image_be) {
+  if (!image_be || lx < 2 || ly < 2) return fail(LBMDEM_EINVAL, "bad lbmdem_write_vtk_image arguments");
+  char msg[4400];
+  const int rc = write_image_files(dir, nfile, lx, ly, image_be, msg, sizeof msg);
+  return rc == LBMDEM_OK ? rc : fail(rc, "%s", msg);
+}
+
+int lbmdem_download_vtk_image(lbmdem_handle* h, void* image_be) {
+  CHECK_H(h);
+  CHECK_NOT_SPLIT(h);
+  if (!image_be) return fail(LBMDEM_EINVAL, "null buffer");
+  CHECK_WHOLE_LATTICE(h, "lbmdem_download_vtk_image");
+  const size_t bytes = lbmdem_vtk_image_bytes(h->L.lx, h->L.ly);
+  void* tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, bytes));
+  launch_frame(h, tmp);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(image_be, tmp, bytes, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  (void)hipFree(tmp);
+  HIP_TRY(e);
+  return LBMDEM_OK;
+}
+
+// The request is carried out first (an earlier set-up is drained, joined and freed; the new one made); a failure of the old
+// writer that nobody has been told about is what the call then returns.
+int lbmdem_set_async_output(lbmdem_handle* h, int frames) {
+  CHECK_H(h);
+  if (frames < 0 || frames > LBMDEM_ASYNC_MAX_FRAMES)
+    return fail(LBMDEM_EINVAL, "lbmdem_set_async_output: frames must be 0..%d, not %d", LBMDEM_ASYNC_MAX_FRAMES, frames);
+  if (frames > 0) CHECK_WHOLE_LATTICE(h, "lbmdem_set_async_output");
+  if (h->aout && h->aout->frames == frames) return LBMDEM_OK;
+  int old_code = LBMDEM_OK;
+  char old_msg[sizeof h->aout->err_msg];
+  if (h->aout) {
+    {
+      std::unique_lock<std::mutex> lk(h->aout->mu);
+      h->aout->cv_free.wait(lk, [&] { return h->aout->pending == 0; });
+      old_code = h->aout->err_code;
+      if (old_code != LBMDEM_OK) memcpy(old_msg, h->aout->err_msg, sizeof old_msg);
+    }
+    lbmdem_async_release(h);
+  }
+  if (frames > 0) {
+    AsyncOut* a = new (std::nothrow) AsyncOut;
+    if (!a) return fail(LBMDEM_ENOMEM, "host memory allocation failed");
+    a->frames = frames; a->lx = h->L.lx; a->ly = h->L.ly; a->device = h->cfg.device;
+    a->image_bytes = lbmdem_vtk_image_bytes(a->lx, a->ly);
+    hipError_t e = hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking);
+    for (int s = 0; s < frames && e == hipSuccess; ++s) {
+      AsyncSlot& S = a->slot[s];
+      e = hipMalloc(&S.staging, a->image_bytes);
+      if (e == hipSuccess) e = hipHostMalloc(&S.pinned, a->image_bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      const size_t bytes = a->image_bytes;
+      async_free(a);
+      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_output: %d frame slots of %zu bytes (device staging + pinned host memory each) "
+                                 "cannot be had: %s", frames, bytes, hipGetErrorString(e));
+    }
+    try {
+      a->writer = std::thread(async_writer, a);
+    } catch (const std::system_error&) {
+      async_free(a);
+      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_output: the writer thread cannot be started");
+    }
+    h->aout = a;
+  }
+  if (old_code != LBMDEM_OK) return fail(old_code, "background frame writer: %s", old_msg);
+  return LBMDEM_OK;
+}
+
+int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
+  CHECK_H(h);   // (a launch of k_dem_chain that gave up is undone and replayed here: nothing unconfirmed lies ahead of the snapshot)
+  AsyncOut* a = h->aout;
+  if (!a) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: async output is off (lbmdem_set_async_output)");
+  CHECK_NOT_SPLIT(h);
+  CHECK_WHOLE_LATTICE(h, "lbmdem_write_vtk_async");
+  RC_TRY(lbmdem_async_report(h));   // an earlier frame's failure: this call queues nothing
+  const char* d = (dir && *dir) ? dir : ".";
+  if (strlen(d) >= sizeof a->slot[0].dir) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: directory name too long");
+  int s = -1;
+  {
+    std::unique_lock<std::mutex> lk(a->mu);
+    auto free_slot = [&] { for (int k = 0; k < a->frames; ++k) if (!a->slot[k].busy) return k; return -1; };
+    if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop a frame
+      const auto t0 = std::chrono::steady_clock::now();
+      a->slot_waits++;
+      a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
+      a->ms_slot_wait += ms_since(t0);
+    }
+    a->slot[s].busy = true;
+  }
+  AsyncSlot& S = a->slot[s];
+  strcpy(S.dir, d);
+  S.nfile = nfile;
+  launch_frame(h, S.staging);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(S.snapped, h->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, a->image_bytes, hipMemcpyDeviceToHost, a->copy_stream);
+  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
+    { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
+    a->cv_free.notify_all();
+    HIP_TRY(e);
+  }
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    a->jobs.push_back(s);
+    a->pending++;
+    a->queued++;
+  }
+  a->cv_job.notify_one();
+  return LBMDEM_OK;
+}
+
+int lbmdem_output_drain(lbmdem_handle* h) {
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  AsyncOut* a = h->aout;
+  if (!a) return LBMDEM_OK;
+  {
+    std::unique_lock<std::mutex> lk(a->mu);
+    if (a->pending != 0) {
+      const auto t0 = std::chrono::steady_clock::now();
+      a->cv_free.wait(lk, [&] { return a->pending == 0; });
+      a->ms_drain += ms_since(t0);
+    }
+  }
+  return lbmdem_async_report(h);
+}
+
+int lbmdem_output_stats(lbmdem_handle* h, long* counts4, double* ms4) {
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  AsyncOut* a = h->aout;
+  long c[4] = {0, 0, 0, 0};
+  double m[4] = {0, 0, 0, 0};
+  if (a) {
+    std::lock_guard<std::mutex> lk(a->mu);
+    c[0] = a->queued; c[1] = a->written; c[2] = a->failed; c[3] = a->slot_waits;
+    m[0] = a->ms_slot_wait; m[1] = a->ms_copy_wait; m[2] = a->ms_io; m[3] = a->ms_drain;
+  }
+  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
   return LBMDEM_OK;
 }
 

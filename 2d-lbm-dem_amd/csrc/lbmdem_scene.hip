@@ -102,7 +102,7 @@ int lbmdem_scene_schedule(const lbmdem_config* cfg, long nbsteps0, long n, doubl
   return LBMDEM_OK;
 }
 
-int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
+static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
   CHECK_H(h);
   if (!sc || n < 0) return fail(LBMDEM_EINVAL, "bad argument");
   if (comm && !sc->fluid) return fail(LBMDEM_EINVAL, "a run without the fluid is a single-domain run (the strips exist for the fluid)");
@@ -152,7 +152,7 @@ int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_s
     }
     s = e + 1;
     if (cad.vtk(e)) {   // write_vtk sits inside `#ifdef _FLUIDE_` (main.c:1768-1770); nFile++ does not
-      if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
+      if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else if (h->aout) RC_TRY(lbmdem_write_vtk_async(h, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
       nfile++;
     }
     // (with strips the sub-step before was run by rank 0 on a full replica, lbmdem_comm_run: it holds the whole table)
@@ -177,6 +177,20 @@ int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_s
     res->last_density = density;
   }
   return LBMDEM_OK;
+}
+
+// With frames in the background (lbmdem_set_async_output) the loop's VTK events are only queued: the files of the schedule
+// exist when the call returns, so it drains first -- also when the loop ends early with an error, which is then the one
+// returned; otherwise a failure of the writer is.
+int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
+  const int rc = run_scene_loop(h, comm, n, sc, res);
+  if (!h || !h->aout) return rc;
+  if (rc != LBMDEM_OK) {   // keep the loop's error text: wait here, leave the writer's report to the next call
+    std::unique_lock<std::mutex> lk(h->aout->mu);
+    h->aout->cv_free.wait(lk, [&] { return h->aout->pending == 0; });
+    return rc;
+  }
+  return lbmdem_output_drain(h);
 }
 
 }  // extern "C"

@@ -356,6 +356,37 @@ int lbmdem_download_vtk_fields(lbmdem_handle* h, float* grain_pressure, float* g
  * <dir>/{grain_pressure,grain_velocity,grain_acceleration,fluid_pressure,fluid_velocity}_NNNNNN.vtk,
  * byte-identical to the reference's. Single-domain handles only. */
 int lbmdem_write_vtk(lbmdem_handle* h, const char* dir, int nfile);
+/* The same five files, written in the background while the run goes on. lbmdem_set_async_output(h, frames), frames in
+ * 1..LBMDEM_ASYNC_MAX_FRAMES, sets up that many frame slots (device staging + pinned host memory of lbmdem_vtk_image_bytes
+ * each), a copy stream and one writer thread; 0 drains, joins and frees them (the default: nothing is allocated, no thread
+ * exists). lbmdem_write_vtk_async settles the handle like every writer, takes a free slot -- when none is free it waits for
+ * the writer: a frame is never dropped --, launches ONE kernel on the handle's stream that leaves the frame in the slot as the
+ * files hold it (the five payloads back to back, big-endian float32, 44 bytes per node: the "image"), queues the copy to
+ * pinned memory on the copy stream behind an event, hands the slot to the writer and returns without synchronising: the
+ * step stream is held for that kernel only, and what is stepped afterwards does not reach the frame. The files are those of
+ * lbmdem_write_vtk byte for byte. The writer reports nothing itself: its first failure (a directory that does not exist,
+ * a full disk) is returned, with its text as lbmdem_last_error, by the next lbmdem_write_vtk_async, lbmdem_output_drain or
+ * lbmdem_run_scene on the handle and is then forgotten (lbmdem_destroy drops it); the handle stays usable.
+ * lbmdem_output_drain returns when every queued frame is on disk and closed. On a handle with async output on,
+ * lbmdem_run_scene (comm = NULL) hands its VTK events to lbmdem_write_vtk_async and drains before it returns: its files exist
+ * when it returns, as before. write_DEM / write_forces stay synchronous. lbmdem_output_stats -- counts4: frames queued,
+ * written, failed, calls that had to wait for a slot; ms4: the caller waiting for a slot, the writer waiting for copies,
+ * the writer in file I/O, the caller in lbmdem_output_drain (all 0 while off).
+ * LBMDEM_EINVAL: frames outside 0..4, lbmdem_write_vtk_async while off, a strip of a decomposition or distributed grains
+ * (and lbmdem_dist_enable on a handle with async output on). LBMDEM_ENOMEM: the slots cannot be had (then the feature is
+ * off). Vibrating and probing handles and the single-precision library have it. Checkpoints do not carry the setting. */
+#define LBMDEM_ASYNC_MAX_FRAMES 4
+int lbmdem_set_async_output(lbmdem_handle* h, int frames);          /* 0: off (default) */
+int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_output_drain(lbmdem_handle* h);                          /* LBMDEM_OK at once while off */
+int lbmdem_output_stats(lbmdem_handle* h, long* counts4, double* ms4);
+/* Host only, no handle, no device: the size of an image (44 * lx * ly), and the five files from one -- the header of
+ * lbmdem_write_vtk's files, then each payload in one write straight from the image. */
+size_t lbmdem_vtk_image_bytes(int lx, int ly);
+int lbmdem_write_vtk_image(const char* dir, int nfile, int lx, int ly, const void* image_be);
+/* the image of the present state into a caller's host buffer of lbmdem_vtk_image_bytes (the snapshot kernel alone,
+ * synchronously; whole-lattice handles, async output on or off) */
+int lbmdem_download_vtk_image(lbmdem_handle* h, void* image_be);
 /* Contact diagnostics of the last DEM sub-step (what write_DEM prints, main.c:340-438). They are produced
  * in the sub-step that brings the step counter to a multiple of stepStrob = 4000 (main.c:142,1773), or in
  * every sub-step after lbmdem_set_diagnostics(h, 1). Table: 30 doubles per grain in the reference's struct
