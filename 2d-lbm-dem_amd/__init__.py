@@ -155,6 +155,11 @@ def _open_library(LIB_PATH):
     L.lbmdem_vtk_image_bytes.restype = C.c_size_t
     L.lbmdem_write_vtk_image.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.lbmdem_download_vtk_image.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_dem_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_set_async_dem.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_write_dem_async.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
+    L.lbmdem_output_stats_dem.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_write_dem_rows.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.lbmdem_set_diagnostics.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_download_grain_table.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_write_dem.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
@@ -249,6 +254,20 @@ def write_vtk_image(directory, nFile, lx, ly, image):
     if buf.size != 44 * max(int(lx), 0) * max(int(ly), 0):
         raise LbmDemError(-1, f"write_vtk_image: the image of a {lx} x {ly} lattice has {44 * int(lx) * int(ly)} bytes, not {buf.size}")
     _chk(load_library().lbmdem_write_vtk_image(os.fsencode(directory), int(nFile), int(lx), int(ly), _vp(buf)))
+
+
+DEM_ROW_DOUBLES = 28   # LBMDEM_DEM_ROW_DOUBLES
+
+
+def write_dem_rows(directory, nFile, rows, stats22, forces=True, lx=0, ly=0):
+    """DEM%06d.dat, one line appended to stats.data and (forces) DEM%06d.ps from a table's rows, (n, 28): r x1 x2 x3 v1 v2 v3
+    a1 a2 a3 fhf1 fhf2 fhf3 p s ESE fr ifr ice slip rw fm M11 M12 M21 M22 z zz, and the 22 numbers of the stats line. Host only."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    st = np.ascontiguousarray(stats22, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != DEM_ROW_DOUBLES or st.shape != (22,):
+        raise LbmDemError(-1, f"write_dem_rows: rows must be (n, {DEM_ROW_DOUBLES}) and stats22 (22,)")
+    _chk(load_library().lbmdem_write_dem_rows(os.fsencode(directory), int(nFile), rows.shape[0], _vp(rows), _vp(st),
+                                              int(bool(forces)), int(lx), int(ly)))
 
 
 def exported_symbols():
@@ -579,6 +598,36 @@ class LbmDem:
     def write_forces(self, directory=".", nFile=0):
         """write_forces (main.c:440-478): DEM%06d.ps, grains + one line per overlapping pair."""
         _chk(self._L.lbmdem_write_forces(self._h, os.fsencode(directory), int(nFile)))
+
+    def dem_stats(self):
+        """the 22 numbers of the stats.data line of the last table sub-step (main.c:428-434), computed on the device, bit-equal
+        to write_DEM's: time xfront xgrainmax height zmean energie_x energie_y energie_teta energie_cin N0..N5 energy_p SE WF IFR
+        INCE TSLIP TRW"""
+        out = np.zeros(22)
+        _chk(self._L.lbmdem_dem_stats(self._h, _vp(out)))
+        return out
+
+    def set_async_dem(self, slots=2):
+        """write_DEM / write_forces in the background: `slots` table slots (1..4) of device staging + pinned host memory; the
+        writer thread and copy stream are those of set_async_output. 0 switches it off again (writes what is queued first).
+        While on, run_scene queues its DEM events instead of writing them."""
+        _chk(self._L.lbmdem_set_async_dem(self._h, int(slots)))
+
+    def write_DEM_async(self, directory=".", nFile=0, forces=True):
+        """write_DEM (+ write_forces) without the files' wait: two kernels and 22 numbers back, then copy, formatting, pair search
+        and file I/O behind the run's back. Same files byte for byte once output_drain() has returned.
+        -> (KE, PE, SE, IFR, WF, INCE, TSLIP, TRW), as write_DEM"""
+        e = np.zeros(8)
+        _chk(self._L.lbmdem_write_dem_async(self._h, os.fsencode(directory), int(nFile), int(bool(forces)), _vp(e)))
+        return tuple(e)
+
+    def output_stats_dem(self):
+        """dict: DEM events queued / written / failed, calls that waited for a slot; ms the caller waited for a slot, the writer
+        waited for copies, the writer spent formatting and in file I/O, the caller waited for the 22 numbers"""
+        c = np.zeros(4, np.int64); m = np.zeros(4)
+        _chk(self._L.lbmdem_output_stats_dem(self._h, _vp(c), _vp(m)))
+        return dict(queued=int(c[0]), written=int(c[1]), failed=int(c[2]), slot_waits=int(c[3]), ms_slot_wait=float(m[0]),
+                    ms_copy_wait=float(m[1]), ms_io=float(m[2]), ms_stats_wait=float(m[3]))
 
     def write_vtk(self, directory=".", nFile=0):
         """write_vtk (main.c:237-338): five binary legacy-VTK files, byte-identical to the reference's."""

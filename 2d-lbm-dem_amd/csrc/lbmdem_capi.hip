@@ -489,7 +489,7 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
 int lbmdem_destroy(lbmdem_handle* h) {
   if (!h) return LBMDEM_OK;
   (void)hipSetDevice(h->cfg.device);
-  lbmdem_async_release(h);   // every queued frame on disk first
+  lbmdem_async_release(h);   // every queued frame and table on disk first
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   chain_forget_stream(h->cfg.device, h->stream);
   for (int b = 0; b < 2; ++b) {

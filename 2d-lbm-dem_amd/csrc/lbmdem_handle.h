@@ -83,22 +83,44 @@ struct AsyncSlot {
   char dir[4096];
   int nfile = 0;
 };
+// A write_DEM / write_forces event written in the background (lbmdem_set_async_dem): the same pipeline with the table's rows
+// (k_dem_frame, lbm_demframe.hip) in place of the image, and the stats.data line as it stood when the event was queued.
+struct AsyncDemSlot {
+  double* staging = nullptr;   // device, [n][LBMDEM_DEM_ROW_DOUBLES]
+  double* pinned = nullptr;    // host, the same
+  hipEvent_t snapped = nullptr, copied = nullptr;
+  bool busy = false;           // (under AsyncOut::mu)
+  char dir[4096];
+  int nfile = 0, with_forces = 0;
+  double stats22[22];
+};
+// The counters of lbmdem_output_stats / lbmdem_output_stats_dem: each feature has its own set, reset when its slots change
+struct AsyncCounters {
+  long queued = 0, written = 0, failed = 0, slot_waits = 0;
+  double ms_slot_wait = 0, ms_copy_wait = 0, ms_io = 0, ms_last = 0;   // ms_last: frames -- the caller in lbmdem_output_drain; tables -- the caller waiting for the 22 numbers
+};
+// One per handle while either feature is on: ONE copy stream, ONE writer thread, ONE queue (strictly first in, first out:
+// the lines of stats.data land in call order).
 struct AsyncOut {
   int frames = 0, lx = 0, ly = 0, device = 0;
   size_t image_bytes = 0;
   AsyncSlot slot[LBMDEM_ASYNC_MAX_FRAMES];
+  int dem_slots = 0, n = 0;                  // lbmdem_set_async_dem; grains
+  AsyncDemSlot dslot[LBMDEM_ASYNC_MAX_DEM];
+  double* dem_scratch = nullptr;             // device: the addends of the ten sums [10][n], then the 22 numbers (k_dem_stats)
+  double* dem_stats_host = nullptr;          // pinned [22]
   hipStream_t copy_stream = nullptr;
   std::thread writer;
   std::mutex mu;
   std::condition_variable cv_job, cv_free;   // writer: a job or quit; callers: a slot freed / a frame finished
-  std::deque<int> jobs;                      // slots in the order they were queued
+  std::deque<int> jobs;                      // in the order they were queued: frame slot s as s, table slot s as LBMDEM_ASYNC_MAX_FRAMES + s
   bool quit = false;
   int pending = 0;                           // queued and not yet on disk
   // the first failure of the writer since the last one was reported (the writer never touches the callers' error text)
   int err_code = 0;
+  bool err_dem = false;                      // ... was a table's
   char err_msg[4400];
-  long queued = 0, written = 0, failed = 0, slot_waits = 0;
-  double ms_slot_wait = 0, ms_copy_wait = 0, ms_io = 0, ms_drain = 0;
+  AsyncCounters fc, dc;                      // frames, tables
 };
 
 struct lbmdem_handle {
@@ -206,7 +228,7 @@ struct lbmdem_handle {
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
   ProbeState probe;
-  AsyncOut* aout = nullptr;   // null: frames are written synchronously (the default)
+  AsyncOut* aout = nullptr;   // null: frames and tables are written synchronously (the default)
   // KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM of lbmdem_run_scene: its "steps" line prints them (main.c:1885-1889)
   double scene_energies[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int force_mode = 0;
@@ -353,9 +375,11 @@ LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_probe_sample(lbmdem_handle* h, const int* obst);
 LBMDEM_INTERNAL int lbmdem_probe_sync_counters(lbmdem_handle* h);
 LBMDEM_INTERNAL void lbmdem_probe_release(lbmdem_handle* h);
-// background frames (lbmdem_output.hip): every queued frame on disk, the writer joined, everything freed (-> off); the
+// background frames and tables (lbmdem_output.hip): every queued job on disk, the writer joined, everything freed (-> off); the
 // writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);
+static inline bool async_frames_on(const lbmdem_handle* h) { return h->aout && h->aout->frames > 0; }
+static inline bool async_dem_on(const lbmdem_handle* h) { return h->aout && h->aout->dem_slots > 0; }
 LBMDEM_INTERNAL int lbmdem_async_report(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {

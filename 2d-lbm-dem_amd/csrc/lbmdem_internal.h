@@ -309,6 +309,20 @@ void launch_vtk_fields(const real* f, const int* obst, const LatticeView& L, con
 // bytes per node), owned rows only
 void launch_vtk_frame(const real* f, const int* obst, const LatticeView& L, const real* gp, const real* v1, const real* v2,
                       const real* a1, const real* a2, real rho_moy, void* image_be, hipStream_t st);
+// lbm_demframe.hip (double build): the table of a write_DEM event on the device. What the kernels read -- the arrays
+// lbmdem_download_grain_table copies, and fhf -- and the scalars of the derived columns:
+struct DemTableView {
+  int n;
+  Kin K;
+  const real *r, *m, *It, *gp, *diag, *fr, *ice, *slip, *rw, *fhf;   // diag: [8][n] reals, then [2][n] ints z zz; fhf: [3][n]
+  real G, dt, dt2, kg, kt;
+};
+constexpr int DEM_ROW = 28;            // doubles per grain in the rows (LBMDEM_DEM_ROW_DOUBLES): DEM%06d.dat's columns after the index, then zz
+constexpr int DEM_STATS_CHAINS = 10;   // the serial sums of the stats.data line
+// rows [n][DEM_ROW] (null: none) and the addends of the ten sums, [10][n]
+void launch_dem_frame(const DemTableView& T, double* rows, double* addends, hipStream_t st);
+// the 22 numbers of the stats.data line from the table and the addends ([0], the time, is left 0 for the host)
+void launch_dem_stats(const DemTableView& T, const double* addends, double* stats22, hipStream_t st);
 
 // dem_kernels.hip
 struct VerletDevice {

@@ -1,7 +1,7 @@
 // lbmdem_output.hip -- the reference's file outputs over the C ABI: write_vtk (main.c:237-338 + visit_writer's binary
 // rectilinear path), write_DEM (main.c:340-438: DEM%06d.dat, stats.data), write_forces (main.c:440-478), the per-grain
-// diagnostics table they print, the merged-strip forms of the VTK writer, and the frames written in the background
-// (lbmdem_set_async_output: snapshot kernel, copy stream, writer thread).
+// diagnostics table they print, the merged-strip forms of the VTK writer, and the frames and tables written in the background
+// (lbmdem_set_async_output, lbmdem_set_async_dem: snapshot kernels, copy stream, writer thread).
 
 #include "lbmdem_handle.h"
 
@@ -148,91 +148,60 @@ int lbmdem_download_grain_table(lbmdem_handle* h, double* t) try {
   return fail(LBMDEM_EINVAL, "unexpected C++ exception");
 }
 
-// write_DEM, main.c:340-438: DEM%06d.dat (28 tab-separated columns per grain) and one line appended to
-// stats.data. energies8 (may be NULL): KE, PE, SE, IFR, WF, INCE, TSLIP, TRW.
-int lbmdem_write_dem(lbmdem_handle* h, const char* dir, int nfile, double* energies8) try {
-  SP_UNAVAILABLE("write_DEM");
-  CHECK_H(h);
-  const int n = h->n;
-  std::vector<double> t(30 * (size_t)n), hf(3 * (size_t)n);
-  int rc = lbmdem_download_grain_table(h, t.data());
-  if (rc != LBMDEM_OK) return rc;
-  rc = lbmdem_download_fhf(h, hf.data());
-  if (rc != LBMDEM_OK) return rc;
-  const lbmdem_config& c = h->cfg;
-  const lbmdem_physics& p = c.phys;
-  char path[4096];
-  snprintf(path, sizeof path, "%s/DEM%.6i.dat", (dir && *dir) ? dir : ".", nfile);
-  FILE* fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
-  auto G = [&](int i, int col) { return t[(size_t)i * 30 + col]; };
-  double xfront = G(0, 0) + G(0, 9), height = G(0, 1) + G(0, 9), xgrainmax = G(0, 0);
-  double energie_x = 0., energie_y = 0., energie_teta = 0., energy_p = 0., SE = 0., IFR = 0., zmean = 0;
-  double WF = 0., INCE = 0., TSLIP = 0., TRW = 0.;
-  double N[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < n; i++) {
-    const double x1 = G(i, 0), x2 = G(i, 1), v1 = G(i, 3), v2 = G(i, 4), v3 = G(i, 5), r = G(i, 9), m = G(i, 10),
-                 It = G(i, 12), pp = G(i, 13), ss = G(i, 14);
-    const int z = (int)G(i, 28), zz = (int)G(i, 29);
-    zmean += z;
-    if (z >= 0 && z <= 5) N[z] += 1;
-    energie_x += 0.5 * m * v1 * v1;
-    energie_y += 0.5 * m * v2 * v2;
-    energie_teta += 0.5 * It * v3 * v3;
-    energy_p += m * p.G * x2;
-    SE += 0.5 * (((pp * pp) / p.kg) + ((ss * ss) / p.kt));
-    WF += G(i, 19);
-    IFR += G(i, 20);
-    TSLIP += G(i, 26);
-    TRW += G(i, 27);
-    INCE += G(i, 25);
-    const double ESE = 0.5 * (((pp * pp) / p.kg) + ((ss * ss) / p.kt));
-    if (x1 + r > xgrainmax) xgrainmax = x1 + r;
-    if (x2 + r > height) height = x2 + r;
-    if (zz > 0 && x1 + r >= xfront) xfront = x1 + r;
-    fprintf(fp,
-            "%i\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%i\n",
-            i, r, x1, x2, G(i, 2), v1, v2, v3, G(i, 6), G(i, 7), G(i, 8), hf[3 * (size_t)i], hf[3 * (size_t)i + 1],
-            hf[3 * (size_t)i + 2], pp, ss, ESE, G(i, 19), G(i, 20), G(i, 25), G(i, 26), G(i, 27), G(i, 18), G(i, 21),
-            G(i, 22), G(i, 23), G(i, 24), z);
-  }
-  fclose(fp);
-  const double energie_cin = energie_x + energie_y + energie_teta;
-  zmean = zmean / n;
-  snprintf(path, sizeof path, "%s/stats.data", (dir && *dir) ? dir : ".");
-  fp = fopen(path, "a");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for appending", path);
-  fprintf(fp, "%le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le\n",
-          h->nbsteps * c.dt - p.dtt, xfront, xgrainmax, height, zmean, energie_x, energie_y, energie_teta, energie_cin,
-          N[0] / n, N[1] / n, N[2] / n, N[3] / n, N[4] / n, N[5] / n, energy_p, SE, WF, IFR, INCE, TSLIP, TRW);
-  fclose(fp);
-  if (energies8) {
-    energies8[0] = energie_cin; energies8[1] = energy_p; energies8[2] = SE; energies8[3] = IFR;
-    energies8[4] = WF; energies8[5] = INCE; energies8[6] = TSLIP; energies8[7] = TRW;
+// ---- the table as text: ONE formatter and ONE pair search for the synchronous writers and the writer thread ---------------------
+// `rows`: LBMDEM_DEM_ROW_DOUBLES per grain -- r x1 x2 x3 v1 v2 v3 a1 a2 a3 fhf1 fhf2 fhf3 p s ESE fr ifr ice slip rw fm M11
+// M12 M21 M22 z zz: the columns of main.c:413-420 after the index, then zz. On failure the text goes to `msg`, not to the
+// thread's error text (the writer thread reports through its job).
+static_assert(LBMDEM_DEM_ROW_DOUBLES == DEM_ROW, "the rows of k_dem_frame are the rows of the ABI");
+
+static int close_checked(FILE* fp, const char* path, char* msg, size_t msglen) {
+  const bool bad = ferror(fp) != 0;
+  const int err = errno;
+  if (fclose(fp) != 0 || bad) {
+    snprintf(msg, msglen, "writing '%s' failed: %s", path, strerror(bad ? err : errno));
+    return LBMDEM_EINVAL;
   }
   return LBMDEM_OK;
-} catch (const std::bad_alloc&) {
-  return fail(LBMDEM_ENOMEM, "host memory allocation failed");
-} catch (...) {
-  return fail(LBMDEM_EINVAL, "unexpected C++ exception");
 }
 
-int lbmdem_write_forces(lbmdem_handle* h, const char* dir, int nfile) try {
-  SP_UNAVAILABLE("write_forces");
-  CHECK_H(h);
-  const int n = h->n;
-  std::vector<double> t(30 * (size_t)n);
-  int rc = lbmdem_download_grain_table(h, t.data());
+// DEM%06d.dat (28 tab-separated columns per grain) and one line appended to stats.data, main.c:413-434
+static int write_dem_text(const char* dir, int nfile, int n, const double* rows, const double* stats22, char* msg, size_t msglen) {
+  char path[4200];
+  snprintf(path, sizeof path, "%s/DEM%.6i.dat", (dir && *dir) ? dir : ".", nfile);
+  FILE* fp = fopen(path, "w");
+  if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing", path); return LBMDEM_EINVAL; }
+  for (int i = 0; i < n; i++) {
+    const double* o = rows + (size_t)i * LBMDEM_DEM_ROW_DOUBLES;
+    fprintf(fp,
+            "%i\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%le\t%i\n",
+            i, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7], o[8], o[9], o[10], o[11], o[12], o[13], o[14], o[15], o[16],
+            o[17], o[18], o[19], o[20], o[21], o[22], o[23], o[24], o[25], (int)o[26]);
+  }
+  int rc = close_checked(fp, path, msg, msglen);
   if (rc != LBMDEM_OK) return rc;
-  auto X1 = [&](int i) { return t[(size_t)i * 30 + 0]; };
-  auto X2 = [&](int i) { return t[(size_t)i * 30 + 1]; };
-  auto R = [&](int i) { return t[(size_t)i * 30 + 9]; };
-  auto FM = [&](int i) { return t[(size_t)i * 30 + 18]; };
-  char path[4096];
+  snprintf(path, sizeof path, "%s/stats.data", (dir && *dir) ? dir : ".");
+  fp = fopen(path, "a");
+  if (!fp) { snprintf(msg, msglen, "cannot open '%s' for appending", path); return LBMDEM_EINVAL; }
+  const double* t = stats22;
+  fprintf(fp, "%le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le %le\n", t[0], t[1], t[2],
+          t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15], t[16], t[17], t[18], t[19], t[20],
+          t[21]);
+  return close_checked(fp, path, msg, msglen);
+}
+
+// DEM%06d.ps, main.c:440-478. The four columns it needs from a table of `stride` doubles per grain: centre, radius, fm.
+struct MapCols { const double* base; size_t stride; int x1, x2, r, fm; };
+
+static int write_forces_text(const char* dir, int nfile, int n, MapCols T, int lx, int ly, char* msg, size_t msglen) try {
+  auto X1 = [&](int i) { return T.base[(size_t)i * T.stride + T.x1]; };
+  auto X2 = [&](int i) { return T.base[(size_t)i * T.stride + T.x2]; };
+  auto R = [&](int i) { return T.base[(size_t)i * T.stride + T.r]; };
+  auto FM = [&](int i) { return T.base[(size_t)i * T.stride + T.fm]; };
+  char path[4200];
   snprintf(path, sizeof path, "%s/DEM%.6i.ps", (dir && *dir) ? dir : ".", nfile);
   FILE* fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
-  const double margin = 10 * R(0), hrx1 = h->cfg.lx, hry2 = h->cfg.ly;  // main.c:449
+  if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing", path); return LBMDEM_EINVAL; }
+  const double margin = 10 * R(0), hrx1 = lx, hry2 = ly;  // main.c:449
   fprintf(fp, "%%!PS-Adobe-3.0 EPSF-3.0 \n");
   fprintf(fp, "%%%%BoundingBox: %f %f %f %f \n", -margin, -margin, hrx1 + margin, hry2 + margin);
   fprintf(fp, "%%%%Creator: lbmdem-hip \n");
@@ -298,8 +267,100 @@ int lbmdem_write_forces(lbmdem_handle* h, const char* dir, int nfile) try {
       fprintf(fp, "stroke \n");
     }
   }
-  fclose(fp);
+  return close_checked(fp, path, msg, msglen);
+} catch (const std::bad_alloc&) {
+  snprintf(msg, msglen, "host memory allocation failed");
+  return LBMDEM_ENOMEM;
+}
+
+static int write_dem_rows_files(const char* dir, int nfile, int n, const double* rows, const double* stats22, int with_forces,
+                                int lx, int ly, char* msg, size_t msglen) {
+  const int rc = write_dem_text(dir, nfile, n, rows, stats22, msg, msglen);
+  if (rc != LBMDEM_OK || !with_forces) return rc;
+  return write_forces_text(dir, nfile, n, MapCols{rows, LBMDEM_DEM_ROW_DOUBLES, 1, 2, 0, 21}, lx, ly, msg, msglen);
+}
+
+int lbmdem_write_dem_rows(const char* dir, int nfile, int n, const double* rows, const double* stats22, int with_forces, int lx,
+                          int ly) {
+  if (n < 1 || !rows || !stats22) return fail(LBMDEM_EINVAL, "bad lbmdem_write_dem_rows arguments");
+  char msg[4400];
+  const int rc = write_dem_rows_files(dir, nfile, n, rows, stats22, with_forces, lx, ly, msg, sizeof msg);
+  return rc == LBMDEM_OK ? rc : fail(rc, "%s", msg);
+}
+
+// write_DEM, main.c:340-438: DEM%06d.dat and one line appended to stats.data, from the table brought to the host.
+// energies8 (may be NULL): KE, PE, SE, IFR, WF, INCE, TSLIP, TRW.
+int lbmdem_write_dem(lbmdem_handle* h, const char* dir, int nfile, double* energies8) try {
+  SP_UNAVAILABLE("write_DEM");
+  CHECK_H(h);
+  const int n = h->n;
+  std::vector<double> t(30 * (size_t)n), hf(3 * (size_t)n), rows(LBMDEM_DEM_ROW_DOUBLES * (size_t)n);
+  int rc = lbmdem_download_grain_table(h, t.data());
+  if (rc != LBMDEM_OK) return rc;
+  rc = lbmdem_download_fhf(h, hf.data());
+  if (rc != LBMDEM_OK) return rc;
+  const lbmdem_config& c = h->cfg;
+  const lbmdem_physics& p = c.phys;
+  auto G = [&](int i, int col) { return t[(size_t)i * 30 + col]; };
+  double xfront = G(0, 0) + G(0, 9), height = G(0, 1) + G(0, 9), xgrainmax = G(0, 0);
+  double energie_x = 0., energie_y = 0., energie_teta = 0., energy_p = 0., SE = 0., IFR = 0., zmean = 0;
+  double WF = 0., INCE = 0., TSLIP = 0., TRW = 0.;
+  double N[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < n; i++) {
+    const double x1 = G(i, 0), x2 = G(i, 1), v1 = G(i, 3), v2 = G(i, 4), v3 = G(i, 5), r = G(i, 9), m = G(i, 10),
+                 It = G(i, 12), pp = G(i, 13), ss = G(i, 14);
+    const int z = (int)G(i, 28), zz = (int)G(i, 29);
+    zmean += z;
+    if (z >= 0 && z <= 5) N[z] += 1;
+    energie_x += 0.5 * m * v1 * v1;
+    energie_y += 0.5 * m * v2 * v2;
+    energie_teta += 0.5 * It * v3 * v3;
+    energy_p += m * p.G * x2;
+    SE += 0.5 * (((pp * pp) / p.kg) + ((ss * ss) / p.kt));
+    WF += G(i, 19);
+    IFR += G(i, 20);
+    TSLIP += G(i, 26);
+    TRW += G(i, 27);
+    INCE += G(i, 25);
+    const double ESE = 0.5 * (((pp * pp) / p.kg) + ((ss * ss) / p.kt));
+    if (x1 + r > xgrainmax) xgrainmax = x1 + r;
+    if (x2 + r > height) height = x2 + r;
+    if (zz > 0 && x1 + r >= xfront) xfront = x1 + r;
+    const double row[LBMDEM_DEM_ROW_DOUBLES] = {
+        r, x1, x2, G(i, 2), v1, v2, v3, G(i, 6), G(i, 7), G(i, 8), hf[3 * (size_t)i], hf[3 * (size_t)i + 1],
+        hf[3 * (size_t)i + 2], pp, ss, ESE, G(i, 19), G(i, 20), G(i, 25), G(i, 26), G(i, 27), G(i, 18), G(i, 21),
+        G(i, 22), G(i, 23), G(i, 24), (double)z, (double)zz};
+    memcpy(&rows[(size_t)i * LBMDEM_DEM_ROW_DOUBLES], row, sizeof row);
+  }
+  const double energie_cin = energie_x + energie_y + energie_teta;
+  zmean = zmean / n;
+  const double stats22[22] = {h->nbsteps * c.dt - p.dtt, xfront, xgrainmax, height, zmean, energie_x, energie_y, energie_teta,
+                              energie_cin, N[0] / n, N[1] / n, N[2] / n, N[3] / n, N[4] / n, N[5] / n, energy_p, SE, WF, IFR,
+                              INCE, TSLIP, TRW};
+  char msg[4400];
+  rc = write_dem_text(dir, nfile, n, rows.data(), stats22, msg, sizeof msg);
+  if (rc != LBMDEM_OK) return fail(rc, "%s", msg);
+  if (energies8) {
+    energies8[0] = energie_cin; energies8[1] = energy_p; energies8[2] = SE; energies8[3] = IFR;
+    energies8[4] = WF; energies8[5] = INCE; energies8[6] = TSLIP; energies8[7] = TRW;
+  }
   return LBMDEM_OK;
+} catch (const std::bad_alloc&) {
+  return fail(LBMDEM_ENOMEM, "host memory allocation failed");
+} catch (...) {
+  return fail(LBMDEM_EINVAL, "unexpected C++ exception");
+}
+
+int lbmdem_write_forces(lbmdem_handle* h, const char* dir, int nfile) try {
+  SP_UNAVAILABLE("write_forces");
+  CHECK_H(h);
+  const int n = h->n;
+  std::vector<double> t(30 * (size_t)n);
+  int rc = lbmdem_download_grain_table(h, t.data());
+  if (rc != LBMDEM_OK) return rc;
+  char msg[4400];
+  rc = write_forces_text(dir, nfile, n, MapCols{t.data(), 30, 0, 1, 9, 18}, h->cfg.lx, h->cfg.ly, msg, sizeof msg);
+  return rc == LBMDEM_OK ? rc : fail(rc, "%s", msg);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 } catch (...) {
@@ -407,55 +468,86 @@ static inline double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// the writer thread: slot by slot in the order they were queued -- wait for the copy, write the files, free the slot
+// the writer thread: job by job in the order they were queued -- wait for the copy, write the files, free the slot
 static void async_writer(AsyncOut* a) {
   (void)hipSetDevice(a->device);
   for (;;) {
-    int s;
+    int job;
     {
       std::unique_lock<std::mutex> lk(a->mu);
       a->cv_job.wait(lk, [&] { return a->quit || !a->jobs.empty(); });
       if (a->jobs.empty()) return;
-      s = a->jobs.front();
+      job = a->jobs.front();
       a->jobs.pop_front();
     }
-    AsyncSlot& S = a->slot[s];
+    const bool dem = job >= LBMDEM_ASYNC_MAX_FRAMES;
+    AsyncSlot* F = dem ? nullptr : &a->slot[job];
+    AsyncDemSlot* D = dem ? &a->dslot[job - LBMDEM_ASYNC_MAX_FRAMES] : nullptr;
     char msg[sizeof a->err_msg];
     int code = LBMDEM_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = hipEventSynchronize(S.copied);
+    const hipError_t e = hipEventSynchronize(dem ? D->copied : F->copied);
     const double ms_copy = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
     if (e != hipSuccess) {
-      snprintf(msg, sizeof msg, "frame %d: the copy to host memory failed: %s", S.nfile, hipGetErrorString(e));
+      snprintf(msg, sizeof msg, "%s %d: the copy to host memory failed: %s", dem ? "table" : "frame", dem ? D->nfile : F->nfile,
+               hipGetErrorString(e));
       code = LBMDEM_EHIP;
+    } else if (dem) {
+      code = write_dem_rows_files(D->dir, D->nfile, a->n, D->pinned, D->stats22, D->with_forces, a->lx, a->ly, msg, sizeof msg);
     } else {
-      code = write_image_files(S.dir, S.nfile, a->lx, a->ly, S.pinned, msg, sizeof msg);
+      code = write_image_files(F->dir, F->nfile, a->lx, a->ly, F->pinned, msg, sizeof msg);
     }
     const double ms_io = ms_since(t1);
     {
       std::lock_guard<std::mutex> lk(a->mu);
-      a->ms_copy_wait += ms_copy;
-      a->ms_io += ms_io;
-      if (code == LBMDEM_OK) a->written++;
+      AsyncCounters& C = dem ? a->dc : a->fc;
+      C.ms_copy_wait += ms_copy;
+      C.ms_io += ms_io;
+      if (code == LBMDEM_OK) C.written++;
       else {
-        a->failed++;
-        if (!a->err_code) { a->err_code = code; memcpy(a->err_msg, msg, sizeof msg); }
+        C.failed++;
+        if (!a->err_code) { a->err_code = code; a->err_dem = dem; memcpy(a->err_msg, msg, sizeof msg); }
       }
-      S.busy = false;
+      if (dem) D->busy = false; else F->busy = false;
       a->pending--;
     }
     a->cv_free.notify_all();
   }
 }
 
-static void async_free(AsyncOut* a) {
+static void async_free_frames(AsyncOut* a) {
   for (AsyncSlot& S : a->slot) {
     if (S.staging) (void)hipFree(S.staging);
     if (S.pinned) (void)hipHostFree(S.pinned);
     if (S.snapped) (void)hipEventDestroy(S.snapped);
     if (S.copied) (void)hipEventDestroy(S.copied);
+    S.staging = S.pinned = nullptr;
+    S.snapped = S.copied = nullptr;
   }
+  a->frames = 0;
+  a->fc = AsyncCounters{};
+}
+
+static void async_free_dem(AsyncOut* a) {
+  for (AsyncDemSlot& S : a->dslot) {
+    if (S.staging) (void)hipFree(S.staging);
+    if (S.pinned) (void)hipHostFree(S.pinned);
+    if (S.snapped) (void)hipEventDestroy(S.snapped);
+    if (S.copied) (void)hipEventDestroy(S.copied);
+    S.staging = S.pinned = nullptr;
+    S.snapped = S.copied = nullptr;
+  }
+  if (a->dem_scratch) (void)hipFree(a->dem_scratch);
+  if (a->dem_stats_host) (void)hipHostFree(a->dem_stats_host);
+  a->dem_scratch = a->dem_stats_host = nullptr;
+  a->dem_slots = 0;
+  a->dc = AsyncCounters{};
+}
+
+static void async_free(AsyncOut* a) {
+  async_free_frames(a);
+  async_free_dem(a);
   if (a->copy_stream) (void)hipStreamDestroy(a->copy_stream);
   delete a;
 }
@@ -479,23 +571,67 @@ int lbmdem_async_report(lbmdem_handle* h) {
   if (!a) return LBMDEM_OK;
   char msg[sizeof a->err_msg];
   int code;
+  bool dem;
   {
     std::lock_guard<std::mutex> lk(a->mu);
     code = a->err_code;
     if (code == LBMDEM_OK) return LBMDEM_OK;
     memcpy(msg, a->err_msg, sizeof msg);
+    dem = a->err_dem;
     a->err_code = LBMDEM_OK;
   }
-  return fail(code, "background frame writer: %s", msg);
+  return fail(code, "background %s writer: %s", dem ? "table" : "frame", msg);
 }
 
-#define CHECK_WHOLE_LATTICE(h, who)                                                                                    \
+// What both features share -- the AsyncOut, its copy stream and its writer thread -- made when the first of them is switched on
+static int async_ensure(lbmdem_handle* h, const char* who) {
+  if (h->aout) return LBMDEM_OK;
+  AsyncOut* a = new (std::nothrow) AsyncOut;
+  if (!a) return fail(LBMDEM_ENOMEM, "host memory allocation failed");
+  a->lx = h->L.lx; a->ly = h->L.ly; a->n = h->n; a->device = h->cfg.device;
+  const hipError_t e = hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    async_free(a);
+    return fail(LBMDEM_ENOMEM, "%s: the copy stream cannot be had: %s", who, hipGetErrorString(e));
+  }
+  try {
+    a->writer = std::thread(async_writer, a);
+  } catch (const std::system_error&) {
+    async_free(a);
+    return fail(LBMDEM_ENOMEM, "%s: the writer thread cannot be started", who);
+  }
+  h->aout = a;
+  return LBMDEM_OK;
+}
+
+// Before the slots of a feature change: everything queued is on disk (the writer sleeps, no slot is in use), and a failure
+// of the writer that nobody has been told about is taken out -- it is what the call returns once the request is carried out.
+struct AsyncOldError { int code = LBMDEM_OK; bool dem = false; char msg[sizeof AsyncOut::err_msg]; };
+static void async_settle(AsyncOut* a, AsyncOldError* old) {
+  if (!a) return;
+  std::unique_lock<std::mutex> lk(a->mu);
+  a->cv_free.wait(lk, [&] { return a->pending == 0; });
+  old->code = a->err_code;
+  old->dem = a->err_dem;
+  if (old->code != LBMDEM_OK) memcpy(old->msg, a->err_msg, sizeof old->msg);
+  a->err_code = LBMDEM_OK;
+}
+static int async_settled(lbmdem_handle* h, const AsyncOldError& old) {
+  if (h->aout && !h->aout->frames && !h->aout->dem_slots) lbmdem_async_release(h);   // the last feature went off
+  if (old.code != LBMDEM_OK) return fail(old.code, "background %s writer: %s", old.dem ? "table" : "frame", old.msg);
+  return LBMDEM_OK;
+}
+
+#define CHECK_WHOLE_LATTICE_OR(h, who, instead)                                                                        \
   do {                                                                                                                 \
     const LatticeView& L_ = (h)->L;                                                                                    \
     if (L_.xo0 != 0 || L_.xo1 != L_.lx || L_.gx0 != 0 || (h)->dist)                                                    \
       return fail(LBMDEM_EINVAL, who " needs the whole lattice and all grains on this handle (not a strip of a "       \
-                                     "decomposition, no distributed grains): use lbmdem_comm_write_vtk there");        \
+                                     "decomposition, no distributed grains): " instead);                               \
   } while (0)
+#define CHECK_WHOLE_LATTICE(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "use lbmdem_comm_write_vtk there")
+#define CHECK_WHOLE_TABLE(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "there rank 0 writes the tables with lbmdem_write_dem")
 
 static void launch_frame(lbmdem_handle* h, void* image_dev) {
   const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
@@ -529,31 +665,23 @@ int lbmdem_download_vtk_image(lbmdem_handle* h, void* image_be) {
   return LBMDEM_OK;
 }
 
-// The request is carried out first (an earlier set-up is drained, joined and freed; the new one made); a failure of the old
-// writer that nobody has been told about is what the call then returns.
+// The request is carried out first (the frames queued are written, the old slots freed, the new ones made; the writer thread
+// and the copy stream go when neither frames nor tables need them any more); a failure of the writer that nobody has been
+// told about is what the call then returns.
 int lbmdem_set_async_output(lbmdem_handle* h, int frames) {
   CHECK_H(h);
   if (frames < 0 || frames > LBMDEM_ASYNC_MAX_FRAMES)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_output: frames must be 0..%d, not %d", LBMDEM_ASYNC_MAX_FRAMES, frames);
   if (frames > 0) CHECK_WHOLE_LATTICE(h, "lbmdem_set_async_output");
-  if (h->aout && h->aout->frames == frames) return LBMDEM_OK;
-  int old_code = LBMDEM_OK;
-  char old_msg[sizeof h->aout->err_msg];
-  if (h->aout) {
-    {
-      std::unique_lock<std::mutex> lk(h->aout->mu);
-      h->aout->cv_free.wait(lk, [&] { return h->aout->pending == 0; });
-      old_code = h->aout->err_code;
-      if (old_code != LBMDEM_OK) memcpy(old_msg, h->aout->err_msg, sizeof old_msg);
-    }
-    lbmdem_async_release(h);
-  }
+  if ((h->aout ? h->aout->frames : 0) == frames) return LBMDEM_OK;
+  AsyncOldError old;
+  async_settle(h->aout, &old);
+  if (h->aout) async_free_frames(h->aout);
   if (frames > 0) {
-    AsyncOut* a = new (std::nothrow) AsyncOut;
-    if (!a) return fail(LBMDEM_ENOMEM, "host memory allocation failed");
-    a->frames = frames; a->lx = h->L.lx; a->ly = h->L.ly; a->device = h->cfg.device;
+    RC_TRY(async_ensure(h, "lbmdem_set_async_output"));
+    AsyncOut* a = h->aout;
     a->image_bytes = lbmdem_vtk_image_bytes(a->lx, a->ly);
-    hipError_t e = hipStreamCreateWithFlags(&a->copy_stream, hipStreamNonBlocking);
+    hipError_t e = hipSuccess;
     for (int s = 0; s < frames && e == hipSuccess; ++s) {
       AsyncSlot& S = a->slot[s];
       e = hipMalloc(&S.staging, a->image_bytes);
@@ -564,26 +692,20 @@ int lbmdem_set_async_output(lbmdem_handle* h, int frames) {
     if (e != hipSuccess) {
       (void)hipGetLastError();
       const size_t bytes = a->image_bytes;
-      async_free(a);
+      async_free_frames(a);
+      (void)async_settled(h, AsyncOldError{});
       return fail(LBMDEM_ENOMEM, "lbmdem_set_async_output: %d frame slots of %zu bytes (device staging + pinned host memory each) "
                                  "cannot be had: %s", frames, bytes, hipGetErrorString(e));
     }
-    try {
-      a->writer = std::thread(async_writer, a);
-    } catch (const std::system_error&) {
-      async_free(a);
-      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_output: the writer thread cannot be started");
-    }
-    h->aout = a;
+    a->frames = frames;
   }
-  if (old_code != LBMDEM_OK) return fail(old_code, "background frame writer: %s", old_msg);
-  return LBMDEM_OK;
+  return async_settled(h, old);
 }
 
 int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
   CHECK_H(h);   // (a launch of k_dem_chain that gave up is undone and replayed here: nothing unconfirmed lies ahead of the snapshot)
   AsyncOut* a = h->aout;
-  if (!a) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: async output is off (lbmdem_set_async_output)");
+  if (!async_frames_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: async output is off (lbmdem_set_async_output)");
   CHECK_NOT_SPLIT(h);
   CHECK_WHOLE_LATTICE(h, "lbmdem_write_vtk_async");
   RC_TRY(lbmdem_async_report(h));   // an earlier frame's failure: this call queues nothing
@@ -595,9 +717,9 @@ int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
     auto free_slot = [&] { for (int k = 0; k < a->frames; ++k) if (!a->slot[k].busy) return k; return -1; };
     if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop a frame
       const auto t0 = std::chrono::steady_clock::now();
-      a->slot_waits++;
+      a->fc.slot_waits++;
       a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
-      a->ms_slot_wait += ms_since(t0);
+      a->fc.ms_slot_wait += ms_since(t0);
     }
     a->slot[s].busy = true;
   }
@@ -620,7 +742,7 @@ int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
     std::lock_guard<std::mutex> lk(a->mu);
     a->jobs.push_back(s);
     a->pending++;
-    a->queued++;
+    a->fc.queued++;
   }
   a->cv_job.notify_one();
   return LBMDEM_OK;
@@ -635,7 +757,7 @@ int lbmdem_output_drain(lbmdem_handle* h) {
     if (a->pending != 0) {
       const auto t0 = std::chrono::steady_clock::now();
       a->cv_free.wait(lk, [&] { return a->pending == 0; });
-      a->ms_drain += ms_since(t0);
+      if (a->frames) a->fc.ms_last += ms_since(t0);   // (lbmdem_output_stats is all 0 while frames are off)
     }
   }
   return lbmdem_async_report(h);
@@ -648,8 +770,165 @@ int lbmdem_output_stats(lbmdem_handle* h, long* counts4, double* ms4) {
   double m[4] = {0, 0, 0, 0};
   if (a) {
     std::lock_guard<std::mutex> lk(a->mu);
-    c[0] = a->queued; c[1] = a->written; c[2] = a->failed; c[3] = a->slot_waits;
-    m[0] = a->ms_slot_wait; m[1] = a->ms_copy_wait; m[2] = a->ms_io; m[3] = a->ms_drain;
+    c[0] = a->fc.queued; c[1] = a->fc.written; c[2] = a->fc.failed; c[3] = a->fc.slot_waits;
+    m[0] = a->fc.ms_slot_wait; m[1] = a->fc.ms_copy_wait; m[2] = a->fc.ms_io; m[3] = a->fc.ms_last;
+  }
+  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
+  return LBMDEM_OK;
+}
+
+// ---- tables in the background ------------------------------------------------------------------------------------------------------
+
+#ifndef LBMDEM_SINGLE_PRECISION
+static DemTableView dem_table_view(const lbmdem_handle* h) {
+  const lbmdem_config& c = h->cfg;
+  return DemTableView{h->n, h->kin[h->kcur], h->r, h->m, h->It, h->gp, h->diag, h->dx.fr, h->dx.ice, h->dx.slip, h->dx.rw,
+                      h->fhf, c.phys.G, c.dt, c.dt2, c.phys.kg, c.phys.kt};
+}
+#endif
+
+#define CHECK_TABLE(h)                                                                                                           \
+  do {                                                                                                                           \
+    if (!(h)->diag_valid || !(h)->dx_ready)                                                                                      \
+      return fail(LBMDEM_EINVAL, "no contact diagnostics for the last sub-step (lbmdem_set_diagnostics, or the sub-step that "  \
+                                 "reaches a multiple of 4000)");                                                                 \
+  } while (0)
+
+int lbmdem_dem_stats(lbmdem_handle* h, double* stats22) {
+  SP_UNAVAILABLE("write_DEM");
+#ifndef LBMDEM_SINGLE_PRECISION
+  CHECK_H(h);
+  if (!stats22) return fail(LBMDEM_EINVAL, "null buffer");
+  CHECK_TABLE(h);
+  const size_t n = (size_t)h->n;
+  double* tmp = nullptr;   // (the scratch of the background writer, where there is one: it is idle between two events)
+  double* scratch = async_dem_on(h) ? h->aout->dem_scratch : nullptr;
+  if (!scratch) { HIP_TRY(hipMalloc((void**)&tmp, sizeof(double) * (DEM_STATS_CHAINS * n + 22))); scratch = tmp; }
+  const DemTableView T = dem_table_view(h);
+  launch_dem_frame(T, nullptr, scratch, h->stream);
+  launch_dem_stats(T, scratch, scratch + DEM_STATS_CHAINS * n, h->stream);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(stats22, scratch + DEM_STATS_CHAINS * n, sizeof(double) * 22, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (tmp) (void)hipFree(tmp);
+  HIP_TRY(e);
+  stats22[0] = h->nbsteps * h->cfg.dt - h->cfg.phys.dtt;   // main.c:428
+  return LBMDEM_OK;
+#endif
+}
+
+int lbmdem_set_async_dem(lbmdem_handle* h, int slots) {
+  SP_UNAVAILABLE("write_DEM");
+#ifndef LBMDEM_SINGLE_PRECISION
+  CHECK_H(h);
+  if (slots < 0 || slots > LBMDEM_ASYNC_MAX_DEM)
+    return fail(LBMDEM_EINVAL, "lbmdem_set_async_dem: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_DEM, slots);
+  if (slots > 0) CHECK_WHOLE_TABLE(h, "lbmdem_set_async_dem");
+  if ((h->aout ? h->aout->dem_slots : 0) == slots) return LBMDEM_OK;
+  AsyncOldError old;
+  async_settle(h->aout, &old);
+  if (h->aout) async_free_dem(h->aout);
+  if (slots > 0) {
+    RC_TRY(async_ensure(h, "lbmdem_set_async_dem"));
+    AsyncOut* a = h->aout;
+    const size_t bytes = sizeof(double) * LBMDEM_DEM_ROW_DOUBLES * (size_t)a->n;
+    hipError_t e = hipMalloc((void**)&a->dem_scratch, sizeof(double) * (DEM_STATS_CHAINS * (size_t)a->n + 22));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&a->dem_stats_host, sizeof(double) * 22, hipHostMallocDefault);
+    for (int s = 0; s < slots && e == hipSuccess; ++s) {
+      AsyncDemSlot& S = a->dslot[s];
+      e = hipMalloc((void**)&S.staging, bytes);
+      if (e == hipSuccess) e = hipHostMalloc((void**)&S.pinned, bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      async_free_dem(a);
+      (void)async_settled(h, AsyncOldError{});
+      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_dem: %d table slots of %zu bytes (device staging + pinned host memory each) "
+                                 "cannot be had: %s", slots, bytes, hipGetErrorString(e));
+    }
+    a->dem_slots = slots;
+  }
+  return async_settled(h, old);
+#endif
+}
+
+int lbmdem_write_dem_async(lbmdem_handle* h, const char* dir, int nfile, int with_forces, double* energies8) {
+  SP_UNAVAILABLE("write_DEM");
+#ifndef LBMDEM_SINGLE_PRECISION
+  CHECK_H(h);   // (a launch of k_dem_chain that gave up is undone and replayed here: the table is the confirmed one)
+  if (!async_dem_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_write_dem_async: tables in the background are off (lbmdem_set_async_dem)");
+  AsyncOut* a = h->aout;
+  CHECK_WHOLE_TABLE(h, "lbmdem_write_dem_async");
+  CHECK_TABLE(h);
+  RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
+  const char* d = (dir && *dir) ? dir : ".";
+  if (strlen(d) >= sizeof a->dslot[0].dir) return fail(LBMDEM_EINVAL, "lbmdem_write_dem_async: directory name too long");
+  int s = -1;
+  {
+    std::unique_lock<std::mutex> lk(a->mu);
+    auto free_slot = [&] { for (int k = 0; k < a->dem_slots; ++k) if (!a->dslot[k].busy) return k; return -1; };
+    if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop an event
+      const auto t0 = std::chrono::steady_clock::now();
+      a->dc.slot_waits++;
+      a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
+      a->dc.ms_slot_wait += ms_since(t0);
+    }
+    a->dslot[s].busy = true;
+  }
+  AsyncDemSlot& S = a->dslot[s];
+  strcpy(S.dir, d);
+  S.nfile = nfile;
+  S.with_forces = with_forces != 0;
+  const size_t n = (size_t)a->n;
+  double* stats_dev = a->dem_scratch + DEM_STATS_CHAINS * n;
+  const DemTableView T = dem_table_view(h);
+  launch_dem_frame(T, S.staging, a->dem_scratch, h->stream);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(S.snapped, h->stream);   // the rows are complete: their copy may start under k_dem_stats
+  if (e == hipSuccess) { launch_dem_stats(T, a->dem_scratch, stats_dev, h->stream); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipMemcpyAsync(a->dem_stats_host, stats_dev, sizeof(double) * 22, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, sizeof(double) * LBMDEM_DEM_ROW_DOUBLES * n, hipMemcpyDeviceToHost, a->copy_stream);
+  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // the 22 numbers: the only wait on the step stream
+  const double ms_stats = ms_since(t0);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
+    { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
+    a->cv_free.notify_all();
+    HIP_TRY(e);
+  }
+  memcpy(S.stats22, a->dem_stats_host, sizeof S.stats22);
+  S.stats22[0] = h->nbsteps * h->cfg.dt - h->cfg.phys.dtt;   // main.c:428
+  if (energies8) {
+    const double* t = S.stats22;
+    energies8[0] = t[8]; energies8[1] = t[15]; energies8[2] = t[16]; energies8[3] = t[18];
+    energies8[4] = t[17]; energies8[5] = t[19]; energies8[6] = t[20]; energies8[7] = t[21];
+  }
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    a->jobs.push_back(LBMDEM_ASYNC_MAX_FRAMES + s);
+    a->pending++;
+    a->dc.queued++;
+    a->dc.ms_last += ms_stats;
+  }
+  a->cv_job.notify_one();
+  return LBMDEM_OK;
+#endif
+}
+
+int lbmdem_output_stats_dem(lbmdem_handle* h, long* counts4, double* ms4) {
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  AsyncOut* a = h->aout;
+  long c[4] = {0, 0, 0, 0};
+  double m[4] = {0, 0, 0, 0};
+  if (a) {
+    std::lock_guard<std::mutex> lk(a->mu);
+    c[0] = a->dc.queued; c[1] = a->dc.written; c[2] = a->dc.failed; c[3] = a->dc.slot_waits;
+    m[0] = a->dc.ms_slot_wait; m[1] = a->dc.ms_copy_wait; m[2] = a->dc.ms_io; m[3] = a->dc.ms_last;
   }
   for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
   return LBMDEM_OK;

@@ -152,13 +152,17 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
     }
     s = e + 1;
     if (cad.vtk(e)) {   // write_vtk sits inside `#ifdef _FLUIDE_` (main.c:1768-1770); nFile++ does not
-      if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else if (h->aout) RC_TRY(lbmdem_write_vtk_async(h, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
+      if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else if (async_frames_on(h)) RC_TRY(lbmdem_write_vtk_async(h, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
       nfile++;
     }
     // (with strips the sub-step before was run by rank 0 on a full replica, lbmdem_comm_run: it holds the whole table)
     if (cad.dem(e) && dir && rank == 0) {
-      RC_TRY(lbmdem_write_dem(h, dir, nfile, h->scene_energies));
-      RC_TRY(lbmdem_write_forces(h, dir, nfile));
+      if (!comm && async_dem_on(h)) {
+        RC_TRY(lbmdem_write_dem_async(h, dir, nfile, 1, h->scene_energies));   // the energies now, the files behind the run's back
+      } else {
+        RC_TRY(lbmdem_write_dem(h, dir, nfile, h->scene_energies));
+        RC_TRY(lbmdem_write_forces(h, dir, nfile));
+      }
     }
     if (cad.line(e)) {   // main.c:1884-1889
       const double* E = h->scene_energies;
@@ -179,8 +183,8 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
   return LBMDEM_OK;
 }
 
-// With frames in the background (lbmdem_set_async_output) the loop's VTK events are only queued: the files of the schedule
-// exist when the call returns, so it drains first -- also when the loop ends early with an error, which is then the one
+// With frames or tables in the background (lbmdem_set_async_output, lbmdem_set_async_dem) the loop's VTK and DEM events are
+// only queued: the files of the schedule exist when the call returns, so it drains first -- also when the loop ends early with an error, which is then the one
 // returned; otherwise a failure of the writer is.
 int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
   const int rc = run_scene_loop(h, comm, n, sc, res);

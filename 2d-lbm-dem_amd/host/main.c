@@ -25,6 +25,11 @@
  * the run goes on while a frame is copied and written; same files. The frames still in flight at the end are waited for
  * before `time:` is taken. With --run-stats one more line, `async_output: queued Q written W failed F slot_waits S
  * ms_slot_wait .. ms_copy_wait .. ms_io .. ms_drain ..` (lbmdem_output_stats). Single GPU only.
+ * --async-dem [N]: the write_DEM / write_forces events are written in the background as well (lbmdem_set_async_dem, N = 1..4
+ * table slots, default 2): the loop waits for the 22 numbers of the stats.data line only; formatting, pair search and file
+ * I/O happen on the writer thread; same files. Waited for before `time:` like the frames. With --run-stats one more line,
+ * `async_dem: queued Q written W failed F slot_waits S ms_slot_wait .. ms_copy_wait .. ms_io .. ms_stats_wait ..`
+ * (lbmdem_output_stats_dem). Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -47,6 +52,7 @@
  * through a file in a private temporary directory. Rank 0 prints and writes the VTK frames and DEM tables (merged over the ranks); checkpoints are single-GPU. */
 static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_stats = 0;
 static int g_async_frames = 0;   /* --async-output [N] */
+static int g_async_dem = 0;      /* --async-dem [N] */
 /* the optional count behind --async-output: all digits */
 static int is_count(const char* s) {
   if (!s || !*s) return 0;
@@ -139,7 +145,7 @@ static int check_decomposition(int argc, char** argv, int gpus) {
     else if (!strcmp(argv[a], "--ly") && a + 1 < argc) ly = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--scale") && a + 1 < argc) scale = atof(argv[++a]);
     else if (argv[a][0] == '-' && argv[a][1] == '-' && strcmp(argv[a], "--comm") && strcmp(argv[a], "--dry") &&
-             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && strcmp(argv[a], "--async-output") && a + 1 < argc) ++a;
+             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && strcmp(argv[a], "--async-output") && strcmp(argv[a], "--async-dem") && a + 1 < argc) ++a;
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
   }
   if (!sample) return 0;   /* run() prints the usage line */
@@ -179,6 +185,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--async-output")) g_async_frames = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
+    if (!strcmp(argv[a], "--async-dem")) g_async_dem = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--comm-timeout") && a + 1 < argc) g_comm_timeout = atof(argv[a + 1]);
     if (!strcmp(argv[a], "--devices") && a + 1 < argc) {
       for (const char* p = argv[a + 1]; *p && g_ndevices < 64;) {
@@ -196,6 +203,7 @@ int main(int argc, char** argv) {
   if (g_vib && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--vib is a single-GPU mode (vibrating walls are not available on strips)\n"); return EXIT_FAILURE; }
   if (probes && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--probes is a single-GPU mode (the probes are not available on strips)\n"); return EXIT_FAILURE; }
   if (g_async_frames && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-output is a single-GPU mode (with --gpus N rank 0 merges the strips' columns and writes the frames itself)\n"); return EXIT_FAILURE; }
+  if (g_async_dem && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-dem is a single-GPU mode (with --gpus N rank 0 runs the table sub-step on a full replica and writes the tables itself)\n"); return EXIT_FAILURE; }
   if (gpus <= 1) return run(argc, argv);
   g_world = gpus; g_use_comm = 1;
   { /* every strip must be at least one margin wide (lbmdem_dist_enable would refuse on the ranks whose strip is one
@@ -329,6 +337,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--vib")) {}
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--async-output")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
+    else if (!strcmp(argv[a], "--async-dem")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (!strcmp(argv[a], "--probes") && a + 1 < argc) probe_path = argv[++a];
@@ -346,7 +355,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --probes FILE --probe-every K --probe-row Y --probe-point X,Y]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --probes FILE --probe-every K --probe-row Y --probe-point X,Y]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   SAY("Opening file : %s\n", sample);
@@ -406,6 +415,7 @@ static int run(int argc, char** argv) {
   }
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */
+  if (g_async_dem) DIE(lbmdem_set_async_dem(h, g_async_dem), "set_async_dem");
   lbmdem_comm* comm = NULL;
   if (g_use_comm) {
     unsigned char id[LBMDEM_COMM_ID_BYTES];
@@ -498,6 +508,13 @@ static int run(int argc, char** argv) {
         double oms[4];
         DIE(lbmdem_output_stats(h, oc, oms), "output_stats");
         fprintf(stderr, "async_output: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_drain %.3f\n",
+                oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
+      }
+      if (g_async_dem) {
+        long oc[4];
+        double oms[4];
+        DIE(lbmdem_output_stats_dem(h, oc, oms), "output_stats_dem");
+        fprintf(stderr, "async_dem: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_stats_wait %.3f\n",
                 oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
       }
     }

@@ -369,7 +369,7 @@ int lbmdem_write_vtk(lbmdem_handle* h, const char* dir, int nfile);
  * lbmdem_run_scene on the handle and is then forgotten (lbmdem_destroy drops it); the handle stays usable.
  * lbmdem_output_drain returns when every queued frame is on disk and closed. On a handle with async output on,
  * lbmdem_run_scene (comm = NULL) hands its VTK events to lbmdem_write_vtk_async and drains before it returns: its files exist
- * when it returns, as before. write_DEM / write_forces stay synchronous. lbmdem_output_stats -- counts4: frames queued,
+ * when it returns, as before. write_DEM / write_forces stay synchronous (lbmdem_set_async_dem, below, is their switch). lbmdem_output_stats -- counts4: frames queued,
  * written, failed, calls that had to wait for a slot; ms4: the caller waiting for a slot, the writer waiting for copies,
  * the writer in file I/O, the caller in lbmdem_output_drain (all 0 while off).
  * LBMDEM_EINVAL: frames outside 0..4, lbmdem_write_vtk_async while off, a strip of a decomposition or distributed grains
@@ -408,6 +408,44 @@ int lbmdem_write_dem(lbmdem_handle* h, const char* dir, int nfile, double* energ
  * evidently mean. Every other line is character-identical to the reference's file. The pair search is a
  * host-side uniform grid (same pairs as the reference's O(N^2) loop). */
 int lbmdem_write_forces(lbmdem_handle* h, const char* dir, int nfile);
+/* The same two events written in the background while the run goes on, by the writer thread of lbmdem_set_async_output (one
+ * thread and one copy stream per handle, made for whichever of the two features is switched on first; its jobs are strictly
+ * first in, first out, so the lines of stats.data land in call order). lbmdem_set_async_dem(h, slots), slots in
+ * 1..LBMDEM_ASYNC_MAX_DEM, sets up that many table slots (device staging + pinned host memory of LBMDEM_DEM_ROW_DOUBLES
+ * doubles per grain each); 0 writes what is queued and frees them (the default: nothing is allocated, no thread exists, and
+ * lbmdem_write_dem, lbmdem_write_forces and lbmdem_run_scene do what they did). A row is what DEM%06d.dat prints after the
+ * index -- r x1 x2 x3 v1 v2 v3 a1 a2 a3 fhf1 fhf2 fhf3 p s ESE fr ifr ice slip rw fm M11 M12 M21 M22 z -- and zz, all as
+ * doubles. lbmdem_write_dem_async settles the handle like every writer, takes a free slot -- when none is free it waits for
+ * the writer: an event is never dropped --, launches two kernels on the handle's stream (the rows into the slot as the file
+ * holds them; the 22 numbers of the stats.data line, whose ten sums are added in grain order by one lane each, as the host
+ * loop adds them: bit-equal to lbmdem_write_dem's), queues the copy of the rows on the copy stream behind an event, waits
+ * for the 22 numbers -- the only wait on the step stream --, hands the slot to the writer and returns energies8 exactly as
+ * lbmdem_write_dem does. The writer formats DEM%06d.dat, appends the line to stats.data and, when with_forces, searches the
+ * pairs and prints DEM%06d.ps: the files of lbmdem_write_dem + lbmdem_write_forces byte for byte. What is stepped afterwards
+ * does not reach them. Failures of the writer travel as for frames: the first one is returned by the next
+ * lbmdem_write_dem_async or lbmdem_write_vtk_async (which then queues nothing), lbmdem_output_drain or lbmdem_run_scene and
+ * is then forgotten. lbmdem_output_drain and lbmdem_destroy cover tables as well. On a handle with tables in the background,
+ * lbmdem_run_scene (comm = NULL) hands its DEM events to lbmdem_write_dem_async (with_forces = 1) and drains before it
+ * returns.
+ * lbmdem_dem_stats: the stats.data line of the last table sub-step alone (the two kernels without the rows, 176 bytes
+ * back), feature on or off; energies8 = stats22[{8, 15, 16, 18, 17, 19, 20, 21}].
+ * lbmdem_output_stats_dem -- counts4: events queued, written, failed, calls that had to wait for a slot; ms4: the caller
+ * waiting for a slot, the writer waiting for copies, the writer in file I/O, the caller waiting for the 22 numbers.
+ * lbmdem_write_dem_rows: host only, no handle, no device -- DEM%06d.dat, one line appended to stats.data, and DEM%06d.ps
+ * (bounding box from lx, ly) when with_forces, from n rows and a stats line: the formatter and the pair search that the
+ * synchronous writers and the writer thread share.
+ * LBMDEM_EINVAL: slots outside 0..4, lbmdem_write_dem_async while off or without a valid table, a strip of a decomposition or
+ * distributed grains (and lbmdem_dist_enable on a handle with tables in the background), the single-precision library (it
+ * has no write_DEM). LBMDEM_ENOMEM: the slots cannot be had (then the feature is off). Vibrating and probing handles have it.
+ * Checkpoints do not carry the setting. */
+#define LBMDEM_DEM_ROW_DOUBLES 28
+#define LBMDEM_ASYNC_MAX_DEM 4
+int lbmdem_dem_stats(lbmdem_handle* h, double* stats22);
+int lbmdem_set_async_dem(lbmdem_handle* h, int slots);            /* 0: off (default) */
+int lbmdem_write_dem_async(lbmdem_handle* h, const char* dir, int nfile, int with_forces, double* energies8);
+int lbmdem_output_stats_dem(lbmdem_handle* h, long* counts4, double* ms4);
+int lbmdem_write_dem_rows(const char* dir, int nfile, int n, const double* rows, const double* stats22,
+                          int with_forces, int lx, int ly);
 /* Checkpoint / restart (absent in the reference, which cannot resume a run: SURVEY.md section 5). The file
  * holds exactly the state that defines the continuation at a renderScene() boundary -- populations,
  * current obstacle map, grain kinematics, hydrodynamic forces, Verlet lists, wall positions, step
