@@ -167,6 +167,12 @@ def _open_library(LIB_PATH):
     L.lbmdem_collide_stream_part.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_checkpoint_save.argtypes = [C.c_void_p, C.c_char_p]
     L.lbmdem_checkpoint_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+    L.lbmdem_set_async_checkpoint.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_checkpoint_save_async.argtypes = [C.c_void_p, C.c_char_p]
+    L.lbmdem_output_stats_checkpoint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_set_checkpoint_every.argtypes = [C.c_void_p, C.c_long, C.c_char_p]
+    L.lbmdem_checkpoint_digest.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
+    L.lbmdem_checkpoint_verify.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     L.lbmdem_set_force_mode.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_set_dem_chain.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_dem_chain_paints.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
@@ -418,6 +424,50 @@ class LbmDem:
         self.cfg = self.config()
         self.lx, self.ly, self.n = self.cfg.lx, self.cfg.ly, self.cfg.nbgrains
         return self
+
+    def set_async_checkpoint(self, slots=1):
+        """Checkpoints in the background: `slots` checkpoint slots (1..2) of device staging + pinned host memory of the file's
+        size; the writer thread and copy stream are those of set_async_output. 0 switches it off again (writes what is queued
+        first)."""
+        _chk(self._L.lbmdem_set_async_checkpoint(self._h, int(slots)))
+
+    def checkpoint_save_async(self, path):
+        """checkpoint_save without the wait: one snapshot kernel on the step stream, then copy and file I/O behind the run's back.
+        The file is checkpoint_save's followed by a digest trailer (checkpoint_verify); it replaces `path` atomically once
+        complete (output_drain() returns when it has). Waits for a free slot when all are in flight."""
+        _chk(self._L.lbmdem_checkpoint_save_async(self._h, os.fsencode(path)))
+
+    def set_checkpoint_every(self, every_substeps, path=None):
+        """run_scene saves a checkpoint to `path` whenever the step counter reaches a multiple of `every_substeps` -- in the
+        background when set_async_checkpoint has made slots, else synchronously; always by way of path + ".tmp" and rename.
+        0 switches it off."""
+        _chk(self._L.lbmdem_set_checkpoint_every(self._h, int(every_substeps), os.fsencode(path) if path is not None else None))
+
+    def output_stats_checkpoint(self):
+        """dict: checkpoints queued / written / failed, calls that waited for a slot; ms the caller waited for a slot, the writer
+        waited for copies, the writer spent in file I/O, callers were held in checkpoint_save_async behind their slot"""
+        c = np.zeros(4, np.int64); m = np.zeros(4)
+        _chk(self._L.lbmdem_output_stats_checkpoint(self._h, _vp(c), _vp(m)))
+        return dict(queued=int(c[0]), written=int(c[1]), failed=int(c[2]), slot_waits=int(c[3]), ms_slot_wait=float(m[0]),
+                    ms_copy_wait=float(m[1]), ms_io=float(m[2]), ms_hold=float(m[3]))
+
+    @staticmethod
+    def checkpoint_verify(path):
+        """Recompute every section of a checkpoint file against its digest trailer (host only, no device). -> True when the file
+        has a trailer and matches it, False for a file without one (checkpoint_save's); raises naming the first section that
+        differs, or for a trailer that is cut short."""
+        has = C.c_int(0)
+        _chk(load_library().lbmdem_checkpoint_verify(os.fsencode(path), C.byref(has)))
+        return bool(has.value)
+
+    @staticmethod
+    def checkpoint_digest(data):
+        """(S1, S2) of a byte string as a checkpoint section: of its little-endian uint64 words w_i (the last zero-padded)
+        S1 = sum w_i, S2 = sum (i + 1) w_i, both mod 2**64. Host only."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        out = np.zeros(2, np.uint64)
+        _chk(load_library().lbmdem_checkpoint_digest(_vp(buf) if buf.size else None, int(buf.size), _vp(out)))
+        return int(out[0]), int(out[1])
 
     @classmethod
     def from_sample(cls, path, lx, ly, **kw):

@@ -1,8 +1,10 @@
 // lbmdem_checkpoint.hip -- checkpoint / restart of a handle (the reference cannot resume a run): single domain, or one
-// file per rank of a strip decomposition with distributed grains.
+// file per rank of a strip decomposition with distributed grains; the digest trailer of the checkpoints written in the
+// background (lbmdem_checkpoint_save_async, lbmdem_output.hip), its verifier, and the cadence setting of lbmdem_run_scene.
 
 #include "lbmdem_handle.h"
 
+#include <errno.h>
 #include <sys/stat.h>
 
 #pragma GCC visibility push(default)
@@ -34,7 +36,179 @@ struct FileCloser {   // closes on every exit path, exceptions included
   FILE* fp;
   ~FileCloser() { if (fp) fclose(fp); }
 };
+static bool header_plausible(const CkptHeader& H) {
+  const lbmdem_config& hc = H.cfg;
+  return !(hc.nbgrains < 1 || hc.nbgrains > (1 << 28) || hc.lx < 3 || hc.ly < 3 || hc.lx > (1 << 24) || hc.ly > (1 << 24) ||
+           hc.x_begin < 0 || hc.x_end > hc.lx || hc.x_begin >= hc.x_end || hc.halo < 0 || hc.halo > hc.lx || hc.npDEM < 1 ||
+           H.nnbr < 0 || H.nbsteps < 0 || H.plane < 1 || (H.has_dist != 0 && H.has_dist != 1) || (H.vib != 0 && H.vib != 1));
+}
+
+// ---- the digest trailer ("LBMCKSM1") --------------------------------------------------------------------------------------
+// Behind everything lbmdem_checkpoint_save writes: magic, int nsections, int 0, then {bytes, S1, S2} per section in file order.
+// Every byte in front of the trailer belongs to exactly one section; the header is its own first section.
+typedef unsigned long long u64;
+constexpr int CKSM_SECTIONS = 1 + CKPT_DEV_SECTIONS;
+static const char* const CKSM_NAMES[CKSM_SECTIONS] = {"header", "r", "kin", "fhf", "gp", "offsets", "nbr", "wallflags", "obst", "f"};
+struct CksmEntry { u64 bytes, s1, s2; };
+struct CksmTrailer {
+  char magic[8];
+  int nsections, pad;
+  CksmEntry e[CKSM_SECTIONS];
+};
+static_assert(sizeof(CksmTrailer) == 16 + 24 * CKSM_SECTIONS, "the trailer has no padding");
+
+// THE digest routine (the writer thread, the verifier, lbmdem_checkpoint_digest): `nbytes` bytes that begin at word
+// `first_word` of their section are added to acc = {S1, S2}; a piece that ends inside a word ends the section (zero-padded)
+static void digest_add(const void* bytes, size_t nbytes, u64 first_word, u64 acc[2]) {
+  const unsigned char* p = static_cast<const unsigned char*>(bytes);
+  u64 s1 = acc[0], s2 = acc[1], i = first_word;
+  size_t k = 0;
+  for (; k + 8 <= nbytes; k += 8, ++i) {
+    u64 w;
+    memcpy(&w, p + k, 8);   // (the library runs on little-endian hosts only)
+    s1 += w;
+    s2 += (i + 1) * w;
+  }
+  if (k < nbytes) {
+    u64 w = 0;
+    memcpy(&w, p + k, nbytes - k);
+    s1 += w;
+    s2 += (i + 1) * w;
+  }
+  acc[0] = s1; acc[1] = s2;
+}
+
+// the lengths of the ten sections of a file with this header
+static void section_lengths(const CkptHeader& H, u64 len[CKSM_SECTIONS]) {
+  const CkptLayout Y = ckpt_layout(H.cfg.nbgrains, H.nnbr, H.plane);
+  len[0] = sizeof(CkptHeader);
+  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) len[1 + s] = Y.bytes[s];
+}
+
+// lbmdem_checkpoint_verify. A trailer is looked for where a complete file has it, at the very end: its presence does not hang
+// on a header that may itself be damaged, and the header is then the first section checked. A file that ends differently
+// has a trailer only if one begins right behind the sections its header announces -- cut short, then. `lenient`
+// (lbmdem_checkpoint_load's use): a file WITHOUT a trailer whose header cannot be read, or that is shorter than its header
+// claims, passes -- the loader's own checks and messages follow, as before.
+static int verify_file(const char* path, int* has_digest, bool lenient) {
+  *has_digest = 0;
+  FILE* fp = fopen(path, "rb");
+  if (!fp) return lenient ? LBMDEM_OK : fail(LBMDEM_EINVAL, "cannot open checkpoint '%s'", path);
+  FileCloser closer{fp};
+  struct stat stt{};
+  if (fstat(fileno(fp), &stt) != 0) return lenient ? LBMDEM_OK : fail(LBMDEM_EINVAL, "checkpoint '%s': cannot take its size", path);
+  const u64 size = (u64)stt.st_size;
+  CkptHeader H;
+  CksmTrailer T;
+  memset(&T, 0, sizeof T);
+  const bool at_end = size >= sizeof H + sizeof T && fseeko(fp, (off_t)(size - sizeof T), SEEK_SET) == 0 && rd(fp, &T, sizeof T) &&
+                      memcmp(T.magic, "LBMCKSM1", 8) == 0;
+  if (fseeko(fp, 0, SEEK_SET) != 0) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot rewind", path);
+  const bool have_header = rd(fp, &H, sizeof H);
+  if (at_end) {
+    *has_digest = 1;
+    u64 acc[2] = {0, 0};
+    digest_add(&H, sizeof H, 0, acc);
+    if (T.nsections != CKSM_SECTIONS || T.pad != 0 || T.e[0].bytes != sizeof H)
+      return fail(LBMDEM_EINVAL, "checkpoint '%s': its digest trailer is malformed", path);
+    if (!have_header || acc[0] != T.e[0].s1 || acc[1] != T.e[0].s2)
+      return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'header' does not match its digest (the file is torn or corrupted)", path);
+  }
+  if (!have_header || memcmp(H.magic, "LBMDEMC5", 8) != 0 || H.layout != CKPT_LAYOUT || !header_plausible(H))
+    return lenient && !at_end ? LBMDEM_OK : fail(LBMDEM_EINVAL, "'%s' is not a checkpoint of this library version", path);
+  u64 len[CKSM_SECTIONS], fixed = 0;
+  section_lengths(H, len);
+  for (int s = 0; s < CKSM_SECTIONS; ++s) fixed += len[s];
+  if (!at_end) {
+    if (size < fixed) return lenient ? LBMDEM_OK : fail(LBMDEM_EINVAL, "checkpoint '%s' is shorter than its header claims (%llu of at least %llu bytes)", path, size, fixed);
+    const u64 rest = size - fixed;
+    char head[8];
+    const size_t k = rest < 8 ? (size_t)rest : 8;
+    if (k == 0) return LBMDEM_OK;
+    if (fseeko(fp, (off_t)fixed, SEEK_SET) != 0 || !rd(fp, head, k)) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot read behind its sections", path);
+    if (memcmp(head, "LBMCKSM1", k) != 0) return LBMDEM_OK;   // (e.g. the strips' "LBMDIST1" section)
+    *has_digest = 1;
+    return fail(LBMDEM_EINVAL, "checkpoint '%s': its digest trailer is cut short (%llu of %zu bytes)", path, rest, sizeof T);
+  }
+  if (fixed + sizeof T != size)
+    return fail(LBMDEM_EINVAL, "checkpoint '%s': %llu bytes by its header and digest trailer, %llu in the file", path, fixed + (u64)sizeof T, size);
+  if (fseeko(fp, (off_t)sizeof H, SEEK_SET) != 0) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot seek", path);
+  std::vector<unsigned char> buf((size_t)1 << 22);
+  for (int s = 1; s < CKSM_SECTIONS; ++s) {
+    if (T.e[s].bytes != len[s])
+      return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' is %llu bytes long by the header and %llu by the digest trailer", path,
+                  CKSM_NAMES[s], len[s], T.e[s].bytes);
+    u64 acc[2] = {0, 0};
+    for (u64 done = 0; done < len[s];) {
+      const size_t piece = len[s] - done < buf.size() ? (size_t)(len[s] - done) : buf.size();
+      if (!rd(fp, buf.data(), piece)) return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' cannot be read", path, CKSM_NAMES[s]);
+      digest_add(buf.data(), piece, done / 8, acc);
+      done += piece;
+    }
+    if (acc[0] != T.e[s].s1 || acc[1] != T.e[s].s2)
+      return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' does not match its digest (the file is torn or corrupted)", path, CKSM_NAMES[s]);
+  }
+  return LBMDEM_OK;
+}
 }  // namespace
+
+#ifndef LBMDEM_SINGLE_PRECISION
+// ---- checkpoints in the background: the two ends of a slot's way (the middle is lbmdem_output.hip's) --------------------------
+void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned char* staging, CkptFrameJob* J) {
+  const void* src[CKPT_DEV_SECTIONS] = {h->r, h->kin[h->kcur].x1, h->fhf, h->gp, h->verlet_ok ? h->V.offsets : nullptr,
+                                        h->V.nbr, h->V.wallflags, h->obst[h->ocur], h->f[h->fcur]};
+  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) { J->src[s] = src[s]; J->bytes[s] = Y.bytes[s]; J->at[s] = Y.at[s]; }
+  J->nnbr = h->verlet_ok ? h->V.offsets + h->n : nullptr;   // (lbmdem_checkpoint_save: zero offsets, no entries without a list)
+  J->carry = h->ct.carry;
+  J->staging = staging;
+  J->gate = h->L.gate;
+}
+
+int lbmdem_ckpt_write_slot(const AsyncCkptSlot* S, const CkptLayout* Y, int n, char* msg, size_t msglen) {
+  (void)n;
+  const u64* words = reinterpret_cast<const u64*>(S->pinned);
+  const CkptShot& C = S->shot;
+  CkptHeader H;
+  memset(&H, 0, sizeof H);
+  memcpy(H.magic, "LBMDEMC5", 8);
+  H.lid6 = C.lid6;
+  H.layout = CKPT_LAYOUT; H.force_mode = C.force_mode; H.diag_always = C.diag_always;
+  H.has_carry = 1;
+  memcpy(H.carry, words + 1, sizeof H.carry);
+  H.cfg = C.cfg; H.nbsteps = C.nbsteps; H.verlet_ok = C.verlet_ok; H.nnbr = (int)words[0]; H.plane = C.plane;
+  H.has_dist = 0;
+  H.vib = C.vib;
+  CksmTrailer T;
+  memset(&T, 0, sizeof T);
+  memcpy(T.magic, "LBMCKSM1", 8);
+  T.nsections = CKSM_SECTIONS;
+  {
+    u64 acc[2] = {0, 0};
+    digest_add(&H, sizeof H, 0, acc);
+    T.e[0] = CksmEntry{sizeof H, acc[0], acc[1]};
+  }
+  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) {
+    const u64 bytes = s == CKPT_NBR ? 4 * (u64)H.nnbr : Y->bytes[s];
+    T.e[1 + s] = CksmEntry{bytes, words[4 + 2 * s], words[5 + 2 * s]};
+  }
+  char tmp[sizeof S->path + 8];
+  snprintf(tmp, sizeof tmp, "%s.tmp", S->path);
+  FILE* fp = fopen(tmp, "wb");
+  if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing: %s", tmp, strerror(errno)); return LBMDEM_EINVAL; }
+  bool ok = wr(fp, &H, sizeof H);
+  for (int s = 0; s < CKPT_DEV_SECTIONS && ok; ++s) ok = wr(fp, S->pinned + Y->at[s], (size_t)T.e[1 + s].bytes);   // exact lengths
+  if (ok) ok = wr(fp, &T, sizeof T);
+  int err = errno;
+  if (fclose(fp) != 0) { if (ok) err = errno; ok = false; }
+  if (ok && rename(tmp, S->path) != 0) { err = errno; ok = false; }
+  if (!ok) {
+    (void)remove(tmp);
+    snprintf(msg, msglen, "writing checkpoint '%s' by way of '%s' failed: %s", S->path, tmp, strerror(err));
+    return LBMDEM_EINVAL;
+  }
+  return LBMDEM_OK;
+}
+#endif
 
 int lbmdem_checkpoint_save(lbmdem_handle* h, const char* path) try {
   SP_UNAVAILABLE("checkpointing");
@@ -103,6 +277,10 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
   SP_UNAVAILABLE("checkpointing");
   if (!path || !out) return fail(LBMDEM_EINVAL, "null argument");
   *out = nullptr;
+  {   // a file that carries digests (lbmdem_checkpoint_save_async) is checked against them before anything else is done with it
+    int has_digest = 0;
+    RC_TRY(verify_file(path, &has_digest, true));
+  }
   FILE* fp = fopen(path, "rb");
   if (!fp) return fail(LBMDEM_EINVAL, "cannot open checkpoint '%s'", path);
   FileCloser closer{fp};
@@ -111,9 +289,7 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
   if (H.layout != CKPT_LAYOUT) return fail(LBMDEM_EINVAL, "checkpoint '%s' holds another device layout (%d)", path, H.layout);
   // the header is not trusted: sizes are checked before anything is allocated from them
   const lbmdem_config& hc = H.cfg;
-  if (hc.nbgrains < 1 || hc.nbgrains > (1 << 28) || hc.lx < 3 || hc.ly < 3 || hc.lx > (1 << 24) || hc.ly > (1 << 24) ||
-      hc.x_begin < 0 || hc.x_end > hc.lx || hc.x_begin >= hc.x_end || hc.halo < 0 || hc.halo > hc.lx || hc.npDEM < 1 ||
-      H.nnbr < 0 || H.nbsteps < 0 || H.plane < 1 || (H.has_dist != 0 && H.has_dist != 1) || (H.vib != 0 && H.vib != 1))
+  if (!header_plausible(H))
     return fail(LBMDEM_EINVAL, "checkpoint '%s': implausible header (grains %d, lattice %d x %d, rows [%d, %d))", path,
                 hc.nbgrains, hc.lx, hc.ly, hc.x_begin, hc.x_end);
   const int n = H.cfg.nbgrains;
@@ -201,6 +377,52 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 } catch (...) {
   return fail(LBMDEM_EINVAL, "unexpected C++ exception");
+}
+
+int lbmdem_checkpoint_digest(const void* bytes, size_t n, unsigned long long* out2) {
+  if ((!bytes && n > 0) || !out2) return fail(LBMDEM_EINVAL, "null argument");
+  u64 acc[2] = {0, 0};
+  digest_add(bytes, n, 0, acc);
+  out2[0] = acc[0]; out2[1] = acc[1];
+  return LBMDEM_OK;
+}
+
+int lbmdem_checkpoint_verify(const char* path, int* has_digest) try {
+  SP_UNAVAILABLE("checkpointing");
+  if (!path || !has_digest) return fail(LBMDEM_EINVAL, "null argument");
+  return verify_file(path, has_digest, false);
+} catch (const std::bad_alloc&) {
+  return fail(LBMDEM_ENOMEM, "host memory allocation failed");
+}
+
+int lbmdem_set_checkpoint_every(lbmdem_handle* h, long every_substeps, const char* path) {
+  SP_UNAVAILABLE("checkpointing");
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  if (every_substeps < 0) return fail(LBMDEM_EINVAL, "lbmdem_set_checkpoint_every: the cadence must be >= 0, not %ld", every_substeps);
+  if (every_substeps > 0) {
+    const LatticeView& L = h->L;
+    if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
+      return fail(LBMDEM_EINVAL, "lbmdem_set_checkpoint_every needs the whole lattice and all grains on this handle (not a strip of a "
+                                 "decomposition, no distributed grains): there every rank saves its own file with lbmdem_checkpoint_save");
+    if (!path || !*path || strlen(path) >= sizeof h->ckpt_path) return fail(LBMDEM_EINVAL, "lbmdem_set_checkpoint_every: no path, or one that is too long");
+    strcpy(h->ckpt_path, path);
+  }
+  h->ckpt_every = every_substeps;
+  return LBMDEM_OK;
+}
+
+// the cadence's save without slots (lbmdem_run_scene): lbmdem_checkpoint_save's file, by way of `<path>.tmp` and rename
+int lbmdem_ckpt_save_replacing(lbmdem_handle* h, const char* path) {
+  char tmp[sizeof h->ckpt_path + 8];
+  snprintf(tmp, sizeof tmp, "%s.tmp", path);
+  const int rc = lbmdem_checkpoint_save(h, tmp);
+  if (rc != LBMDEM_OK) { (void)remove(tmp); return rc; }
+  if (rename(tmp, path) != 0) {
+    const int err = errno;
+    (void)remove(tmp);
+    return fail(LBMDEM_EINVAL, "renaming '%s' onto '%s' failed: %s", tmp, path, strerror(err));
+  }
+  return LBMDEM_OK;
 }
 
 }  // extern "C"

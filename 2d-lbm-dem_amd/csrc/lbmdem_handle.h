@@ -94,12 +94,34 @@ struct AsyncDemSlot {
   int nfile = 0, with_forces = 0;
   double stats22[22];
 };
-// The counters of lbmdem_output_stats / lbmdem_output_stats_dem: each feature has its own set, reset when its slots change
+// A checkpoint written in the background (lbmdem_set_async_checkpoint): the same pipeline with the sections of the file
+// (k_ckpt_frame, lbm_ckptframe.hip) in place of the image, and the host's side of the header as it stood when the checkpoint
+// was queued. The pair list's length, the carries and the sections' digests come back with the copy (the staging's word area).
+struct CkptShot {
+  lbmdem_config cfg;   // incl. the clock and the walls
+  long nbsteps = 0, plane = 0;
+  double lid6 = 0;
+  int force_mode = 0, diag_always = 0, verlet_ok = 0, vib = 0;
+};
+struct AsyncCkptSlot {
+  unsigned char* staging = nullptr;   // device, CkptLayout::total bytes
+  unsigned char* pinned = nullptr;    // host, the same
+  hipEvent_t snapped = nullptr, copied = nullptr;
+  bool busy = false;                  // (under AsyncOut::mu)
+  char path[4096];
+  CkptShot shot;
+};
+// The counters of lbmdem_output_stats / lbmdem_output_stats_dem / lbmdem_output_stats_checkpoint: each feature has its own set,
+// reset when its slots change
 struct AsyncCounters {
   long queued = 0, written = 0, failed = 0, slot_waits = 0;
-  double ms_slot_wait = 0, ms_copy_wait = 0, ms_io = 0, ms_last = 0;   // ms_last: frames -- the caller in lbmdem_output_drain; tables -- the caller waiting for the 22 numbers
+  // ms_last: frames -- the caller in lbmdem_output_drain; tables -- the caller waiting for the 22 numbers; checkpoints -- the
+  // caller inside lbmdem_checkpoint_save_async behind its slot (header fields, launch, queueing)
+  double ms_slot_wait = 0, ms_copy_wait = 0, ms_io = 0, ms_last = 0;
 };
-// One per handle while either feature is on: ONE copy stream, ONE writer thread, ONE queue (strictly first in, first out:
+enum : int { ASYNC_FRAME = 0, ASYNC_TABLE = 1, ASYNC_CKPT = 2 };
+static const char* const ASYNC_KIND_NAMES[3] = {"frame", "table", "checkpoint"};
+// One per handle while any of the three features is on: ONE copy stream, ONE writer thread, ONE queue (strictly first in, first out:
 // the lines of stats.data land in call order).
 struct AsyncOut {
   int frames = 0, lx = 0, ly = 0, device = 0;
@@ -109,18 +131,21 @@ struct AsyncOut {
   AsyncDemSlot dslot[LBMDEM_ASYNC_MAX_DEM];
   double* dem_scratch = nullptr;             // device: the addends of the ten sums [10][n], then the 22 numbers (k_dem_stats)
   double* dem_stats_host = nullptr;          // pinned [22]
+  int ckpt_slots = 0;                        // lbmdem_set_async_checkpoint
+  AsyncCkptSlot cslot[LBMDEM_ASYNC_MAX_CKPT];
+  CkptLayout ckpt_layout{};                  // of the handle: n grains, the pair list at its capacity, the slab
   hipStream_t copy_stream = nullptr;
   std::thread writer;
   std::mutex mu;
   std::condition_variable cv_job, cv_free;   // writer: a job or quit; callers: a slot freed / a frame finished
-  std::deque<int> jobs;                      // in the order they were queued: frame slot s as s, table slot s as LBMDEM_ASYNC_MAX_FRAMES + s
+  std::deque<int> jobs;                      // in the order they were queued: frame slot s as s, table slot s as LBMDEM_ASYNC_MAX_FRAMES + s, checkpoint slot s behind those
   bool quit = false;
   int pending = 0;                           // queued and not yet on disk
   // the first failure of the writer since the last one was reported (the writer never touches the callers' error text)
   int err_code = 0;
-  bool err_dem = false;                      // ... was a table's
+  int err_kind = ASYNC_FRAME;                // ... was a frame's, a table's, a checkpoint's
   char err_msg[4400];
-  AsyncCounters fc, dc;                      // frames, tables
+  AsyncCounters fc, dc, cc;                  // frames, tables, checkpoints
 };
 
 struct lbmdem_handle {
@@ -228,7 +253,10 @@ struct lbmdem_handle {
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
   ProbeState probe;
-  AsyncOut* aout = nullptr;   // null: frames and tables are written synchronously (the default)
+  AsyncOut* aout = nullptr;   // null: frames, tables and checkpoints are written synchronously (the default)
+  // lbmdem_set_checkpoint_every: lbmdem_run_scene saves to ckpt_path whenever the step counter reaches a multiple (0: never)
+  long ckpt_every = 0;
+  char ckpt_path[4096] = "";
   // KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM of lbmdem_run_scene: its "steps" line prints them (main.c:1885-1889)
   double scene_energies[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int force_mode = 0;
@@ -380,6 +408,13 @@ LBMDEM_INTERNAL void lbmdem_probe_release(lbmdem_handle* h);
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);
 static inline bool async_frames_on(const lbmdem_handle* h) { return h->aout && h->aout->frames > 0; }
 static inline bool async_dem_on(const lbmdem_handle* h) { return h->aout && h->aout->dem_slots > 0; }
+static inline bool async_ckpt_on(const lbmdem_handle* h) { return h->aout && h->aout->ckpt_slots > 0; }
+// lbmdem_checkpoint.hip, for the background writer (lbmdem_output.hip): what a slot's launch reads, and the file of a slot
+// whose copy has arrived -- header, sections, digest trailer to `<path>.tmp`, then renamed onto `<path>`; on failure the text
+// goes to `msg`, the .tmp file is removed and `<path>` is not touched
+LBMDEM_INTERNAL void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned char* staging, CkptFrameJob* J);
+LBMDEM_INTERNAL int lbmdem_ckpt_save_replacing(lbmdem_handle* h, const char* path);
+LBMDEM_INTERNAL int lbmdem_ckpt_write_slot(const AsyncCkptSlot* S, const CkptLayout* Y, int n, char* msg, size_t msglen);
 LBMDEM_INTERNAL int lbmdem_async_report(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {

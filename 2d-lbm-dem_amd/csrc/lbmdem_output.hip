@@ -1,7 +1,8 @@
 // lbmdem_output.hip -- the reference's file outputs over the C ABI: write_vtk (main.c:237-338 + visit_writer's binary
 // rectilinear path), write_DEM (main.c:340-438: DEM%06d.dat, stats.data), write_forces (main.c:440-478), the per-grain
-// diagnostics table they print, the merged-strip forms of the VTK writer, and the frames and tables written in the background
-// (lbmdem_set_async_output, lbmdem_set_async_dem: snapshot kernels, copy stream, writer thread).
+// diagnostics table they print, the merged-strip forms of the VTK writer, and the frames, tables and checkpoints written in the
+// background (lbmdem_set_async_output, lbmdem_set_async_dem, lbmdem_set_async_checkpoint: snapshot kernels, copy stream, writer
+// thread).
 
 #include "lbmdem_handle.h"
 
@@ -480,19 +481,28 @@ static void async_writer(AsyncOut* a) {
       job = a->jobs.front();
       a->jobs.pop_front();
     }
-    const bool dem = job >= LBMDEM_ASYNC_MAX_FRAMES;
-    AsyncSlot* F = dem ? nullptr : &a->slot[job];
+    const int kind = job >= LBMDEM_ASYNC_MAX_FRAMES + LBMDEM_ASYNC_MAX_DEM ? ASYNC_CKPT : (job >= LBMDEM_ASYNC_MAX_FRAMES ? ASYNC_TABLE : ASYNC_FRAME);
+    const bool dem = kind == ASYNC_TABLE;
+    AsyncSlot* F = kind == ASYNC_FRAME ? &a->slot[job] : nullptr;
     AsyncDemSlot* D = dem ? &a->dslot[job - LBMDEM_ASYNC_MAX_FRAMES] : nullptr;
+    AsyncCkptSlot* K = kind == ASYNC_CKPT ? &a->cslot[job - LBMDEM_ASYNC_MAX_FRAMES - LBMDEM_ASYNC_MAX_DEM] : nullptr;
     char msg[sizeof a->err_msg];
     int code = LBMDEM_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = hipEventSynchronize(dem ? D->copied : F->copied);
+    const hipError_t e = hipEventSynchronize(K ? K->copied : (dem ? D->copied : F->copied));
     const double ms_copy = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
-    if (e != hipSuccess) {
+    if (e != hipSuccess && K) {
+      snprintf(msg, sizeof msg, "checkpoint '%.4000s': the copy to host memory failed: %s", K->path, hipGetErrorString(e));
+      code = LBMDEM_EHIP;
+    } else if (e != hipSuccess) {
       snprintf(msg, sizeof msg, "%s %d: the copy to host memory failed: %s", dem ? "table" : "frame", dem ? D->nfile : F->nfile,
                hipGetErrorString(e));
       code = LBMDEM_EHIP;
+#ifndef LBMDEM_SINGLE_PRECISION
+    } else if (K) {
+      code = lbmdem_ckpt_write_slot(K, &a->ckpt_layout, a->n, msg, sizeof msg);
+#endif
     } else if (dem) {
       code = write_dem_rows_files(D->dir, D->nfile, a->n, D->pinned, D->stats22, D->with_forces, a->lx, a->ly, msg, sizeof msg);
     } else {
@@ -501,15 +511,15 @@ static void async_writer(AsyncOut* a) {
     const double ms_io = ms_since(t1);
     {
       std::lock_guard<std::mutex> lk(a->mu);
-      AsyncCounters& C = dem ? a->dc : a->fc;
+      AsyncCounters& C = K ? a->cc : (dem ? a->dc : a->fc);
       C.ms_copy_wait += ms_copy;
       C.ms_io += ms_io;
       if (code == LBMDEM_OK) C.written++;
       else {
         C.failed++;
-        if (!a->err_code) { a->err_code = code; a->err_dem = dem; memcpy(a->err_msg, msg, sizeof msg); }
+        if (!a->err_code) { a->err_code = code; a->err_kind = kind; memcpy(a->err_msg, msg, sizeof msg); }
       }
-      if (dem) D->busy = false; else F->busy = false;
+      if (K) K->busy = false; else if (dem) D->busy = false; else F->busy = false;
       a->pending--;
     }
     a->cv_free.notify_all();
@@ -545,9 +555,23 @@ static void async_free_dem(AsyncOut* a) {
   a->dc = AsyncCounters{};
 }
 
+static void async_free_ckpt(AsyncOut* a) {
+  for (AsyncCkptSlot& S : a->cslot) {
+    if (S.staging) (void)hipFree(S.staging);
+    if (S.pinned) (void)hipHostFree(S.pinned);
+    if (S.snapped) (void)hipEventDestroy(S.snapped);
+    if (S.copied) (void)hipEventDestroy(S.copied);
+    S.staging = S.pinned = nullptr;
+    S.snapped = S.copied = nullptr;
+  }
+  a->ckpt_slots = 0;
+  a->cc = AsyncCounters{};
+}
+
 static void async_free(AsyncOut* a) {
   async_free_frames(a);
   async_free_dem(a);
+  async_free_ckpt(a);
   if (a->copy_stream) (void)hipStreamDestroy(a->copy_stream);
   delete a;
 }
@@ -570,20 +594,19 @@ int lbmdem_async_report(lbmdem_handle* h) {
   AsyncOut* a = h->aout;
   if (!a) return LBMDEM_OK;
   char msg[sizeof a->err_msg];
-  int code;
-  bool dem;
+  int code, kind;
   {
     std::lock_guard<std::mutex> lk(a->mu);
     code = a->err_code;
     if (code == LBMDEM_OK) return LBMDEM_OK;
     memcpy(msg, a->err_msg, sizeof msg);
-    dem = a->err_dem;
+    kind = a->err_kind;
     a->err_code = LBMDEM_OK;
   }
-  return fail(code, "background %s writer: %s", dem ? "table" : "frame", msg);
+  return fail(code, "background %s writer: %s", ASYNC_KIND_NAMES[kind], msg);
 }
 
-// What both features share -- the AsyncOut, its copy stream and its writer thread -- made when the first of them is switched on
+// What the three features share -- the AsyncOut, its copy stream and its writer thread -- made when the first of them is switched on
 static int async_ensure(lbmdem_handle* h, const char* who) {
   if (h->aout) return LBMDEM_OK;
   AsyncOut* a = new (std::nothrow) AsyncOut;
@@ -607,19 +630,19 @@ static int async_ensure(lbmdem_handle* h, const char* who) {
 
 // Before the slots of a feature change: everything queued is on disk (the writer sleeps, no slot is in use), and a failure
 // of the writer that nobody has been told about is taken out -- it is what the call returns once the request is carried out.
-struct AsyncOldError { int code = LBMDEM_OK; bool dem = false; char msg[sizeof AsyncOut::err_msg]; };
+struct AsyncOldError { int code = LBMDEM_OK; int kind = ASYNC_FRAME; char msg[sizeof AsyncOut::err_msg]; };
 static void async_settle(AsyncOut* a, AsyncOldError* old) {
   if (!a) return;
   std::unique_lock<std::mutex> lk(a->mu);
   a->cv_free.wait(lk, [&] { return a->pending == 0; });
   old->code = a->err_code;
-  old->dem = a->err_dem;
+  old->kind = a->err_kind;
   if (old->code != LBMDEM_OK) memcpy(old->msg, a->err_msg, sizeof old->msg);
   a->err_code = LBMDEM_OK;
 }
 static int async_settled(lbmdem_handle* h, const AsyncOldError& old) {
-  if (h->aout && !h->aout->frames && !h->aout->dem_slots) lbmdem_async_release(h);   // the last feature went off
-  if (old.code != LBMDEM_OK) return fail(old.code, "background %s writer: %s", old.dem ? "table" : "frame", old.msg);
+  if (h->aout && !h->aout->frames && !h->aout->dem_slots && !h->aout->ckpt_slots) lbmdem_async_release(h);   // the last feature went off
+  if (old.code != LBMDEM_OK) return fail(old.code, "background %s writer: %s", ASYNC_KIND_NAMES[old.kind], old.msg);
   return LBMDEM_OK;
 }
 
@@ -929,6 +952,118 @@ int lbmdem_output_stats_dem(lbmdem_handle* h, long* counts4, double* ms4) {
     std::lock_guard<std::mutex> lk(a->mu);
     c[0] = a->dc.queued; c[1] = a->dc.written; c[2] = a->dc.failed; c[3] = a->dc.slot_waits;
     m[0] = a->dc.ms_slot_wait; m[1] = a->dc.ms_copy_wait; m[2] = a->dc.ms_io; m[3] = a->dc.ms_last;
+  }
+  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
+  return LBMDEM_OK;
+}
+
+// ---- checkpoints in the background -------------------------------------------------------------------------------------------------
+
+int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots) {
+  SP_UNAVAILABLE("checkpointing");
+#ifndef LBMDEM_SINGLE_PRECISION
+  CHECK_H(h);
+  if (slots < 0 || slots > LBMDEM_ASYNC_MAX_CKPT)
+    return fail(LBMDEM_EINVAL, "lbmdem_set_async_checkpoint: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_CKPT, slots);
+  if (slots > 0) CHECK_WHOLE_LATTICE_OR(h, "lbmdem_set_async_checkpoint", "there every rank saves its own file with lbmdem_checkpoint_save");
+  if ((h->aout ? h->aout->ckpt_slots : 0) == slots) return LBMDEM_OK;
+  AsyncOldError old;
+  async_settle(h->aout, &old);
+  if (h->aout) async_free_ckpt(h->aout);
+  if (slots > 0) {
+    RC_TRY(async_ensure(h, "lbmdem_set_async_checkpoint"));
+    AsyncOut* a = h->aout;
+    a->ckpt_layout = ckpt_layout(h->n, h->V.cap, h->L.plane);
+    const size_t bytes = a->ckpt_layout.total;
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < slots && e == hipSuccess; ++s) {
+      AsyncCkptSlot& S = a->cslot[s];
+      e = hipMalloc((void**)&S.staging, bytes);
+      if (e == hipSuccess) e = hipHostMalloc((void**)&S.pinned, bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      async_free_ckpt(a);
+      (void)async_settled(h, AsyncOldError{});
+      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_checkpoint: %d checkpoint slots of %zu bytes (device staging + pinned host memory "
+                                 "each) cannot be had: %s", slots, bytes, hipGetErrorString(e));
+    }
+    a->ckpt_slots = slots;
+  }
+  return async_settled(h, old);
+#endif
+}
+
+int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
+  SP_UNAVAILABLE("checkpointing");
+#ifndef LBMDEM_SINGLE_PRECISION
+  CHECK_H(h);   // (a launch of k_dem_chain that gave up is undone and replayed here: the checkpoint is the confirmed state's)
+  if (!async_ckpt_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: checkpoints in the background are off (lbmdem_set_async_checkpoint)");
+  AsyncOut* a = h->aout;
+  CHECK_NOT_SPLIT(h);
+  CHECK_WHOLE_LATTICE_OR(h, "lbmdem_checkpoint_save_async", "there every rank saves its own file with lbmdem_checkpoint_save");
+  if (!path || !*path) return fail(LBMDEM_EINVAL, "null path");
+  if (strlen(path) >= sizeof a->cslot[0].path) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: path too long");
+  if (h->obst_pending) return fail(LBMDEM_EINVAL, "checkpoint between obst_construction and collide_stream");
+  RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
+  int s = -1;
+  {
+    std::unique_lock<std::mutex> lk(a->mu);
+    auto free_slot = [&] { for (int k = 0; k < a->ckpt_slots; ++k) if (!a->cslot[k].busy) return k; return -1; };
+    if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop a checkpoint
+      const auto t0 = std::chrono::steady_clock::now();
+      a->cc.slot_waits++;
+      a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
+      a->cc.ms_slot_wait += ms_since(t0);
+    }
+    a->cslot[s].busy = true;
+  }
+  const auto t_hold = std::chrono::steady_clock::now();
+  AsyncCkptSlot& S = a->cslot[s];
+  strcpy(S.path, path);
+  // the host's side of the header, as of now: the run goes on behind this call
+  S.shot.cfg = h->cfg; S.shot.nbsteps = h->nbsteps; S.shot.plane = h->L.plane; S.shot.lid6 = h->L.lid6;
+  S.shot.force_mode = h->force_mode; S.shot.diag_always = h->diag_always ? 1 : 0; S.shot.verlet_ok = h->verlet_ok ? 1 : 0;
+  S.shot.vib = h->vib ? 1 : 0;
+  if (h->carry_from < h->substep_seq) launch_carry_resolve(h->ct, h->carry_from, h->stream);   // as lbmdem_checkpoint_save
+  CkptFrameJob J;
+  lbmdem_ckpt_frame_job(h, a->ckpt_layout, S.staging, &J);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemsetAsync(S.staging, 0, CKPT_WORDS_BYTES, h->stream);   // the digests are sums: from zero
+  if (e == hipSuccess) { launch_ckpt_frame(J, h->stream); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipEventRecord(S.snapped, h->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, a->ckpt_layout.total, hipMemcpyDeviceToHost, a->copy_stream);
+  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
+    { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
+    a->cv_free.notify_all();
+    HIP_TRY(e);
+  }
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    a->jobs.push_back(LBMDEM_ASYNC_MAX_FRAMES + LBMDEM_ASYNC_MAX_DEM + s);
+    a->pending++;
+    a->cc.queued++;
+    a->cc.ms_last += ms_since(t_hold);
+  }
+  a->cv_job.notify_one();
+  return LBMDEM_OK;
+#endif
+}
+
+int lbmdem_output_stats_checkpoint(lbmdem_handle* h, long* counts4, double* ms4) {
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  AsyncOut* a = h->aout;
+  long c[4] = {0, 0, 0, 0};
+  double m[4] = {0, 0, 0, 0};
+  if (a) {
+    std::lock_guard<std::mutex> lk(a->mu);
+    c[0] = a->cc.queued; c[1] = a->cc.written; c[2] = a->cc.failed; c[3] = a->cc.slot_waits;
+    m[0] = a->cc.ms_slot_wait; m[1] = a->cc.ms_copy_wait; m[2] = a->cc.ms_io; m[3] = a->cc.ms_last;
   }
   for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
   return LBMDEM_OK;

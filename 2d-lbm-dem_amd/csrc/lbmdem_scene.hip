@@ -2,7 +2,9 @@
 // (main.c:1879-1890) with everything renderScene hangs on the step counter besides the step itself -- check_density's
 // console line (main.c:1715), write_vtk (main.c:1767-1772), write_DEM / write_forces (main.c:1773-1776), the "steps" line
 // (main.c:1884-1889). The cadences live in ONE place, the Cadence struct below: lbmdem_scene_schedule lists the events,
-// lbmdem_run_scene walks the same list and hands the sub-steps between two events to the run loop in one piece.
+// lbmdem_run_scene walks the same list and hands the sub-steps between two events to the run loop in one piece. A handle with
+// lbmdem_set_checkpoint_every has one more stop that is no event of the schedule: the step counters that are multiples of its
+// cadence, where the loop saves a checkpoint behind whatever else that sub-step brings.
 
 #include "lbmdem_handle.h"
 
@@ -124,8 +126,13 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
     if (comm) return lbmdem_comm_run(h, comm, k);
     return sc->fluid ? lbmdem_run(h, k) : lbmdem_run_dem(h, k);
   };
+  const long ck = comm ? 0 : h->ckpt_every;   // lbmdem_set_checkpoint_every: single-domain runs
   for (long s = first; s < end && !stopped;) {
-    const long e = cad.next(s, end);
+    long e = cad.next(s, end);
+    if (ck > 0) {   // the sub-step that brings the counter to the next multiple of the cadence ends a stretch as well
+      const long c = (s + ck) / ck * ck - 1;
+      if (c < e) e = c;
+    }
     if (e >= end) { RC_TRY(stretch(end - s)); break; }
     if (cad.console(e)) {
       // check_density is printed between the fluid step of sub-step e and the rest of it (main.c:1710-1718): the phases
@@ -171,6 +178,10 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
                s * cfg.dt, E[0], E[1], E[2], E[4], E[5], E[6], E[7], asctime(localtime(&now)));
       say(text);
     }
+    if (ck > 0 && s % ck == 0) {   // behind the sub-step's other events; in the background where slots exist
+      if (async_ckpt_on(h)) RC_TRY(lbmdem_checkpoint_save_async(h, h->ckpt_path));
+      else RC_TRY(lbmdem_ckpt_save_replacing(h, h->ckpt_path));
+    }
     if (cad.stops(e)) stopped = 1;   // main.c:1890
   }
   if (res) {
@@ -183,8 +194,8 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
   return LBMDEM_OK;
 }
 
-// With frames or tables in the background (lbmdem_set_async_output, lbmdem_set_async_dem) the loop's VTK and DEM events are
-// only queued: the files of the schedule exist when the call returns, so it drains first -- also when the loop ends early with an error, which is then the one
+// With frames, tables or checkpoints in the background (lbmdem_set_async_output, lbmdem_set_async_dem,
+// lbmdem_set_async_checkpoint) the loop's VTK and DEM events and its cadence checkpoints are only queued: the files of the schedule exist when the call returns, so it drains first -- also when the loop ends early with an error, which is then the one
 // returned; otherwise a failure of the writer is.
 int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
   const int rc = run_scene_loop(h, comm, n, sc, res);

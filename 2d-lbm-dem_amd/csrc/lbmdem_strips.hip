@@ -83,6 +83,7 @@ int lbmdem_dist_enable(lbmdem_handle* h, int margin_rows) try {
   if (h->probe.on) return fail(LBMDEM_EINVAL, "probes are not available with distributed grains (lbmdem_probe_disable first)");
   if (async_frames_on(h)) return fail(LBMDEM_EINVAL, "frames in the background are not available with distributed grains (lbmdem_set_async_output(h, 0) first)");
   if (async_dem_on(h)) return fail(LBMDEM_EINVAL, "tables in the background are not available with distributed grains (lbmdem_set_async_dem(h, 0) first)");
+  if (async_ckpt_on(h) || h->ckpt_every > 0) return fail(LBMDEM_EINVAL, "checkpoints in the background or on a cadence are not available with distributed grains (lbmdem_set_async_checkpoint(h, 0), lbmdem_set_checkpoint_every(h, 0, NULL) first)");
   if (!h->fs.tab) return fail(LBMDEM_EINVAL, "distributed grains need the link-sum table (reductionR < 1, < 2^18 grains)");
   const int M = margin_rows > 0 ? margin_rows : lbmdem_dist_default_margin(h);
   const bool cut_lo = c.x_begin > 0, cut_hi = c.x_end < c.lx;

@@ -30,6 +30,13 @@
  * I/O happen on the writer thread; same files. Waited for before `time:` like the frames. With --run-stats one more line,
  * `async_dem: queued Q written W failed F slot_waits S ms_slot_wait .. ms_copy_wait .. ms_io .. ms_stats_wait ..`
  * (lbmdem_output_stats_dem). Single GPU only.
+ * --checkpoint-every N (needs --checkpoint FILE): FILE is also written whenever the step counter reaches a multiple of N DEM
+ * steps (lbmdem_set_checkpoint_every), always by way of FILE.tmp and rename: FILE is a complete checkpoint at every instant.
+ * --async-checkpoint [N]: those checkpoints and the final one are snapshotted by one kernel and written in the background
+ * (lbmdem_set_async_checkpoint, N = 1..2 slots, default 1), with a digest trailer that --restart checks. With --run-stats one more
+ * line, `async_checkpoint: queued Q written W failed F slot_waits S ms_slot_wait .. ms_copy_wait .. ms_io .. ms_hold ..`
+ * (lbmdem_output_stats_checkpoint). Both single GPU only. --verify-checkpoint FILE: checks FILE against its digests without a
+ * GPU and exits: 0 for a file that matches or has no digests, 1 with the section that differs.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -53,6 +60,8 @@
 static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_stats = 0;
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
+static int g_async_ckpt = 0;     /* --async-checkpoint [N] */
+static long g_ckpt_every = 0;    /* --checkpoint-every N */
 /* the optional count behind --async-output: all digits */
 static int is_count(const char* s) {
   if (!s || !*s) return 0;
@@ -145,7 +154,7 @@ static int check_decomposition(int argc, char** argv, int gpus) {
     else if (!strcmp(argv[a], "--ly") && a + 1 < argc) ly = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--scale") && a + 1 < argc) scale = atof(argv[++a]);
     else if (argv[a][0] == '-' && argv[a][1] == '-' && strcmp(argv[a], "--comm") && strcmp(argv[a], "--dry") &&
-             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && strcmp(argv[a], "--async-output") && strcmp(argv[a], "--async-dem") && a + 1 < argc) ++a;
+             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && strcmp(argv[a], "--async-output") && strcmp(argv[a], "--async-dem") && strcmp(argv[a], "--async-checkpoint") && a + 1 < argc) ++a;
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
   }
   if (!sample) return 0;   /* run() prints the usage line */
@@ -186,6 +195,14 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--async-output")) g_async_frames = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--async-dem")) g_async_dem = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
+    if (!strcmp(argv[a], "--async-checkpoint")) g_async_ckpt = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 1;
+    if (!strcmp(argv[a], "--checkpoint-every") && a + 1 < argc) g_ckpt_every = atol(argv[a + 1]);
+    if (!strcmp(argv[a], "--verify-checkpoint") && a + 1 < argc) {   /* host only: no device is touched */
+      int has = 0;
+      if (lbmdem_checkpoint_verify(argv[a + 1], &has) != LBMDEM_OK) { fprintf(stderr, "verify-checkpoint: %s\n", lbmdem_last_error()); return EXIT_FAILURE; }
+      printf("%s: %s\n", argv[a + 1], has ? "every section matches its digest" : "no digests (written by lbmdem_checkpoint_save)");
+      return 0;
+    }
     if (!strcmp(argv[a], "--comm-timeout") && a + 1 < argc) g_comm_timeout = atof(argv[a + 1]);
     if (!strcmp(argv[a], "--devices") && a + 1 < argc) {
       for (const char* p = argv[a + 1]; *p && g_ndevices < 64;) {
@@ -204,6 +221,8 @@ int main(int argc, char** argv) {
   if (probes && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--probes is a single-GPU mode (the probes are not available on strips)\n"); return EXIT_FAILURE; }
   if (g_async_frames && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-output is a single-GPU mode (with --gpus N rank 0 merges the strips' columns and writes the frames itself)\n"); return EXIT_FAILURE; }
   if (g_async_dem && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-dem is a single-GPU mode (with --gpus N rank 0 runs the table sub-step on a full replica and writes the tables itself)\n"); return EXIT_FAILURE; }
+  if ((g_async_ckpt || g_ckpt_every) && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--checkpoint-every and --async-checkpoint are single-GPU modes (with --gpus N every rank saves its own file at the end)\n"); return EXIT_FAILURE; }
+  if (g_ckpt_every < 0) { fprintf(stderr, "--checkpoint-every N: a number of DEM steps\n"); return EXIT_FAILURE; }
   if (gpus <= 1) return run(argc, argv);
   g_world = gpus; g_use_comm = 1;
   { /* every strip must be at least one margin wide (lbmdem_dist_enable would refuse on the ranks whose strip is one
@@ -338,6 +357,8 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--async-output")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--async-dem")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
+    else if (!strcmp(argv[a], "--async-checkpoint")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
+    else if (!strcmp(argv[a], "--checkpoint-every") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (!strcmp(argv[a], "--probes") && a + 1 < argc) probe_path = argv[++a];
@@ -355,9 +376,10 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --probes FILE --probe-every K --probe-row Y --probe-point X,Y]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
+  if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
   SAY("Opening file : %s\n", sample);
 
   int n = 0;
@@ -416,6 +438,8 @@ static int run(int argc, char** argv) {
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */
   if (g_async_dem) DIE(lbmdem_set_async_dem(h, g_async_dem), "set_async_dem");
+  if (g_async_ckpt) DIE(lbmdem_set_async_checkpoint(h, g_async_ckpt), "set_async_checkpoint");
+  if (g_ckpt_every > 0) DIE(lbmdem_set_checkpoint_every(h, g_ckpt_every, ckpt_out), "set_checkpoint_every");
   lbmdem_comm* comm = NULL;
   if (g_use_comm) {
     unsigned char id[LBMDEM_COMM_ID_BYTES];
@@ -480,7 +504,17 @@ static int run(int argc, char** argv) {
   clock_gettime(CLOCK_MONOTONIC, &t1);
   if (ckpt_out) {
     if (comm) DIE(lbmdem_comm_sync_carries(h, comm), "comm_sync_carries");
-    DIE(lbmdem_checkpoint_save(h, ckpt_out), "checkpoint_save");
+    if (g_async_ckpt) {   /* the same way as the periodic ones: snapshot, background write with digests, rename */
+      DIE(lbmdem_checkpoint_save_async(h, ckpt_out), "checkpoint_save_async");
+      DIE(lbmdem_output_drain(h), "output_drain");
+    } else if (g_ckpt_every > 0) {   /* FILE holds a periodic checkpoint: replaced only by a complete one */
+      char tmp[4200];
+      snprintf(tmp, sizeof tmp, "%s.tmp", ckpt_out);
+      DIE(lbmdem_checkpoint_save(h, tmp), "checkpoint_save");
+      if (rename(tmp, ckpt_out) != 0) { perror(ckpt_out); return EXIT_FAILURE; }
+    } else {
+      DIE(lbmdem_checkpoint_save(h, ckpt_out), "checkpoint_save");
+    }
   }
   double sum = serial_density(h, comm);
   double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
@@ -508,6 +542,13 @@ static int run(int argc, char** argv) {
         double oms[4];
         DIE(lbmdem_output_stats(h, oc, oms), "output_stats");
         fprintf(stderr, "async_output: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_drain %.3f\n",
+                oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
+      }
+      if (g_async_ckpt) {
+        long oc[4];
+        double oms[4];
+        DIE(lbmdem_output_stats_checkpoint(h, oc, oms), "output_stats_checkpoint");
+        fprintf(stderr, "async_checkpoint: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_hold %.3f\n",
                 oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
       }
       if (g_async_dem) {

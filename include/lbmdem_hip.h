@@ -455,6 +455,41 @@ int lbmdem_write_dem_rows(const char* dir, int nfile, int n, const double* rows,
  * run. load creates a new handle on `device`. */
 int lbmdem_checkpoint_save(lbmdem_handle* h, const char* path);
 int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out);
+/* Checkpoints on a cadence, written in the background, replaced atomically, with digests. lbmdem_set_async_checkpoint(h,
+ * slots), slots in 1..LBMDEM_ASYNC_MAX_CKPT, sets up that many checkpoint slots (device staging + pinned host memory of the
+ * file's size, the pair list at its capacity) on the copy stream, writer thread and queue of lbmdem_set_async_output; 0
+ * switches it off again (writes what is queued first); off is the default, and then nothing is allocated.
+ * lbmdem_checkpoint_save_async settles the handle like lbmdem_checkpoint_save, takes a free slot -- when none is free it waits
+ * for the writer, a checkpoint is never dropped --, notes the host's side of the header as it stands, gathers every
+ * device-resident section into the slot with ONE kernel on the handle's stream (which also adds up the sections' digests and
+ * reads the pair list's length and the carries on the device), queues the copy to host memory behind it on the copy stream
+ * and returns without synchronising: nothing stepped afterwards reaches the file. The writer thread writes `<path>.tmp`,
+ * closes it and renames it onto `<path>`: at every instant `<path>` is the previous complete checkpoint or the new one; on
+ * failure the .tmp file is removed and `<path>` is not touched. The failure is handed over like a frame's or a table's: returned
+ * once by the next lbmdem_*_async call (which then queues nothing), lbmdem_output_drain or lbmdem_run_scene.
+ * The file is lbmdem_checkpoint_save's, byte for byte, followed by a digest trailer: "LBMCKSM1", int nsections (10), int 0,
+ * then per section {uint64 bytes, uint64 S1, uint64 S2} in file order -- header, r, kin, fhf, gp, offsets, nbr, wallflags,
+ * obst, f. Of a section's little-endian 64-bit words w_0 .. w_{W-1} (the last zero-padded) S1 = sum w_i and S2 = sum (i + 1)
+ * w_i, both mod 2^64: lbmdem_checkpoint_digest (host only). lbmdem_checkpoint_verify (host only, no device) recomputes every
+ * section of a file against its trailer: LBMDEM_EINVAL naming the first section that differs, or for a trailer that is cut
+ * short; LBMDEM_OK with *has_digest = 0 for a file without a trailer (lbmdem_checkpoint_save's). lbmdem_checkpoint_load verifies a
+ * file that has a trailer first and refuses it when it does not match; a file without one loads as before.
+ * lbmdem_set_checkpoint_every(h, every_substeps, path): on such a handle lbmdem_run_scene (comm = NULL) ends a stretch at
+ * every step counter that is a multiple of every_substeps and saves to `path` there, after that sub-step's other events --
+ * through lbmdem_checkpoint_save_async when slots exist, else with lbmdem_checkpoint_save by way of `<path>.tmp` and rename -- and
+ * drains before it returns. Its schedule, console lines and other files are unchanged. 0 is off (the default).
+ * lbmdem_output_stats_checkpoint: as lbmdem_output_stats; ms4[3] is the time callers spent in lbmdem_checkpoint_save_async
+ * behind their slot. LBMDEM_EINVAL: slots outside 0..2, lbmdem_checkpoint_save_async while off, a strip of a decomposition or
+ * distributed grains (and lbmdem_dist_enable on a handle that has either setting on), the single-precision library (it has no
+ * checkpoints). LBMDEM_ENOMEM: the slots cannot be had (then the feature is off). Vibrating and probing handles have it. A
+ * checkpoint carries neither setting. */
+#define LBMDEM_ASYNC_MAX_CKPT 2
+int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots);     /* 0: off (default) */
+int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path);
+int lbmdem_output_stats_checkpoint(lbmdem_handle* h, long* counts4, double* ms4);
+int lbmdem_set_checkpoint_every(lbmdem_handle* h, long every_substeps, const char* path);   /* 0: off (default) */
+int lbmdem_checkpoint_digest(const void* bytes, size_t n, unsigned long long* out2);      /* S1, S2 */
+int lbmdem_checkpoint_verify(const char* path, int* has_digest);
 long lbmdem_nbsteps(lbmdem_handle* h);
 int lbmdem_set_nbsteps(lbmdem_handle* h, long n);
 int lbmdem_get_config(lbmdem_handle* h, lbmdem_config* out);
