@@ -6,11 +6,14 @@ import numpy as np
 import samples
 
 
-def run_case(pkg, po, seed):
+def run_case(pkg, po, seed, shape=None):
     """Returns (description, ok, grain-steps served by the table, by the gather queue, oracle's act anomalies); ok is
-    None when the case could not be built."""
+    None when the case could not be built. shape = (lx, ly): that lattice in place of the drawn one (the draws are still
+    made: a seed gives the same case as before otherwise)."""
     rng = np.random.default_rng(seed)
     lx = int(rng.choice([384, 512, 640])); ly = int(rng.choice([256, 320, 448]))
+    if shape is not None:
+        lx, ly = int(shape[0]), int(shape[1])
     rmin = float(rng.choice([0.3, 0.5, 0.7])); rmax = rmin + float(rng.choice([0.1, 0.4, 0.8]))
     overlap = float(rng.choice([4e-3, 0.05, 0.3]))           # up to 0.3 mm: reduced discs of neighbours overlap
     n = int(rng.integers(200, 1500))

@@ -8,6 +8,7 @@ reference's .data units, initial perturbation seeds) and the reference's outputs
 reference's source.
 
     python tests/golden/make_golden.py            # regenerate every fixture
+    python tests/golden/make_golden.py --shapes   # only the odd-shape cases S_* (fp64 and float) and vtk_S_61x59/
 
 Each case runs in its own process (the reference keeps its state in file-scope globals).
 Large arrays are stored as a strided sample plus the SHA-256 of the full little-endian float64
@@ -81,7 +82,26 @@ def cases():
     x = np.concatenate([x, [0.6 - 0.002, 20.0, 64 - 0.8 + 0.002, 30.0]])
     y = np.concatenate([y, [30.0, 0.7 - 0.003, 10.0, 48 - 0.9 + 0.003]])
     c["G5_dem_64x48"] = dict(kind="dem", lx=64, ly=48, r_mm=r, x_mm=x, y_mm=y, seed=505, dumps=(1, 120, 240))
+    # S: odd and ragged lattice shapes, fully coupled and agitated. lx % 8 = 1 ... 7 (a last segment of the fused kernel's row
+    # march that is short, down to one row) and ly % 60 in {0, 1, 2, 3, 17, 59} (a last 60-column window that produces the wall
+    # column alone, one or two interior columns and the wall, or is one column short of full); ly is no multiple of 16 or 32
+    # (the padded row pitch of the double and of the float build). Where the lattice is at least 60 nodes wide (lx >= 60: all but
+    # 13 x 61 and 33 x 62, which hold six grains each), grains 0-3 are pushed into the left, bottom, right and top walls so that
+    # the lattice clamp clips a disc at every edge.
+    for lx, ly in SHAPES:
+        seed = SHAPE_SEEDS.get((lx, ly), 1000 * lx + ly)
+        r, x, y = samples.row_packing(lx, ly, 400, seed=seed, margin=0.05)
+        if len(r) < 3:       # 13 rows = 1.3 mm: only small grains fit
+            r, x, y = samples.row_packing(lx, ly, 400, seed=seed, margin=0.05, rmin=0.3, rmax=0.45)
+        elif lx >= 60:
+            x[0], y[1], x[2], y[3] = 0.35, 0.35, 0.1 * lx - 0.35, 0.1 * ly - 0.35
+        c[f"S_{lx}x{ly}"] = dict(kind="shape", lx=lx, ly=ly, r_mm=r, x_mm=x, y_mm=y, seed=7, dumps=SHAPE_DUMPS)
     return c
+
+
+SHAPES = ((13, 61), (33, 62), (61, 59), (67, 60), (98, 119), (100, 63), (126, 77), (127, 121), (75, 183), (203, 122))
+SHAPE_SEEDS = {(61, 59): 61061}     # 1000 lx + ly packs 10 grains there; the checkpoint tests want an odd count (11)
+SHAPE_DUMPS = (1, 3, 6)      # whole fluid periods (npDEM sub-steps each); the run ends 5 sub-steps after the last
 
 
 def kin_table(case):
@@ -99,6 +119,13 @@ def dem_initial_kinematics(case):
     k = kin_table(case)
     rng = np.random.default_rng(case["seed"])
     k[:, 3:6] = rng.normal(0, 1, (len(k), 3)) * [0.05, 0.05, 30.0]
+    return k
+
+
+def shape_initial_kinematics(case):
+    k = kin_table(case)
+    rng = np.random.default_rng(case["seed"])
+    k[:, 3:6] = rng.normal(0, 1, (len(k), 3)) * [0.3, 0.3, 40.0]
     return k
 
 
@@ -144,26 +171,60 @@ def run_dem_case(sim, case):
     return out
 
 
-def _generate(name, case, q, sp=False):
+def run_shape_case(sim, case):
+    """6 npDEM + 5 sub-steps from agitated grains. After 1, 3 and 6 fluid periods and at the end ("end"): SHA-256 of f, obst,
+    fhf and the kinematics, and the serial total density; at the end the arrays themselves as well. `sim` has
+    set_kinematics/steps/get_f/get_obst/get_fhf/get_grains/total_density/scalars."""
+    sim.set_kinematics(shape_initial_kinematics(case))
+    npdem = sim.scalars()["npDEM"]
+    out = {}
+    done = 0
+    for d in tuple(case["dumps"]) + ("end",):
+        target = case["dumps"][-1] * npdem + 5 if d == "end" else d * npdem
+        sim.steps(target - done)
+        done = target
+        f, obst, fhf, grains = sim.get_f(), sim.get_obst(), sim.get_fhf(), sim.get_grains()
+        out[f"sha_f_{d}"] = sha(f)
+        out[f"sha_obst_{d}"] = sha(np.asarray(obst).astype(np.int32))
+        out[f"sha_fhf_{d}"] = sha(fhf)
+        out[f"sha_kin_{d}"] = sha(grains[:, :9])
+        out[f"density_{d}"] = np.float64(sim.total_density())
+    out.update(f_end=f, obst_end=obst, fhf_end=fhf, grains_end=grains)
+    return out
+
+
+def _reference(name, case, sp=False):
     import pyoracle as po
-    lx, ly = case["lx"], case["ly"]
     tmp = tempfile.NamedTemporaryFile("w", suffix=".data", delete=False)
     tmp.close()
     po.write_sample(tmp.name, case["r_mm"], case["x_mm"], case["y_mm"], comment=f"#golden {name}")
-    R = po.Reference(lx, ly, tmp.name, sp=sp)      # sp: the reference compiled -DSINGLE_PRECISION (main.c:34-40)
+    R = po.Reference(case["lx"], case["ly"], tmp.name, sp=sp)      # sp: the reference compiled -DSINGLE_PRECISION (main.c:34-40)
     os.unlink(tmp.name)
+    return R
+
+
+def _generate(name, case, q, sp=False):
+    import pyoracle as po
+    R = _reference(name, case, sp)
     if case["kind"] == "lbm":
         res = run_lbm_case(R, case)
     elif case["kind"] == "coupled":
         res = run_coupled_case(R, case)
+    elif case["kind"] == "shape":
+        res = run_shape_case(R, case)
     else:
         res = run_dem_case(R, case)
     res["scalars"] = np.array([R.scalars()[k] for k in po.SCALARS], float)
     q.put(res)
 
 
-def pack(name, case, res):
-    """Reduce a result dict to what is stored."""
+SHAPE_FILE_MAX = 65536      # shape cases: a fixture file stays below this; the f sample is the first thing to go
+
+
+def pack(name, case, res, f_sample=True):
+    """Reduce a result dict to what is stored. Shape cases: f as a strided sample whatever the lattice size (f_sample = False:
+    its digest alone, for a file that would not stay under SHAPE_FILE_MAX with it); the obstacle map in full."""
+    shape = case["kind"] == "shape"
     out = {"r_mm": np.asarray(case["r_mm"], float), "x_mm": np.asarray(case["x_mm"], float),
            "y_mm": np.asarray(case["y_mm"], float), "scalars": res["scalars"]}
     for k, v in res.items():
@@ -174,7 +235,12 @@ def pack(name, case, res):
             continue
         v = np.asarray(v)
         out[k + "_sha"] = np.array(sha(v))
-        if v.ndim == 3 and v.shape[0] * v.shape[1] > 64 * 48:      # big f dump: strided sample
+        if shape and v.ndim == 3:
+            if f_sample:
+                out[k + "_sample"] = v[::4, ::4, :].copy()
+        elif shape:
+            out[k] = v
+        elif v.ndim == 3 and v.shape[0] * v.shape[1] > 64 * 48:      # big f dump: strided sample
             out[k + "_sample"] = v[::4, ::4, :].copy()
         elif v.ndim == 2 and v.dtype.kind == "i" and v.size > 64 * 48:
             out[k + "_sample"] = v[::4, ::4].copy()
@@ -183,21 +249,28 @@ def pack(name, case, res):
     return out
 
 
-def make_vtk_fixture():
+VTK_NFILE = 3
+
+
+def make_vtk_fixture(name="G5_dem_64x48"):
     """tests/golden/vtk_G5_25steps/*.vtk: the five files the reference's write_vtk (main.c:237-338)
-    produces for case G5 after 25 renderScene calls with nFile = 3 (data written by the reference)."""
-    import pyoracle as po
-    c = cases()["G5_dem_64x48"]
-    tmp = tempfile.NamedTemporaryFile("w", suffix=".data", delete=False)
-    tmp.close()
-    po.write_sample(tmp.name, c["r_mm"], c["x_mm"], c["y_mm"])
-    R = po.Reference(64, 48, tmp.name)
-    os.unlink(tmp.name)
-    R.set_kinematics(dem_initial_kinematics(c))
-    R.steps(25)
-    out = os.path.join(HERE, "vtk_G5_25steps")
+    produces for case G5 after 25 renderScene calls with nFile = 3 (data written by the reference).
+    For a shape case, tests/golden/vtk_<case>/: the same five files after the case's last dump."""
+    c = cases()[name]
+    R = _reference(name, c)
+    if c["kind"] == "shape":
+        run_shape_case(R, c)
+        out = os.path.join(HERE, "vtk_" + name)
+    else:
+        R.set_kinematics(dem_initial_kinematics(c))
+        R.steps(25)
+        out = os.path.join(HERE, "vtk_G5_25steps")
     os.makedirs(out, exist_ok=True)
-    assert R.L.ref_write_vtk(os.fsencode(out), 3) == 0
+    assert R.L.ref_write_vtk(os.fsencode(out), VTK_NFILE) == 0
+
+
+def make_vtk_shape_fixture():
+    make_vtk_fixture("S_61x59")
 
 
 def make_dry_output_fixture():
@@ -305,19 +378,32 @@ def make_real_fixtures(only=None):
         print("wrote", name, {k: str(v)[:20] for k, v in res.items() if k.startswith(("sha_f", "mass"))})
 
 
-def make_f32_fixtures():
-    """<case>_f32.npz: the same cases on the reference compiled -DSINGLE_PRECISION (typedef float real, main.c:34-40):
-    the oracle of the float build of the library (liblbmdem_hip_sp.so). Stored as float64 arrays holding float values."""
+def make_case_fixtures(sp=False, kinds=None):
+    """<case>.npz / <case>_f32.npz for every case (of these kinds) that is stored as one file"""
     for name, case in cases().items():
-        if case["kind"] == "output":
+        if case["kind"] == "output" or (kinds is not None and case["kind"] not in kinds):
             continue
         q = mp.Queue()
-        p = mp.Process(target=_generate, args=(name, case, q, True))
+        p = mp.Process(target=_generate, args=(name, case, q, sp))
         p.start()
         res = q.get()
         p.join()
-        np.savez_compressed(os.path.join(HERE, name + "_f32.npz"), **pack(name, case, res))
-        print("wrote", name + "_f32")
+        path = os.path.join(HERE, name + ("_f32" if sp else "") + ".npz")
+        packed = pack(name, case, res)
+        np.savez_compressed(path, **packed)
+        if case["kind"] == "shape" and os.path.getsize(path) >= SHAPE_FILE_MAX:      # does not fit: without the f sample
+            packed = pack(name, case, res, f_sample=False)
+            np.savez_compressed(path, **packed)
+            assert os.path.getsize(path) < SHAPE_FILE_MAX, (path, os.path.getsize(path))
+        print("wrote", os.path.basename(path), os.path.getsize(path), {k: getattr(v, "shape", None) for k, v in packed.items()})
+
+
+def make_f32_fixtures(kinds=None):
+    """<case>_f32.npz: the same cases on the reference compiled -DSINGLE_PRECISION (typedef float real, main.c:34-40):
+    the oracle of the float build of the library (liblbmdem_hip_sp.so). Stored as float64 arrays holding float values."""
+    make_case_fixtures(sp=True, kinds=kinds)
+    if kinds is not None:
+        return
     for name in F32_REAL_CASES:
         q = mp.Queue()
         p = mp.Process(target=_real_case, args=(name, q, True))
@@ -335,24 +421,22 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--f32":
         make_f32_fixtures()
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "--shapes":     # only the S_* cases, both precisions, and their VTK frame
+        make_case_fixtures(kinds=("shape",))
+        make_f32_fixtures(kinds=("shape",))
+        p = mp.Process(target=make_vtk_shape_fixture)
+        p.start()
+        p.join()
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--dry":
         make_dry_output_fixture()
         return
     if len(sys.argv) > 1:      # python make_golden.py real_50000_8192x4096 ...: only these real-sample fixtures
         make_real_fixtures(sys.argv[1:])
         return
-    for name, case in cases().items():
-        if case["kind"] == "output":
-            continue
-        q = mp.Queue()
-        p = mp.Process(target=_generate, args=(name, case, q))
-        p.start()
-        res = q.get()
-        p.join()
-        np.savez_compressed(os.path.join(HERE, name + ".npz"), **pack(name, case, res))
-        print("wrote", name, {k: getattr(v, "shape", None) for k, v in pack(name, case, res).items()})
+    make_case_fixtures()
     make_real_fixtures()
-    for target in (make_vtk_fixture, make_dem_output_fixture, make_dry_output_fixture):
+    for target in (make_vtk_fixture, make_vtk_shape_fixture, make_dem_output_fixture, make_dry_output_fixture):
         p = mp.Process(target=target)
         p.start()
         p.join()

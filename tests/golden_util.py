@@ -39,6 +39,8 @@ def run_case(sim, name):
         return mg.run_lbm_case(sim, case)
     if case["kind"] == "coupled":
         return mg.run_coupled_case(sim, case)
+    if case["kind"] == "shape":
+        return mg.run_shape_case(sim, case)
     return mg.run_dem_case(sim, case)
 
 
@@ -46,9 +48,16 @@ def compare(name, res, grain_cols=None):
     """Exact comparison with the fixture. grain_cols: restrict grain tables to these columns (the HIP
     path carries the 9 kinematic columns only)."""
     g = load(name)
+    # a shape case's file may hold the digest of f without the strided sample (where the file would not fit with it); every
+    # other case must have the sample: a missing one is a KeyError, as ever
+    digest_only_ok = ALL_CASES.get(name.removesuffix("_f32"), {}).get("kind") == "shape"
     checked = 0
     for key, val in res.items():
         val = np.asarray(val)
+        if val.dtype.kind == "U":       # a digest of an earlier dump (shape cases)
+            assert str(val) == str(g[key]), f"{name}/{key}: SHA-256 differs from the reference's"
+            checked += 1
+            continue
         if key.startswith("grains") and grain_cols is not None:
             ref = g[key][:, grain_cols]
             assert np.array_equal(val, ref), f"{name}/{key}: max abs {np.abs(val - ref).max():.3e}"
@@ -56,7 +65,7 @@ def compare(name, res, grain_cols=None):
             continue
         if key in g:
             assert np.array_equal(val, g[key], equal_nan=True), f"{name}/{key} differs from the reference dump"
-        else:
+        elif key + "_sample" in g or not digest_only_ok:
             samp = val[::4, ::4] if val.ndim == 2 else val[::4, ::4, :]
             assert np.array_equal(samp, g[key + "_sample"]), f"{name}/{key} (strided sample) differs"
         ref_sha = str(g[key + "_sha"])
@@ -81,6 +90,7 @@ class GpuAdapter:
     def get_fhf(self): return self.sim.fhf
     def get_grains(self): return self.sim.kinematics
     def scalars(self): return {"npDEM": self.sim.cfg.npDEM}
+    def total_density(self): return self.sim.final_density()
     def steps(self, n): self.sim.renderScene(n)
 
     def lbm_steps(self, n):

@@ -20,6 +20,42 @@ def test_oracle_matches_reference_dump(po, name):
     assert np.array_equal(np.array([s[k] for k in po.SCALARS], float), g["scalars"])
 
 
+SHAPE_CASES = sorted(k for k, v in gu.CASES.items() if v["kind"] == "shape")
+
+
+def test_shape_fixtures_reach_the_ragged_ends():
+    """What the S_* cases are for, checked from the stored files alone: ten shapes with lx % 8 = 1 ... 7 and ly % 60 in
+    {0, 1, 2, 3, 17, 59}, no ly a multiple of the 16- or 32-column row pitch; at least 3 grains, odd counts among them; nodes
+    changed owner during the run; and, where grains were pushed into the walls (lattices at least 60 nodes wide, lx >= 60: all
+    but 13 x 61 and 33 x 62), solid grain nodes in the rows of the short last 8-row segment and in the columns of the last
+    60-column window. (The wall nodes carry the id n, grains 0 ... n-1. Where ly % 60 == 1 the last window holds the wall
+    column alone, which no grain can own: there, and only there, the grain nodes must reach the column next to it, the last
+    one of the window before.)"""
+    assert len(SHAPE_CASES) == 10
+    shapes = [(gu.CASES[n]["lx"], gu.CASES[n]["ly"]) for n in SHAPE_CASES]
+    assert {lx % 8 for lx, _ in shapes} == {1, 2, 3, 4, 5, 6, 7}
+    assert {ly % 60 for _, ly in shapes} == {0, 1, 2, 3, 17, 59}
+    assert all(ly % 16 and ly % 32 for _, ly in shapes)
+    odd = 0
+    for name in SHAPE_CASES:
+        lx, ly = gu.CASES[name]["lx"], gu.CASES[name]["ly"]
+        for g in (gu.load(name), gu.load(name + "_f32")):
+            n = len(g["r_mm"])
+            assert n >= 3 and g["grains_end"].shape == (n, 30) and g["fhf_end"].shape == (n, 3), name
+            assert np.array_equal(g["r_mm"], gu.CASES[name]["r_mm"]), name
+            obst = g["obst_end"]
+            assert obst.shape == (lx, ly) and obst.max() == n, name
+            grain = (obst >= 0) & (obst < n)
+            assert str(g["sha_obst_end"]) != str(g["sha_obst_1"]), name
+            assert gu.sha(obst.astype(np.int32)) == str(g["sha_obst_end"]), name
+            if lx >= 60:
+                assert grain[lx - lx % 8:, :].any(), (name, "last segment")
+                first = ly - 2 if ly % 60 == 1 else 60 * ((ly - 1) // 60)
+                assert grain[:, first:].any(), (name, "last window")
+        odd += n % 2
+    assert odd >= 2
+
+
 @pytest.mark.parametrize("name,dumps", [("real_a08d83_600x500", None), ("real_7000_2048x2048", (1, 2)),
                                         ("real_50000_4096x4096", (1,)), ("real_50000test_3072x3072", (1,)),
                                         ("real_50000_8192x4096", (1,)),

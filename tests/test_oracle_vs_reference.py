@@ -106,3 +106,28 @@ def test_f32_goldens_are_what_the_single_precision_reference_produces(po):
             if np.asarray(fresh[k]).dtype == np.float64 and k not in ("r_mm", "x_mm", "y_mm", "scalars"):
                 v = np.asarray(fresh[k])
                 assert np.array_equal(v, v.astype(np.float32).astype(np.float64), equal_nan=True), (name, k, "not floats")
+
+
+def test_shape_goldens_are_what_the_reference_produces(po):
+    """tests/golden/S_*.npz and S_*_f32.npz (odd and ragged lattice shapes): regenerate two of them live, in both precisions,
+    and compare every key with what is stored."""
+    import multiprocessing as mp
+    import golden_util as gu
+    if not po.reference_available():
+        pytest.skip("the reference is not present on this machine")
+    for name in ("S_61x59", "S_127x121"):
+        case = gu.ALL_CASES[name]
+        for sp in (False, True):
+            q = mp.Queue()
+            p = mp.Process(target=gu.mg._generate, args=(name, case, q, sp))
+            p.start()
+            res = q.get()
+            p.join()
+            stored = gu.load(name + ("_f32" if sp else ""))
+            fresh = gu.mg.pack(name, case, res, f_sample="f_end_sample" in stored)   # (left out only where the file would not fit)
+            assert set(fresh) == set(stored)
+            for k in fresh:
+                a, b = np.asarray(fresh[k]), np.asarray(stored[k])
+                assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), (name, sp, k)
+                if sp and a.dtype == np.float64 and k not in ("r_mm", "x_mm", "y_mm", "scalars"):
+                    assert np.array_equal(a, a.astype(np.float32).astype(np.float64), equal_nan=True), (name, k, "not floats")
