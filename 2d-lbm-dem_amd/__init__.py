@@ -446,10 +446,14 @@ class LbmDem:
     def output_stats_checkpoint(self):
         """dict: checkpoints queued / written / failed, calls that waited for a slot; ms the caller waited for a slot, the writer
         waited for copies, the writer spent in file I/O, callers were held in checkpoint_save_async behind their slot"""
+        return self._output_stats(self._L.lbmdem_output_stats_checkpoint, "ms_hold")
+
+    def _output_stats(self, fn, last_key):
+        """the four counters and four times of one kind of background job; the last time means something else for each kind"""
         c = np.zeros(4, np.int64); m = np.zeros(4)
-        _chk(self._L.lbmdem_output_stats_checkpoint(self._h, _vp(c), _vp(m)))
-        return dict(queued=int(c[0]), written=int(c[1]), failed=int(c[2]), slot_waits=int(c[3]), ms_slot_wait=float(m[0]),
-                    ms_copy_wait=float(m[1]), ms_io=float(m[2]), ms_hold=float(m[3]))
+        _chk(fn(self._h, _vp(c), _vp(m)))
+        return {"queued": int(c[0]), "written": int(c[1]), "failed": int(c[2]), "slot_waits": int(c[3]),
+                "ms_slot_wait": float(m[0]), "ms_copy_wait": float(m[1]), "ms_io": float(m[2]), last_key: float(m[3])}
 
     @staticmethod
     def checkpoint_verify(path):
@@ -674,10 +678,7 @@ class LbmDem:
     def output_stats_dem(self):
         """dict: DEM events queued / written / failed, calls that waited for a slot; ms the caller waited for a slot, the writer
         waited for copies, the writer spent formatting and in file I/O, the caller waited for the 22 numbers"""
-        c = np.zeros(4, np.int64); m = np.zeros(4)
-        _chk(self._L.lbmdem_output_stats_dem(self._h, _vp(c), _vp(m)))
-        return dict(queued=int(c[0]), written=int(c[1]), failed=int(c[2]), slot_waits=int(c[3]), ms_slot_wait=float(m[0]),
-                    ms_copy_wait=float(m[1]), ms_io=float(m[2]), ms_stats_wait=float(m[3]))
+        return self._output_stats(self._L.lbmdem_output_stats_dem, "ms_stats_wait")
 
     def write_vtk(self, directory=".", nFile=0):
         """write_vtk (main.c:237-338): five binary legacy-VTK files, byte-identical to the reference's."""
@@ -700,10 +701,7 @@ class LbmDem:
     def output_stats(self):
         """dict: frames queued / written / failed, calls that waited for a slot; ms the caller waited for a slot, the writer
         waited for copies, the writer spent in file I/O, the caller spent in output_drain"""
-        c = np.zeros(4, np.int64); m = np.zeros(4)
-        _chk(self._L.lbmdem_output_stats(self._h, _vp(c), _vp(m)))
-        return dict(queued=int(c[0]), written=int(c[1]), failed=int(c[2]), slot_waits=int(c[3]), ms_slot_wait=float(m[0]),
-                    ms_copy_wait=float(m[1]), ms_io=float(m[2]), ms_drain=float(m[3]))
+        return self._output_stats(self._L.lbmdem_output_stats, "ms_drain")
 
     def vtk_image(self):
         """the frame image of the present state (the snapshot kernel alone, synchronously): bytes-like uint8[44 * lx * ly]"""

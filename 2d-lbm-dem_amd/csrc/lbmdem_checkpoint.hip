@@ -164,9 +164,9 @@ void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned
   J->gate = h->L.gate;
 }
 
-int lbmdem_ckpt_write_slot(const AsyncCkptSlot* S, const CkptLayout* Y, int n, char* msg, size_t msglen) {
-  (void)n;
-  const u64* words = reinterpret_cast<const u64*>(S->pinned);
+int lbmdem_ckpt_write_slot(const AsyncSlot* S, const CkptLayout* Y, char* msg, size_t msglen) {
+  const unsigned char* image = static_cast<const unsigned char*>(S->pinned);
+  const u64* words = reinterpret_cast<const u64*>(image);
   const CkptShot& C = S->shot;
   CkptHeader H;
   memset(&H, 0, sizeof H);
@@ -196,7 +196,7 @@ int lbmdem_ckpt_write_slot(const AsyncCkptSlot* S, const CkptLayout* Y, int n, c
   FILE* fp = fopen(tmp, "wb");
   if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing: %s", tmp, strerror(errno)); return LBMDEM_EINVAL; }
   bool ok = wr(fp, &H, sizeof H);
-  for (int s = 0; s < CKPT_DEV_SECTIONS && ok; ++s) ok = wr(fp, S->pinned + Y->at[s], (size_t)T.e[1 + s].bytes);   // exact lengths
+  for (int s = 0; s < CKPT_DEV_SECTIONS && ok; ++s) ok = wr(fp, image + Y->at[s], (size_t)T.e[1 + s].bytes);   // exact lengths
   if (ok) ok = wr(fp, &T, sizeof T);
   int err = errno;
   if (fclose(fp) != 0) { if (ok) err = errno; ok = false; }

@@ -70,48 +70,31 @@ struct ProbeState {
   long issued = 0;            // samples launched since the ring was last emptied: min(issued, capacity) are in it, the rest were dropped
 };
 
-// Frames written in the background (lbmdem_set_async_output, lbmdem_output.hip). A frame is snapshotted on the handle's
-// stream into its slot's device staging (k_vtk_frame: the image the files hold), copied to the slot's pinned buffer on the
-// copy stream behind an event, and written by the writer thread once the copy's event has completed. A slot is free again
-// when its files are closed: staging and pinned buffer are never overwritten while anything reads them. Does not exist
-// while the feature is off.
-struct AsyncSlot {
-  void* staging = nullptr;   // device, image_bytes
-  void* pinned = nullptr;    // host, image_bytes
-  hipEvent_t snapped = nullptr, copied = nullptr;
-  bool busy = false;         // (under AsyncOut::mu)
-  char dir[4096];
-  int nfile = 0;
-};
-// A write_DEM / write_forces event written in the background (lbmdem_set_async_dem): the same pipeline with the table's rows
-// (k_dem_frame, lbm_demframe.hip) in place of the image, and the stats.data line as it stood when the event was queued.
-struct AsyncDemSlot {
-  double* staging = nullptr;   // device, [n][LBMDEM_DEM_ROW_DOUBLES]
-  double* pinned = nullptr;    // host, the same
-  hipEvent_t snapped = nullptr, copied = nullptr;
-  bool busy = false;           // (under AsyncOut::mu)
-  char dir[4096];
-  int nfile = 0, with_forces = 0;
-  double stats22[22];
-};
-// A checkpoint written in the background (lbmdem_set_async_checkpoint): the same pipeline with the sections of the file
-// (k_ckpt_frame, lbm_ckptframe.hip) in place of the image, and the host's side of the header as it stood when the checkpoint
-// was queued. The pair list's length, the carries and the sections' digests come back with the copy (the staging's word area).
-struct CkptShot {
-  lbmdem_config cfg;   // incl. the clock and the walls
-  long nbsteps = 0, plane = 0;
+// Frames, tables and checkpoints written in the background (lbmdem_set_async_output, lbmdem_set_async_dem,
+// lbmdem_set_async_checkpoint; lbmdem_output.hip). A job is snapshotted on the handle's stream into its slot's device staging
+// (k_vtk_frame: the image the files hold; k_dem_frame: the table's rows; k_ckpt_frame: the sections of the file), copied to the
+// slot's pinned buffer on the copy stream behind an event, and written by the writer thread once the copy's event has completed.
+// A slot is free again when its files are closed: staging and pinned buffer are never overwritten while anything reads them.
+// Nothing of this exists while the three features are off.
+struct CkptShot {      // the host's side of a checkpoint's header as it stood when the checkpoint was queued. The pair list's
+  lbmdem_config cfg;   // length, the carries and the sections' digests come back with the copy (the staging's word area).
+  long nbsteps = 0, plane = 0;   // (cfg: incl. the clock and the walls)
   double lid6 = 0;
   int force_mode = 0, diag_always = 0, verlet_ok = 0, vib = 0;
 };
-struct AsyncCkptSlot {
-  unsigned char* staging = nullptr;   // device, CkptLayout::total bytes
-  unsigned char* pinned = nullptr;    // host, the same
+struct AsyncSlot {
+  void* staging = nullptr;   // device, AsyncLane::bytes
+  void* pinned = nullptr;    // host, the same
   hipEvent_t snapped = nullptr, copied = nullptr;
-  bool busy = false;                  // (under AsyncOut::mu)
-  char path[4096];
+  bool busy = false;         // (under AsyncOut::mu)
+  char path[4096];           // the directory; a checkpoint's file name
+  // what the job's kind needs besides: the frame's or table's number, the map with the table, the stats.data line as it stood
+  // when the event was queued, the checkpoint's header
+  int nfile = 0, with_forces = 0;
+  double stats22[22];
   CkptShot shot;
 };
-// The counters of lbmdem_output_stats / lbmdem_output_stats_dem / lbmdem_output_stats_checkpoint: each feature has its own set,
+// The counters of lbmdem_output_stats / lbmdem_output_stats_dem / lbmdem_output_stats_checkpoint: each kind has its own set,
 // reset when its slots change
 struct AsyncCounters {
   long queued = 0, written = 0, failed = 0, slot_waits = 0;
@@ -119,33 +102,36 @@ struct AsyncCounters {
   // caller inside lbmdem_checkpoint_save_async behind its slot (header fields, launch, queueing)
   double ms_slot_wait = 0, ms_copy_wait = 0, ms_io = 0, ms_last = 0;
 };
-enum : int { ASYNC_FRAME = 0, ASYNC_TABLE = 1, ASYNC_CKPT = 2 };
-static const char* const ASYNC_KIND_NAMES[3] = {"frame", "table", "checkpoint"};
-// One per handle while any of the three features is on: ONE copy stream, ONE writer thread, ONE queue (strictly first in, first out:
+enum : int { ASYNC_FRAME = 0, ASYNC_TABLE = 1, ASYNC_CKPT = 2, ASYNC_KINDS = 3 };
+static const char* const ASYNC_KIND_NAMES[ASYNC_KINDS] = {"frame", "table", "checkpoint"};
+// A kind's slots (0: the kind is off; at most LBMDEM_ASYNC_MAX_FRAMES, _DEM, _CKPT of them), the size of a job's copy, its counters
+struct AsyncLane {
+  int slots = 0;
+  size_t bytes = 0;
+  AsyncSlot slot[4];
+  AsyncCounters c;
+};
+static_assert(LBMDEM_ASYNC_MAX_FRAMES <= 4 && LBMDEM_ASYNC_MAX_DEM <= 4 && LBMDEM_ASYNC_MAX_CKPT <= 4, "AsyncLane::slot");
+struct AsyncJob { int kind, slot; };
+// One per handle while any of the three kinds is on: ONE copy stream, ONE writer thread, ONE queue (strictly first in, first out:
 // the lines of stats.data land in call order).
 struct AsyncOut {
-  int frames = 0, lx = 0, ly = 0, device = 0;
-  size_t image_bytes = 0;
-  AsyncSlot slot[LBMDEM_ASYNC_MAX_FRAMES];
-  int dem_slots = 0, n = 0;                  // lbmdem_set_async_dem; grains
-  AsyncDemSlot dslot[LBMDEM_ASYNC_MAX_DEM];
+  int lx = 0, ly = 0, n = 0, device = 0;     // lattice, grains
+  AsyncLane lane[ASYNC_KINDS];
   double* dem_scratch = nullptr;             // device: the addends of the ten sums [10][n], then the 22 numbers (k_dem_stats)
   double* dem_stats_host = nullptr;          // pinned [22]
-  int ckpt_slots = 0;                        // lbmdem_set_async_checkpoint
-  AsyncCkptSlot cslot[LBMDEM_ASYNC_MAX_CKPT];
   CkptLayout ckpt_layout{};                  // of the handle: n grains, the pair list at its capacity, the slab
   hipStream_t copy_stream = nullptr;
   std::thread writer;
   std::mutex mu;
-  std::condition_variable cv_job, cv_free;   // writer: a job or quit; callers: a slot freed / a frame finished
-  std::deque<int> jobs;                      // in the order they were queued: frame slot s as s, table slot s as LBMDEM_ASYNC_MAX_FRAMES + s, checkpoint slot s behind those
+  std::condition_variable cv_job, cv_free;   // writer: a job or quit; callers: a slot freed / a job finished
+  std::deque<AsyncJob> jobs;                 // in the order they were queued
   bool quit = false;
   int pending = 0;                           // queued and not yet on disk
   // the first failure of the writer since the last one was reported (the writer never touches the callers' error text)
   int err_code = 0;
   int err_kind = ASYNC_FRAME;                // ... was a frame's, a table's, a checkpoint's
   char err_msg[4400];
-  AsyncCounters fc, dc, cc;                  // frames, tables, checkpoints
 };
 
 struct lbmdem_handle {
@@ -406,15 +392,18 @@ LBMDEM_INTERNAL void lbmdem_probe_release(lbmdem_handle* h);
 // background frames and tables (lbmdem_output.hip): every queued job on disk, the writer joined, everything freed (-> off); the
 // writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);
-static inline bool async_frames_on(const lbmdem_handle* h) { return h->aout && h->aout->frames > 0; }
-static inline bool async_dem_on(const lbmdem_handle* h) { return h->aout && h->aout->dem_slots > 0; }
-static inline bool async_ckpt_on(const lbmdem_handle* h) { return h->aout && h->aout->ckpt_slots > 0; }
+// ... and every queued job on disk, nothing else touched (the writer's failure, if any, stays for lbmdem_async_report)
+LBMDEM_INTERNAL void lbmdem_async_wait_idle(lbmdem_handle* h);
+static inline bool lane_on(const lbmdem_handle* h, int kind) { return h->aout && h->aout->lane[kind].slots > 0; }
+static inline bool async_frames_on(const lbmdem_handle* h) { return lane_on(h, ASYNC_FRAME); }
+static inline bool async_dem_on(const lbmdem_handle* h) { return lane_on(h, ASYNC_TABLE); }
+static inline bool async_ckpt_on(const lbmdem_handle* h) { return lane_on(h, ASYNC_CKPT); }
 // lbmdem_checkpoint.hip, for the background writer (lbmdem_output.hip): what a slot's launch reads, and the file of a slot
 // whose copy has arrived -- header, sections, digest trailer to `<path>.tmp`, then renamed onto `<path>`; on failure the text
 // goes to `msg`, the .tmp file is removed and `<path>` is not touched
 LBMDEM_INTERNAL void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned char* staging, CkptFrameJob* J);
 LBMDEM_INTERNAL int lbmdem_ckpt_save_replacing(lbmdem_handle* h, const char* path);
-LBMDEM_INTERNAL int lbmdem_ckpt_write_slot(const AsyncCkptSlot* S, const CkptLayout* Y, int n, char* msg, size_t msglen);
+LBMDEM_INTERNAL int lbmdem_ckpt_write_slot(const AsyncSlot* S, const CkptLayout* Y, char* msg, size_t msglen);
 LBMDEM_INTERNAL int lbmdem_async_report(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {

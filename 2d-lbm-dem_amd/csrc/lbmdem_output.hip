@@ -42,6 +42,9 @@ int lbmdem_download_vtk_fields(lbmdem_handle* h, float* grain_pressure, float* g
 // the byte layout the reference obtains from write_rectilinear_mesh(..., useBinary = 1, ...)
 // (main.c:326-328): header, DIMENSIONS, X/Y/Z_COORDINATES, CELL_DATA, POINT_DATA, one SCALARS
 // (+ LOOKUP_TABLE default) or VECTORS block, no separators after binary blocks.
+static const char* const VTK_NAMES[5] = {"grain_pressure", "grain_velocity", "grain_acceleration", "fluid_pressure", "fluid_velocity"};
+static const int VTK_DIMS[5] = {1, 3, 3, 1, 3};
+
 static void put_be(FILE* fp, const float* v, size_t n) {
   std::vector<unsigned char> buf(n * 4);
   for (size_t k = 0; k < n; ++k) {
@@ -52,9 +55,8 @@ static void put_be(FILE* fp, const float* v, size_t n) {
   fwrite(buf.data(), 1, buf.size(), fp);
 }
 
-int lbmdem_write_vtk_file(const char* path, int nx, int ny, const char* name, int dim, const float* data) {
-  FILE* fp = fopen(path, "w+");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+// everything in front of the variable's payload
+static void put_vtk_head(FILE* fp, int nx, int ny, const char* name, int dim) {
   fprintf(fp, "# vtk DataFile Version 2.0\nWritten using VisIt writer\nBINARY\n");
   fprintf(fp, "DATASET RECTILINEAR_GRID\nDIMENSIONS %d %d 1\n", nx, ny);
   // coordinates: i * (float)(1/nx) on BOTH axes, z = 0 (main.c:255-258)
@@ -69,6 +71,12 @@ int lbmdem_write_vtk_file(const char* path, int nx, int ny, const char* name, in
   fprintf(fp, "CELL_DATA %d\nPOINT_DATA %d\n", (nx - 1) * (ny - 1), nx * ny);
   if (dim == 1) fprintf(fp, "SCALARS %s float\nLOOKUP_TABLE default\n", name);
   else fprintf(fp, "VECTORS %s float\n", name);
+}
+
+int lbmdem_write_vtk_file(const char* path, int nx, int ny, const char* name, int dim, const float* data) {
+  FILE* fp = fopen(path, "w+");
+  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  put_vtk_head(fp, nx, ny, name, dim);
   put_be(fp, data, (size_t)nx * ny * dim);
   fclose(fp);
   return LBMDEM_OK;
@@ -81,19 +89,10 @@ int lbmdem_write_vtk(lbmdem_handle* h, const char* dir, int nfile) try {
     return fail(LBMDEM_EINVAL, "lbmdem_write_vtk needs the whole lattice on this handle; gather strips with "
                                "lbmdem_download_vtk_fields");
   const size_t cnt = (size_t)L.lx * L.ly;
-  std::vector<float> gp(cnt), gv(3 * cnt), ga(3 * cnt), fp(cnt), fv(3 * cnt);
-  int rc = lbmdem_download_vtk_fields(h, gp.data(), gv.data(), ga.data(), fp.data(), fv.data());
-  if (rc != LBMDEM_OK) return rc;
-  const char* names[5] = {"grain_pressure", "grain_velocity", "grain_acceleration", "fluid_pressure", "fluid_velocity"};
-  const int dims[5] = {1, 3, 3, 1, 3};
-  const float* data[5] = {gp.data(), gv.data(), ga.data(), fp.data(), fv.data()};
-  for (int k = 0; k < 5; ++k) {
-    char path[4096];
-    snprintf(path, sizeof path, "%s/%s_%.6i.vtk", (dir && *dir) ? dir : ".", names[k], nfile);  // main.c:241-249
-    rc = lbmdem_write_vtk_file(path, L.lx, L.ly, names[k], dims[k], data[k]);
-    if (rc != LBMDEM_OK) return rc;
-  }
-  return LBMDEM_OK;
+  std::vector<float> f11(11 * cnt);
+  float* f = f11.data();
+  RC_TRY(lbmdem_download_vtk_fields(h, f, f + cnt, f + 4 * cnt, f + 7 * cnt, f + 8 * cnt));
+  return lbmdem_write_vtk_fields(dir, nfile, L.lx, L.ly, f);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 } catch (...) {
@@ -374,10 +373,9 @@ int lbmdem_vtk_place_block(float* fields11, int lx, int ly, int x0, int nx, cons
   const size_t part = (size_t)nx * ly, cnt = (size_t)lx * ly;
   const float* lp[5] = {block11, block11 + part, block11 + 4 * part, block11 + 7 * part, block11 + 8 * part};
   float* fp[5] = {fields11, fields11 + cnt, fields11 + 4 * cnt, fields11 + 7 * cnt, fields11 + 8 * cnt};
-  const int dims[5] = {1, 3, 3, 1, 3};
   for (int k = 0; k < 5; ++k)
     for (int y = 0; y < ly; ++y)
-      memcpy(fp[k] + ((size_t)y * lx + x0) * dims[k], lp[k] + (size_t)y * nx * dims[k], sizeof(float) * nx * dims[k]);
+      memcpy(fp[k] + ((size_t)y * lx + x0) * VTK_DIMS[k], lp[k] + (size_t)y * nx * VTK_DIMS[k], sizeof(float) * nx * VTK_DIMS[k]);
   return LBMDEM_OK;
 }
 
@@ -390,12 +388,11 @@ int lbmdem_vtk_place_owned(lbmdem_handle* h, float* fields11) try {
   if (!fields11) return fail(LBMDEM_EINVAL, "null buffer");
   const LatticeView& L = h->L;
   const int nx = L.xo1 - L.xo0, x0 = L.gx0 + L.xo0;
-  const size_t part = (size_t)nx * L.ly, cnt = (size_t)L.lx * L.ly;
+  const size_t part = (size_t)nx * L.ly;
   std::vector<float> loc(11 * part);
   float* lp[5] = {loc.data(), loc.data() + part, loc.data() + 4 * part, loc.data() + 7 * part, loc.data() + 8 * part};
   int rc = lbmdem_download_vtk_fields(h, lp[0], lp[1], lp[2], lp[3], lp[4]);
   if (rc != LBMDEM_OK) return rc;
-  (void)cnt;
   lbmdem_vtk_place_block(fields11, L.lx, L.ly, x0, nx, loc.data());
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -408,49 +405,30 @@ int lbmdem_vtk_place_owned(lbmdem_handle* h, float* fields11) try {
 int lbmdem_write_vtk_fields(const char* dir, int nfile, int lx, int ly, const float* fields11) {
   if (!fields11 || lx < 2 || ly < 2) return fail(LBMDEM_EINVAL, "bad lbmdem_write_vtk_fields arguments");
   const size_t cnt = (size_t)lx * ly;
-  const char* names[5] = {"grain_pressure", "grain_velocity", "grain_acceleration", "fluid_pressure", "fluid_velocity"};
-  const int dims[5] = {1, 3, 3, 1, 3};
   const float* data[5] = {fields11, fields11 + cnt, fields11 + 4 * cnt, fields11 + 7 * cnt, fields11 + 8 * cnt};
   for (int k = 0; k < 5; ++k) {
     char path[4096];
-    snprintf(path, sizeof path, "%s/%s_%.6i.vtk", (dir && *dir) ? dir : ".", names[k], nfile);  // main.c:241-249
-    const int rc = lbmdem_write_vtk_file(path, lx, ly, names[k], dims[k], data[k]);
-    if (rc != LBMDEM_OK) return rc;
+    snprintf(path, sizeof path, "%s/%s_%.6i.vtk", (dir && *dir) ? dir : ".", VTK_NAMES[k], nfile);  // main.c:241-249
+    RC_TRY(lbmdem_write_vtk_file(path, lx, ly, VTK_NAMES[k], VTK_DIMS[k], data[k]));
   }
   return LBMDEM_OK;
 }
 
-// ---- frames in the background -------------------------------------------------------------------------------------------
+// ---- frames, tables and checkpoints in the background ------------------------------------------------------------------
 // The image: the five payloads as the files hold them, back to back (k_vtk_frame, lbm_frame.hip).
-
-static const char* const IMAGE_NAMES[5] = {"grain_pressure", "grain_velocity", "grain_acceleration", "fluid_pressure", "fluid_velocity"};
-static const int IMAGE_DIMS[5] = {1, 3, 3, 1, 3};
 
 // the five files from an image; on failure the text goes to `msg`, not to the thread's error text (the writer thread
 // reports through its job)
 static int write_image_files(const char* dir, int nfile, int nx, int ny, const void* image, char* msg, size_t msglen) try {
   const size_t cnt = (size_t)nx * ny;
   const unsigned char* at = static_cast<const unsigned char*>(image);
-  // coordinates: as lbmdem_write_vtk_file
-  const float pas = 1. / nx;
-  std::vector<float> xs(nx), ys(ny);
-  for (int i = 0; i < nx; ++i) xs[i] = i * pas;
-  for (int i = 0; i < ny; ++i) ys[i] = i * pas;
-  const float z = 0.f;
   for (int k = 0; k < 5; ++k) {
     char path[4200];
-    snprintf(path, sizeof path, "%s/%s_%.6i.vtk", (dir && *dir) ? dir : ".", IMAGE_NAMES[k], nfile);  // main.c:241-249
+    snprintf(path, sizeof path, "%s/%s_%.6i.vtk", (dir && *dir) ? dir : ".", VTK_NAMES[k], nfile);  // main.c:241-249
     FILE* fp = fopen(path, "w+");
     if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing", path); return LBMDEM_EINVAL; }
-    fprintf(fp, "# vtk DataFile Version 2.0\nWritten using VisIt writer\nBINARY\n");
-    fprintf(fp, "DATASET RECTILINEAR_GRID\nDIMENSIONS %d %d 1\n", nx, ny);
-    fprintf(fp, "X_COORDINATES %d float\n", nx); put_be(fp, xs.data(), nx);
-    fprintf(fp, "Y_COORDINATES %d float\n", ny); put_be(fp, ys.data(), ny);
-    fprintf(fp, "Z_COORDINATES 1 float\n"); put_be(fp, &z, 1);
-    fprintf(fp, "CELL_DATA %d\nPOINT_DATA %d\n", (nx - 1) * (ny - 1), nx * ny);
-    if (IMAGE_DIMS[k] == 1) fprintf(fp, "SCALARS %s float\nLOOKUP_TABLE default\n", IMAGE_NAMES[k]);
-    else fprintf(fp, "VECTORS %s float\n", IMAGE_NAMES[k]);
-    const size_t bytes = cnt * 4 * IMAGE_DIMS[k];
+    put_vtk_head(fp, nx, ny, VTK_NAMES[k], VTK_DIMS[k]);
+    const size_t bytes = cnt * 4 * VTK_DIMS[k];
     const bool short_write = fwrite(at, 1, bytes, fp) != bytes;
     const int err = errno;
     if (fclose(fp) != 0 || short_write) {
@@ -473,7 +451,7 @@ static inline double ms_since(std::chrono::steady_clock::time_point t0) {
 static void async_writer(AsyncOut* a) {
   (void)hipSetDevice(a->device);
   for (;;) {
-    int job;
+    AsyncJob job;
     {
       std::unique_lock<std::mutex> lk(a->mu);
       a->cv_job.wait(lk, [&] { return a->quit || !a->jobs.empty(); });
@@ -481,53 +459,52 @@ static void async_writer(AsyncOut* a) {
       job = a->jobs.front();
       a->jobs.pop_front();
     }
-    const int kind = job >= LBMDEM_ASYNC_MAX_FRAMES + LBMDEM_ASYNC_MAX_DEM ? ASYNC_CKPT : (job >= LBMDEM_ASYNC_MAX_FRAMES ? ASYNC_TABLE : ASYNC_FRAME);
-    const bool dem = kind == ASYNC_TABLE;
-    AsyncSlot* F = kind == ASYNC_FRAME ? &a->slot[job] : nullptr;
-    AsyncDemSlot* D = dem ? &a->dslot[job - LBMDEM_ASYNC_MAX_FRAMES] : nullptr;
-    AsyncCkptSlot* K = kind == ASYNC_CKPT ? &a->cslot[job - LBMDEM_ASYNC_MAX_FRAMES - LBMDEM_ASYNC_MAX_DEM] : nullptr;
+    AsyncSlot& S = a->lane[job.kind].slot[job.slot];
     char msg[sizeof a->err_msg];
-    int code = LBMDEM_OK;
+    int code = LBMDEM_EHIP;
     const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = hipEventSynchronize(K ? K->copied : (dem ? D->copied : F->copied));
+    const hipError_t e = hipEventSynchronize(S.copied);
     const double ms_copy = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
-    if (e != hipSuccess && K) {
-      snprintf(msg, sizeof msg, "checkpoint '%.4000s': the copy to host memory failed: %s", K->path, hipGetErrorString(e));
-      code = LBMDEM_EHIP;
+    if (e != hipSuccess && job.kind == ASYNC_CKPT) {
+      snprintf(msg, sizeof msg, "checkpoint '%.4000s': the copy to host memory failed: %s", S.path, hipGetErrorString(e));
     } else if (e != hipSuccess) {
-      snprintf(msg, sizeof msg, "%s %d: the copy to host memory failed: %s", dem ? "table" : "frame", dem ? D->nfile : F->nfile,
-               hipGetErrorString(e));
-      code = LBMDEM_EHIP;
+      snprintf(msg, sizeof msg, "%s %d: the copy to host memory failed: %s", ASYNC_KIND_NAMES[job.kind], S.nfile, hipGetErrorString(e));
+    } else switch (job.kind) {
+      case ASYNC_FRAME:
+        code = write_image_files(S.path, S.nfile, a->lx, a->ly, S.pinned, msg, sizeof msg);
+        break;
+      case ASYNC_TABLE:
+        code = write_dem_rows_files(S.path, S.nfile, a->n, static_cast<const double*>(S.pinned), S.stats22, S.with_forces, a->lx,
+                                    a->ly, msg, sizeof msg);
+        break;
 #ifndef LBMDEM_SINGLE_PRECISION
-    } else if (K) {
-      code = lbmdem_ckpt_write_slot(K, &a->ckpt_layout, a->n, msg, sizeof msg);
+      case ASYNC_CKPT:
+        code = lbmdem_ckpt_write_slot(&S, &a->ckpt_layout, msg, sizeof msg);
+        break;
 #endif
-    } else if (dem) {
-      code = write_dem_rows_files(D->dir, D->nfile, a->n, D->pinned, D->stats22, D->with_forces, a->lx, a->ly, msg, sizeof msg);
-    } else {
-      code = write_image_files(F->dir, F->nfile, a->lx, a->ly, F->pinned, msg, sizeof msg);
     }
     const double ms_io = ms_since(t1);
     {
       std::lock_guard<std::mutex> lk(a->mu);
-      AsyncCounters& C = K ? a->cc : (dem ? a->dc : a->fc);
+      AsyncCounters& C = a->lane[job.kind].c;
       C.ms_copy_wait += ms_copy;
       C.ms_io += ms_io;
       if (code == LBMDEM_OK) C.written++;
       else {
         C.failed++;
-        if (!a->err_code) { a->err_code = code; a->err_kind = kind; memcpy(a->err_msg, msg, sizeof msg); }
+        if (!a->err_code) { a->err_code = code; a->err_kind = job.kind; memcpy(a->err_msg, msg, sizeof msg); }
       }
-      if (K) K->busy = false; else if (dem) D->busy = false; else F->busy = false;
+      S.busy = false;
       a->pending--;
     }
     a->cv_free.notify_all();
   }
 }
 
-static void async_free_frames(AsyncOut* a) {
-  for (AsyncSlot& S : a->slot) {
+// a kind's slots and counters (the table's scratch is its caller's)
+static void lane_free(AsyncOut* a, int kind) {
+  for (AsyncSlot& S : a->lane[kind].slot) {
     if (S.staging) (void)hipFree(S.staging);
     if (S.pinned) (void)hipHostFree(S.pinned);
     if (S.snapped) (void)hipEventDestroy(S.snapped);
@@ -535,45 +512,32 @@ static void async_free_frames(AsyncOut* a) {
     S.staging = S.pinned = nullptr;
     S.snapped = S.copied = nullptr;
   }
-  a->frames = 0;
-  a->fc = AsyncCounters{};
+  a->lane[kind].slots = 0;
+  a->lane[kind].c = AsyncCounters{};
 }
 
-static void async_free_dem(AsyncOut* a) {
-  for (AsyncDemSlot& S : a->dslot) {
-    if (S.staging) (void)hipFree(S.staging);
-    if (S.pinned) (void)hipHostFree(S.pinned);
-    if (S.snapped) (void)hipEventDestroy(S.snapped);
-    if (S.copied) (void)hipEventDestroy(S.copied);
-    S.staging = S.pinned = nullptr;
-    S.snapped = S.copied = nullptr;
-  }
+static void dem_scratch_free(AsyncOut* a) {
   if (a->dem_scratch) (void)hipFree(a->dem_scratch);
   if (a->dem_stats_host) (void)hipHostFree(a->dem_stats_host);
   a->dem_scratch = a->dem_stats_host = nullptr;
-  a->dem_slots = 0;
-  a->dc = AsyncCounters{};
-}
-
-static void async_free_ckpt(AsyncOut* a) {
-  for (AsyncCkptSlot& S : a->cslot) {
-    if (S.staging) (void)hipFree(S.staging);
-    if (S.pinned) (void)hipHostFree(S.pinned);
-    if (S.snapped) (void)hipEventDestroy(S.snapped);
-    if (S.copied) (void)hipEventDestroy(S.copied);
-    S.staging = S.pinned = nullptr;
-    S.snapped = S.copied = nullptr;
-  }
-  a->ckpt_slots = 0;
-  a->cc = AsyncCounters{};
 }
 
 static void async_free(AsyncOut* a) {
-  async_free_frames(a);
-  async_free_dem(a);
-  async_free_ckpt(a);
+  for (int kind = 0; kind < ASYNC_KINDS; ++kind) lane_free(a, kind);
+  dem_scratch_free(a);
   if (a->copy_stream) (void)hipStreamDestroy(a->copy_stream);
   delete a;
+}
+
+// everything queued is on disk: the writer sleeps, no slot is in use
+static void async_wait_idle(AsyncOut* a, std::unique_lock<std::mutex>& lk) {
+  a->cv_free.wait(lk, [&] { return a->pending == 0; });
+}
+
+void lbmdem_async_wait_idle(lbmdem_handle* h) {
+  if (!h->aout) return;
+  std::unique_lock<std::mutex> lk(h->aout->mu);
+  async_wait_idle(h->aout, lk);
 }
 
 void lbmdem_async_release(lbmdem_handle* h) {
@@ -581,7 +545,7 @@ void lbmdem_async_release(lbmdem_handle* h) {
   if (!a) return;
   {
     std::unique_lock<std::mutex> lk(a->mu);
-    a->cv_free.wait(lk, [&] { return a->pending == 0; });
+    async_wait_idle(a, lk);
     a->quit = true;
   }
   a->cv_job.notify_all();
@@ -606,7 +570,7 @@ int lbmdem_async_report(lbmdem_handle* h) {
   return fail(code, "background %s writer: %s", ASYNC_KIND_NAMES[kind], msg);
 }
 
-// What the three features share -- the AsyncOut, its copy stream and its writer thread -- made when the first of them is switched on
+// What the three kinds share -- the AsyncOut, its copy stream and its writer thread -- made when the first of them is switched on
 static int async_ensure(lbmdem_handle* h, const char* who) {
   if (h->aout) return LBMDEM_OK;
   AsyncOut* a = new (std::nothrow) AsyncOut;
@@ -628,21 +592,116 @@ static int async_ensure(lbmdem_handle* h, const char* who) {
   return LBMDEM_OK;
 }
 
-// Before the slots of a feature change: everything queued is on disk (the writer sleeps, no slot is in use), and a failure
-// of the writer that nobody has been told about is taken out -- it is what the call returns once the request is carried out.
-struct AsyncOldError { int code = LBMDEM_OK; int kind = ASYNC_FRAME; char msg[sizeof AsyncOut::err_msg]; };
-static void async_settle(AsyncOut* a, AsyncOldError* old) {
-  if (!a) return;
-  std::unique_lock<std::mutex> lk(a->mu);
-  a->cv_free.wait(lk, [&] { return a->pending == 0; });
-  old->code = a->err_code;
-  old->kind = a->err_kind;
-  if (old->code != LBMDEM_OK) memcpy(old->msg, a->err_msg, sizeof old->msg);
-  a->err_code = LBMDEM_OK;
+// The last kind went off: the writer thread and the copy stream go with it
+static void async_release_if_unused(lbmdem_handle* h) {
+  for (int kind = 0; kind < ASYNC_KINDS; ++kind) if (lane_on(h, kind)) return;
+  lbmdem_async_release(h);
 }
-static int async_settled(lbmdem_handle* h, const AsyncOldError& old) {
-  if (h->aout && !h->aout->frames && !h->aout->dem_slots && !h->aout->ckpt_slots) lbmdem_async_release(h);   // the last feature went off
-  if (old.code != LBMDEM_OK) return fail(old.code, "background %s writer: %s", ASYNC_KIND_NAMES[old.kind], old.msg);
+
+// A kind's number of slots changes (`who`: the setter, `noun`: what a slot holds). The request is carried out first: everything
+// queued is written, the old slots are freed, the new ones made, `bytes` of device staging and of pinned host memory each; a
+// failure of the writer that nobody has been told about is taken out beforehand and is what the call then returns.
+static int lane_resize(lbmdem_handle* h, int kind, int slots, size_t bytes, const char* who, const char* noun) {
+  if ((h->aout ? h->aout->lane[kind].slots : 0) == slots) return LBMDEM_OK;
+  int old_code = LBMDEM_OK, old_kind = ASYNC_FRAME;
+  char old_msg[sizeof AsyncOut::err_msg];
+  if (AsyncOut* a = h->aout) {
+    {
+      std::unique_lock<std::mutex> lk(a->mu);
+      async_wait_idle(a, lk);
+      old_code = a->err_code;
+      old_kind = a->err_kind;
+      if (old_code != LBMDEM_OK) memcpy(old_msg, a->err_msg, sizeof old_msg);
+      a->err_code = LBMDEM_OK;
+    }
+    lane_free(a, kind);
+    if (kind == ASYNC_TABLE) dem_scratch_free(a);
+  }
+  if (slots > 0) {
+    RC_TRY(async_ensure(h, who));
+    AsyncOut* a = h->aout;
+    hipError_t e = hipSuccess;
+    if (kind == ASYNC_TABLE) {
+      e = hipMalloc((void**)&a->dem_scratch, sizeof(double) * (DEM_STATS_CHAINS * (size_t)a->n + 22));
+      if (e == hipSuccess) e = hipHostMalloc((void**)&a->dem_stats_host, sizeof(double) * 22, hipHostMallocDefault);
+    }
+    for (int s = 0; s < slots && e == hipSuccess; ++s) {
+      AsyncSlot& S = a->lane[kind].slot[s];
+      e = hipMalloc(&S.staging, bytes);
+      if (e == hipSuccess) e = hipHostMalloc(&S.pinned, bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
+      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      lane_free(a, kind);
+      if (kind == ASYNC_TABLE) dem_scratch_free(a);
+      async_release_if_unused(h);
+      return fail(LBMDEM_ENOMEM, "%s: %d %s slots of %zu bytes (device staging + pinned host memory each) cannot be had: %s", who,
+                  slots, noun, bytes, hipGetErrorString(e));
+    }
+    a->lane[kind].slots = slots;
+    a->lane[kind].bytes = bytes;
+  }
+  async_release_if_unused(h);
+  if (old_code != LBMDEM_OK) return fail(old_code, "background %s writer: %s", ASYNC_KIND_NAMES[old_kind], old_msg);
+  return LBMDEM_OK;
+}
+
+// A free slot of the kind, marked busy. Back-pressure: with none free the caller waits for the writer, a job is never dropped.
+static int lane_acquire(AsyncOut* a, int kind) {
+  AsyncLane& Ln = a->lane[kind];
+  std::unique_lock<std::mutex> lk(a->mu);
+  auto free_slot = [&] { for (int k = 0; k < Ln.slots; ++k) if (!Ln.slot[k].busy) return k; return -1; };
+  int s = free_slot();
+  if (s < 0) {
+    const auto t0 = std::chrono::steady_clock::now();
+    Ln.c.slot_waits++;
+    a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
+    Ln.c.ms_slot_wait += ms_since(t0);
+  }
+  Ln.slot[s].busy = true;
+  return s;
+}
+
+// Behind what the handle's stream holds so far -- the slot's snapshot -- the copy stream takes the staging to the pinned buffer
+static hipError_t slot_copy_behind(lbmdem_handle* h, AsyncOut* a, AsyncSlot& S, size_t bytes) {
+  hipError_t e = hipEventRecord(S.snapped, h->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, bytes, hipMemcpyDeviceToHost, a->copy_stream);
+  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
+  return e;
+}
+
+// A job that could not be launched: its slot is free again
+static void lane_abandon(AsyncOut* a, AsyncSlot& S) {
+  (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
+  { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
+  a->cv_free.notify_all();
+}
+
+// ... and one that was: the writer's from here (ms_last: AsyncCounters)
+static void lane_commit(AsyncOut* a, int kind, int s, double ms_last) {
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    a->jobs.push_back(AsyncJob{kind, s});
+    a->pending++;
+    a->lane[kind].c.queued++;
+    a->lane[kind].c.ms_last += ms_last;
+  }
+  a->cv_job.notify_one();
+}
+
+static int output_stats_of(lbmdem_handle* h, int kind, long* counts4, double* ms4) {
+  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  AsyncCounters C;
+  if (AsyncOut* a = h->aout) {
+    std::lock_guard<std::mutex> lk(a->mu);
+    C = a->lane[kind].c;
+  }
+  const long c[4] = {C.queued, C.written, C.failed, C.slot_waits};
+  const double m[4] = {C.ms_slot_wait, C.ms_copy_wait, C.ms_io, C.ms_last};
+  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
   return LBMDEM_OK;
 }
 
@@ -655,6 +714,7 @@ static int async_settled(lbmdem_handle* h, const AsyncOldError& old) {
   } while (0)
 #define CHECK_WHOLE_LATTICE(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "use lbmdem_comm_write_vtk there")
 #define CHECK_WHOLE_TABLE(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "there rank 0 writes the tables with lbmdem_write_dem")
+#define CHECK_WHOLE_CKPT(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "there every rank saves its own file with lbmdem_checkpoint_save")
 
 static void launch_frame(lbmdem_handle* h, void* image_dev) {
   const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
@@ -688,41 +748,14 @@ int lbmdem_download_vtk_image(lbmdem_handle* h, void* image_be) {
   return LBMDEM_OK;
 }
 
-// The request is carried out first (the frames queued are written, the old slots freed, the new ones made; the writer thread
-// and the copy stream go when neither frames nor tables need them any more); a failure of the writer that nobody has been
-// told about is what the call then returns.
+// ---- frames ----------------------------------------------------------------------------------------------------------------
+
 int lbmdem_set_async_output(lbmdem_handle* h, int frames) {
   CHECK_H(h);
   if (frames < 0 || frames > LBMDEM_ASYNC_MAX_FRAMES)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_output: frames must be 0..%d, not %d", LBMDEM_ASYNC_MAX_FRAMES, frames);
   if (frames > 0) CHECK_WHOLE_LATTICE(h, "lbmdem_set_async_output");
-  if ((h->aout ? h->aout->frames : 0) == frames) return LBMDEM_OK;
-  AsyncOldError old;
-  async_settle(h->aout, &old);
-  if (h->aout) async_free_frames(h->aout);
-  if (frames > 0) {
-    RC_TRY(async_ensure(h, "lbmdem_set_async_output"));
-    AsyncOut* a = h->aout;
-    a->image_bytes = lbmdem_vtk_image_bytes(a->lx, a->ly);
-    hipError_t e = hipSuccess;
-    for (int s = 0; s < frames && e == hipSuccess; ++s) {
-      AsyncSlot& S = a->slot[s];
-      e = hipMalloc(&S.staging, a->image_bytes);
-      if (e == hipSuccess) e = hipHostMalloc(&S.pinned, a->image_bytes, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
-    }
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      const size_t bytes = a->image_bytes;
-      async_free_frames(a);
-      (void)async_settled(h, AsyncOldError{});
-      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_output: %d frame slots of %zu bytes (device staging + pinned host memory each) "
-                                 "cannot be had: %s", frames, bytes, hipGetErrorString(e));
-    }
-    a->frames = frames;
-  }
-  return async_settled(h, old);
+  return lane_resize(h, ASYNC_FRAME, frames, lbmdem_vtk_image_bytes(h->L.lx, h->L.ly), "lbmdem_set_async_output", "frame");
 }
 
 int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
@@ -733,41 +766,19 @@ int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
   CHECK_WHOLE_LATTICE(h, "lbmdem_write_vtk_async");
   RC_TRY(lbmdem_async_report(h));   // an earlier frame's failure: this call queues nothing
   const char* d = (dir && *dir) ? dir : ".";
-  if (strlen(d) >= sizeof a->slot[0].dir) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: directory name too long");
-  int s = -1;
-  {
-    std::unique_lock<std::mutex> lk(a->mu);
-    auto free_slot = [&] { for (int k = 0; k < a->frames; ++k) if (!a->slot[k].busy) return k; return -1; };
-    if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop a frame
-      const auto t0 = std::chrono::steady_clock::now();
-      a->fc.slot_waits++;
-      a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
-      a->fc.ms_slot_wait += ms_since(t0);
-    }
-    a->slot[s].busy = true;
-  }
-  AsyncSlot& S = a->slot[s];
-  strcpy(S.dir, d);
+  if (strlen(d) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: directory name too long");
+  const int s = lane_acquire(a, ASYNC_FRAME);
+  AsyncSlot& S = a->lane[ASYNC_FRAME].slot[s];
+  strcpy(S.path, d);
   S.nfile = nfile;
   launch_frame(h, S.staging);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(S.snapped, h->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, a->image_bytes, hipMemcpyDeviceToHost, a->copy_stream);
-  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
+  if (e == hipSuccess) e = slot_copy_behind(h, a, S, a->lane[ASYNC_FRAME].bytes);
   if (e != hipSuccess) {
-    (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
-    { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
-    a->cv_free.notify_all();
+    lane_abandon(a, S);
     HIP_TRY(e);
   }
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    a->jobs.push_back(s);
-    a->pending++;
-    a->fc.queued++;
-  }
-  a->cv_job.notify_one();
+  lane_commit(a, ASYNC_FRAME, s, 0.);
   return LBMDEM_OK;
 }
 
@@ -779,28 +790,16 @@ int lbmdem_output_drain(lbmdem_handle* h) {
     std::unique_lock<std::mutex> lk(a->mu);
     if (a->pending != 0) {
       const auto t0 = std::chrono::steady_clock::now();
-      a->cv_free.wait(lk, [&] { return a->pending == 0; });
-      if (a->frames) a->fc.ms_last += ms_since(t0);   // (lbmdem_output_stats is all 0 while frames are off)
+      async_wait_idle(a, lk);
+      if (a->lane[ASYNC_FRAME].slots) a->lane[ASYNC_FRAME].c.ms_last += ms_since(t0);   // (lbmdem_output_stats is all 0 while frames are off)
     }
   }
   return lbmdem_async_report(h);
 }
 
-int lbmdem_output_stats(lbmdem_handle* h, long* counts4, double* ms4) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
-  AsyncOut* a = h->aout;
-  long c[4] = {0, 0, 0, 0};
-  double m[4] = {0, 0, 0, 0};
-  if (a) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    c[0] = a->fc.queued; c[1] = a->fc.written; c[2] = a->fc.failed; c[3] = a->fc.slot_waits;
-    m[0] = a->fc.ms_slot_wait; m[1] = a->fc.ms_copy_wait; m[2] = a->fc.ms_io; m[3] = a->fc.ms_last;
-  }
-  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
-  return LBMDEM_OK;
-}
+int lbmdem_output_stats(lbmdem_handle* h, long* counts4, double* ms4) { return output_stats_of(h, ASYNC_FRAME, counts4, ms4); }
 
-// ---- tables in the background ------------------------------------------------------------------------------------------------------
+// ---- tables ----------------------------------------------------------------------------------------------------------------
 
 #ifndef LBMDEM_SINGLE_PRECISION
 static DemTableView dem_table_view(const lbmdem_handle* h) {
@@ -847,33 +846,7 @@ int lbmdem_set_async_dem(lbmdem_handle* h, int slots) {
   if (slots < 0 || slots > LBMDEM_ASYNC_MAX_DEM)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_dem: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_DEM, slots);
   if (slots > 0) CHECK_WHOLE_TABLE(h, "lbmdem_set_async_dem");
-  if ((h->aout ? h->aout->dem_slots : 0) == slots) return LBMDEM_OK;
-  AsyncOldError old;
-  async_settle(h->aout, &old);
-  if (h->aout) async_free_dem(h->aout);
-  if (slots > 0) {
-    RC_TRY(async_ensure(h, "lbmdem_set_async_dem"));
-    AsyncOut* a = h->aout;
-    const size_t bytes = sizeof(double) * LBMDEM_DEM_ROW_DOUBLES * (size_t)a->n;
-    hipError_t e = hipMalloc((void**)&a->dem_scratch, sizeof(double) * (DEM_STATS_CHAINS * (size_t)a->n + 22));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&a->dem_stats_host, sizeof(double) * 22, hipHostMallocDefault);
-    for (int s = 0; s < slots && e == hipSuccess; ++s) {
-      AsyncDemSlot& S = a->dslot[s];
-      e = hipMalloc((void**)&S.staging, bytes);
-      if (e == hipSuccess) e = hipHostMalloc((void**)&S.pinned, bytes, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
-    }
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_free_dem(a);
-      (void)async_settled(h, AsyncOldError{});
-      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_dem: %d table slots of %zu bytes (device staging + pinned host memory each) "
-                                 "cannot be had: %s", slots, bytes, hipGetErrorString(e));
-    }
-    a->dem_slots = slots;
-  }
-  return async_settled(h, old);
+  return lane_resize(h, ASYNC_TABLE, slots, sizeof(double) * LBMDEM_DEM_ROW_DOUBLES * (size_t)h->n, "lbmdem_set_async_dem", "table");
 #endif
 }
 
@@ -887,41 +860,24 @@ int lbmdem_write_dem_async(lbmdem_handle* h, const char* dir, int nfile, int wit
   CHECK_TABLE(h);
   RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
   const char* d = (dir && *dir) ? dir : ".";
-  if (strlen(d) >= sizeof a->dslot[0].dir) return fail(LBMDEM_EINVAL, "lbmdem_write_dem_async: directory name too long");
-  int s = -1;
-  {
-    std::unique_lock<std::mutex> lk(a->mu);
-    auto free_slot = [&] { for (int k = 0; k < a->dem_slots; ++k) if (!a->dslot[k].busy) return k; return -1; };
-    if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop an event
-      const auto t0 = std::chrono::steady_clock::now();
-      a->dc.slot_waits++;
-      a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
-      a->dc.ms_slot_wait += ms_since(t0);
-    }
-    a->dslot[s].busy = true;
-  }
-  AsyncDemSlot& S = a->dslot[s];
-  strcpy(S.dir, d);
+  if (strlen(d) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_write_dem_async: directory name too long");
+  const int s = lane_acquire(a, ASYNC_TABLE);
+  AsyncSlot& S = a->lane[ASYNC_TABLE].slot[s];
+  strcpy(S.path, d);
   S.nfile = nfile;
   S.with_forces = with_forces != 0;
-  const size_t n = (size_t)a->n;
-  double* stats_dev = a->dem_scratch + DEM_STATS_CHAINS * n;
+  double* stats_dev = a->dem_scratch + DEM_STATS_CHAINS * (size_t)a->n;
   const DemTableView T = dem_table_view(h);
-  launch_dem_frame(T, S.staging, a->dem_scratch, h->stream);
+  launch_dem_frame(T, static_cast<double*>(S.staging), a->dem_scratch, h->stream);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(S.snapped, h->stream);   // the rows are complete: their copy may start under k_dem_stats
+  if (e == hipSuccess) e = slot_copy_behind(h, a, S, a->lane[ASYNC_TABLE].bytes);   // the rows are complete: their copy may start under k_dem_stats
   if (e == hipSuccess) { launch_dem_stats(T, a->dem_scratch, stats_dev, h->stream); e = hipGetLastError(); }
   if (e == hipSuccess) e = hipMemcpyAsync(a->dem_stats_host, stats_dev, sizeof(double) * 22, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, sizeof(double) * LBMDEM_DEM_ROW_DOUBLES * n, hipMemcpyDeviceToHost, a->copy_stream);
-  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
   const auto t0 = std::chrono::steady_clock::now();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // the 22 numbers: the only wait on the step stream
   const double ms_stats = ms_since(t0);
   if (e != hipSuccess) {
-    (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
-    { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
-    a->cv_free.notify_all();
+    lane_abandon(a, S);
     HIP_TRY(e);
   }
   memcpy(S.stats22, a->dem_stats_host, sizeof S.stats22);
@@ -931,33 +887,14 @@ int lbmdem_write_dem_async(lbmdem_handle* h, const char* dir, int nfile, int wit
     energies8[0] = t[8]; energies8[1] = t[15]; energies8[2] = t[16]; energies8[3] = t[18];
     energies8[4] = t[17]; energies8[5] = t[19]; energies8[6] = t[20]; energies8[7] = t[21];
   }
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    a->jobs.push_back(LBMDEM_ASYNC_MAX_FRAMES + s);
-    a->pending++;
-    a->dc.queued++;
-    a->dc.ms_last += ms_stats;
-  }
-  a->cv_job.notify_one();
+  lane_commit(a, ASYNC_TABLE, s, ms_stats);
   return LBMDEM_OK;
 #endif
 }
 
-int lbmdem_output_stats_dem(lbmdem_handle* h, long* counts4, double* ms4) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
-  AsyncOut* a = h->aout;
-  long c[4] = {0, 0, 0, 0};
-  double m[4] = {0, 0, 0, 0};
-  if (a) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    c[0] = a->dc.queued; c[1] = a->dc.written; c[2] = a->dc.failed; c[3] = a->dc.slot_waits;
-    m[0] = a->dc.ms_slot_wait; m[1] = a->dc.ms_copy_wait; m[2] = a->dc.ms_io; m[3] = a->dc.ms_last;
-  }
-  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
-  return LBMDEM_OK;
-}
+int lbmdem_output_stats_dem(lbmdem_handle* h, long* counts4, double* ms4) { return output_stats_of(h, ASYNC_TABLE, counts4, ms4); }
 
-// ---- checkpoints in the background -------------------------------------------------------------------------------------------------
+// ---- checkpoints -----------------------------------------------------------------------------------------------------------
 
 int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots) {
   SP_UNAVAILABLE("checkpointing");
@@ -965,34 +902,11 @@ int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots) {
   CHECK_H(h);
   if (slots < 0 || slots > LBMDEM_ASYNC_MAX_CKPT)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_checkpoint: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_CKPT, slots);
-  if (slots > 0) CHECK_WHOLE_LATTICE_OR(h, "lbmdem_set_async_checkpoint", "there every rank saves its own file with lbmdem_checkpoint_save");
-  if ((h->aout ? h->aout->ckpt_slots : 0) == slots) return LBMDEM_OK;
-  AsyncOldError old;
-  async_settle(h->aout, &old);
-  if (h->aout) async_free_ckpt(h->aout);
-  if (slots > 0) {
-    RC_TRY(async_ensure(h, "lbmdem_set_async_checkpoint"));
-    AsyncOut* a = h->aout;
-    a->ckpt_layout = ckpt_layout(h->n, h->V.cap, h->L.plane);
-    const size_t bytes = a->ckpt_layout.total;
-    hipError_t e = hipSuccess;
-    for (int s = 0; s < slots && e == hipSuccess; ++s) {
-      AsyncCkptSlot& S = a->cslot[s];
-      e = hipMalloc((void**)&S.staging, bytes);
-      if (e == hipSuccess) e = hipHostMalloc((void**)&S.pinned, bytes, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
-    }
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      async_free_ckpt(a);
-      (void)async_settled(h, AsyncOldError{});
-      return fail(LBMDEM_ENOMEM, "lbmdem_set_async_checkpoint: %d checkpoint slots of %zu bytes (device staging + pinned host memory "
-                                 "each) cannot be had: %s", slots, bytes, hipGetErrorString(e));
-    }
-    a->ckpt_slots = slots;
-  }
-  return async_settled(h, old);
+  if (slots > 0) CHECK_WHOLE_CKPT(h, "lbmdem_set_async_checkpoint");
+  const CkptLayout Y = ckpt_layout(h->n, h->V.cap, h->L.plane);   // (the same whenever it is asked for: none of the three changes)
+  const int rc = lane_resize(h, ASYNC_CKPT, slots, Y.total, "lbmdem_set_async_checkpoint", "checkpoint");
+  if (async_ckpt_on(h)) h->aout->ckpt_layout = Y;
+  return rc;
 #endif
 }
 
@@ -1003,25 +917,14 @@ int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
   if (!async_ckpt_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: checkpoints in the background are off (lbmdem_set_async_checkpoint)");
   AsyncOut* a = h->aout;
   CHECK_NOT_SPLIT(h);
-  CHECK_WHOLE_LATTICE_OR(h, "lbmdem_checkpoint_save_async", "there every rank saves its own file with lbmdem_checkpoint_save");
+  CHECK_WHOLE_CKPT(h, "lbmdem_checkpoint_save_async");
   if (!path || !*path) return fail(LBMDEM_EINVAL, "null path");
-  if (strlen(path) >= sizeof a->cslot[0].path) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: path too long");
+  if (strlen(path) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: path too long");
   if (h->obst_pending) return fail(LBMDEM_EINVAL, "checkpoint between obst_construction and collide_stream");
   RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
-  int s = -1;
-  {
-    std::unique_lock<std::mutex> lk(a->mu);
-    auto free_slot = [&] { for (int k = 0; k < a->ckpt_slots; ++k) if (!a->cslot[k].busy) return k; return -1; };
-    if ((s = free_slot()) < 0) {   // back-pressure: wait for the writer, never drop a checkpoint
-      const auto t0 = std::chrono::steady_clock::now();
-      a->cc.slot_waits++;
-      a->cv_free.wait(lk, [&] { return (s = free_slot()) >= 0; });
-      a->cc.ms_slot_wait += ms_since(t0);
-    }
-    a->cslot[s].busy = true;
-  }
+  const int s = lane_acquire(a, ASYNC_CKPT);
   const auto t_hold = std::chrono::steady_clock::now();
-  AsyncCkptSlot& S = a->cslot[s];
+  AsyncSlot& S = a->lane[ASYNC_CKPT].slot[s];
   strcpy(S.path, path);
   // the host's side of the header, as of now: the run goes on behind this call
   S.shot.cfg = h->cfg; S.shot.nbsteps = h->nbsteps; S.shot.plane = h->L.plane; S.shot.lid6 = h->L.lid6;
@@ -1029,45 +932,21 @@ int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
   S.shot.vib = h->vib ? 1 : 0;
   if (h->carry_from < h->substep_seq) launch_carry_resolve(h->ct, h->carry_from, h->stream);   // as lbmdem_checkpoint_save
   CkptFrameJob J;
-  lbmdem_ckpt_frame_job(h, a->ckpt_layout, S.staging, &J);
+  lbmdem_ckpt_frame_job(h, a->ckpt_layout, static_cast<unsigned char*>(S.staging), &J);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemsetAsync(S.staging, 0, CKPT_WORDS_BYTES, h->stream);   // the digests are sums: from zero
   if (e == hipSuccess) { launch_ckpt_frame(J, h->stream); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipEventRecord(S.snapped, h->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(a->copy_stream, S.snapped, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(S.pinned, S.staging, a->ckpt_layout.total, hipMemcpyDeviceToHost, a->copy_stream);
-  if (e == hipSuccess) e = hipEventRecord(S.copied, a->copy_stream);
+  if (e == hipSuccess) e = slot_copy_behind(h, a, S, a->lane[ASYNC_CKPT].bytes);
   if (e != hipSuccess) {
-    (void)hipStreamSynchronize(a->copy_stream);   // (whatever part was queued no longer touches the slot)
-    { std::lock_guard<std::mutex> lk(a->mu); S.busy = false; }
-    a->cv_free.notify_all();
+    lane_abandon(a, S);
     HIP_TRY(e);
   }
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    a->jobs.push_back(LBMDEM_ASYNC_MAX_FRAMES + LBMDEM_ASYNC_MAX_DEM + s);
-    a->pending++;
-    a->cc.queued++;
-    a->cc.ms_last += ms_since(t_hold);
-  }
-  a->cv_job.notify_one();
+  lane_commit(a, ASYNC_CKPT, s, ms_since(t_hold));
   return LBMDEM_OK;
 #endif
 }
 
-int lbmdem_output_stats_checkpoint(lbmdem_handle* h, long* counts4, double* ms4) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
-  AsyncOut* a = h->aout;
-  long c[4] = {0, 0, 0, 0};
-  double m[4] = {0, 0, 0, 0};
-  if (a) {
-    std::lock_guard<std::mutex> lk(a->mu);
-    c[0] = a->cc.queued; c[1] = a->cc.written; c[2] = a->cc.failed; c[3] = a->cc.slot_waits;
-    m[0] = a->cc.ms_slot_wait; m[1] = a->cc.ms_copy_wait; m[2] = a->cc.ms_io; m[3] = a->cc.ms_last;
-  }
-  for (int k = 0; k < 4; ++k) { if (counts4) counts4[k] = c[k]; if (ms4) ms4[k] = m[k]; }
-  return LBMDEM_OK;
-}
+int lbmdem_output_stats_checkpoint(lbmdem_handle* h, long* counts4, double* ms4) { return output_stats_of(h, ASYNC_CKPT, counts4, ms4); }
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -201,8 +201,7 @@ int lbmdem_run_scene(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_s
   const int rc = run_scene_loop(h, comm, n, sc, res);
   if (!h || !h->aout) return rc;
   if (rc != LBMDEM_OK) {   // keep the loop's error text: wait here, leave the writer's report to the next call
-    std::unique_lock<std::mutex> lk(h->aout->mu);
-    h->aout->cv_free.wait(lk, [&] { return h->aout->pending == 0; });
+    lbmdem_async_wait_idle(h);
     return rc;
   }
   return lbmdem_output_drain(h);

@@ -326,6 +326,17 @@ static double serial_density(lbmdem_handle* h, lbmdem_comm* comm) {
   return s;
 }
 
+/* --run-stats: the line of one kind of background job (lbmdem_output_stats*: `last` is what the kind's fourth time means) */
+static int print_async_stats(lbmdem_handle* h, int (*stats)(lbmdem_handle*, long*, double*), const char* label, const char* last) {
+  long oc[4];
+  double oms[4];
+  const int rc = stats(h, oc, oms);
+  if (rc == LBMDEM_OK)
+    fprintf(stderr, "%s: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f %s %.3f\n",
+            label, oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], last, oms[3]);
+  return rc;
+}
+
 static int run(int argc, char** argv) {
   int lx = 7826, ly = 2325, device = 0; /* main.c:27-32 */
   double scale = 1., duration = 1.5;   /* main.c:24-26,47 */
@@ -537,27 +548,9 @@ static int run(int argc, char** argv) {
       DIE(lbmdem_dem_chain_recoveries(h, &recoveries), "dem_chain_recoveries");
       DIE(lbmdem_dem_chain_paints(h, &paints), "dem_chain_paints");
       fprintf(stderr, "dem_chain: launches %ld substeps %ld recoveries %ld paints %ld\n", launches, substeps, recoveries, paints);
-      if (g_async_frames) {
-        long oc[4];
-        double oms[4];
-        DIE(lbmdem_output_stats(h, oc, oms), "output_stats");
-        fprintf(stderr, "async_output: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_drain %.3f\n",
-                oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
-      }
-      if (g_async_ckpt) {
-        long oc[4];
-        double oms[4];
-        DIE(lbmdem_output_stats_checkpoint(h, oc, oms), "output_stats_checkpoint");
-        fprintf(stderr, "async_checkpoint: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_hold %.3f\n",
-                oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
-      }
-      if (g_async_dem) {
-        long oc[4];
-        double oms[4];
-        DIE(lbmdem_output_stats_dem(h, oc, oms), "output_stats_dem");
-        fprintf(stderr, "async_dem: queued %ld written %ld failed %ld slot_waits %ld ms_slot_wait %.3f ms_copy_wait %.3f ms_io %.3f ms_stats_wait %.3f\n",
-                oc[0], oc[1], oc[2], oc[3], oms[0], oms[1], oms[2], oms[3]);
-      }
+      if (g_async_frames) DIE(print_async_stats(h, lbmdem_output_stats, "async_output", "ms_drain"), "output_stats");
+      if (g_async_ckpt) DIE(print_async_stats(h, lbmdem_output_stats_checkpoint, "async_checkpoint", "ms_hold"), "output_stats_checkpoint");
+      if (g_async_dem) DIE(print_async_stats(h, lbmdem_output_stats_dem, "async_dem", "ms_stats_wait"), "output_stats_dem");
     }
   }
   now = time(NULL);
