@@ -164,6 +164,12 @@ def _open_library(LIB_PATH):
     L.lbmdem_download_grain_table.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_write_dem.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
     L.lbmdem_write_forces.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_geometry_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_download_act.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_download_links.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_geometry_obst.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_write_obst.argtypes = [C.c_void_p, C.c_char_p]
+    L.lbmdem_write_obst_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
     L.lbmdem_collide_stream_part.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_checkpoint_save.argtypes = [C.c_void_p, C.c_char_p]
     L.lbmdem_checkpoint_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
@@ -260,6 +266,23 @@ def write_vtk_image(directory, nFile, lx, ly, image):
     if buf.size != 44 * max(int(lx), 0) * max(int(ly), 0):
         raise LbmDemError(-1, f"write_vtk_image: the image of a {lx} x {ly} lattice has {44 * int(lx) * int(ly)} bytes, not {buf.size}")
     _chk(load_library().lbmdem_write_vtk_image(os.fsencode(directory), int(nFile), int(lx), int(ly), _vp(buf)))
+
+
+# struct lbmdem_link: an effective boundary link (LbmDem.download_links); q < 0 flags a delta of exactly zero
+LINK_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("q", np.int32), ("grain", np.int32), ("delta", np.float64)])
+GEOMETRY_COUNTERS = ("solid_nodes", "active_nodes", "links", "links_near", "links_far", "solid_slots")
+
+
+def write_obst_files(directory, obst, act, links):
+    """obst_writing (main.c:1601-1641): obst_LB.dat, active_nodes.dat and links.dat from the two [lx][ly] maps and a link list
+    (LINK_DTYPE, the file's order). Host only."""
+    obst = np.ascontiguousarray(obst, dtype=np.int32)
+    act = np.ascontiguousarray(act, dtype=np.int32)
+    links = np.ascontiguousarray(links, dtype=LINK_DTYPE)
+    if obst.ndim != 2 or act.shape != obst.shape or links.ndim != 1:
+        raise LbmDemError(-1, "write_obst_files: obst and act must be [lx][ly] maps of one shape, links a list of LINK_DTYPE")
+    _chk(load_library().lbmdem_write_obst_files(os.fsencode(directory), obst.shape[0], obst.shape[1], _vp(obst), _vp(act),
+                                                _vp(links), len(links)))
 
 
 DEM_ROW_DOUBLES = 28   # LBMDEM_DEM_ROW_DOUBLES
@@ -601,6 +624,37 @@ class LbmDem:
         out = np.zeros((self.lx, self.ly), dtype=np.int32)
         _chk(self._L.lbmdem_download_obst(self._h, _vp(out)))
         return out
+
+    # the boundary-link export: act, delta and obst_writing's files of the most recent rasterisation (include/lbmdem_hip.h)
+    def geometry_stats(self):
+        """-> dict of GEOMETRY_COUNTERS: solid interior nodes, active solid nodes, effective links, links with 0 < delta < 1/2,
+        links with delta >= 1/2, solid -> solid slots at active nodes"""
+        c = np.zeros(6, np.int64)
+        _chk(self._L.lbmdem_geometry_stats(self._h, _vp(c)))
+        return dict(zip(GEOMETRY_COUNTERS, (int(v) for v in c)))
+
+    def download_act(self):
+        out = np.zeros((self.lx, self.ly), dtype=np.int32)
+        _chk(self._L.lbmdem_download_act(self._h, _vp(out)))
+        return out
+
+    def download_links(self):
+        """the effective links in the order of links.dat (y outer, x inner, q = 1..8): structured array of LINK_DTYPE"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_links(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=LINK_DTYPE)
+        if n.value:
+            _chk(self._L.lbmdem_download_links(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def download_geometry_obst(self):
+        """the map the three calls above describe (after a run that has painted for the coming fluid step: that new map)"""
+        out = np.zeros((self.lx, self.ly), dtype=np.int32)
+        _chk(self._L.lbmdem_download_geometry_obst(self._h, _vp(out)))
+        return out
+
+    def write_obst(self, directory="."):
+        _chk(self._L.lbmdem_write_obst(self._h, os.fsencode(directory)))
 
     def macro(self):
         rho, ux, uy = (np.zeros((self.lx, self.ly)) for _ in range(3))

@@ -161,6 +161,40 @@ __device__ __forceinline__ real link_delta(int x, int y, real xc, real yc, real 
 // the fused fluid kernel
 // ---------------------------------------------------------------------------------------------
 
+// A solid node is "active" when one of its 8 neighbours was fluid at the moment its owning grain
+// was painted (main.c:1039-1052). Grains are painted in ascending index, so besides the
+// neighbours that are fluid in the final map this also counts neighbours now covered by a
+// HIGHER-index grain that do not lie inside the owner's own disc (they were still fluid when the
+// owner was painted). Only reachable when reduced discs of different grains touch or overlap.
+// A neighbour additionally covered by a third, LOWER-index disc was not fluid then: decided with the
+// rasteriser's record of the lowest index covering a multiply covered node (min_cover).
+// `ob(ex, ey)` = the obstacle id of node (gx + ex, gy + ey), (gx, gy) global, a node of a grain. One body for the
+// fused kernel's tile (Tile::active) and the boundary-link export (lbm_links.hip).
+template <class ObAt>
+__device__ __forceinline__ bool act_rule(const LatticeView& L, const GrainFluidView& G, ObAt ob, int gx, int gy) {
+  const int oS = ob(0, 0);
+  bool higher = false;
+#pragma unroll
+  for (int q = 1; q < 9; ++q) {
+    const int o = ob(EXq(q), EYq(q));
+    if (o == -1) return true;
+    higher |= (o > oS && o != L.n);
+  }
+  if (!higher) return false;
+  const real xc = G.xc[oS], yc = G.yc[oS], r2 = G.r2[oS], rb = G.rbl0[oS];
+  const real R2 = rb * rb;
+#pragma unroll
+  for (int q = 1; q < 9; ++q) {
+    const int o = ob(EXq(q), EYq(q));
+    if (o > oS && o != L.n) {
+      const int x = gx + EXq(q), y = gy + EYq(q);
+      const real d2 = (x - xc) * (x - xc) + (y - yc) * (y - yc);
+      if (!(d2 <= R2 && d2 <= r2) && min_cover(G, (long)(x - L.gx0) * L.sy + y, o) > oS) return true;
+    }
+  }
+  return false;
+}
+
 template <int TX, int TY>
 struct Tile {
   static constexpr int RX = TX + 2, RY = TY + 2;  // staged populations: halo 1
@@ -171,36 +205,10 @@ struct Tile {
     return sF[(q * RX + (tx + 1)) * RY + (ty + 1)];
   }
   __device__ __forceinline__ int O(int tx, int ty) const { return sO[(tx + 2) * OY + (ty + 2)]; }
-  // A solid node is "active" when one of its 8 neighbours was fluid at the moment its owning grain
-  // was painted (main.c:1039-1052). Grains are painted in ascending index, so besides the
-  // neighbours that are fluid in the final map this also counts neighbours now covered by a
-  // HIGHER-index grain that do not lie inside the owner's own disc (they were still fluid when the
-  // owner was painted). Only reachable when reduced discs of different grains touch or overlap.
-  // A neighbour additionally covered by a third, LOWER-index disc was not fluid then: decided with the
-  // rasteriser's record of the lowest index covering a multiply covered node (min_cover).
+  // `act` of the tile's node (tx, ty) = global (gx, gy): act_rule over the staged ids
   __device__ __forceinline__ bool active(const LatticeView& L, const GrainFluidView& G, int tx, int ty,
                                          int gx, int gy) const {
-    const int oS = O(tx, ty);
-    bool higher = false;
-#pragma unroll
-    for (int q = 1; q < 9; ++q) {
-      const int o = O(tx + EXq(q), ty + EYq(q));
-      if (o == -1) return true;
-      higher |= (o > oS && o != L.n);
-    }
-    if (!higher) return false;
-    const real xc = G.xc[oS], yc = G.yc[oS], r2 = G.r2[oS], rb = G.rbl0[oS];
-    const real R2 = rb * rb;
-#pragma unroll
-    for (int q = 1; q < 9; ++q) {
-      const int o = O(tx + EXq(q), ty + EYq(q));
-      if (o > oS && o != L.n) {
-        const int x = gx + EXq(q), y = gy + EYq(q);
-        const real d2 = (x - xc) * (x - xc) + (y - yc) * (y - yc);
-        if (!(d2 <= R2 && d2 <= r2) && min_cover(G, (long)(x - L.gx0) * L.sy + y, o) > oS) return true;
-      }
-    }
-    return false;
+    return act_rule(L, G, [&](int ex, int ey) { return O(tx + ex, ty + ey); }, gx, gy);
   }
 };
 

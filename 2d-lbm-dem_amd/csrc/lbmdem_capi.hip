@@ -195,6 +195,7 @@ static int paint_into(lbmdem_handle* h, int* obst) {
     h->obst_repaints++;
   }
   h->obst_reset_rows = 0;
+  h->geo_buf = b;
   h->slots_valid = false;  // the grain geometry the table is indexed with has changed
   HIP_TRY(hipGetLastError());
   return LBMDEM_OK;
@@ -1056,7 +1057,7 @@ int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid) {
   launch_dem_chain(h->kin[h->kcur], h->kin[1 - h->kcur], h->r, h->m, h->It, h->fhf, h->V, h->gp, P,
                    h->dist ? h->dd.active : nullptr, &h->ct, h->substep_seq, h->dist ? h->owner : nullptr, fill, chain,
                    (int)k, paint, h->stream);
-  if (paint.obst) { h->chain_painted = true; h->chain_paints++; }
+  if (paint.obst) { h->chain_painted = true; h->chain_paints++; h->geo_buf = 1 - h->ocur; }
   if (h->dist && h->dist_poison) launch_dist_poison(h->dd, h->kin[0], h->kin[1], h->n, h->stream);
   h->substep_seq += k;
   h->chain_launches++; h->chain_substeps += k;
@@ -1205,6 +1206,7 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   const int b = 1 - s.ocur;
   h->snap_ok[b] = false; h->chg_state[b] = 0;
   h->obst_reset_rows = 0; h->chain_painted = false;
+  h->geo_buf = -1;   // (the centres may be those of the picture the failed launch began; the next rasterisation sets them again)
 }
 
 static int run_steps(lbmdem_handle* h, int fluid, long n, bool logged, bool resumed = false);

@@ -340,6 +340,7 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
   h->ocur = 0; h->obst_pending = false;
   h->chg_state[0] = h->chg_state[1] = 0;
   h->snap_ok[0] = h->snap_ok[1] = false;   // (the loaded map is not the picture lbmdem_create has just painted)
+  h->geo_buf = -1;                         // (... nor do the centres of that paint describe it)
   for (int q = 0; q < 9 && ok; ++q) fill(h->f[0] + (size_t)q * h->L.plane, sizeof(double) * (size_t)h->L.plane);
   h->fcur = 0;
   if (ok && H.has_dist) {   // a strip with distributed grains: masks and message capacities as the writer had them. A

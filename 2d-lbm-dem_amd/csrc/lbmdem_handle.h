@@ -200,6 +200,10 @@ struct lbmdem_handle {
   unsigned char* owner = nullptr;
   unsigned* mincov = nullptr;   // GrainFluidView::mincov
   unsigned paint_epoch = 0;
+  // the map buffer that xc, yc, r2, rbl0 and the mincov record describe: the one the most recent rasterisation painted (what
+  // the boundary-link export shows, lbm_links.hip). -1: none -- the picture those centres belong to has been given up
+  // (drop_chain_paint, a launch of k_dem_chain undone) or replaced (a loaded checkpoint's map)
+  int geo_buf = -1;
   // link sums handed from the fused kernel to the force kernel (ForceSlots, lbmdem_internal.h)
   ForceSlots fs{};
   int* gathered2 = nullptr;   // both counters (fs.gathered / fs.gathered_next alternate between them)
@@ -415,7 +419,7 @@ static inline bool obst_update_planned(const lbmdem_handle* h) {
 LBMDEM_INTERNAL long lbmdem_dem_chain_length(lbmdem_handle* h, long remaining, int fluid);
 LBMDEM_INTERNAL int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid);   // fluid: a fluid step may follow (the run may rasterise for it)
 static inline void drop_chain_paint(lbmdem_handle* h) {
-  if (h->chain_painted) { h->chain_painted = false; h->obst_reset_rows = 0; }   // (the canvas holds a picture nobody will use)
+  if (h->chain_painted) { h->chain_painted = false; h->obst_reset_rows = 0; h->geo_buf = -1; }   // (the canvas holds a picture nobody will use)
 }
 // pieces of the fluid step for the C transport (lbmdem_comm.hip), which runs the edge rows on its halo lane's stream:
 LBMDEM_INTERNAL int lbmdem_collide_stream_prepare(lbmdem_handle* h);

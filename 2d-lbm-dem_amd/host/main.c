@@ -37,6 +37,10 @@
  * line, `async_checkpoint: queued Q written W failed F slot_waits S ms_slot_wait .. ms_copy_wait .. ms_io .. ms_hold ..`
  * (lbmdem_output_stats_checkpoint). Both single GPU only. --verify-checkpoint FILE: checks FILE against its digests without a
  * GPU and exits: 0 for a file that matches or has no digests, 1 with the section that differs.
+ * --dump-geometry DIR: after the run's last sub-step and before the `final_density:` line, the reference's obst_writing
+ * (main.c:1601-1641) for the most recent rasterisation: DIR/obst_LB.dat, DIR/active_nodes.dat, DIR/links.dat
+ * (lbmdem_write_obst). With --run-stats one more line, `geometry: solid_nodes A active_nodes B links C links_near D links_far E
+ * solid_slots F` (lbmdem_geometry_stats). Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -58,6 +62,7 @@
  * distributed, neighbour messages over RCCL (lbmdem_comm_*). Rank 0 creates the RCCL id and hands it to the others
  * through a file in a private temporary directory. Rank 0 prints and writes the VTK frames and DEM tables (merged over the ranks); checkpoints are single-GPU. */
 static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_stats = 0;
+static const char* g_dump_geometry = NULL;   /* --dump-geometry DIR */
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
 static int g_async_ckpt = 0;     /* --async-checkpoint [N] */
@@ -193,6 +198,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--vib")) g_vib = 1;
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--probes")) probes = 1;
+    if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) g_dump_geometry = argv[a + 1];
     if (!strcmp(argv[a], "--async-output")) g_async_frames = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--async-dem")) g_async_dem = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--async-checkpoint")) g_async_ckpt = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 1;
@@ -219,6 +225,7 @@ int main(int argc, char** argv) {
   if (g_dry && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dry is a single-GPU mode (the strips exist for the fluid)\n"); return EXIT_FAILURE; }
   if (g_vib && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--vib is a single-GPU mode (vibrating walls are not available on strips)\n"); return EXIT_FAILURE; }
   if (probes && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--probes is a single-GPU mode (the probes are not available on strips)\n"); return EXIT_FAILURE; }
+  if (g_dump_geometry && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dump-geometry is a single-GPU mode (the boundary-link export needs the whole lattice on one handle)\n"); return EXIT_FAILURE; }
   if (g_async_frames && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-output is a single-GPU mode (with --gpus N rank 0 merges the strips' columns and writes the frames itself)\n"); return EXIT_FAILURE; }
   if (g_async_dem && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-dem is a single-GPU mode (with --gpus N rank 0 runs the table sub-step on a full replica and writes the tables itself)\n"); return EXIT_FAILURE; }
   if ((g_async_ckpt || g_ckpt_every) && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--checkpoint-every and --async-checkpoint are single-GPU modes (with --gpus N every rank saves its own file at the end)\n"); return EXIT_FAILURE; }
@@ -373,6 +380,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (!strcmp(argv[a], "--probes") && a + 1 < argc) probe_path = argv[++a];
+    else if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--probe-every") && a + 1 < argc) probe_every = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--probe-row") && a + 1 < argc) probe_row = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--probe-point") && a + 1 < argc) {
@@ -387,7 +395,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -527,6 +535,11 @@ static int run(int argc, char** argv) {
       DIE(lbmdem_checkpoint_save(h, ckpt_out), "checkpoint_save");
     }
   }
+  long geometry[6] = {0, 0, 0, 0, 0, 0};
+  if (g_dump_geometry) {   /* obst_writing (main.c:1601-1641) */
+    DIE(lbmdem_write_obst(h, g_dump_geometry), "write_obst");
+    if (g_run_stats) DIE(lbmdem_geometry_stats(h, geometry), "geometry_stats");
+  }
   double sum = serial_density(h, comm);
   double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
   if (comm) { /* the slowest rank's time */
@@ -548,6 +561,9 @@ static int run(int argc, char** argv) {
       DIE(lbmdem_dem_chain_recoveries(h, &recoveries), "dem_chain_recoveries");
       DIE(lbmdem_dem_chain_paints(h, &paints), "dem_chain_paints");
       fprintf(stderr, "dem_chain: launches %ld substeps %ld recoveries %ld paints %ld\n", launches, substeps, recoveries, paints);
+      if (g_dump_geometry)
+        fprintf(stderr, "geometry: solid_nodes %ld active_nodes %ld links %ld links_near %ld links_far %ld solid_slots %ld\n",
+                geometry[0], geometry[1], geometry[2], geometry[3], geometry[4], geometry[5]);
       if (g_async_frames) DIE(print_async_stats(h, lbmdem_output_stats, "async_output", "ms_drain"), "output_stats");
       if (g_async_ckpt) DIE(print_async_stats(h, lbmdem_output_stats_checkpoint, "async_checkpoint", "ms_hold"), "output_stats_checkpoint");
       if (g_async_dem) DIE(print_async_stats(h, lbmdem_output_stats_dem, "async_dem", "ms_stats_wait"), "output_stats_dem");

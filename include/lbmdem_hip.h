@@ -408,6 +408,44 @@ int lbmdem_write_dem(lbmdem_handle* h, const char* dir, int nfile, double* energ
  * evidently mean. Every other line is character-identical to the reference's file. The pair search is a
  * host-side uniform grid (same pairs as the reference's O(N^2) loop). */
 int lbmdem_write_forces(lbmdem_handle* h, const char* dir, int nfile);
+/* The boundary-link export: the two arrays of obst_construction (main.c:991-1065) that the library never stores -- act[x][y],
+ * which solid nodes take part in the bounce-back, and delta[x][y][q], the wall distance of every link -- derived on the device
+ * from the obstacle map with the device functions the fluid step itself uses, and obst_writing (main.c:1601-1641), the
+ * reference's dump of them: <dir>/obst_LB.dat, <dir>/active_nodes.dat, <dir>/links.dat.
+ * Which geometry: the MOST RECENT RASTERISATION -- the map the library painted last, together with the centres it was painted
+ * from. After lbmdem_create, lbmdem_obst_construction, lbmdem_lbm_step or a fluid step inside a run that is the map
+ * lbmdem_download_obst returns. After a run whose last sub-steps have already rasterised the discs for the coming fluid step
+ * (lbmdem_dem_chain_paints) it is that new map, which lbmdem_download_obst does not show yet: lbmdem_download_geometry_obst
+ * hands back the map the other three calls describe, whichever it is. The export launches no rasterisation and changes nothing
+ * a later step reads: a run with exports in between is bit-equal to the run without them.
+ * A link is an EFFECTIVE link: a (node P, direction q) that the reference's bounce-back loop (main.c:1154-1222) takes into its
+ * interpolation branch -- P an interior node of a grain (obst[P] != -1, != nbgrains), act[P] == 1, obst[P + e_q] == -1. Its
+ * delta is bit for bit the reference's delta[P][q] (the owner of P is the last grain to write that entry). The reference's
+ * delta array can hold further non-zero entries that its loop never reads: left by a lower-index disc at a node, or towards a
+ * neighbour, that a higher-index disc painted afterwards. These STALE entries are no links and are not exported; they exist
+ * only where two reduced discs overlap or sit on adjacent nodes -- in every other packing the links are exactly the
+ * reference's delta != 0 entries and links.dat is the reference's file character for character.
+ * Links come in the file's order: y outer, x inner, q = 1..8. A link whose delta is exactly zero -- which the reference's file
+ * leaves out (its `!= 0` test, main.c:1634) -- stays in the list with q NEGATED; the formatter skips it.
+ *   lbmdem_geometry_stats          counts6 = solid interior nodes, active solid nodes, effective links (zero deltas included),
+ *                                  links with 0 < delta < 1/2, links with delta >= 1/2, solid -> solid slots at active nodes
+ *                                  (the w[q] resets of main.c:1161, 1192). The counting pass alone.
+ *   lbmdem_download_act            [lx][ly], the reference's values: 1 on interior fluid, 0 on the lattice-edge rows and columns
+ *                                  (init_obst, main.c:675-683), 0 or 1 on grains
+ *   lbmdem_download_links          cap = 0 (out may be NULL) only reports *count; a buffer of fewer than *count records is refused
+ *   lbmdem_write_obst_files        host only, no handle, no device: the one formatter -- "%d " per node and "\n" per y for the two
+ *                                  maps, "%d  %d  %d  %f\n" per link. Unlike the reference it checks fopen.
+ * LBMDEM_EINVAL: a strip of a decomposition or distributed grains; the single-precision library; null buffers; a handle whose
+ * last rasterisation was given up or replaced (the grains moved on by sub-steps or an upload after a run had painted for a
+ * fluid step that never came; a loaded checkpoint before its first fluid step). Vibrating and probing handles have the export;
+ * a checkpoint carries nothing of it. */
+typedef struct lbmdem_link { int x, y, q, grain; double delta; } lbmdem_link;
+int lbmdem_geometry_stats(lbmdem_handle* h, long* counts6);
+int lbmdem_download_act(lbmdem_handle* h, int* act);
+int lbmdem_download_links(lbmdem_handle* h, lbmdem_link* out, long cap, long* count);
+int lbmdem_download_geometry_obst(lbmdem_handle* h, int* obst);
+int lbmdem_write_obst(lbmdem_handle* h, const char* dir);
+int lbmdem_write_obst_files(const char* dir, int lx, int ly, const int* obst, const int* act, const lbmdem_link* links, long n);
 /* The same two events written in the background while the run goes on, by the writer thread of lbmdem_set_async_output (one
  * thread and one copy stream per handle, made for whichever of the two features is switched on first; its jobs are strictly
  * first in, first out, so the lines of stats.data land in call order). lbmdem_set_async_dem(h, slots), slots in
