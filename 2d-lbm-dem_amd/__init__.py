@@ -170,6 +170,12 @@ def _open_library(LIB_PATH):
     L.lbmdem_download_geometry_obst.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_write_obst.argtypes = [C.c_void_p, C.c_char_p]
     L.lbmdem_write_obst_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
+    L.lbmdem_densities_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_write_densities_host.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    L.lbmdem_format_fixed4.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
     L.lbmdem_collide_stream_part.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_checkpoint_save.argtypes = [C.c_void_p, C.c_char_p]
     L.lbmdem_checkpoint_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
@@ -285,6 +291,28 @@ def write_obst_files(directory, obst, act, links):
                                                 _vp(links), len(links)))
 
 
+def write_densities_host(directory, nFile, f, obst, t=0.0, rho_moy=1000.0):
+    """write_densities (main.c:482-566) over host arrays f[lx][ly][9] and obst[lx][ly]: densities%.6i.vtk and
+    pressure_base%.6i.dat, the reference's loops with one fprintf per value. Host only."""
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    obst = np.ascontiguousarray(obst, dtype=np.int32)
+    if f.ndim != 3 or f.shape[2] != 9 or obst.shape != f.shape[:2]:
+        raise LbmDemError(-1, "write_densities_host: f must be [lx][ly][9] and obst [lx][ly]")
+    _chk(load_library().lbmdem_write_densities_host(os.fsencode(directory), int(nFile), f.shape[0], f.shape[1], float(t),
+                                                    float(rho_moy), _vp(f), _vp(obst)))
+
+
+def format_fixed4(values):
+    """bytes: every value as printf's "%.4lf" followed by a newline, made by the formatter the device uses (finite values
+    below 1e9 in magnitude). Host only."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    out = np.empty(17 * len(v) + 1, np.uint8)
+    n = C.c_long(0)
+    _chk(load_library().lbmdem_format_fixed4(_vp(v), len(v), _vp(out), len(out), C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+DENSITIES_COUNTERS = ("pressure_bytes", "velocity_bytes", "bands", "refused_nodes")
 DEM_ROW_DOUBLES = 28   # LBMDEM_DEM_ROW_DOUBLES
 
 
@@ -655,6 +683,30 @@ class LbmDem:
 
     def write_obst(self, directory="."):
         _chk(self._L.lbmdem_write_obst(self._h, os.fsencode(directory)))
+
+    def write_densities(self, directory=".", nFile=0):
+        """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""
+        _chk(self._L.lbmdem_write_densities(self._h, os.fsencode(directory), int(nFile)))
+
+    def densities_text(self):
+        """bytes: the body of densities%.6i.vtk without its header lines -- all Pressure lines, then all velocity lines"""
+        n = C.c_size_t(0)
+        if self._L.lbmdem_download_densities_text(self._h, None, 0, C.byref(n)) == 0 or n.value == 0:
+            _chk(self._L.lbmdem_download_densities_text(self._h, None, 0, C.byref(n)))   # (refused: say why)
+            return b""
+        out = np.empty(n.value, np.uint8)
+        _chk(self._L.lbmdem_download_densities_text(self._h, _vp(out), n.value, C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def set_densities_staging(self, nbytes):
+        """the budget in bytes of the device and of the pinned staging buffer of write_densities; 0: the default (64 MiB)"""
+        _chk(self._L.lbmdem_set_densities_staging(self._h, int(nbytes)))
+
+    def densities_stats(self):
+        """of the last write_densities / densities_text: (pressure bytes, velocity bytes, bands, nodes the device refused)"""
+        c = np.zeros(4, np.int64)
+        _chk(self._L.lbmdem_densities_stats(self._h, _vp(c)))
+        return tuple(int(x) for x in c)
 
     def macro(self):
         rho, ux, uy = (np.zeros((self.lx, self.ly)) for _ in range(3))

@@ -243,6 +243,10 @@ struct lbmdem_handle {
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
   ProbeState probe;
+  // write_densities (lbm_densities.hip): the staging budget in bytes (0: the default) and, of the last call, the bytes of the
+  // two sections, the bands, the nodes the device refused to format (lbmdem_densities_stats)
+  size_t dens_budget = 0;
+  long dens_stats[4] = {0, 0, 0, 0};
   AsyncOut* aout = nullptr;   // null: frames, tables and checkpoints are written synchronously (the default)
   // lbmdem_set_checkpoint_every: lbmdem_run_scene saves to ckpt_path whenever the step counter reaches a multiple (0: never)
   long ckpt_every = 0;

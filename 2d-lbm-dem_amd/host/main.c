@@ -41,6 +41,10 @@
  * (main.c:1601-1641) for the most recent rasterisation: DIR/obst_LB.dat, DIR/active_nodes.dat, DIR/links.dat
  * (lbmdem_write_obst). With --run-stats one more line, `geometry: solid_nodes A active_nodes B links C links_near D links_far E
  * solid_slots F` (lbmdem_geometry_stats). Single GPU only.
+ * --densities DIR: at the same place, the reference's write_densities (main.c:482-566) with the run's frame counter:
+ * DIR/densities%.6i.vtk and DIR/pressure_base%.6i.dat, the text made on the device (lbmdem_write_densities), and one line after
+ * `final_density:`, `densities: pressure_bytes P velocity_bytes V bands B` (lbmdem_densities_stats). Single GPU only, and not
+ * with --dry (there is no fluid).
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -63,6 +67,7 @@
  * through a file in a private temporary directory. Rank 0 prints and writes the VTK frames and DEM tables (merged over the ranks); checkpoints are single-GPU. */
 static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_stats = 0;
 static const char* g_dump_geometry = NULL;   /* --dump-geometry DIR */
+static const char* g_densities = NULL;       /* --densities DIR */
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
 static int g_async_ckpt = 0;     /* --async-checkpoint [N] */
@@ -199,6 +204,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) g_dump_geometry = argv[a + 1];
+    if (!strcmp(argv[a], "--densities") && a + 1 < argc) g_densities = argv[a + 1];
     if (!strcmp(argv[a], "--async-output")) g_async_frames = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--async-dem")) g_async_dem = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--async-checkpoint")) g_async_ckpt = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 1;
@@ -226,6 +232,8 @@ int main(int argc, char** argv) {
   if (g_vib && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--vib is a single-GPU mode (vibrating walls are not available on strips)\n"); return EXIT_FAILURE; }
   if (probes && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--probes is a single-GPU mode (the probes are not available on strips)\n"); return EXIT_FAILURE; }
   if (g_dump_geometry && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dump-geometry is a single-GPU mode (the boundary-link export needs the whole lattice on one handle)\n"); return EXIT_FAILURE; }
+  if (g_densities && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--densities is a single-GPU mode (write_densities needs the whole lattice on one handle)\n"); return EXIT_FAILURE; }
+  if (g_densities && g_dry) { fprintf(stderr, "--densities cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_async_frames && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-output is a single-GPU mode (with --gpus N rank 0 merges the strips' columns and writes the frames itself)\n"); return EXIT_FAILURE; }
   if (g_async_dem && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-dem is a single-GPU mode (with --gpus N rank 0 runs the table sub-step on a full replica and writes the tables itself)\n"); return EXIT_FAILURE; }
   if ((g_async_ckpt || g_ckpt_every) && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--checkpoint-every and --async-checkpoint are single-GPU modes (with --gpus N every rank saves its own file at the end)\n"); return EXIT_FAILURE; }
@@ -381,6 +389,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (!strcmp(argv[a], "--probes") && a + 1 < argc) probe_path = argv[++a];
     else if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--densities") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--probe-every") && a + 1 < argc) probe_every = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--probe-row") && a + 1 < argc) probe_row = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--probe-point") && a + 1 < argc) {
@@ -395,7 +404,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -540,6 +549,12 @@ static int run(int argc, char** argv) {
     DIE(lbmdem_write_obst(h, g_dump_geometry), "write_obst");
     if (g_run_stats) DIE(lbmdem_geometry_stats(h, geometry), "geometry_stats");
   }
+  long densities[4] = {0, 0, 0, 0};
+  if (g_densities) {   /* write_densities (main.c:482-566), numbered like the next frame */
+    int nfile = max_steps < 0 || done.steps_done > 0 ? done.nfile : (int)(nbsteps / cfg.phys.stepFilm);
+    DIE(lbmdem_write_densities(h, g_densities, nfile), "write_densities");
+    DIE(lbmdem_densities_stats(h, densities), "densities_stats");
+  }
   double sum = serial_density(h, comm);
   double secs = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
   if (comm) { /* the slowest rank's time */
@@ -551,6 +566,7 @@ static int run(int argc, char** argv) {
   long lbm_steps = g_dry ? 0 : (nbsteps + cfg.npDEM - 1) / cfg.npDEM;
   if (g_rank == 0) {
     fprintf(stderr, "final_density: %f\n", sum);
+    if (g_densities) fprintf(stderr, "densities: pressure_bytes %ld velocity_bytes %ld bands %ld\n", densities[0], densities[1], densities[2]);
     fprintf(stderr, "time: %e\n", secs);
     fprintf(stderr, "dem_steps: %ld\n", nbsteps);
     fprintf(stderr, "MLUPS: %.1f  DEM-steps/s: %.1f  (%d GPU%s)\n", 1e-6 * (double)lx * ly * lbm_steps / secs, nbsteps / secs,

@@ -446,6 +446,40 @@ int lbmdem_download_links(lbmdem_handle* h, lbmdem_link* out, long cap, long* co
 int lbmdem_download_geometry_obst(lbmdem_handle* h, int* obst);
 int lbmdem_write_obst(lbmdem_handle* h, const char* dir);
 int lbmdem_write_obst_files(const char* dir, int lx, int ly, const int* obst, const int* act, const lbmdem_link* links, long n);
+/* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
+ * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
+ * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
+ * section of "%.4lf %.4lf 0.\n" lines, both in file order [y][x] -- and <dir>/pressure_base%.6i.dat, "%le %le\n" per x for
+ * row y == 2 (no lines when ly <= 2). Per node P = (1./3.) * rho_moy * (sum_i f[i] - 1.), u_x = sum_i f[i] * ex[i],
+ * u_y = sum_i f[i] * ey[i], i = 0..8 in that order; all three +0.0 where obst >= 0. The map is the one
+ * lbmdem_download_obst and lbmdem_download_vtk_fields show: what the last fluid step saw, not a rasterisation a run has
+ * already made for the coming one.
+ * The "%.4lf" text is made ON THE DEVICE, byte for byte what printf prints (the exact binary value rounded to nearest, ties to
+ * even; "-0.0000" for -0.0 and for negatives that round to zero): a count pass, a scan and an emit pass over BANDS of whole
+ * file rows, each band through a device staging buffer and pinned host memory to the file. Both buffers are bounded by the
+ * staging budget -- 64 MiB unless lbmdem_set_densities_staging says otherwise (0 restores the default); a budget below the
+ * file's longest row counts as that row. A section's bands hold as many rows as the budget has room for that section's
+ * longest row. The device formats finite values below 1e9 in magnitude; if a single node holds anything else, the whole
+ * file is written by lbmdem_write_densities_host from a download instead.
+ *   lbmdem_write_densities          both files; synchronises; f, obst, the grains and every counter are left as they were
+ *   lbmdem_download_densities_text  the body without the header lines: all Pressure lines, then all velocity lines. A cap that
+ *                                   is too small (0 included; out may then be NULL): LBMDEM_EINVAL, *bytes = what is needed
+ *   lbmdem_densities_stats          counts4, of the last of those two calls: bytes of the Pressure lines, bytes of the
+ *                                   velocity lines, bands (both sections together; 0 when the host wrote the text), nodes the
+ *                                   device refused to format
+ *   lbmdem_write_densities_host     host only, no handle, no device: the reference's loops, one fprintf per value, over
+ *                                   f[lx][ly][9] and obst[lx][ly]. Unlike the reference it checks fopen.
+ *   lbmdem_format_fixed4            host only: the device's formatter on the host, every value followed by "\n"; *bytes = the
+ *                                   length; LBMDEM_EINVAL for a value that is not finite or not below 1e9, or a cap too small
+ * LBMDEM_EINVAL: a strip of a decomposition or distributed grains; the single-precision library (the two host-only calls
+ * exist there too); null arguments; a directory that cannot be written ("cannot open"). */
+int lbmdem_write_densities(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_download_densities_text(lbmdem_handle* h, char* out, size_t cap, size_t* bytes);
+int lbmdem_set_densities_staging(lbmdem_handle* h, size_t bytes);
+int lbmdem_densities_stats(lbmdem_handle* h, long* counts4);
+int lbmdem_write_densities_host(const char* dir, int nfile, int lx, int ly, double t, double rho_moy, const double* f_aos,
+                                const int* obst);
+int lbmdem_format_fixed4(const double* v, long n, char* out, long cap, long* bytes);
 /* The same two events written in the background while the run goes on, by the writer thread of lbmdem_set_async_output (one
  * thread and one copy stream per handle, made for whichever of the two features is switched on first; its jobs are strictly
  * first in, first out, so the lines of stats.data land in call order). lbmdem_set_async_dem(h, slots), slots in
