@@ -194,6 +194,7 @@ def _open_library(LIB_PATH):
         L.lbmdem_dem_chain_recoveries.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     if hasattr(L, "lbmdem_debug_chain_giveup"):   # experiment build only
         L.lbmdem_debug_chain_giveup.argtypes = [C.c_void_p, C.c_int]
+        L.lbmdem_debug_live_memory.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.lbmdem_set_obst_update.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_obst_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.lbmdem_set_change_mask.argtypes = [C.c_void_p, C.c_int]
@@ -246,6 +247,16 @@ def _open_library(LIB_PATH):
     L.lbmdem_read_sample.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_double)),
                                      C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(C.c_double))]
     return L
+
+
+def live_memory():
+    """(blocks, bytes) of device and pinned memory the library holds in this process right now. Experiment build only."""
+    L = load_library()
+    if not hasattr(L, "lbmdem_debug_live_memory"):
+        raise LbmDemError(-1, "live_memory: only the experiment build (make AB=1) counts its memory")
+    blocks, nbytes = C.c_long(0), C.c_long(0)
+    _chk(L.lbmdem_debug_live_memory(C.byref(blocks), C.byref(nbytes)))
+    return int(blocks.value), int(nbytes.value)
 
 
 def strips_module():

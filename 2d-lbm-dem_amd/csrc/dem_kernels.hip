@@ -1631,30 +1631,22 @@ __global__ __launch_bounds__(256) void k_tile_halo(int n, const int* __restrict_
 
 }  // namespace
 
-int carry_track_alloc(CarryTrack& T, int n) {
+// (this and the other *_alloc below: the blocks belong to `mem`, which frees them; on failure they return at the first error)
+int carry_track_alloc(MemPool& mem, CarryTrack& T, int n) {
   T = CarryTrack{};
   T.tiles = (n + DEM_TILE - 1) / DEM_TILE;
   if (T.tiles >= (1 << 24)) return -1;
   const size_t recs = (size_t)T.tiles * 4;
-  if (hipMalloc((void**)&T.stamp, sizeof(long long) * recs) != hipSuccess) return -1;
-  if (hipMalloc((void**)&T.val, sizeof(real) * (2 * recs + 3)) != hipSuccess) { carry_track_free(T); return -1; }
-  if (hipMalloc((void**)&T.who, sizeof(long long) * (recs + 6)) != hipSuccess) { carry_track_free(T); return -1; }
-  if (hipMemset(T.who, 0, sizeof(long long) * (recs + 6)) != hipSuccess) { carry_track_free(T); return -1; }
+  if (mem.dev(&T.stamp, recs) != hipSuccess) return -1;
+  if (mem.dev(&T.val, 2 * recs + 3) != hipSuccess) return -1;
+  if (mem.dev(&T.who, recs + 6) != hipSuccess) return -1;
+  if (hipMemset(T.who, 0, sizeof(long long) * (recs + 6)) != hipSuccess) return -1;
   T.best_key = T.who + recs;
   T.carry = T.val + 2 * recs;
   if (hipMemset(T.stamp, 0xFF, sizeof(long long) * recs) != hipSuccess ||
-      hipMemset(T.val, 0, sizeof(real) * (2 * recs + 3)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    carry_track_free(T);
+      hipMemset(T.val, 0, sizeof(real) * (2 * recs + 3)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return -1;
-  }
   return 0;
-}
-
-void carry_track_free(CarryTrack& T) {
-  if (T.stamp) (void)hipFree(T.stamp);
-  if (T.who) (void)hipFree(T.who);
-  if (T.val) (void)hipFree(T.val);
-  T = CarryTrack{};
 }
 
 void launch_carry_resolve(const CarryTrack& T, long long min_stamp, hipStream_t st) {
@@ -1662,45 +1654,39 @@ void launch_carry_resolve(const CarryTrack& T, long long min_stamp, hipStream_t 
 }
 
 
-int verlet_alloc(VerletDevice& V, int n, real cs, real ox, real oy, real wx, real wy) {
+int verlet_alloc(MemPool& mem, VerletDevice& V, int n, real cs, real ox, real oy, real wx, real wy) {
   V = VerletDevice{};
   V.cs = cs; V.ox = ox; V.oy = oy;
   V.ncx = (int)ceil(wx / cs) + 1; if (V.ncx < 1) V.ncx = 1;
   V.ncy = (int)ceil(wy / cs) + 1; if (V.ncy < 1) V.ncy = 1;
   const size_t ncell = (size_t)V.ncx * V.ncy;
   V.cap = (long)n * 32;
-  hipError_t e = hipSuccess;
-  auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16); };
-  A((void**)&V.keys_in, sizeof(unsigned) * n);                                  // cell of grain i
-  A((void**)&V.vals_in, sizeof(int) * n); A((void**)&V.vals_out, sizeof(int) * n);   // rank within its cell; grains by cell
-  // cell_start[0 .. ncell] (exclusive scan of the counts), cell_end[0 .. ncell] = the per-cell counts (zero between rebuilds)
-  A((void**)&V.cell_start, sizeof(int) * (ncell + 1)); A((void**)&V.cell_end, sizeof(int) * (ncell + 1));
-  A((void**)&V.counts, sizeof(int) * n); A((void**)&V.offsets, sizeof(int) * (n + 1));
-  A((void**)&V.nbr, sizeof(int) * V.cap); A((void**)&V.own, sizeof(int) * V.cap); A((void**)&V.wallflags, n);
-  A((void**)&V.overflow, sizeof(int));
-  {
-    const size_t tiles = ((size_t)n + DEM_TILE - 1) / DEM_TILE;
-    A((void**)&V.halo_ids, sizeof(int) * tiles * DEM_CHAIN_HALO); A((void**)&V.halo_cnt, sizeof(int) * tiles);
-    A((void**)&V.emeta, sizeof(unsigned) * V.cap);
-    A((void**)&V.tile_far, tiles);
-    A((void**)&V.tile_grains, sizeof(int) * tiles * DEM_TILE); A((void**)&V.where, sizeof(int) * (size_t)n);
-    A((void**)&V.xreb, sizeof(real) * 2 * (size_t)n);
-  }
-  if (e != hipSuccess) return -1;
+  const size_t N = (size_t)n, tiles = (N + DEM_TILE - 1) / DEM_TILE;
+  const bool ok =
+      mem.dev(&V.keys_in, N) == hipSuccess &&                                            // cell of grain i
+      mem.dev(&V.vals_in, N) == hipSuccess && mem.dev(&V.vals_out, N) == hipSuccess &&   // rank within its cell; grains by cell
+      // cell_start[0 .. ncell] (exclusive scan of the counts), cell_end[0 .. ncell] = the per-cell counts (zero between rebuilds)
+      mem.dev(&V.cell_start, ncell + 1) == hipSuccess && mem.dev(&V.cell_end, ncell + 1) == hipSuccess &&
+      mem.dev(&V.counts, N) == hipSuccess && mem.dev(&V.offsets, N + 1) == hipSuccess &&
+      mem.dev(&V.nbr, (size_t)V.cap) == hipSuccess && mem.dev(&V.own, (size_t)V.cap) == hipSuccess &&
+      mem.dev(&V.wallflags, N) == hipSuccess && mem.dev(&V.overflow, 1) == hipSuccess &&
+      mem.dev(&V.halo_ids, tiles * DEM_CHAIN_HALO) == hipSuccess && mem.dev(&V.halo_cnt, tiles) == hipSuccess &&
+      mem.dev(&V.emeta, (size_t)V.cap) == hipSuccess && mem.dev(&V.tile_far, tiles) == hipSuccess &&
+      mem.dev(&V.tile_grains, tiles * DEM_TILE) == hipSuccess && mem.dev(&V.where, N) == hipSuccess &&
+      mem.dev(&V.xreb, 2 * N) == hipSuccess;
+  if (!ok) return -1;
   V.yreb = V.xreb + n;
   V.scan_tmp_bytes = 0;
   size_t cells_tmp = 0;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, V.scan_tmp_bytes, V.counts, V.offsets, n) != hipSuccess) return -1;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, cells_tmp, V.cell_end, V.cell_start, (int)(ncell + 1)) != hipSuccess) return -1;
   if (cells_tmp > V.scan_tmp_bytes) V.scan_tmp_bytes = cells_tmp;
-  A(&V.scan_tmp, V.scan_tmp_bytes);
-  if (e != hipSuccess) return -1;
+  if (mem.dev(&V.scan_tmp, V.scan_tmp_bytes) != hipSuccess) return -1;
   if (hipMemset(V.cell_end, 0, sizeof(int) * (ncell + 1)) != hipSuccess) return -1;
   if (hipMemset(V.offsets, 0, sizeof(int) * (n + 1)) != hipSuccess) return -1;
   if (hipMemset(V.wallflags, 0, n) != hipSuccess) return -1;
   if (hipMemset(V.overflow, 0, sizeof(int)) != hipSuccess) return -1;
   {   // tiles by index until somebody says otherwise (verlet_set_tiles)
-    const size_t tiles = ((size_t)n + DEM_TILE - 1) / DEM_TILE;
     std::vector<int> tg(tiles * DEM_TILE);
     for (size_t k = 0; k < tg.size(); ++k) tg[k] = k < (size_t)n ? (int)k : -1;
     if (verlet_set_tiles(V, n, tg.data()) != 0) return -1;
@@ -1725,13 +1711,6 @@ int verlet_set_tiles(VerletDevice& V, int n, const int* tg) {
   if (hipMemcpy(V.tile_grains, tg, sizeof(int) * tiles * DEM_TILE, hipMemcpyHostToDevice) != hipSuccess) return -1;
   if (hipMemcpy(V.where, where.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) return -1;
   return 0;
-}
-
-void verlet_free(VerletDevice& V) {
-  void* ps[] = {V.keys_in, V.vals_in, V.vals_out, V.cell_start, V.cell_end,
-                V.scan_tmp, V.counts, V.offsets, V.nbr, V.own, V.wallflags, V.overflow, V.halo_ids, V.halo_cnt, V.emeta, V.tile_far, V.xreb, V.tile_grains, V.where};
-  for (void* p : ps) if (p) (void)hipFree(p);
-  V = VerletDevice{};
 }
 
 int launch_verlet_rebuild(VerletDevice& V, const Kin& K, const real* r, const DemParams& P,
@@ -1763,31 +1742,23 @@ int launch_verlet_rebuild(VerletDevice& V, const Kin& K, const real* r, const De
   return (int)hipGetLastError();
 }
 
-int diag_extra_alloc(DiagExtra& X, int n, long cap, real* carry) {
+int diag_extra_alloc(MemPool& mem, DiagExtra& X, int n, long cap, real* carry) {
   X = DiagExtra{};
   real* d = nullptr;
   const size_t nd = 5 * (size_t)n + 6 * (size_t)cap;
-  if (hipMalloc((void**)&d, sizeof(real) * nd) != hipSuccess) return -1;
-  X.fr = d;   // from here on diag_extra_free() releases whatever was allocated
-  if (hipMemset(d, 0, sizeof(real) * nd) != hipSuccess) { diag_extra_free(X); return -1; }
+  if (mem.dev(&d, nd) != hipSuccess) return -1;
+  if (hipMemset(d, 0, sizeof(real) * nd) != hipSuccess) return -1;
   X.fr = d; X.ice = d + n; X.slip = d + 2 * (size_t)n; X.rw = d + 3 * (size_t)n; X.a1gc = d + 4 * (size_t)n;
   real* e = d + 5 * (size_t)n;
   X.e_ft = e; X.e_f3 = e + cap; X.e_avt = e + 2 * cap; X.e_av3 = e + 3 * cap; X.e_dslip = e + 4 * cap; X.e_drw = e + 5 * cap;
   X.carry = carry;   // lives with the handle's CarryTrack
-  if (hipMalloc((void**)&X.e_touched, (size_t)cap) != hipSuccess) { diag_extra_free(X); return -1; }
-  if (hipMemset(X.e_touched, 0, (size_t)cap) != hipSuccess) { diag_extra_free(X); return -1; }
-  if (hipMalloc((void**)&X.wlist, sizeof(int) * (4 * (size_t)n + 4)) != hipSuccess) { diag_extra_free(X); return -1; }
+  if (mem.dev(&X.e_touched, (size_t)cap) != hipSuccess) return -1;
+  if (hipMemset(X.e_touched, 0, (size_t)cap) != hipSuccess) return -1;
+  if (mem.dev(&X.wlist, 4 * (size_t)n + 4) != hipSuccess) return -1;
   X.wcount = X.wlist + 4 * (size_t)n;
   // the consumers run on a non-blocking stream that does not order itself after the NULL stream's memsets
-  if (hipDeviceSynchronize() != hipSuccess) { diag_extra_free(X); return -1; }
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
   return 0;
-}
-
-void diag_extra_free(DiagExtra& X) {
-  if (X.fr) (void)hipFree(X.fr);
-  if (X.e_touched) (void)hipFree(X.e_touched);
-  if (X.wlist) (void)hipFree(X.wlist);
-  X = DiagExtra{};
 }
 
 void launch_diag_extra(const DiagExtra& X, const Kin& in, const real* r, const VerletDevice& V,
@@ -1860,28 +1831,21 @@ void launch_tile_halo(const VerletDevice& V, int n, hipStream_t st) {
 
 int dem_chain_tslots(int n) { return DEM_GRID((n + DEM_GRAINS - 1) / DEM_GRAINS); }
 
-int dem_chain_alloc(DemChain& C, int n) {
+int dem_chain_alloc(MemPool& mem, DemChain& C, int n) {
   C = DemChain{};
   const size_t bytes = (size_t)4 * n * 128;   // two parities x (local copy, remote copy)
   if (bytes >= ((size_t)1 << 31)) return 0;   // 32-bit buffer offsets: the chain stays off (capacity 0)
-  if (hipMalloc(&C.pub, bytes ? bytes : 128) != hipSuccess) return -1;
+  // (lbmdem_create refuses n < 1, so bytes >= 512; the lines' 128-byte alignment is the allocation's own)
+  if (mem.dev(&C.pub, bytes) != hipSuccess) return -1;
   C.pub_bytes = bytes;
-  if (hipMalloc((void**)&C.census, 4 * sizeof(int)) != hipSuccess) { dem_chain_free(C); return -1; }   // counter, pad, 64-bit placement map
-  if (hipMalloc((void**)&C.gate, sizeof(int)) != hipSuccess || hipMemset(C.gate, 0, sizeof(int)) != hipSuccess) { dem_chain_free(C); return -1; }
-  if (hipHostMalloc((void**)&C.err_host, sizeof(int), hipHostMallocDefault) != hipSuccess) { dem_chain_free(C); return -1; }
+  if (mem.dev(&C.census, 4) != hipSuccess) return -1;   // counter, pad, 64-bit placement map
+  if (mem.dev(&C.gate, 1) != hipSuccess || hipMemset(C.gate, 0, sizeof(int)) != hipSuccess) return -1;
+  if (mem.pinned(&C.err_host, 1) != hipSuccess) return -1;
   *C.err_host = 0;
-  if (hipHostGetDevicePointer((void**)&C.err, (void*)C.err_host, 0) != hipSuccess) { dem_chain_free(C); return -1; }
-  if (hipMemset(C.pub, 0, bytes ? bytes : 128) != hipSuccess || hipMemset(C.census, 0, 4 * sizeof(int)) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) { dem_chain_free(C); return -1; }
+  if (hipHostGetDevicePointer((void**)&C.err, (void*)C.err_host, 0) != hipSuccess) return -1;
+  if (hipMemset(C.pub, 0, bytes) != hipSuccess || hipMemset(C.census, 0, 4 * sizeof(int)) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) return -1;
   return 0;
-}
-
-void dem_chain_free(DemChain& C) {
-  if (C.pub) (void)hipFree(C.pub);
-  if (C.census) (void)hipFree(C.census);
-  if (C.gate) (void)hipFree(C.gate);
-  if (C.err_host) (void)hipHostFree((void*)C.err_host);
-  C = DemChain{};
 }
 
 // All workgroups of the tile slots have to run at the same time (a tile waits for the tiles of its partners). The

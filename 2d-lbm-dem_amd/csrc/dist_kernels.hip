@@ -218,32 +218,21 @@ __global__ void k_poison(const unsigned char* __restrict__ active, Kin a, Kin b,
 
 }  // namespace
 
-int dist_alloc(DistDevice& D, int n, int cap_g, int cap_t, int cap_l) {
+int dist_alloc(MemPool& mem, DistDevice& D, int n, int cap_g, int cap_t, int cap_l) {
   D = DistDevice{};
   D.cap_g = cap_g; D.cap_t = cap_t; D.cap_l = cap_l;
-  hipError_t e = hipSuccess;
-  auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 16); };
-  A((void**)&D.active, n); A((void**)&D.fluidmask, n);
-  for (int s = 0; s < 2; ++s) {
-    A((void**)&D.send_list[s], sizeof(int) * cap_g);
-    A((void**)&D.strad_list[s], sizeof(int) * cap_t);
-    A((void**)&D.recv_ids[s], sizeof(int) * cap_g);
-  }
-  A((void**)&D.local_list, sizeof(int) * cap_l);
-  A((void**)&D.counters, sizeof(int) * 16);   // two sets of 8, used by alternate periods
-  if (e != hipSuccess) return -1;
+  if (mem.dev(&D.active, (size_t)n) != hipSuccess || mem.dev(&D.fluidmask, (size_t)n) != hipSuccess) return -1;
+  for (int s = 0; s < 2; ++s)
+    if (mem.dev(&D.send_list[s], (size_t)cap_g) != hipSuccess || mem.dev(&D.strad_list[s], (size_t)cap_t) != hipSuccess ||
+        mem.dev(&D.recv_ids[s], (size_t)cap_g) != hipSuccess)
+      return -1;
+  if (mem.dev(&D.local_list, (size_t)cap_l) != hipSuccess) return -1;
+  if (mem.dev(&D.counters, 16) != hipSuccess) return -1;   // two sets of 8, used by alternate periods
   D.counters_alt = D.counters + 8;
   if (hipMemset(D.active, 1, n) != hipSuccess || hipMemset(D.fluidmask, 1, n) != hipSuccess ||
       hipMemset(D.counters, 0, sizeof(int) * 16) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return -1;
   return 0;
-}
-
-void dist_free(DistDevice& D) {
-  void* ps[] = {D.active, D.fluidmask, D.send_list[0], D.send_list[1], D.strad_list[0], D.strad_list[1],
-                D.recv_ids[0], D.recv_ids[1], D.counters < D.counters_alt ? D.counters : D.counters_alt, D.local_list};
-  for (void* p : ps) if (p) (void)hipFree(p);
-  D = DistDevice{};
 }
 
 void launch_dist_classify(const DistDevice& D, const DistGeom& Gm, int n, const real* x1, const real* r,

@@ -164,17 +164,6 @@ __global__ __launch_bounds__(256) void k_dens_emit(const DensJob J) {
   }
 }
 
-struct DevBuf {   // device memory of one call
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-};
-struct PinnedBuf {   // pinned host memory of one call
-  void* p = nullptr;
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-  hipError_t alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault); }
-};
-
 // what the count pass and the scan leave on the host
 struct DensPlan {
   std::vector<long long> rowoff;   // [2 * ly + 1] where every file row of the Pressure, then of the VecVelocity section begins
@@ -200,39 +189,43 @@ int dens_job(lbmdem_handle* h, const char* who, DensJob* J) {
   return LBMDEM_OK;
 }
 
-// count pass and scan; J.cells is the scan afterwards (`cells` and `offsets` own the memory)
-int dens_plan(lbmdem_handle* h, DensJob& J, DevBuf& cells, DevBuf& offsets, DensPlan* P) {
+// count pass and scan; J.cells is the scan afterwards (in memory of `mem`, the caller's pool: it outlives this function)
+int dens_plan(lbmdem_handle* h, DensJob& J, MemPool& mem, DensPlan* P) {
   const LatticeView& L = J.L;
   const size_t nall = 2 * (size_t)J.ncell + 1;
-  DevBuf prow, refused, tmp;
-  HIP_TRY(cells.alloc(sizeof(long long) * nall));
-  HIP_TRY(offsets.alloc(sizeof(long long) * nall));
-  HIP_TRY(prow.alloc(sizeof(double) * L.lx));
-  HIP_TRY(refused.alloc(sizeof(unsigned)));
-  HIP_TRY(hipMemsetAsync((long long*)cells.p + nall - 1, 0, sizeof(long long), h->stream));
-  HIP_TRY(hipMemsetAsync(prow.p, 0, sizeof(double) * L.lx, h->stream));
-  HIP_TRY(hipMemsetAsync(refused.p, 0, sizeof(unsigned), h->stream));
-  J.cells = (long long*)cells.p;
-  J.prow = (double*)prow.p;
-  J.refused = (unsigned*)refused.p;
+  MemPool scratch;
+  long long *cells = nullptr, *offsets = nullptr;
+  double* prow = nullptr;
+  unsigned* refused = nullptr;
+  void* tmp = nullptr;
+  HIP_TRY(mem.dev(&cells, nall));
+  HIP_TRY(mem.dev(&offsets, nall));
+  HIP_TRY(scratch.dev(&prow, (size_t)L.lx));
+  HIP_TRY(scratch.dev(&refused, 1));
+  HIP_TRY(hipMemsetAsync(cells + nall - 1, 0, sizeof(long long), h->stream));
+  HIP_TRY(hipMemsetAsync(prow, 0, sizeof(double) * L.lx, h->stream));
+  HIP_TRY(hipMemsetAsync(refused, 0, sizeof(unsigned), h->stream));
+  J.cells = cells;
+  J.prow = prow;
+  J.refused = refused;
   hipLaunchKernelGGL(k_dens_count, dim3(J.nxb, (L.ly + DN_TY - 1) / DN_TY), dim3(256), 0, h->stream, J);
   HIP_TRY(hipGetLastError());
   size_t tmp_bytes = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (long long*)cells.p, (long long*)offsets.p, (int)nall, h->stream));
-  HIP_TRY(tmp.alloc(tmp_bytes));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, (long long*)cells.p, (long long*)offsets.p, (int)nall, h->stream));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cells, offsets, (int)nall, h->stream));
+  HIP_TRY(scratch.dev(&tmp, tmp_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cells, offsets, (int)nall, h->stream));
   P->rowoff.assign(2 * (size_t)L.ly + 1, 0);
   P->prow.assign(L.lx, 0.);
   unsigned bad = 0;
   // every file row's first cell: the cells of both sections lie row after row, nxb apart
-  HIP_TRY(hipMemcpy2DAsync(P->rowoff.data(), sizeof(long long), offsets.p, sizeof(long long) * J.nxb, sizeof(long long),
+  HIP_TRY(hipMemcpy2DAsync(P->rowoff.data(), sizeof(long long), offsets, sizeof(long long) * J.nxb, sizeof(long long),
                            2 * (size_t)L.ly, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&P->rowoff[2 * (size_t)L.ly], (long long*)offsets.p + nall - 1, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(P->prow.data(), prow.p, sizeof(double) * L.lx, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(&bad, refused.p, sizeof bad, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&P->rowoff[2 * (size_t)L.ly], offsets + nall - 1, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(P->prow.data(), prow, sizeof(double) * L.lx, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, refused, sizeof bad, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   P->refused = (long)bad;
-  J.cells = (long long*)offsets.p;
+  J.cells = offsets;
   J.prow = nullptr;
   J.refused = nullptr;
   return LBMDEM_OK;
@@ -265,11 +258,12 @@ int dens_emit(lbmdem_handle* h, DensJob J, const DensPlan& P, Put put, long* ban
       if (b > need) need = b;
     }
   }
-  DevBuf staging;
-  PinnedBuf pinned;
-  HIP_TRY(staging.alloc((size_t)need));
-  HIP_TRY(pinned.alloc((size_t)need));
-  J.out = (unsigned char*)staging.p;
+  MemPool scratch;
+  unsigned char* staging = nullptr;
+  char* pinned = nullptr;
+  HIP_TRY(scratch.dev(&staging, (size_t)need));
+  HIP_TRY(scratch.pinned(&pinned, (size_t)need));
+  J.out = staging;
   *bands = 0;
   for (int s = 0; s < 2; ++s)
     for (int y0 = 0; y0 < ly; y0 += rows[s]) {
@@ -281,9 +275,9 @@ int dens_emit(lbmdem_handle* h, DensJob J, const DensPlan& P, Put put, long* ban
       if (J.cap == 0) continue;
       hipLaunchKernelGGL(k_dens_emit, dim3(J.nxb, (y1 - 1) / DN_TY - y0 / DN_TY + 1), dim3(256), 0, h->stream, J);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(pinned.p, staging.p, (size_t)J.cap, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipMemcpyAsync(pinned, staging, (size_t)J.cap, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(hipStreamSynchronize(h->stream));
-      put((const char*)pinned.p, (size_t)J.cap);
+      put(pinned, (size_t)J.cap);
     }
   return LBMDEM_OK;
 }
@@ -470,9 +464,9 @@ int lbmdem_write_densities(lbmdem_handle* h, const char* dir, int nfile) try {
   const int lx = J.L.lx, ly = J.L.ly;
   DensFiles F;
   RC_TRY(F.open(dir, nfile));
-  DevBuf cells, offsets;
+  MemPool scratch;   // (the plan's cell offsets live here until the body is out)
   DensPlan P;
-  RC_TRY(dens_plan(h, J, cells, offsets, &P));
+  RC_TRY(dens_plan(h, J, scratch, &P));
   if (P.refused > 0) {   // the reference's own loops print what the device does not: nan, inf, ten digits and more
     std::vector<double> f((size_t)lx * ly * 9);
     std::vector<int> obst((size_t)lx * ly);
@@ -513,9 +507,9 @@ int lbmdem_download_densities_text(lbmdem_handle* h, char* out, size_t cap, size
   DensJob J;
   RC_TRY(dens_job(h, "lbmdem_download_densities_text", &J));
   const int lx = J.L.lx, ly = J.L.ly;
-  DevBuf cells, offsets;
+  MemPool scratch;   // (the plan's cell offsets live here until the body is out)
   DensPlan P;
-  RC_TRY(dens_plan(h, J, cells, offsets, &P));
+  RC_TRY(dens_plan(h, J, scratch, &P));
   if (P.refused > 0) {
     std::vector<double> f((size_t)lx * ly * 9);
     std::vector<int> obst((size_t)lx * ly);

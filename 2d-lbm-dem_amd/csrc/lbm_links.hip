@@ -206,12 +206,6 @@ int geometry_job(lbmdem_handle* h, const char* who, LinksJob* J) {
   return LBMDEM_OK;
 }
 
-struct DevBuf {   // device memory of one call
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-};
-
 dim3 links_grid(const LinksJob& J) { return dim3(J.nxb, (J.L.ly + LK_BY - 1) / LK_BY); }
 
 // pass 1 into act_dev ([lx][ly] bytes, may be null), cells (J.cells, may be null) and census6_dev
@@ -275,11 +269,12 @@ int lbmdem_geometry_stats(lbmdem_handle* h, long* counts6) try {
   if (!counts6) return fail(LBMDEM_EINVAL, "null buffer");
   LinksJob J;
   RC_TRY(geometry_job(h, "lbmdem_geometry_stats", &J));
-  DevBuf census;
-  HIP_TRY(census.alloc(6 * sizeof(unsigned long long)));
-  RC_TRY(links_count(h, J, nullptr, (unsigned long long*)census.p));
+  MemPool scratch;   // (device memory of this call)
+  unsigned long long* census = nullptr;
+  HIP_TRY(scratch.dev(&census, 6));
+  RC_TRY(links_count(h, J, nullptr, census));
   unsigned long long c[6];
-  HIP_TRY(hipMemcpyAsync(c, census.p, sizeof c, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(c, census, sizeof c, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int k = 0; k < 6; ++k) counts6[k] = (long)c[k];
   return LBMDEM_OK;
@@ -294,12 +289,14 @@ int lbmdem_download_act(lbmdem_handle* h, int* act) try {
   LinksJob J;
   RC_TRY(geometry_job(h, "lbmdem_download_act", &J));
   const size_t nodes = (size_t)J.L.lx * J.L.ly;
-  DevBuf census, bytes;
-  HIP_TRY(census.alloc(6 * sizeof(unsigned long long)));
-  HIP_TRY(bytes.alloc(nodes));
-  RC_TRY(links_count(h, J, (unsigned char*)bytes.p, (unsigned long long*)census.p));
+  MemPool scratch;
+  unsigned long long* census = nullptr;
+  unsigned char* bytes = nullptr;
+  HIP_TRY(scratch.dev(&census, 6));
+  HIP_TRY(scratch.dev(&bytes, nodes));
+  RC_TRY(links_count(h, J, bytes, census));
   std::vector<unsigned char> host(nodes);
-  HIP_TRY(hipMemcpyAsync(host.data(), bytes.p, nodes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(host.data(), bytes, nodes, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (size_t k = 0; k < nodes; ++k) act[k] = host[k];
   return LBMDEM_OK;
@@ -314,31 +311,35 @@ int lbmdem_download_links(lbmdem_handle* h, lbmdem_link* out, long cap, long* co
   LinksJob J;
   RC_TRY(geometry_job(h, "lbmdem_download_links", &J));
   const size_t ncell = (size_t)J.L.ly * J.nxb;
-  DevBuf census, cells, offsets, tmp, links;
-  HIP_TRY(census.alloc(6 * sizeof(unsigned long long)));
-  HIP_TRY(cells.alloc(sizeof(long long) * (ncell + 1)));
-  HIP_TRY(offsets.alloc(sizeof(long long) * (ncell + 1)));
-  J.cells = (long long*)cells.p;
-  RC_TRY(links_count(h, J, nullptr, (unsigned long long*)census.p));
+  MemPool scratch;
+  unsigned long long* census = nullptr;
+  long long *cells = nullptr, *offsets = nullptr;
+  void* tmp = nullptr;
+  lbmdem_link* links = nullptr;
+  HIP_TRY(scratch.dev(&census, 6));
+  HIP_TRY(scratch.dev(&cells, ncell + 1));
+  HIP_TRY(scratch.dev(&offsets, ncell + 1));
+  J.cells = cells;
+  RC_TRY(links_count(h, J, nullptr, census));
   // the cells in file order, one empty cell behind the last: its offset is the number of links
   size_t tmp_bytes = 0;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (long long*)cells.p, (long long*)offsets.p, (int)(ncell + 1), h->stream));
-  HIP_TRY(tmp.alloc(tmp_bytes));
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, (long long*)cells.p, (long long*)offsets.p, (int)(ncell + 1), h->stream));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cells, offsets, (int)(ncell + 1), h->stream));
+  HIP_TRY(scratch.dev(&tmp, tmp_bytes));
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cells, offsets, (int)(ncell + 1), h->stream));
   long long total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, (long long*)offsets.p + ncell, sizeof total, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&total, offsets + ncell, sizeof total, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   *count = (long)total;
   if (cap == 0) return LBMDEM_OK;   // (how many there are)
   if (cap < total) return fail(LBMDEM_EINVAL, "lbmdem_download_links: there are %lld links, the buffer holds %ld", total, cap);
   if (total == 0) return LBMDEM_OK;
-  HIP_TRY(links.alloc(sizeof(lbmdem_link) * (size_t)total));
-  J.cells = (long long*)offsets.p;
-  J.out = (lbmdem_link*)links.p;
+  HIP_TRY(scratch.dev(&links, (size_t)total));
+  J.cells = offsets;
+  J.out = links;
   J.cap = total;
   hipLaunchKernelGGL(k_links_emit, links_grid(J), dim3(256), 0, h->stream, J);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, links.p, sizeof(lbmdem_link) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(out, links, sizeof(lbmdem_link) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {

@@ -126,10 +126,11 @@ hipError_t probe_clear(const ProbeState& P, long records, hipStream_t st) {
   return records > 0 ? hipMemsetAsync(P.ring, 0, sizeof(double) * (size_t)P.rec * (size_t)records, st) : hipSuccess;
 }
 
-void probe_free(ProbeState& P) {
-  if (P.ring) (void)hipFree(P.ring);
-  if (P.ctr) (void)hipFree(P.ctr);
-  if (P.points) (void)hipFree(P.points);
+// the recorder off and its buffers given back now, not when the handle ends
+void probe_free(MemPool& mem, ProbeState& P) {
+  mem.release(P.ring);
+  mem.release(P.ctr);
+  mem.release(P.points);
   P = ProbeState{};
 }
 
@@ -148,8 +149,6 @@ int lbmdem_probe_sync_counters(lbmdem_handle* h) {
   HIP_TRY(hipMemcpy(P.ctr, both, sizeof both, hipMemcpyHostToDevice));
   return LBMDEM_OK;
 }
-
-void lbmdem_probe_release(lbmdem_handle* h) { probe_free(h->probe); }
 
 // behind the force kernels of a fluid step (lbmdem_forces_fluid): `obst` is the map they have just used
 int lbmdem_probe_sample(lbmdem_handle* h, const int* obst) {
@@ -187,7 +186,7 @@ extern "C" {
 int lbmdem_probe_disable(lbmdem_handle* h) try {
   CHECK_H(h);
   HIP_TRY(hipStreamSynchronize(h->stream));
-  probe_free(h->probe);
+  probe_free(h->mem, h->probe);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -221,17 +220,17 @@ int lbmdem_probe_enable(lbmdem_handle* h, const lbmdem_probe_config* pc) try {
   if (bytes > PROBE_MAX_BYTES)
     return fail(LBMDEM_EINVAL, "probes: %d records of %ld doubles are more than the %zu MiB a ring may take", P.capacity, P.rec, PROBE_MAX_BYTES >> 20);
   HIP_TRY(hipStreamSynchronize(h->stream));
-  probe_free(h->probe);
-  if (hipMalloc((void**)&P.ring, bytes) != hipSuccess || hipMalloc((void**)&P.ctr, 4 * sizeof(long long)) != hipSuccess ||
-      (P.npoints > 0 && hipMalloc((void**)&P.points, 2 * sizeof(int) * P.npoints) != hipSuccess)) {
-    probe_free(P);
+  probe_free(h->mem, h->probe);
+  if (h->mem.dev(&P.ring, (size_t)P.rec * (size_t)P.capacity) != hipSuccess || h->mem.dev(&P.ctr, 4) != hipSuccess ||
+      (P.npoints > 0 && h->mem.dev(&P.points, 2 * (size_t)P.npoints) != hipSuccess)) {
+    probe_free(h->mem, P);
     return fail(LBMDEM_ENOMEM, "probes: device allocation of %zu bytes failed", bytes);
   }
   h->probe = P;
   h->probe.on = true;
   if (probe_clear(P, P.capacity, h->stream) != hipSuccess || hipMemsetAsync(P.ctr, 0, 4 * sizeof(long long), h->stream) != hipSuccess ||
       (P.npoints > 0 && hipMemcpy(P.points, pc->points, 2 * sizeof(int) * P.npoints, hipMemcpyHostToDevice) != hipSuccess)) {
-    probe_free(h->probe);
+    probe_free(h->mem, h->probe);
     return fail(LBMDEM_EHIP, "probes: initialising the ring failed");
   }
   return LBMDEM_OK;

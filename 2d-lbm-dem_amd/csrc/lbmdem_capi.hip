@@ -272,7 +272,10 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
   if ((cut_lo || cut_hi) && cfg->halo < 2)
     return fail(LBMDEM_EINVAL, "strip decomposition needs halo >= 2 rows");
 
-  lbmdem_handle* h = new lbmdem_handle();
+  // (whatever leaves this function before `*out = h` takes the half-built handle down with it)
+  std::unique_ptr<lbmdem_handle, int (*)(lbmdem_handle*)> guard(new lbmdem_handle(), lbmdem_destroy);
+  lbmdem_handle* h = guard.get();
+  MemPool& mem = h->mem;
   h->cfg = *cfg;
   h->n = n;
   h->rmax = rmax;
@@ -329,24 +332,20 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
 #define CREATE_TRY(expr)                                                                             \
   do {                                                                                               \
     hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess) {                                                                          \
-      int rc_ = fail(e_ == hipErrorOutOfMemory ? LBMDEM_ENOMEM : LBMDEM_EHIP, "%s failed: %s", #expr, \
-                     hipGetErrorString(e_));                                                         \
-      lbmdem_destroy(h);                                                                             \
-      return rc_;                                                                                    \
-    }                                                                                                \
+    if (e_ != hipSuccess)                                                                            \
+      return fail(e_ == hipErrorOutOfMemory ? LBMDEM_ENOMEM : LBMDEM_EHIP, "%s failed: %s", #expr,   \
+                  hipGetErrorString(e_));                                                            \
   } while (0)
 
   CREATE_TRY(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
   h->stream = h->own_stream;
-  const size_t fbytes = sizeof(real) * 9 * (size_t)L.plane;
-  CREATE_TRY(hipMalloc((void**)&h->f[0], fbytes));
-  CREATE_TRY(hipMalloc((void**)&h->f[1], fbytes));
-  CREATE_TRY(hipMalloc((void**)&h->obst[0], sizeof(int) * (size_t)L.plane));
-  CREATE_TRY(hipMalloc((void**)&h->obst[1], sizeof(int) * (size_t)L.plane));
+  CREATE_TRY(mem.dev(&h->f[0], 9 * (size_t)L.plane));
+  CREATE_TRY(mem.dev(&h->f[1], 9 * (size_t)L.plane));
+  CREATE_TRY(mem.dev(&h->obst[0], (size_t)L.plane));
+  CREATE_TRY(mem.dev(&h->obst[1], (size_t)L.plane));
   // grains: 18 kinematic + r m It rLB xc yc r2 rbl0 + 3 fhf + 8 packed + p = 38 columns
   const size_t cols = 18 + 8 + 3 + 8 + 1 + 9;
-  CREATE_TRY(hipMalloc((void**)&h->gbuf, sizeof(real) * cols * n));
+  CREATE_TRY(mem.dev(&h->gbuf, cols * n));
   CREATE_TRY(hipMemset(h->gbuf, 0, sizeof(real) * cols * n));
   {
     real* p0 = h->gbuf;
@@ -363,31 +362,28 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
     h->gp = p0 + 19 * (size_t)n;
     h->diag = p0 + 20 * (size_t)n;
   }
-  CREATE_TRY(hipMalloc((void**)&h->owner, n));
+  CREATE_TRY(mem.dev(&h->owner, (size_t)n));
   CREATE_TRY(hipMemsetAsync(h->owner, 1, n, h->stream));
   for (int b = 0; b < 2; ++b)
     for (int k = 0; k < 2; ++k) {
-      CREATE_TRY(hipMalloc((void**)&h->snap[b][k].xc, sizeof(real) * 3 * (size_t)n + n));
+      CREATE_TRY(mem.dev((void**)&h->snap[b][k].xc, sizeof(real) * 3 * (size_t)n + n));   // (bytes: three real columns and one of bytes)
       h->snap[b][k].yc = h->snap[b][k].xc + n;
       h->snap[b][k].still2 = h->snap[b][k].xc + 2 * (size_t)n;
       h->snap[b][k].mode = reinterpret_cast<unsigned char*>(h->snap[b][k].xc + 3 * (size_t)n);
       CREATE_TRY(hipMemsetAsync(h->snap[b][k].xc, 0, sizeof(real) * 3 * (size_t)n + n, h->stream));
     }
-  if (carry_track_alloc(h->ct, n) != 0) {
-    lbmdem_destroy(h);
-    return fail(LBMDEM_ENOMEM, "carry records: hipMalloc failed");
-  }
+  if (carry_track_alloc(mem, h->ct, n) != 0) return fail(LBMDEM_ENOMEM, "carry records: hipMalloc failed");
   if (n < LBMDEM_MINCOV_IDS) {
-    CREATE_TRY(hipMalloc((void**)&h->mincov, sizeof(unsigned) * (size_t)L.plane));
+    CREATE_TRY(mem.dev(&h->mincov, (size_t)L.plane));
     CREATE_TRY(hipMemsetAsync(h->mincov, 0, sizeof(unsigned) * (size_t)L.plane, h->stream));
   }
-  CREATE_TRY(hipMalloc((void**)&h->fs.queue, sizeof(int) * n));
-  CREATE_TRY(hipMalloc((void**)&h->fs.error, sizeof(int)));
+  CREATE_TRY(mem.dev(&h->fs.queue, (size_t)n));
+  CREATE_TRY(mem.dev(&h->fs.error, 1));
   CREATE_TRY(hipMemsetAsync(h->fs.error, 0, sizeof(int), h->stream));
-  CREATE_TRY(hipMalloc((void**)&h->gathered2, 2 * sizeof(int)));
+  CREATE_TRY(mem.dev(&h->gathered2, 2));
   CREATE_TRY(hipMemsetAsync(h->gathered2, 0, 2 * sizeof(int), h->stream));
   h->fs.gathered = h->gathered2; h->fs.gathered_next = h->gathered2 + 1;
-  CREATE_TRY(hipMalloc((void**)&h->fs.touched, n));
+  CREATE_TRY(mem.dev(&h->fs.touched, (size_t)n));
   CREATE_TRY(hipMemsetAsync(h->fs.touched, 0, n, h->stream));
   {
     // lattice lines through a reduced disc, any direction: |ey dx - ex dy| <= sqrt(2) rLB, +2 for the truncated centre
@@ -404,12 +400,12 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
       h->fs.half = half;
       h->fs.spd = spd;
       h->fs.hb = (int)ceil(p.reductionR * rmax / cfg->dx) + 1;
-      CREATE_TRY(hipMalloc((void**)&h->fs.tab, sizeof(real) * 8 * (size_t)spd * n));
+      CREATE_TRY(mem.dev(&h->fs.tab, 8 * (size_t)spd * n));
       launch_slots_clear(h->fs, n, h->stream);
       h->slots_clean = true;
     }
   }
-  CREATE_TRY(hipMalloc((void**)&h->dpartial, sizeof(double) * 1024));
+  CREATE_TRY(mem.dev(&h->dpartial, 1024));
   {
     // per-grain constants on the host, reference arithmetic: main.c:624-626, 1859
     std::vector<real> hr(n), hm(n), hIt(n), hrLB(n), hx1(n), hx2(n);
@@ -433,27 +429,19 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
     // within the 3 x 3 cells that are scanned)
     const double cs = (2 * rmax + p.distVerlet) * (sizeof(real) == 4 ? 1.001 : 1.0);
     const double wx = cfg->dx * (cfg->lx - 1), wy = cfg->dx * (cfg->ly - 1);
-    if (verlet_alloc(h->V, n, cs, cfg->Mgx, cfg->Mby, wx, wy) != 0) {
-      int rc = fail(LBMDEM_ENOMEM, "verlet_alloc failed");
-      lbmdem_destroy(h);
-      return rc;
-    }
+    if (verlet_alloc(mem, h->V, n, cs, cfg->Mgx, cfg->Mby, wx, wy) != 0) return fail(LBMDEM_ENOMEM, "verlet_alloc failed");
   }
-  if (dem_tiles_compose(h, x1, x2, 1) != LBMDEM_OK) { lbmdem_destroy(h); return LBMDEM_EHIP; }
+  if (dem_tiles_compose(h, x1, x2, 1) != LBMDEM_OK) return LBMDEM_EHIP;
 #ifdef LBMDEM_AB
   if (const char* e = getenv("LBMDEM_DEM_CHAIN")) h->chain_max = atoi(e);   // A/B: 0 = one launch per sub-step
 #endif
-  if (dem_chain_alloc(h->chain, n) != 0) {
-    int rc = fail(LBMDEM_ENOMEM, "sub-step hand-over lines: hipMalloc failed");
-    lbmdem_destroy(h);
-    return rc;
-  }
+  if (dem_chain_alloc(mem, h->chain, n) != 0) return fail(LBMDEM_ENOMEM, "sub-step hand-over lines: hipMalloc failed");
   h->L.gate = h->chain.gate;   // the stop word every kernel of the step path looks at first (LatticeView::gate)
   h->V.gate = h->chain.gate;
   h->ct.gate = h->chain.gate;
-  CREATE_TRY(hipHostMalloc((void**)&h->ovf_host, sizeof(int), hipHostMallocDefault));
+  CREATE_TRY(mem.pinned(&h->ovf_host, 1));
   *h->ovf_host = 0;
-  CREATE_TRY(hipHostMalloc((void**)&h->moved_host, sizeof(int), hipHostMallocDefault));
+  CREATE_TRY(mem.pinned(&h->moved_host, 1));
   *h->moved_host = -1;
   CREATE_TRY(hipHostGetDevicePointer((void**)&h->moved_dev, (void*)h->moved_host, 0));
   if (cfg->x_begin == 0 && cfg->x_end == cfg->lx) {   // (a strip's maps are painted by the stand-alone rasteriser)
@@ -461,25 +449,22 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
     h->chg_windows = (cfg->ly + h->chg_ww - 1) / h->chg_ww;
     h->chg_words = (L.nxl + 31) / 32 + 4;   // four words of padding: a wave reads 128 rows' worth from its first row on
     for (int b = 0; b < 2; ++b) {
-      CREATE_TRY(hipMalloc((void**)&h->chg[b], sizeof(unsigned) * (size_t)h->chg_windows * h->chg_words));
+      CREATE_TRY(mem.dev(&h->chg[b], (size_t)h->chg_windows * h->chg_words));
       CREATE_TRY(hipMemset(h->chg[b], 0, sizeof(unsigned) * (size_t)h->chg_windows * h->chg_words));
     }
-    CREATE_TRY(hipMalloc((void**)&h->chg_bad, 2 * sizeof(int)));
+    CREATE_TRY(mem.dev(&h->chg_bad, 2));
     CREATE_TRY(hipMemset(h->chg_bad, 0, 2 * sizeof(int)));
   }
-  CREATE_TRY(hipHostMalloc((void**)&h->ferr_host, sizeof(int), hipHostMallocDefault));
+  CREATE_TRY(mem.pinned(&h->ferr_host, 1));
   *h->ferr_host = 0;
   CREATE_TRY(hipHostGetDevicePointer((void**)&h->ferr_mirror, (void*)h->ferr_host, 0));
   // init_density (main.c:716-724) and init_obst (main.c:663-711)
   launch_fill_equilibrium(h->f[0], L, h->stream);
   launch_fill_equilibrium(h->f[1], L, h->stream);
-  {
-    int rc = paint_into(h, h->obst[0]);
-    if (rc != LBMDEM_OK) { lbmdem_destroy(h); return rc; }
-  }
+  RC_TRY(paint_into(h, h->obst[0]));
   CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
-  *out = h;
+  *out = guard.release();
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -493,40 +478,11 @@ int lbmdem_destroy(lbmdem_handle* h) {
   lbmdem_async_release(h);   // every queued frame and table on disk first
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   chain_forget_stream(h->cfg.device, h->stream);
-  for (int b = 0; b < 2; ++b) {
-    if (h->f[b]) (void)hipFree(h->f[b]);
-    if (h->obst[b]) (void)hipFree(h->obst[b]);
-  }
-  if (h->gbuf) (void)hipFree(h->gbuf);
-  lbmdem_probe_release(h);
-  for (int b = 0; b < 2; ++b)
-    for (int k = 0; k < 2; ++k)
-      if (h->snap[b][k].xc) (void)hipFree(h->snap[b][k].xc);
-  if (h->owner) (void)hipFree(h->owner);
-  if (h->mincov) (void)hipFree(h->mincov);
-  if (h->fs.touched) (void)hipFree(h->fs.touched);
-  if (h->fs.tab) (void)hipFree(h->fs.tab);
-  if (h->gathered2) (void)hipFree(h->gathered2);
-  if (h->fs.queue) (void)hipFree(h->fs.queue);
-  if (h->fs.error) (void)hipFree(h->fs.error);
-  if (h->dpartial) (void)hipFree(h->dpartial);
-  verlet_free(h->V);
-  dem_chain_free(h->chain);
-  dist_free(h->dd);
-  if (h->ovf_host) (void)hipHostFree((void*)h->ovf_host);
-  if (h->ferr_host) (void)hipHostFree((void*)h->ferr_host);
-  if (h->moved_host) (void)hipHostFree((void*)h->moved_host);
-  for (int b = 0; b < 2; ++b) if (h->chg[b]) (void)hipFree(h->chg[b]);
-  if (h->chg_bad) (void)hipFree(h->chg_bad);
-  if (h->chg_fcheck) (void)hipFree(h->chg_fcheck);
-  diag_extra_free(h->dx);
-  carry_track_free(h->ct);
+  h->mem.release_all();   // (before the events and the stream go: freeing synchronises the device)
   for (hipEvent_t e : h->ev0) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev1) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->ev2) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->vib_ev) if (e) (void)hipEventDestroy(e);
-  if (h->vib_host) (void)hipHostFree(h->vib_host);
-  if (h->vib_dev) (void)hipFree(h->vib_dev);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
   delete h;
   return LBMDEM_OK;
@@ -600,7 +556,7 @@ int lbmdem_collide_stream(lbmdem_handle* h) try {
   launch_collide_stream(h->f[h->fcur], h->f[1 - h->fcur], ob_old, ob_new, h->L, gview(h), S_launch, h->stream, chg);
   if (chg.bits && h->chg_verify) {   // the same launch with both maps read everywhere: the same populations (and the same link sums again)
     const size_t fbytes = sizeof(real) * 9 * (size_t)h->L.plane;
-    if (!h->chg_fcheck) HIP_TRY(hipMalloc((void**)&h->chg_fcheck, fbytes));
+    if (!h->chg_fcheck) HIP_TRY(h->mem.dev(&h->chg_fcheck, 9 * (size_t)h->L.plane));
     HIP_TRY(hipMemcpyAsync(h->chg_fcheck, h->f[1 - h->fcur], fbytes, hipMemcpyDeviceToDevice, h->stream));   // (rows the launch does not write)
     launch_collide_stream(h->f[h->fcur], h->chg_fcheck, ob_old, ob_new, h->L, gview(h), S_launch, h->stream);
     launch_count_differences(h->f[1 - h->fcur], h->chg_fcheck, 9 * (long)h->L.plane, h->chg_bad + 1, h->stream);
@@ -786,7 +742,7 @@ int lbmdem_debug_chain_times(lbmdem_handle* h, long long* out, int tiles_cap) {
   CHECK_H(h);
   const int tiles = (h->n + DEM_TILE - 1) / DEM_TILE;
   if (!h->chain.dbg) {
-    HIP_TRY(hipMalloc((void**)&h->chain.dbg, sizeof(long long) * (16 * (size_t)tiles + 4)));
+    HIP_TRY(h->mem.dev(&h->chain.dbg, 16 * (size_t)tiles + 4));
     HIP_TRY(hipMemset(h->chain.dbg, 0, sizeof(long long) * (16 * (size_t)tiles + 4)));
     return 0;
   }
@@ -859,7 +815,7 @@ int lbmdem_dem_substep(lbmdem_handle* h) {
   const bool want_diag = want_table;
   if (want_diag && !h->dx_ready) {
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (diag_extra_alloc(h->dx, h->n, h->V.cap, h->ct.carry) != 0) return fail(LBMDEM_ENOMEM, "diagnostic buffers: hipMalloc failed");
+    if (diag_extra_alloc(h->mem, h->dx, h->n, h->V.cap, h->ct.carry) != 0) return fail(LBMDEM_ENOMEM, "diagnostic buffers: hipMalloc failed");
     h->dx.gate = h->chain.gate;
     h->dx_ready = true;
   }
@@ -1330,6 +1286,14 @@ int lbmdem_debug_chain_giveup(lbmdem_handle* h, int launch) {
   h->chain_giveup_at = launch;
   return LBMDEM_OK;
 }
+// experiment build: the device and pinned blocks every MemPool of the process holds at this moment, and their bytes as they
+// were asked for (tests/test_gpu_memory.py: what a handle, a communicator or a call took is back when it ends)
+int lbmdem_debug_live_memory(long* blocks, long* bytes) {
+  if (!blocks || !bytes) return fail(LBMDEM_EINVAL, "null argument");
+  *blocks = MemPool::live_blocks().load();
+  *bytes = MemPool::live_bytes().load();
+  return LBMDEM_OK;
+}
 #endif
 
 int lbmdem_set_lid(lbmdem_handle* h, double uw_h) {
@@ -1365,8 +1329,8 @@ int lbmdem_set_vibration(lbmdem_handle* h, int on) {
   if (h->dist || h->cfg.x_begin != 0 || h->cfg.x_end != h->cfg.lx)
     return fail(LBMDEM_EINVAL, "vibrating walls are not available on a strip of a decomposition");
   if (on && !h->vib_host) {
-    HIP_TRY(hipHostMalloc((void**)&h->vib_host, sizeof(VibWall) * 2 * VIB_HALF, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void**)&h->vib_dev, sizeof(VibWall) * 2 * VIB_HALF));
+    HIP_TRY(h->mem.pinned(&h->vib_host, 2 * VIB_HALF));
+    HIP_TRY(h->mem.dev(&h->vib_dev, 2 * VIB_HALF));
     for (int b = 0; b < 2; ++b) HIP_TRY(hipEventCreateWithFlags(&h->vib_ev[b], hipEventDisableTiming));
   }
   if ((on != 0) != h->vib) {   // (the in-place map update starts over from a repaint either way)
@@ -1410,13 +1374,13 @@ int lbmdem_upload_f(lbmdem_handle* h, const double* f_aos) {
   if (!f_aos) return fail(LBMDEM_EINVAL, "null buffer");
   const LatticeView& L = h->L;
   const size_t cnt = (size_t)L.nxl * L.ly * 9;
+  MemPool scratch;
   real* tmp = nullptr;
-  HIP_TRY(hipMalloc((void**)&tmp, sizeof(real) * cnt));
-  hipError_t e = h2d_real(tmp, f_aos + (size_t)L.gx0 * L.ly * 9, cnt, h->stream);
+  HIP_TRY(scratch.dev(&tmp, cnt));
   h->slots_valid = false;  // the populations the link sums were formed from are being replaced
-  if (e == hipSuccess) { launch_aos_to_soa(tmp, h->f[h->fcur], L, h->stream); e = hipStreamSynchronize(h->stream); }
-  (void)hipFree(tmp);
-  HIP_TRY(e);
+  HIP_TRY(h2d_real(tmp, f_aos + (size_t)L.gx0 * L.ly * 9, cnt, h->stream));
+  launch_aos_to_soa(tmp, h->f[h->fcur], L, h->stream);
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 }
 
@@ -1427,12 +1391,11 @@ int lbmdem_download_f(lbmdem_handle* h, double* f_aos) {
   const LatticeView& L = h->L;
   const int rows = L.xo1 - L.xo0;
   const size_t cnt = (size_t)rows * L.ly * 9;
+  MemPool scratch;
   real* tmp = nullptr;
-  HIP_TRY(hipMalloc((void**)&tmp, sizeof(real) * cnt));
+  HIP_TRY(scratch.dev(&tmp, cnt));
   launch_soa_to_aos(h->f[h->fcur], tmp, L, L.xo0, rows, h->stream);
-  hipError_t e = d2h_real(f_aos + (size_t)(L.gx0 + L.xo0) * L.ly * 9, tmp, cnt, h->stream);
-  (void)hipFree(tmp);
-  HIP_TRY(e);
+  HIP_TRY(d2h_real(f_aos + (size_t)(L.gx0 + L.xo0) * L.ly * 9, tmp, cnt, h->stream));
   return LBMDEM_OK;
 }
 
@@ -1455,15 +1418,14 @@ int lbmdem_download_macro(lbmdem_handle* h, double* rho, double* ux, double* uy)
   const LatticeView& L = h->L;
   const int rows = L.xo1 - L.xo0;
   const size_t cnt = (size_t)rows * L.ly;
+  MemPool scratch;
   real* tmp = nullptr;
-  HIP_TRY(hipMalloc((void**)&tmp, sizeof(real) * cnt * 3));
+  HIP_TRY(scratch.dev(&tmp, cnt * 3));
   launch_macro(h->f[h->fcur], L, L.xo0, rows, tmp, tmp + cnt, tmp + 2 * cnt, h->stream);
   const size_t off = (size_t)(L.gx0 + L.xo0) * L.ly;
-  hipError_t e = d2h_real(rho + off, tmp, cnt, h->stream);
-  if (e == hipSuccess) e = d2h_real(ux + off, tmp + cnt, cnt, h->stream);
-  if (e == hipSuccess) e = d2h_real(uy + off, tmp + 2 * cnt, cnt, h->stream);
-  (void)hipFree(tmp);
-  HIP_TRY(e);
+  HIP_TRY(d2h_real(rho + off, tmp, cnt, h->stream));
+  HIP_TRY(d2h_real(ux + off, tmp + cnt, cnt, h->stream));
+  HIP_TRY(d2h_real(uy + off, tmp + 2 * cnt, cnt, h->stream));
   return LBMDEM_OK;
 }
 
@@ -1497,18 +1459,16 @@ int lbmdem_total_density_serial(lbmdem_handle* h, double sum_in, double* sum_out
   std::vector<real> rowbuf((size_t)L.ly * 9);
   std::vector<int> kexp(rows), flag(rows);
   std::vector<unsigned long long> quanta(rows);
-  hipError_t e = hipMalloc((void**)&d_rowsum, sizeof(double) * rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_k, sizeof(int) * rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_q, sizeof(unsigned long long) * rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_flag, sizeof(int) * rows);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_row, sizeof(real) * L.ly * 9);
-  auto cleanup = [&] { (void)hipFree(d_rowsum); (void)hipFree(d_k); (void)hipFree(d_q); (void)hipFree(d_flag); (void)hipFree(d_row); };
-  if (e != hipSuccess) { cleanup(); HIP_TRY(e); }
+  MemPool scratch;
+  HIP_TRY(scratch.dev(&d_rowsum, (size_t)rows));
+  HIP_TRY(scratch.dev(&d_k, (size_t)rows));
+  HIP_TRY(scratch.dev(&d_q, (size_t)rows));
+  HIP_TRY(scratch.dev(&d_flag, (size_t)rows));
+  HIP_TRY(scratch.dev(&d_row, (size_t)L.ly * 9));
   // pass 1: approximate row sums -> the binade the running sum is (most probably) in when it reaches each row
   launch_density_rowsum(f, L, d_rowsum, h->stream);
-  e = hipMemcpyAsync(rowsum.data(), d_rowsum, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { cleanup(); HIP_TRY(e); }
+  HIP_TRY(hipMemcpyAsync(rowsum.data(), d_rowsum, sizeof(double) * rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   {
     double approx = sum_in;
     for (int r = 0; r < rows; ++r) {
@@ -1519,14 +1479,11 @@ int lbmdem_total_density_serial(lbmdem_handle* h, double sum_in, double* sum_out
     }
   }
   // pass 2: integer quanta per row for that binade
-  e = hipMemcpyAsync(d_k, kexp.data(), sizeof(int) * rows, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) {
-    launch_density_rowquanta(f, L, d_k, d_q, d_flag, h->stream);
-    e = hipMemcpyAsync(quanta.data(), d_q, sizeof(unsigned long long) * rows, hipMemcpyDeviceToHost, h->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * rows, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { cleanup(); HIP_TRY(e); }
+  HIP_TRY(hipMemcpyAsync(d_k, kexp.data(), sizeof(int) * rows, hipMemcpyHostToDevice, h->stream));
+  launch_density_rowquanta(f, L, d_k, d_q, d_flag, h->stream);
+  HIP_TRY(hipMemcpyAsync(quanta.data(), d_q, sizeof(unsigned long long) * rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(flag.data(), d_flag, sizeof(int) * rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   // the chain, with the exact running sum
   volatile real s = (real)sum_in;   // the reference's accumulator is a `real` (main.c:1251); volatile: every addition rounded to it
   int replayed = 0;
@@ -1547,14 +1504,12 @@ int lbmdem_total_density_serial(lbmdem_handle* h, double sum_in, double* sum_out
     if (fast) continue;
     // replay this row element by element in the reference's order (y, then q)
     launch_soa_to_aos(f, d_row, L, L.xo0 + r, 1, h->stream);
-    e = hipMemcpyAsync(rowbuf.data(), d_row, sizeof(real) * L.ly * 9, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { cleanup(); HIP_TRY(e); }
+    HIP_TRY(hipMemcpyAsync(rowbuf.data(), d_row, sizeof(real) * L.ly * 9, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     const size_t cnt = (size_t)L.ly * 9;
     for (size_t i = 0; i < cnt; ++i) s = s + rowbuf[i];
     ++replayed;
   }
-  cleanup();
   *sum_out = s;
   if (rows_replayed) *rows_replayed = replayed;
   return LBMDEM_OK;
@@ -1713,8 +1668,9 @@ int lbmdem_measure_copy(lbmdem_handle* h, size_t bytes, int reps, double* gb_per
   bytes &= ~(size_t)15;
   void *a = nullptr, *b = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipMalloc(&a, bytes);
-  if (e == hipSuccess) e = hipMalloc(&b, bytes);
+  MemPool scratch;
+  hipError_t e = scratch.dev(&a, bytes);
+  if (e == hipSuccess) e = scratch.dev(&b, bytes);
   if (e == hipSuccess) e = hipMemsetAsync(a, 0x11, bytes, h->stream);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -1731,8 +1687,6 @@ int lbmdem_measure_copy(lbmdem_handle* h, size_t bytes, int reps, double* gb_per
     }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (a) (void)hipFree(a);
-  if (b) (void)hipFree(b);
   HIP_TRY(e);
   *gb_per_s = best > 0.f ? 2.0 * (double)bytes / (best * 1e-3) / 1e9 : 0.0;
   return LBMDEM_OK;

@@ -72,6 +72,7 @@ struct lbmdem_comm {
   int rank = 0, world = 1, device = 0;
   hipStream_t side[LANE_COUNT] = {};
   hipEvent_t ready[LANE_COUNT] = {}, done[LANE_COUNT] = {};
+  MemPool mem;   // buf, scratch, vtk_dev
   // device buffers for one handle: [kind or halo][side][send/recv]
   lbmdem_handle* bound = nullptr;
   double* buf[3][2][2] = {};
@@ -113,9 +114,7 @@ int lbmdem_comm_destroy(lbmdem_comm* c) {
     if (c->ready[l]) (void)hipEventDestroy(c->ready[l]);
     if (c->done[l]) (void)hipEventDestroy(c->done[l]);
   }
-  for (auto& k : c->buf) for (auto& s : k) for (double*& p : s) if (p) (void)hipFree(p);
-  if (c->scratch) (void)hipFree(c->scratch);
-  if (c->vtk_dev) (void)hipFree(c->vtk_dev);
+  c->mem.release_all();
   for (int l = 0; l < LANE_COUNT; ++l) if (c->nccl[l]) (void)g_rccl.CommDestroy(c->nccl[l]);
   delete c;
   return LBMDEM_OK;
@@ -144,7 +143,7 @@ int lbmdem_comm_create(const void* id128, int rank, int world, int device, lbmde
       return fail(LBMDEM_EHIP, "stream / event creation failed");
     }
   }
-  if (hipMalloc((void**)&c->scratch, sizeof(double) * 1024) != hipSuccess) { lbmdem_comm_destroy(c); return fail(LBMDEM_ENOMEM, "hipMalloc"); }
+  if (c->mem.dev(&c->scratch, 1024) != hipSuccess) { lbmdem_comm_destroy(c); return fail(LBMDEM_ENOMEM, "hipMalloc"); }
   *out = c;
   return LBMDEM_OK;
 } catch (...) {
@@ -202,8 +201,8 @@ static int comm_bind(lbmdem_comm* c, lbmdem_handle* h) {
   for (int k = 0; k < 3; ++k)   // (the f halo rows travel straight between the lattices: halo_exchange)
     for (int s = 0; s < 2; ++s)
       for (int d = 0; d < 2; ++d) {
-        HIP_TRY(hipMalloc((void**)&c->buf[k][s][d], sizeof(double) * (c->count[k] ? c->count[k] : 1)));
-        HIP_TRY(hipMemset(c->buf[k][s][d], 0, sizeof(double) * (c->count[k] ? c->count[k] : 1)));
+        HIP_TRY(c->mem.dev(&c->buf[k][s][d], c->count[k]));
+        HIP_TRY(hipMemset(c->buf[k][s][d], 0, sizeof(double) * c->count[k]));
       }
   HIP_TRY(hipDeviceSynchronize());
   c->bound = h;
@@ -293,17 +292,15 @@ int lbmdem_comm_allreduce_bits(lbmdem_comm* c, void* host_buf, size_t nbytes) {
   if (!c || !host_buf || nbytes == 0) return fail(LBMDEM_EINVAL, "bad lbmdem_comm_allreduce_bits arguments");
   HIP_TRY(hipSetDevice(c->device));
   const size_t words = (nbytes + 7) / 8;
+  MemPool scratch;
   unsigned long long* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, words * 8));
-  hipError_t e = hipMemset(d, 0, words * 8);
-  if (e == hipSuccess) e = hipMemcpy(d, host_buf, nbytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(d); HIP_TRY(e); }
+  HIP_TRY(scratch.dev(&d, words));
+  HIP_TRY(hipMemset(d, 0, words * 8));
+  HIP_TRY(hipMemcpy(d, host_buf, nbytes, hipMemcpyHostToDevice));
   const ncclResult_t r = g_rccl.AllReduce(d, d, words, ncclUint64, ncclSum, c->nccl[0], c->side[0]);
-  if (r != ncclSuccess) { (void)hipFree(d); return fail(LBMDEM_EHIP, "ncclAllReduce failed: %s", g_rccl.GetErrorString(r)); }
-  e = hipStreamSynchronize(c->side[0]);
-  if (e == hipSuccess) e = hipMemcpy(host_buf, d, nbytes, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  HIP_TRY(e);
+  if (r != ncclSuccess) return fail(LBMDEM_EHIP, "ncclAllReduce failed: %s", g_rccl.GetErrorString(r));
+  HIP_TRY(hipStreamSynchronize(c->side[0]));
+  HIP_TRY(hipMemcpy(host_buf, d, nbytes, hipMemcpyDeviceToHost));
   return LBMDEM_OK;
 }
 
@@ -410,8 +407,8 @@ int lbmdem_comm_write_vtk(lbmdem_handle* h, lbmdem_comm* c, const char* dir, int
   if (W > 1) {
     hipError_t e = hipSuccess;
     if (c->vtk_floats < 11 * widest * ly) {
-      if (c->vtk_dev) { (void)hipFree(c->vtk_dev); c->vtk_dev = nullptr; c->vtk_floats = 0; }
-      e = hipMalloc((void**)&c->vtk_dev, sizeof(float) * 11 * widest * ly);
+      c->mem.release(c->vtk_dev); c->vtk_dev = nullptr; c->vtk_floats = 0;
+      e = c->mem.dev(&c->vtk_dev, 11 * widest * ly);
       if (e == hipSuccess) c->vtk_floats = 11 * widest * ly;
     }
     if (e == hipSuccess && c->rank != 0) e = hipMemcpy(c->vtk_dev, loc.data(), sizeof(float) * loc.size(), hipMemcpyHostToDevice);
@@ -455,9 +452,10 @@ int lbmdem_comm_allreduce_sum(lbmdem_comm* c, double* values, int n) {
 int lbmdem_comm_selftest(lbmdem_comm* c, int doubles) {
   if (!c || doubles < 1) return fail(LBMDEM_EINVAL, "bad lbmdem_comm_selftest arguments");
   HIP_TRY(hipSetDevice(c->device));
+  MemPool scratch;
   double *a = nullptr, *b = nullptr;
-  HIP_TRY(hipMalloc((void**)&a, sizeof(double) * doubles));
-  HIP_TRY(hipMalloc((void**)&b, sizeof(double) * doubles));
+  HIP_TRY(scratch.dev(&a, (size_t)doubles));
+  HIP_TRY(scratch.dev(&b, (size_t)doubles));
   std::vector<double> ha(doubles), hb(doubles, -1.0);
   for (int k = 0; k < doubles; ++k) ha[k] = 0.5 * k + 1.0;
   hipStream_t main = nullptr;
@@ -478,7 +476,6 @@ int lbmdem_comm_selftest(lbmdem_comm* c, int doubles) {
   if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(hb.data(), b, sizeof(double) * doubles, hipMemcpyDeviceToHost, main);
   if (e == hipSuccess && r == ncclSuccess) e = hipStreamSynchronize(main);
   if (main) (void)hipStreamDestroy(main);
-  (void)hipFree(a); (void)hipFree(b);
   if (r != ncclSuccess) return fail(LBMDEM_EHIP, "RCCL self send/recv failed: %s", g_rccl.GetErrorString(r));
   HIP_TRY(e);
   for (int k = 0; k < doubles; ++k) if (hb[k] != ha[k]) return fail(LBMDEM_EHIP, "self send/recv returned wrong data at %d", k);
@@ -487,7 +484,7 @@ int lbmdem_comm_selftest(lbmdem_comm* c, int doubles) {
   // flight at once -- with a payload that names sender and lane
   const int left = c->rank - 1, right = c->rank + 1 < c->world ? c->rank + 1 : -1;
   double* d = nullptr;   // [lane][send L, send R, recv L, recv R][doubles]
-  HIP_TRY(hipMalloc((void**)&d, sizeof(double) * doubles * 4 * LANE_COUNT));
+  HIP_TRY(scratch.dev(&d, (size_t)doubles * 4 * LANE_COUNT));
   std::vector<double> host((size_t)doubles * 4 * LANE_COUNT, -1.0);
   auto value = [&](int rank, int lane, int to_right, int k) { return 1000.0 * rank + 100.0 * lane + 10.0 * to_right + 1e-3 * k; };
   for (int l = 0; l < LANE_COUNT; ++l)
@@ -510,7 +507,6 @@ int lbmdem_comm_selftest(lbmdem_comm* c, int doubles) {
     if (e == hipSuccess) e = e2;
   }
   if (e == hipSuccess && r == ncclSuccess) e = hipMemcpy(host.data(), d, sizeof(double) * host.size(), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (r != ncclSuccess) return fail(LBMDEM_EHIP, "RCCL neighbour exchange failed: %s", g_rccl.GetErrorString(r));
   HIP_TRY(e);
   for (int l = 0; l < LANE_COUNT; ++l)
@@ -546,8 +542,9 @@ int lbmdem_comm_exchange_probe(lbmdem_comm* c, int doubles, int iters, double* u
   double *a = nullptr, *b = nullptr;
   hipStream_t main = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipMalloc((void**)&a, sizeof(double) * doubles);
-  if (e == hipSuccess) e = hipMalloc((void**)&b, sizeof(double) * doubles);
+  MemPool scratch;
+  hipError_t e = scratch.dev(&a, (size_t)doubles);
+  if (e == hipSuccess) e = scratch.dev(&b, (size_t)doubles);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&main, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -594,7 +591,6 @@ int lbmdem_comm_exchange_probe(lbmdem_comm* c, int doubles, int iters, double* u
   if (main) { (void)hipStreamSynchronize(main); (void)hipStreamDestroy(main); }
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(a); (void)hipFree(b);
   if (r != ncclSuccess) return fail(LBMDEM_EHIP, "RCCL self send/recv failed: %s", g_rccl.GetErrorString(r));
   HIP_TRY(e);
   return LBMDEM_OK;

@@ -16,6 +16,7 @@
 
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -117,6 +118,10 @@ struct AsyncJob { int kind, slot; };
 // the lines of stats.data land in call order).
 struct AsyncOut {
   int lx = 0, ly = 0, n = 0, device = 0;     // lattice, grains
+  // the slots' staging and pinned buffers, dem_scratch, dem_stats_host. Only the thread that calls into the library allocates
+  // and frees here (lane_resize, lbmdem_async_release, with the writer idle or joined); the writer thread only reads a slot's
+  // pinned buffer and never touches the pool.
+  MemPool mem;
   AsyncLane lane[ASYNC_KINDS];
   double* dem_scratch = nullptr;             // device: the addends of the ten sums [10][n], then the 22 numbers (k_dem_stats)
   double* dem_stats_host = nullptr;          // pinned [22]
@@ -139,6 +144,9 @@ struct lbmdem_handle {
   LatticeView L;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
+  // every device and pinned block of the handle, the members of V, dd, ct, dx, chain and probe included: lbmdem_destroy frees
+  // them in one go; what goes earlier (the probe recorder's buffers) is released by name
+  MemPool mem;
   // lattice
   real* f[2] = {nullptr, nullptr};
   int fcur = 0;
@@ -393,10 +401,9 @@ LBMDEM_INTERNAL int lbmdem_verlet_build_lists(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_chain_settle(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);
 // the probe recorder (lbm_probe.hip): one sample behind the force kernels of a fluid step; the device counters of the ring
-// set to what probe.issued says (after chain_restore has taken it back); its buffers freed
+// set to what probe.issued says (after chain_restore has taken it back)
 LBMDEM_INTERNAL int lbmdem_probe_sample(lbmdem_handle* h, const int* obst);
 LBMDEM_INTERNAL int lbmdem_probe_sync_counters(lbmdem_handle* h);
-LBMDEM_INTERNAL void lbmdem_probe_release(lbmdem_handle* h);
 // background frames and tables (lbmdem_output.hip): every queued job on disk, the writer joined, everything freed (-> off); the
 // writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lbm_mem.h"
+
 // ---------------------------------------------------------------------------------------------
 // `real` -- the reference's arithmetic type (main.c:34-40): double, or float when the reference is compiled
 // -DSINGLE_PRECISION. The library is built once per type (liblbmdem_hip.so / liblbmdem_hip_sp.so, csrc/Makefile SP=1);
@@ -250,8 +252,7 @@ struct DistDevice {
   int cap_g, cap_t, cap_l;
 };
 struct DistGeom { real lo, hi, margin, dx, Mgx; int has_lo, has_hi, first, last, gx0, nxl; };
-int dist_alloc(DistDevice& D, int n, int cap_g, int cap_t, int cap_l);
-void dist_free(DistDevice& D);
+int dist_alloc(MemPool& mem, DistDevice& D, int n, int cap_g, int cap_t, int cap_l);
 // ownership, masks and the send / straddler lists from the current positions of the grains that were active
 // (error_mirror: device address of the pinned host word that follows *error, written by the launch; may be null)
 void launch_dist_classify(const DistDevice& D, const DistGeom& Gm, int n, const real* x1, const real* r,
@@ -396,8 +397,7 @@ struct VerletDevice {
 };
 constexpr int DEM_CHAIN_HALO = 256;          // halo grains staged per tile; partners beyond that are read from memory per entry
 constexpr unsigned DEM_CHAIN_DIRECT = 0xFFFFu;   // emeta slot value of such a partner
-int verlet_alloc(VerletDevice& V, int n, real cs, real ox, real oy, real wx, real wy);
-void verlet_free(VerletDevice& V);
+int verlet_alloc(MemPool& mem, VerletDevice& V, int n, real cs, real ox, real oy, real wx, real wy);
 // returns 0 or the hipError_t of the failing call (hipCUB scan, launch)
 int launch_verlet_rebuild(VerletDevice& V, const Kin& K, const real* r, const DemParams& P,
                           hipStream_t st);
@@ -416,7 +416,7 @@ struct DiagExtra {
   real* carry;                         // pft, pff, pf: persist from sub-step to sub-step
   const int* gate;                     // the handle's stop word (LatticeView::gate)
 };
-int diag_extra_alloc(DiagExtra& X, int n, long cap, real* carry);
+int diag_extra_alloc(MemPool& mem, DiagExtra& X, int n, long cap, real* carry);
 
 // Where the carries come from when the sub-step before was not a diagnostic one: every ordinary sub-step leaves, per
 // tile of DEM_TILE consecutive grains and per kind of contact that assigns a carry (main.c:784-786/1410-1411 grain
@@ -436,11 +436,9 @@ struct CarryTrack {
   long long* best_key;  // [3][2] left by launch_carry_resolve: {(stamp + 1) * 4 + kind, who} of the record each carry came from
   const int* gate;      // the handle's stop word (LatticeView::gate)
 };
-int carry_track_alloc(CarryTrack& T, int n);
-void carry_track_free(CarryTrack& T);
+int carry_track_alloc(MemPool& mem, CarryTrack& T, int n);
 // carry[] <- the youngest records with stamp >= min_stamp (carry[] itself is younger than anything below that)
 void launch_carry_resolve(const CarryTrack& T, long long min_stamp, hipStream_t st);
-void diag_extra_free(DiagExtra& X);
 // after the DIAG sub-step kernel: carries scanned over the contacts in the reference's order, per-grain sums,
 // then the four wall loops replayed serially
 void launch_diag_extra(const DiagExtra& X, const Kin& in, const real* r, const VerletDevice& V,
@@ -503,8 +501,7 @@ struct ChainPaint {
   ObstSnap other;
   int windows;
 };
-int dem_chain_alloc(DemChain& C, int n);
-void dem_chain_free(DemChain& C);
+int dem_chain_alloc(MemPool& mem, DemChain& C, int n);
 // how many workgroups of k_dem_chain this GPU keeps resident at once (occupancy x CUs), verified by a census launch of
 // `tslots` workgroups that all have to see each other; 0 when they do not fit
 int dem_chain_census(DemChain& C, int tslots, hipStream_t st);

@@ -20,21 +20,20 @@ int lbmdem_download_vtk_fields(lbmdem_handle* h, float* grain_pressure, float* g
     return fail(LBMDEM_EINVAL, "null buffer");
   const LatticeView& L = h->L;
   const size_t cnt = (size_t)(L.xo1 - L.xo0) * L.ly;
+  MemPool scratch;
   float* tmp = nullptr;
-  HIP_TRY(hipMalloc((void**)&tmp, sizeof(float) * cnt * 11));
+  HIP_TRY(scratch.dev(&tmp, cnt * 11));
   float *d_gp = tmp, *d_gv = tmp + cnt, *d_ga = tmp + 4 * cnt, *d_fp = tmp + 7 * cnt, *d_fv = tmp + 8 * cnt;
   const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
   const Kin& K = h->kin[h->kcur];
   launch_vtk_fields(h->f[h->fcur], ob, L, h->gp, K.v1, K.v2, K.a1, K.a2, h->cfg.phys.rho_moy, d_gp, d_gv, d_ga,
                     d_fp, d_fv, h->stream);
-  hipError_t e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) e = hipMemcpy(grain_pressure, d_gp, sizeof(float) * cnt, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(grain_velocity, d_gv, sizeof(float) * cnt * 3, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(grain_acceleration, d_ga, sizeof(float) * cnt * 3, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(fluid_pressure, d_fp, sizeof(float) * cnt, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(fluid_velocity, d_fv, sizeof(float) * cnt * 3, hipMemcpyDeviceToHost);
-  (void)hipFree(tmp);
-  HIP_TRY(e);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(grain_pressure, d_gp, sizeof(float) * cnt, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(grain_velocity, d_gv, sizeof(float) * cnt * 3, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(grain_acceleration, d_ga, sizeof(float) * cnt * 3, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fluid_pressure, d_fp, sizeof(float) * cnt, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fluid_velocity, d_fv, sizeof(float) * cnt * 3, hipMemcpyDeviceToHost));
   return LBMDEM_OK;
 }
 
@@ -505,8 +504,8 @@ static void async_writer(AsyncOut* a) {
 // a kind's slots and counters (the table's scratch is its caller's)
 static void lane_free(AsyncOut* a, int kind) {
   for (AsyncSlot& S : a->lane[kind].slot) {
-    if (S.staging) (void)hipFree(S.staging);
-    if (S.pinned) (void)hipHostFree(S.pinned);
+    a->mem.release(S.staging);
+    a->mem.release(S.pinned);
     if (S.snapped) (void)hipEventDestroy(S.snapped);
     if (S.copied) (void)hipEventDestroy(S.copied);
     S.staging = S.pinned = nullptr;
@@ -517,8 +516,8 @@ static void lane_free(AsyncOut* a, int kind) {
 }
 
 static void dem_scratch_free(AsyncOut* a) {
-  if (a->dem_scratch) (void)hipFree(a->dem_scratch);
-  if (a->dem_stats_host) (void)hipHostFree(a->dem_stats_host);
+  a->mem.release(a->dem_scratch);
+  a->mem.release(a->dem_stats_host);
   a->dem_scratch = a->dem_stats_host = nullptr;
 }
 
@@ -622,13 +621,13 @@ static int lane_resize(lbmdem_handle* h, int kind, int slots, size_t bytes, cons
     AsyncOut* a = h->aout;
     hipError_t e = hipSuccess;
     if (kind == ASYNC_TABLE) {
-      e = hipMalloc((void**)&a->dem_scratch, sizeof(double) * (DEM_STATS_CHAINS * (size_t)a->n + 22));
-      if (e == hipSuccess) e = hipHostMalloc((void**)&a->dem_stats_host, sizeof(double) * 22, hipHostMallocDefault);
+      e = a->mem.dev(&a->dem_scratch, DEM_STATS_CHAINS * (size_t)a->n + 22);
+      if (e == hipSuccess) e = a->mem.pinned(&a->dem_stats_host, 22);
     }
     for (int s = 0; s < slots && e == hipSuccess; ++s) {
       AsyncSlot& S = a->lane[kind].slot[s];
-      e = hipMalloc(&S.staging, bytes);
-      if (e == hipSuccess) e = hipHostMalloc(&S.pinned, bytes, hipHostMallocDefault);
+      e = a->mem.dev(&S.staging, bytes);
+      if (e == hipSuccess) e = a->mem.pinned(&S.pinned, bytes);
       if (e == hipSuccess) e = hipEventCreateWithFlags(&S.snapped, hipEventDisableTiming);
       if (e == hipSuccess) e = hipEventCreateWithFlags(&S.copied, hipEventDisableTiming | hipEventBlockingSync);
     }
@@ -737,14 +736,13 @@ int lbmdem_download_vtk_image(lbmdem_handle* h, void* image_be) {
   if (!image_be) return fail(LBMDEM_EINVAL, "null buffer");
   CHECK_WHOLE_LATTICE(h, "lbmdem_download_vtk_image");
   const size_t bytes = lbmdem_vtk_image_bytes(h->L.lx, h->L.ly);
+  MemPool scratch;
   void* tmp = nullptr;
-  HIP_TRY(hipMalloc(&tmp, bytes));
+  HIP_TRY(scratch.dev(&tmp, bytes));
   launch_frame(h, tmp);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(image_be, tmp, bytes, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  (void)hipFree(tmp);
-  HIP_TRY(e);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(image_be, tmp, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 }
 
@@ -823,17 +821,15 @@ int lbmdem_dem_stats(lbmdem_handle* h, double* stats22) {
   if (!stats22) return fail(LBMDEM_EINVAL, "null buffer");
   CHECK_TABLE(h);
   const size_t n = (size_t)h->n;
-  double* tmp = nullptr;   // (the scratch of the background writer, where there is one: it is idle between two events)
+  MemPool own;             // (the scratch of the background writer, where there is one: it is idle between two events)
   double* scratch = async_dem_on(h) ? h->aout->dem_scratch : nullptr;
-  if (!scratch) { HIP_TRY(hipMalloc((void**)&tmp, sizeof(double) * (DEM_STATS_CHAINS * n + 22))); scratch = tmp; }
+  if (!scratch) HIP_TRY(own.dev(&scratch, DEM_STATS_CHAINS * n + 22));
   const DemTableView T = dem_table_view(h);
   launch_dem_frame(T, nullptr, scratch, h->stream);
   launch_dem_stats(T, scratch, scratch + DEM_STATS_CHAINS * n, h->stream);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(stats22, scratch + DEM_STATS_CHAINS * n, sizeof(double) * 22, hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (tmp) (void)hipFree(tmp);
-  HIP_TRY(e);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(stats22, scratch + DEM_STATS_CHAINS * n, sizeof(double) * 22, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   stats22[0] = h->nbsteps * h->cfg.dt - h->cfg.phys.dtt;   // main.c:428
   return LBMDEM_OK;
 #endif

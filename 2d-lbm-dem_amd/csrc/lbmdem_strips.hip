@@ -63,7 +63,7 @@ int lbmdem_dist_default_margin(lbmdem_handle* h) {
 // allocation + switches of the distributed-grain mode with given message capacities (lbmdem_dist_enable derives them
 // from the packing; a restart takes them from the checkpoint: neighbours must agree on the message sizes)
 int lbmdem_dist_enable_caps(lbmdem_handle* h, int M, long cap_g, long cap_t, long cap_l) {
-  if (dist_alloc(h->dd, h->n, (int)cap_g, (int)cap_t, (int)cap_l) != 0) { dist_free(h->dd); return fail(LBMDEM_ENOMEM, "dist_alloc failed"); }
+  if (dist_alloc(h->mem, h->dd, h->n, (int)cap_g, (int)cap_t, (int)cap_l) != 0) return fail(LBMDEM_ENOMEM, "dist_alloc failed");
   RC_TRY(lbmdem_dem_tiles_by_index(h));   // (see there)
   h->dist = true;
   h->dist_margin = M;
@@ -355,7 +355,7 @@ int lbmdem_dist_table_substep(lbmdem_handle* h, const double* state12_full, cons
   if (rc != LBMDEM_OK) return rc;
   if (!h->dx_ready) {
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (diag_extra_alloc(h->dx, h->n, h->V.cap, h->ct.carry) != 0) return fail(LBMDEM_ENOMEM, "diagnostic buffers: hipMalloc failed");
+    if (diag_extra_alloc(h->mem, h->dx, h->n, h->V.cap, h->ct.carry) != 0) return fail(LBMDEM_ENOMEM, "diagnostic buffers: hipMalloc failed");
     h->dx_ready = true;
   }
   const int film = (h->nbsteps % h->cfg.phys.stepFilm == 0) ? 1 : 0;
