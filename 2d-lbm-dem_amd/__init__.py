@@ -170,6 +170,12 @@ def _open_library(LIB_PATH):
     L.lbmdem_download_geometry_obst.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_write_obst.argtypes = [C.c_void_p, C.c_char_p]
     L.lbmdem_write_obst_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.lbmdem_contact_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_download_contacts.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_write_contacts.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_set_contacts_output.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_write_contacts_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_long, C.c_int, C.c_int]
     L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
@@ -300,6 +306,35 @@ def write_obst_files(directory, obst, act, links):
         raise LbmDemError(-1, "write_obst_files: obst and act must be [lx][ly] maps of one shape, links a list of LINK_DTYPE")
     _chk(load_library().lbmdem_write_obst_files(os.fsencode(directory), obst.shape[0], obst.shape[1], _vp(obst), _vp(act),
                                                 _vp(links), len(links)))
+
+
+# struct lbmdem_contact: a contact of the last table sub-step (LbmDem.download_contacts); j < 0 is a wall code
+WALL_B, WALL_T, WALL_L, WALL_R = -1, -2, -3, -4
+
+
+class Contact(C.Structure):
+    """lbmdem_contact"""
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("dn", C.c_double), ("nx", C.c_double), ("ny", C.c_double),
+                ("fn", C.c_double), ("ft", C.c_double)]
+
+
+CONTACT_DTYPE = np.dtype([("i", np.int32), ("j", np.int32), ("dn", np.float64), ("nx", np.float64), ("ny", np.float64),
+                          ("fn", np.float64), ("ft", np.float64)])
+CONTACT_COUNTERS = ("candidate_pairs", "touching_pairs", "coulomb_clamped", "fn_zero", "wall_contacts", "grains_in_contact")
+
+
+def write_contacts_files(directory, nFile, r, x1, x2, fm, contacts, lx, ly, precision="f64"):
+    """contacts%.6i.dat ("# i j dn nx ny fn ft", then one "%d %d %le %le %le %le %le" line per record) and DEM%.6i_chains.ps (the
+    discs of write_forces, then every grain-grain record with fn > 0 as a line of width fn) from per-grain r, x1, x2, fm and a
+    record list (CONTACT_DTYPE). Host only."""
+    cols = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (r, x1, x2, fm)]
+    rec = np.ascontiguousarray(contacts, dtype=CONTACT_DTYPE).reshape(-1)
+    n = len(cols[0])
+    if any(len(a) != n for a in cols):
+        raise LbmDemError(-1, "write_contacts_files: r, x1, x2 and fm must have one value per grain")
+    _chk(load_library(precision).lbmdem_write_contacts_files(os.fsencode(directory), int(nFile), n, _vp(cols[0]), _vp(cols[1]),
+                                                             _vp(cols[2]), _vp(cols[3]), _vp(rec) if len(rec) else None,
+                                                             len(rec), int(lx), int(ly)))
 
 
 def write_densities_host(directory, nFile, f, obst, t=0.0, rho_moy=1000.0):
@@ -694,6 +729,32 @@ class LbmDem:
 
     def write_obst(self, directory="."):
         _chk(self._L.lbmdem_write_obst(self._h, os.fsencode(directory)))
+
+    # the contact network export: the contacts of the last sub-step, when it was a table sub-step (include/lbmdem_hip.h)
+    def contact_stats(self):
+        """-> dict of CONTACT_COUNTERS: list entries i < j, touching pairs, those that took the Coulomb clamp, those with fn == 0,
+        wall contacts, grains with at least one record"""
+        c = np.zeros(6, np.int64)
+        _chk(self._L.lbmdem_contact_stats(self._h, _vp(c)))
+        return dict(zip(CONTACT_COUNTERS, (int(v) for v in c)))
+
+    def download_contacts(self):
+        """structured array of CONTACT_DTYPE: the pair records (i < j, i ascending, j ascending), then the wall records (grain
+        ascending, WALL_B, WALL_T, WALL_L, WALL_R within a grain)"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_contacts(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=CONTACT_DTYPE)
+        if n.value:
+            _chk(self._L.lbmdem_download_contacts(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def write_contacts(self, directory=".", nFile=0):
+        """contacts%.6i.dat and DEM%.6i_chains.ps of the last table sub-step"""
+        _chk(self._L.lbmdem_write_contacts(self._h, os.fsencode(directory), int(nFile)))
+
+    def set_contacts_output(self, on=True):
+        """run_scene writes the contact files at every DEM event, right behind write_DEM / write_forces"""
+        _chk(self._L.lbmdem_set_contacts_output(self._h, 1 if on else 0))
 
     def write_densities(self, directory=".", nFile=0):
         """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""

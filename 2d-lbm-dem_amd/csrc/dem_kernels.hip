@@ -23,32 +23,12 @@
 // diagnostics" below.
 
 #include "lbmdem_internal.h"
+#include "dem_laws.h"   // Force3, GrainState, advance, contact<FILM>, the four wall laws
 #include <vector>
 
 #include <hipcub/hipcub.hpp>
 
 namespace {
-
-struct Force3 { real f1, f2, f3, fn, ft, xij, yij, vt; };  // fn, ft, branch vector, vt: for the diagnostics
-
-__device__ __forceinline__ real maxt(real x, real y) { return (x < y) ? 0. : y; }  // main.c:211-216
-
-struct GrainState { real x1, x2, v1, v2, v3, r; };
-
-// drifted + half-kicked state of grain j from the previous sub-step's state: main.c:1748-1753
-__device__ __forceinline__ GrainState advance(const Kin& K, const real* __restrict__ r, int j,
-                                              const DemParams& P) {
-  GrainState s;
-  const real a1 = K.a1[j], a2 = K.a2[j], a3 = K.a3[j];
-  const real v1 = K.v1[j], v2 = K.v2[j], v3 = K.v3[j];
-  s.x1 = K.x1[j] + P.dt * v1 + P.dt2 * a1 / 2.;
-  s.x2 = K.x2[j] + P.dt * v2 + P.dt2 * a2 / 2.;
-  s.v1 = v1 + P.dt * a1 / 2.;
-  s.v2 = v2 + P.dt * a2 / 2.;
-  s.v3 = v3 + P.dt * a3 / 2.;
-  s.r = r[j];
-  return s;
-}
 
 // strip decomposition: a grain this rank does not integrate keeps its state, and BOTH ping-pong buffers carry it (a
 // run of sub-steps in one launch swaps the buffers once, single sub-steps once each: nothing may depend on the parity)
@@ -56,56 +36,6 @@ __device__ __forceinline__ void carry_over(const Kin& in, const Kin& out, int i)
   out.x1[i] = in.x1[i]; out.x2[i] = in.x2[i]; out.x3[i] = in.x3[i];
   out.v1[i] = in.v1[i]; out.v2[i] = in.v2[i]; out.v3[i] = in.v3[i];
   out.a1[i] = in.a1[i]; out.a2[i] = in.a2[i]; out.a3[i] = in.a3[i];
-}
-
-// contact force on grain A (lower index) from grain B (higher index).
-// FILM = false: force_grains, main.c:739-774. FILM = true: the inline law of main.c:1365-1395.
-template <bool FILM>
-__device__ __forceinline__ Force3 contact(const GrainState& A, const GrainState& B, const DemParams& P,
-                                          bool& touched) {
-  Force3 F = {0., 0., 0., 0., 0., 0., 0., 0.};
-  const real xij = A.x1 - B.x1;
-  const real yij = A.x2 - B.x2;
-  const real dist = (real)sqrt((double)(xij * xij + yij * yij));   // <math.h>'s double sqrt, rounded to real (main.c:742)
-  const real dn = dist - A.r - B.r;
-  touched = !(dn >= 0);
-  if (dn >= 0) return F;
-  const real vx = A.v1 - B.v1;
-  const real vy = A.v2 - B.v2;
-  const real xn = xij / dist;
-  const real yn = yij / dist;
-  const real vn = vx * xn + vy * yn;
-  const real vt = -vx * yn + vy * xn - A.v3 * A.r - B.v3 * B.r;
-  if (!FILM) {
-    // force_grains declares `double fn, ft` (main.c:736) whatever `real` is: f1, f2 and the arguments of Maxt are formed
-    // in double and rounded to real once (fn and ft themselves always hold real values)
-    double fn = -P.kg * dn - P.nug * vn;
-    if (fn < 0) fn = 0.0;
-    double ft = -P.kt * vt * P.dt;
-    const real ftest = P.mu * fn;
-    if (fabs(ft) > ftest) ft = (ft < 0.0) ? ftest : -ftest;
-    F.f3 = -maxt((real)(ft * A.r), (real)(fn * P.murf * A.r * B.r));
-    F.f1 = fn * xn - ft * yn;
-    F.f2 = fn * yn + ft * xn;
-    F.fn = fn;
-    F.ft = ft;
-  } else {
-    // the inline film law uses acceleration_grains' own `real fn, ft` (main.c:1340)
-    real fn = -P.kg * dn - P.nug * vn;
-    if (fn < 0) fn = 0.0;
-    real ft = P.kt * vt * P.dt;
-    const real ftest = P.mu * ft;  // sic, main.c:1385
-    if (fabs((double)ft) > ftest) ft = (ft > 0.0) ? ftest : -ftest;
-    F.f3 = -ft * A.r * P.murf;
-    F.f1 = fn * xn - ft * yn;
-    F.f2 = fn * yn + ft * xn;
-    F.fn = fn;
-    F.ft = ft;
-  }
-  F.xij = xij;
-  F.yij = yij;
-  F.vt = vt;
-  return F;
 }
 
 // The four wall laws applied to one grain, in the reference's order bottom, top, left, right
@@ -119,67 +49,40 @@ __device__ __forceinline__ void walls(const GrainState& me, unsigned wf, const D
                                       real& a2, real& a3, real& pr, real& ds, real& df1, int& dz,
                                       real& dM11, real& dM12, real& dM21, real& dM22, WallHits& wh) {
   if (wf & 1u) {
-    const real dn = me.x2 - me.r - P.Mby;
-    if (dn < 0) {  // force_WallB, main.c:809-828
-      const real vn = me.v2, vt = me.v1;
-      real fn = -P.km * dn - P.num * vn;
-      if (fn < 0) fn = 0.;
-      real ft = P.ktm * vt;
-      const real ftest = P.mumb * fn;
-      if (fabs((double)ft) > ftest) ft = (ft < 0.0) ? ftest : -ftest;
-      a1 = a1 + ft; a2 = a2 + fn; a3 = a3 + (-(ft * me.r * P.murf));
-      wh.mask |= 1u; wh.ftB = ft; wh.f3B = -(ft * me.r * P.murf);
-      pr += fn;
-      if (DIAG) { ds += ft; df1 += ft; dz += 1; dM12 += ft * P.dt; dM22 += fn * P.dt; }  // main.c:830-838
+    const WallForce W = wall_bottom(me, P);
+    if (W.dn < 0) {
+      a1 = a1 + W.f1; a2 = a2 + W.f2; a3 = a3 + W.f3;
+      wh.mask |= 1u; wh.ftB = W.ft; wh.f3B = W.f3;
+      pr += W.fn;
+      if (DIAG) { ds += W.ft; df1 += W.f1; dz += 1; dM12 += W.f1 * P.dt; dM22 += W.f2 * P.dt; }  // main.c:830-838
     }
   }
   if (wf & 2u) {
-    const real dn = -me.x2 - me.r + P.Mhy;
-    if (dn < 0) {  // force_WallT, main.c:846-871
-      const real vn = me.v2;
-      real fn = P.km * dn - P.num * vn;
-      if (fn > 0.) fn = 0.;
-      const real vt = me.v1 + me.v3 * me.r - P.wallT_vel;   // wallT_vel = amp * freq * cos(freq * t) is a double (main.c:855)
-      real ft = fabs((double)(P.ktm * vt));
-      real ftmax;
-      if (vt >= 0) ftmax = P.mumb * fn - P.nugt * vt; else ftmax = P.mumb * fn + P.nugt * vt;
-      if (ft > ftmax) ft = ftmax;
-      if (vt > 0) ft = -ft;
-      a1 = a1 + ft; a2 = a2 + fn; a3 = a3 + ft * me.r * P.murf;
-      if (DIAG) { dM12 += ft * fabs(P.dt); dM22 += fn * fabs(P.dt); }  // main.c:875-882
-      pr += fn;
-      if (DIAG) { ds += ft; dz += 1; }
+    const WallForce W = wall_top(me, P);
+    if (W.dn < 0) {
+      a1 = a1 + W.f1; a2 = a2 + W.f2; a3 = a3 + W.f3;
+      if (DIAG) { dM12 += W.f1 * fabs(P.dt); dM22 += W.f2 * fabs(P.dt); }  // main.c:875-882
+      pr += W.fn;
+      if (DIAG) { ds += W.ft; dz += 1; }
     }
   }
   if (wf & 4u) {
-    const real dn = me.x1 - me.r - P.Mgx;
-    if (dn < 0) {  // force_WallL, main.c:888-904
-      const real vn = me.v1;
-      real fn = -P.km * dn + P.num * vn;
-      if (fn < 0.) fn = 0.;
-      const real vt = me.v2;
-      real ft = P.mum * fn;
-      if (vt > 0) ft = -ft;
-      a1 = a1 + fn; a2 = a2 + ft; a3 = a3 + ft * me.r * P.murf;
-      wh.mask |= 4u; wh.ftL = ft;
-      if (DIAG) { dM11 += fn * fabs(P.dt); dM21 += ft * fabs(P.dt); }  // main.c:907-915
-      pr += fn;
-      if (DIAG) { ds += ft; df1 += fn; dz += 1; }
+    const WallForce W = wall_left(me, P);
+    if (W.dn < 0) {
+      a1 = a1 + W.f1; a2 = a2 + W.f2; a3 = a3 + W.f3;
+      wh.mask |= 4u; wh.ftL = W.ft;
+      if (DIAG) { dM11 += W.f1 * fabs(P.dt); dM21 += W.f2 * fabs(P.dt); }  // main.c:907-915
+      pr += W.fn;
+      if (DIAG) { ds += W.ft; df1 += W.f1; dz += 1; }
     }
   }
   if (wf & 8u) {
-    const real dn = -me.x1 - me.r + P.Mdx;
-    if (dn < 0) {  // force_WallR, main.c:923-936 (ft from the unclamped fn)
-      const real vn = me.v1;
-      real fn = P.km * dn - P.num * vn;
-      const real vt = me.v2;
-      real ft = P.mum * fn;
-      if (vt > 0) ft = -ft;
-      wh.mask |= 8u; wh.ftR = ft;
-      if (fn > 0.) fn = 0.;
-      a1 = a1 + fn; a2 = a2 + (-ft); a3 = a3 + ft * me.r * P.murf;
-      pr += fn;
-      if (DIAG) { df1 += fn; dM11 += fn * fabs(P.dt); dM21 += (-ft) * fabs(P.dt); dz += 1; }  // main.c:938-949
+    const WallForce W = wall_right(me, P);
+    if (W.dn < 0) {
+      wh.mask |= 8u; wh.ftR = W.ft;
+      a1 = a1 + W.f1; a2 = a2 + W.f2; a3 = a3 + W.f3;
+      pr += W.fn;
+      if (DIAG) { df1 += W.f1; dM11 += W.f1 * fabs(P.dt); dM21 += W.f2 * fabs(P.dt); dz += 1; }  // main.c:938-949
     }
   }
 }

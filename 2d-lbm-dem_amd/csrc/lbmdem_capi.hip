@@ -792,6 +792,7 @@ int lbmdem_verlet_build_lists(lbmdem_handle* h) {
   HIP_TRY(hipMemcpyAsync((void*)h->ovf_host, h->V.overflow, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   h->verlet_ok = true;
   h->verlet_tracks_positions = true;
+  h->contacts_valid = false;   // (the list the last table sub-step walked is gone)
   h->list_generation++;
   return LBMDEM_OK;
 }
@@ -851,6 +852,9 @@ int lbmdem_dem_substep(lbmdem_handle* h) {
   if (h->dist && table_cadence) h->carry_from = h->substep_seq + 1;
   h->substep_seq++;
   h->diag_valid = want_table;
+  // the contact network export re-derives this sub-step's contacts from the state it started from: what it was launched with
+  h->contacts_valid = want_table;
+  if (want_table) { h->contacts_film = film; h->contacts_P = P; }
   HIP_TRY(hipGetLastError());
   h->kcur = 1 - h->kcur;
   h->nbsteps++;
@@ -1018,6 +1022,7 @@ int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid) {
   h->substep_seq += k;
   h->chain_launches++; h->chain_substeps += k;
   h->diag_valid = false;
+  h->contacts_valid = false;
   HIP_TRY(hipGetLastError());
   h->kcur = 1 - h->kcur;
   h->nbsteps += k;
@@ -1132,7 +1137,7 @@ static ChainSnap chain_snapshot(const lbmdem_handle* h) {
   s.fcur = h->fcur; s.ocur = h->ocur; s.kcur = h->kcur; s.obst_reset_rows = h->obst_reset_rows;
   for (int b = 0; b < 2; ++b) { s.snap_cur[b] = h->snap_cur[b]; s.snap_ok[b] = h->snap_ok[b]; s.chg_state[b] = h->chg_state[b]; }
   s.list_generation = h->list_generation;
-  s.obst_pending = h->obst_pending; s.diag_valid = h->diag_valid; s.slots_clean = h->slots_clean;
+  s.obst_pending = h->obst_pending; s.diag_valid = h->diag_valid; s.contacts_valid = h->contacts_valid; s.slots_clean = h->slots_clean;
   s.last_forces_from_table = h->last_forces_from_table; s.slots_valid = h->slots_valid; s.verlet_ok = h->verlet_ok;
   s.verlet_tracks_positions = h->verlet_tracks_positions; s.chain_painted = h->chain_painted;
   s.substep_seq = h->substep_seq; s.carry_from = h->carry_from;
@@ -1147,7 +1152,7 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   h->fcur = s.fcur; h->ocur = s.ocur; h->kcur = s.kcur;
   for (int b = 0; b < 2; ++b) { h->snap_cur[b] = s.snap_cur[b]; h->snap_ok[b] = s.snap_ok[b]; h->chg_state[b] = s.chg_state[b]; }
   h->list_generation = s.list_generation;
-  h->obst_pending = s.obst_pending; h->diag_valid = s.diag_valid; h->slots_clean = s.slots_clean;
+  h->obst_pending = s.obst_pending; h->diag_valid = s.diag_valid; h->contacts_valid = s.contacts_valid; h->slots_clean = s.slots_clean;
   h->last_forces_from_table = s.last_forces_from_table; h->slots_valid = s.slots_valid; h->verlet_ok = s.verlet_ok;
   h->verlet_tracks_positions = s.verlet_tracks_positions;
   h->substep_seq = s.substep_seq; h->carry_from = s.carry_from;
@@ -1529,6 +1534,7 @@ int lbmdem_upload_kinematics(lbmdem_handle* h, const double* k9) try {
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(h->kin[h->kcur].x1, soa.data(), sizeof(real) * 9 * n, hipMemcpyHostToDevice));
   h->verlet_tracks_positions = false;   // the pair list no longer bounds which discs can meet (obst_construction: atomics)
+  h->contacts_valid = false;
   drop_chain_paint(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {

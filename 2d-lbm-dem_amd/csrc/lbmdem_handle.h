@@ -48,7 +48,7 @@ struct ChainSnap {
   long long seq;      // sequence number of the launch's first sub-step (what the failing kernel reports)
   long log_idx, done; // the run-log entry the launch belongs to, and the sub-steps of that call that were done before it
   int fcur, ocur, kcur, obst_reset_rows, snap_cur[2], chg_state[2], list_generation;
-  bool obst_pending, snap_ok[2], diag_valid, slots_clean, last_forces_from_table, slots_valid, verlet_ok,
+  bool obst_pending, snap_ok[2], diag_valid, contacts_valid, slots_clean, last_forces_from_table, slots_valid, verlet_ok,
       verlet_tracks_positions, chain_painted;
   long long substep_seq, carry_from;
   int *gathered, *gathered_next;
@@ -204,6 +204,23 @@ struct lbmdem_handle {
   long long substep_seq = 0;  // sequence number of the next sub-step (the records' stamps)
   long long carry_from = 0;   // ct.carry is as of the sub-step before this one; only younger records override it
   bool diag_valid = false; // the last sub-step produced diagnostics
+  // The contact network export (lbm_contacts.hip). contacts_valid: the last sub-step was a table sub-step and nothing has touched
+  // the state it started from (kin[1 - kcur]), its pair list or its wall flags since; contacts_film / contacts_P: the law and the
+  // parameters that sub-step was launched with (the walls and the clock may have moved on since). cx: staging, allocated by the
+  // first export, grown with the record count, freed with the handle.
+  bool contacts_valid = false;
+  int contacts_film = 0;
+  DemParams contacts_P{};
+  bool contacts_output = false;   // lbmdem_set_contacts_output: lbmdem_run_scene writes the contact files at every DEM event
+  struct ContactStage {
+    int nwg = 0;                          // workgroups of the two kernels (0: nothing allocated yet)
+    long long *counts = nullptr, *offsets = nullptr;   // [2 nwg + 1] records per workgroup, pairs then walls; their exclusive scan
+    unsigned long long* census = nullptr; // [6]
+    void* scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    lbmdem_contact* rec = nullptr;        // [rec_cap]
+    long rec_cap = 0;
+  } cx;
   real* fhf = nullptr;  // [3][n]
   unsigned char* owner = nullptr;
   unsigned* mincov = nullptr;   // GrainFluidView::mincov
@@ -397,6 +414,8 @@ static inline VibWall vib_wall(const lbmdem_config& c) {
 // shared between the translation units
 #define LBMDEM_INTERNAL extern "C" __attribute__((visibility("hidden")))
 LBMDEM_INTERNAL int lbmdem_write_vtk_file(const char* path, int nx, int ny, const char* name, int dim, const float* data);
+LBMDEM_INTERNAL void lbmdem_ps_head(FILE* fp, int n, const double* x1, const double* x2, const double* r, const double* fm,
+                                    size_t stride, int lx, int ly);   // lbm_contacts.hip: header and discs of DEM%06d.ps
 LBMDEM_INTERNAL int lbmdem_verlet_build_lists(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_chain_settle(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);

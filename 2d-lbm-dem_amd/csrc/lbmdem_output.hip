@@ -195,20 +195,11 @@ static int write_forces_text(const char* dir, int nfile, int n, MapCols T, int l
   auto X1 = [&](int i) { return T.base[(size_t)i * T.stride + T.x1]; };
   auto X2 = [&](int i) { return T.base[(size_t)i * T.stride + T.x2]; };
   auto R = [&](int i) { return T.base[(size_t)i * T.stride + T.r]; };
-  auto FM = [&](int i) { return T.base[(size_t)i * T.stride + T.fm]; };
   char path[4200];
   snprintf(path, sizeof path, "%s/DEM%.6i.ps", (dir && *dir) ? dir : ".", nfile);
   FILE* fp = fopen(path, "w");
   if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing", path); return LBMDEM_EINVAL; }
-  const double margin = 10 * R(0), hrx1 = lx, hry2 = ly;  // main.c:449
-  fprintf(fp, "%%!PS-Adobe-3.0 EPSF-3.0 \n");
-  fprintf(fp, "%%%%BoundingBox: %f %f %f %f \n", -margin, -margin, hrx1 + margin, hry2 + margin);
-  fprintf(fp, "%%%%Creator: lbmdem-hip \n");
-  fprintf(fp, "%%%%Title: DEM Grains & Forces \n");
-  fprintf(fp, "0.1 setlinewidth 0.0 setgray \n");
-  for (int i = 0; i < n; i++)
-    fprintf(fp, "newpath %le %le %le 0.0 setlinewidth %.2f setgray 0 360 arc gsave fill grestore\n", X1(i) * 10000,
-            X2(i) * 10000, R(i) * 10000, (0.8 - FM(i) / 2));
+  lbmdem_ps_head(fp, n, T.base + T.x1, T.base + T.x2, T.base + T.r, T.base + T.fm, T.stride, lx, ly);
   // overlapping pairs, dn < -1e-10 (main.c:462-466), found on a uniform grid of cell size 2 r_max: any pair
   // with dn < 0 has its centres closer than that, i.e. in adjacent cells
   double xmin = X1(0), xmax = X1(0), ymin = X2(0), ymax = X2(0), rmax = R(0);

@@ -66,6 +66,7 @@ int lbmdem_dist_enable_caps(lbmdem_handle* h, int M, long cap_g, long cap_t, lon
   if (dist_alloc(h->mem, h->dd, h->n, (int)cap_g, (int)cap_t, (int)cap_l) != 0) return fail(LBMDEM_ENOMEM, "dist_alloc failed");
   RC_TRY(lbmdem_dem_tiles_by_index(h));   // (see there)
   h->dist = true;
+  h->contacts_valid = false;
   h->dist_margin = M;
   h->fs.mask = h->dd.fluidmask;
   h->fs.local_list = h->dd.local_list;
@@ -79,6 +80,7 @@ int lbmdem_dist_enable(lbmdem_handle* h, int margin_rows) try {
   CHECK_H(h);
   const lbmdem_config& c = h->cfg;
   if (h->dist) return fail(LBMDEM_EINVAL, "already enabled");
+  if (h->contacts_output) return fail(LBMDEM_EINVAL, "the contact network export is not available with distributed grains (lbmdem_set_contacts_output(h, 0) first)");
   if (h->vib) return fail(LBMDEM_EINVAL, "vibrating walls are not available with distributed grains");
   if (h->probe.on) return fail(LBMDEM_EINVAL, "probes are not available with distributed grains (lbmdem_probe_disable first)");
   if (async_frames_on(h)) return fail(LBMDEM_EINVAL, "frames in the background are not available with distributed grains (lbmdem_set_async_output(h, 0) first)");
@@ -366,6 +368,7 @@ int lbmdem_dist_table_substep(lbmdem_handle* h, const double* state12_full, cons
   h->carry_from = h->substep_seq + 1;
   h->substep_seq++;
   h->diag_valid = true;
+  h->contacts_valid = false;   // (distributed grains have no contact network export)
   HIP_TRY(hipGetLastError());
   h->kcur = 1 - h->kcur;
   h->nbsteps++;

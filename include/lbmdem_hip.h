@@ -446,6 +446,50 @@ int lbmdem_download_links(lbmdem_handle* h, lbmdem_link* out, long cap, long* co
 int lbmdem_download_geometry_obst(lbmdem_handle* h, int* obst);
 int lbmdem_write_obst(lbmdem_handle* h, const char* dir);
 int lbmdem_write_obst_files(const char* dir, int lx, int ly, const int* obst, const int* act, const lbmdem_link* links, long n);
+/* The contact network export: the reference declares `struct contact { int i, j; real nx, ny; real fn, ft; }` ("Luding Friction
+ * Model", main.c:167-174) and never fills it, and write_forces was meant to draw every contact with the line width of its normal
+ * force (the term is commented out, main.c:469). The library keeps only per-grain sums; the per-contact values exist in the
+ * registers of the sub-step kernels. The export re-derives them on the device, with the device functions the sub-step itself
+ * uses, from the state the sub-step STARTED from, which the other half of the kinematics ping-pong still holds.
+ * Which contacts: those of the LAST sub-step, when it was a table sub-step (every 4000th, or every one after
+ * lbmdem_set_diagnostics(h, 1)) -- the condition of lbmdem_download_grain_table -- evaluated with that sub-step's pair list, wall
+ * flags, contact law (regular or film) and parameters (walls and clock as they stood when it was launched). Any other sub-step
+ * or run of sub-steps, lbmdem_verlet_rebuild, lbmdem_upload_kinematics, lbmdem_dist_enable and a loaded checkpoint end that:
+ * every call below then returns LBMDEM_EINVAL and names lbmdem_set_diagnostics.
+ * Grain-grain records: one per pair i < j of the list with dn < 0 (main.c:744), i ascending, j ascending -- the reference's loop
+ * order. dn, nx = xn, ny = yn of main.c:739-753 (the normal points from j to i), fn and ft the law's variables after the clamps
+ * (main.c:761-771; main.c:1380-1390 on a film step), bit for bit what the sub-step used. A pair with fn == 0 is a record.
+ * Wall records follow all pair records: grain ascending, wall B, T, L, R within a grain. j = the wall code, dn the law's gap,
+ * (nx, ny) the inward wall normal (0,1), (0,-1), (1,0), (-1,0), fn and ft the reference's variables of those names in
+ * force_WallB/T/L/R when the function returns (top and right: fn <= 0; the right wall's ft comes from the unclamped fn).
+ *   lbmdem_contact_stats           counts6 = candidate pairs (list entries i < j), touching pairs, touching pairs that took the
+ *                                  Coulomb clamp branch, touching pairs with fn == 0, wall contacts, grains with at least one
+ *                                  record. The counting pass alone.
+ *   lbmdem_download_contacts       cap = 0 (out may be NULL) only reports *count; a buffer of fewer than *count records is refused
+ *                                  with *count set; synchronises; changes nothing a later step reads
+ *   lbmdem_write_contacts_files    host only, no handle, no device: <dir>/contacts%.6i.dat -- "# i j dn nx ny fn ft", then
+ *                                  "%d %d %le %le %le %le %le\n" per record -- and <dir>/DEM%.6i_chains.ps -- header and one arc
+ *                                  per grain as lbmdem_write_forces prints them (fm: the grey level), then per grain-grain record
+ *                                  with fn > 0 the four lines of main.c:469-473 with fn as the line width: one group per contact.
+ *                                  It checks fopen.
+ *   lbmdem_write_contacts          the download, then that formatter with r, x1, x2, fm of lbmdem_download_grain_table
+ *   lbmdem_set_contacts_output     on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_contacts at every DEM event, right
+ *                                  behind write_DEM / write_forces (queued first where tables go to the background), with the same
+ *                                  nFile. Off by default; a checkpoint does not carry it.
+ * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the
+ * single-precision library (the host-only formatter exists there too); null buffers; a directory that cannot be written.
+ * Vibrating and probing handles have the export. */
+#define LBMDEM_WALL_B (-1)   /* bottom, force_WallB main.c:809 */
+#define LBMDEM_WALL_T (-2)   /* top */
+#define LBMDEM_WALL_L (-3)   /* left */
+#define LBMDEM_WALL_R (-4)   /* right */
+typedef struct lbmdem_contact { int i, j; double dn, nx, ny, fn, ft; } lbmdem_contact;   /* 48 bytes */
+int lbmdem_contact_stats(lbmdem_handle* h, long* counts6);
+int lbmdem_download_contacts(lbmdem_handle* h, lbmdem_contact* out, long cap, long* count);
+int lbmdem_write_contacts(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_set_contacts_output(lbmdem_handle* h, int on);            /* 0: off (default) */
+int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double* r, const double* x1, const double* x2,
+                                const double* fm, const lbmdem_contact* c, long count, int lx, int ly);   /* host only */
 /* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
  * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
  * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
