@@ -1372,7 +1372,8 @@ __global__ void k_verlet_scan(int n, const real* __restrict__ x1, const real* __
                               const int* __restrict__ cell_start,
                               const int* __restrict__ sorted, real dV, int* __restrict__ counts,
                               int* __restrict__ offsets, int* __restrict__ nbr, int* __restrict__ own,
-                              long cap, int* __restrict__ overflow, DemParams P, unsigned char* __restrict__ wallflags) {
+                              long cap, int* __restrict__ overflow, DemParams P, unsigned char* __restrict__ wallflags,
+                              const int* __restrict__ raw_offsets) {
   LBMDEM_GATE(P.gate);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1381,17 +1382,20 @@ __global__ void k_verlet_scan(int n, const real* __restrict__ x1, const real* __
   int cnt = 0;
   int base = 0;
   if (MODE) {
-    // offsets[] arrives as the plain exclusive sum of the counts. A list longer than the allocation is truncated (and
-    // flagged): no kernel may index nbr[] / own[] past `cap`, so every grain clamps its own offset, and the last grain
-    // writes the total (before: two more launches, k_set_last_offset and k_clamp_offsets)
-    const long raw = offsets[i];
+    // raw_offsets[] is the plain exclusive sum of the counts (the scan itself does not look at the stop word: it writes
+    // scratch, and only this kernel, which does look, writes offsets[] -- a rebuild queued behind a launch that gave up
+    // leaves the list as it is). A list longer than the allocation is truncated (and flagged): no kernel may index nbr[] /
+    // own[] past `cap`, so every grain clamps its own offset, and the last grain writes the total (before: two more
+    // launches, k_set_last_offset and k_clamp_offsets)
+    const long raw = raw_offsets[i];
     if (i == n - 1) {
       const long total = raw + counts[i];
       if (total > cap) *overflow = 1;
       offsets[n] = (int)(total > cap ? cap : total);
     }
-    if (raw > cap) { offsets[i] = (int)cap; *overflow = 1; }
+    if (raw > cap) *overflow = 1;
     base = (int)(raw > cap ? cap : raw);
+    offsets[i] = base;
     wallflags[i] = wall_flags_of(xi, yi, ri, P);   // VerletWall's four candidate lists (main.c:1563-1593)
   }
   for (int yy = cy - 1; yy <= cy + 1; ++yy) {
@@ -1571,6 +1575,7 @@ int verlet_alloc(MemPool& mem, VerletDevice& V, int n, real cs, real ox, real oy
       // cell_start[0 .. ncell] (exclusive scan of the counts), cell_end[0 .. ncell] = the per-cell counts (zero between rebuilds)
       mem.dev(&V.cell_start, ncell + 1) == hipSuccess && mem.dev(&V.cell_end, ncell + 1) == hipSuccess &&
       mem.dev(&V.counts, N) == hipSuccess && mem.dev(&V.offsets, N + 1) == hipSuccess &&
+      mem.dev(&V.raw_offsets, N) == hipSuccess &&
       mem.dev(&V.nbr, (size_t)V.cap) == hipSuccess && mem.dev(&V.own, (size_t)V.cap) == hipSuccess &&
       mem.dev(&V.wallflags, N) == hipSuccess && mem.dev(&V.overflow, 1) == hipSuccess &&
       mem.dev(&V.halo_ids, tiles * DEM_CHAIN_HALO) == hipSuccess && mem.dev(&V.halo_cnt, tiles) == hipSuccess &&
@@ -1581,12 +1586,13 @@ int verlet_alloc(MemPool& mem, VerletDevice& V, int n, real cs, real ox, real oy
   V.yreb = V.xreb + n;
   V.scan_tmp_bytes = 0;
   size_t cells_tmp = 0;
-  if (hipcub::DeviceScan::ExclusiveSum(nullptr, V.scan_tmp_bytes, V.counts, V.offsets, n) != hipSuccess) return -1;
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, V.scan_tmp_bytes, V.counts, V.raw_offsets, n) != hipSuccess) return -1;
   if (hipcub::DeviceScan::ExclusiveSum(nullptr, cells_tmp, V.cell_end, V.cell_start, (int)(ncell + 1)) != hipSuccess) return -1;
   if (cells_tmp > V.scan_tmp_bytes) V.scan_tmp_bytes = cells_tmp;
   if (mem.dev(&V.scan_tmp, V.scan_tmp_bytes) != hipSuccess) return -1;
   if (hipMemset(V.cell_end, 0, sizeof(int) * (ncell + 1)) != hipSuccess) return -1;
   if (hipMemset(V.offsets, 0, sizeof(int) * (n + 1)) != hipSuccess) return -1;
+  if (hipMemset(V.counts, 0, sizeof(int) * n) != hipSuccess) return -1;   // (= the empty list of offsets[]; a rebuild or a loaded checkpoint fills both)
   if (hipMemset(V.wallflags, 0, n) != hipSuccess) return -1;
   if (hipMemset(V.overflow, 0, sizeof(int)) != hipSuccess) return -1;
   {   // tiles by index until somebody says otherwise (verlet_set_tiles)
@@ -1635,12 +1641,14 @@ int launch_verlet_rebuild(VerletDevice& V, const Kin& K, const real* r, const De
                      V.vals_out, V.gate);
   hipLaunchKernelGGL(k_verlet_scan<0>, dim3(nb), dim3(256), 0, st, n, K.x1, K.x2, r, V.ox, V.oy, V.cs, V.ncx,
                      V.ncy, V.cell_start, V.vals_out, P.distVerlet, V.counts, V.offsets, V.nbr,
-                     V.own, V.cap, V.overflow, P, V.wallflags);
-  e = hipcub::DeviceScan::ExclusiveSum(V.scan_tmp, V.scan_tmp_bytes, V.counts, V.offsets, n, st);
+                     V.own, V.cap, V.overflow, P, V.wallflags, V.raw_offsets);
+  // (neither scan looks at the stop word; both write scratch that only gated kernels of this rebuild read: cell_start[]
+  // and raw_offsets[]. Behind a launch that gave up the list -- counts[], offsets[], nbr[] -- stays what it was.)
+  e = hipcub::DeviceScan::ExclusiveSum(V.scan_tmp, V.scan_tmp_bytes, V.counts, V.raw_offsets, n, st);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(k_verlet_scan<1>, dim3(nb), dim3(256), 0, st, n, K.x1, K.x2, r, V.ox, V.oy, V.cs, V.ncx,
                      V.ncy, V.cell_start, V.vals_out, P.distVerlet, V.counts, V.offsets, V.nbr,
-                     V.own, V.cap, V.overflow, P, V.wallflags);
+                     V.own, V.cap, V.overflow, P, V.wallflags, V.raw_offsets);
   launch_tile_halo(V, n, st);
   return (int)hipGetLastError();
 }

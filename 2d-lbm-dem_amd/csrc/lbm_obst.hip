@@ -320,7 +320,10 @@ __global__ void k_obst_update(int* __restrict__ obst, LatticeView L, int n, cons
 }
 
 // test aid: values that differ between two lattices (the fused kernel run with and without the change bits)
-__global__ void k_count_differences(const real* __restrict__ a, const real* __restrict__ b, long n, int* __restrict__ bad) {
+// (gated like the launches it checks: behind a launch of k_dem_chain that gave up there is nothing to compare)
+__global__ void k_count_differences(const real* __restrict__ a, const real* __restrict__ b, long n, int* __restrict__ bad,
+                                    const int* __restrict__ gate) {
+  LBMDEM_GATE(gate);
   int mine = 0;
   for (long k = (long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long)gridDim.x * blockDim.x)
     mine += __double_as_longlong((double)a[k]) != __double_as_longlong((double)b[k]) ? 1 : 0;
@@ -330,6 +333,8 @@ __global__ void k_count_differences(const real* __restrict__ a, const real* __re
 // test aid (lbmdem_set_change_mask(h, 2)): one wavefront per (row, window) -- does a clear bit hide a difference?
 __global__ __launch_bounds__(64) void k_change_verify(const int* __restrict__ ob_old, const int* __restrict__ ob_new,
                                                       LatticeView L, ObstChange C, int windows, int* __restrict__ bad) {
+  // (behind a launch of k_dem_chain that gave up neither the map nor the bits were written: their mismatch is no finding)
+  LBMDEM_GATE(L.gate);
   const int xl = blockIdx.x / windows, w = blockIdx.x - xl * windows;
   const int y = w * C.ww - C.off + (int)threadIdx.x;
   const bool set = (C.bits[(long)w * C.words + (xl >> 5)] >> (xl & 31)) & 1u;
@@ -381,6 +386,6 @@ void launch_change_verify(const int* ob_old, const int* ob_new, const LatticeVie
   hipLaunchKernelGGL(k_change_verify, dim3((unsigned)(L.nxl * windows)), dim3(64), 0, st, ob_old, ob_new, L, chg, windows, bad);
 }
 
-void launch_count_differences(const real* a, const real* b, long n, int* bad, hipStream_t st) {
-  hipLaunchKernelGGL(k_count_differences, dim3(2048), dim3(256), 0, st, a, b, n, bad);
+void launch_count_differences(const real* a, const real* b, long n, int* bad, const int* gate, hipStream_t st) {
+  hipLaunchKernelGGL(k_count_differences, dim3(2048), dim3(256), 0, st, a, b, n, bad, gate);
 }

@@ -559,7 +559,7 @@ int lbmdem_collide_stream(lbmdem_handle* h) try {
     if (!h->chg_fcheck) HIP_TRY(h->mem.dev(&h->chg_fcheck, 9 * (size_t)h->L.plane));
     HIP_TRY(hipMemcpyAsync(h->chg_fcheck, h->f[1 - h->fcur], fbytes, hipMemcpyDeviceToDevice, h->stream));   // (rows the launch does not write)
     launch_collide_stream(h->f[h->fcur], h->chg_fcheck, ob_old, ob_new, h->L, gview(h), S_launch, h->stream);
-    launch_count_differences(h->f[1 - h->fcur], h->chg_fcheck, 9 * (long)h->L.plane, h->chg_bad + 1, h->stream);
+    launch_count_differences(h->f[1 - h->fcur], h->chg_fcheck, 9 * (long)h->L.plane, h->chg_bad + 1, h->L.gate, h->stream);
   }
   if (e1) HIP_TRY(hipEventRecord(e1, h->stream));
   h->slots_valid = h->fs.tab != nullptr;
@@ -1030,14 +1030,17 @@ int lbmdem_dem_chain(lbmdem_handle* h, long k, int fluid) {
   return LBMDEM_OK;
 }
 
+// The setters below settle like every other entry point that changes the handle (CHECK_H): a launch of k_dem_chain that gave up
+// is undone and the calls since are replayed with the settings they were MADE with -- a setting takes effect at its call, never
+// on sub-steps that were asked for before it.
 int lbmdem_set_obst_update(lbmdem_handle* h, int on) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  CHECK_H(h);
   h->obst_update = on != 0;
   return LBMDEM_OK;
 }
 
 int lbmdem_set_change_mask(lbmdem_handle* h, int mode) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  CHECK_H(h);
   if (mode < 0 || mode > 2) return fail(LBMDEM_EINVAL, "lbmdem_set_change_mask: mode 0 (off), 1 (on) or 2 (on, every use verified)");
   h->chg_on = mode != 0;
   h->chg_verify = mode == 2;
@@ -1067,7 +1070,7 @@ int lbmdem_obst_stats(lbmdem_handle* h, long* updates, long* repaints) {
 }
 
 int lbmdem_set_dem_chain(lbmdem_handle* h, int max_substeps) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  CHECK_H(h);   // (a recovery found here has switched the kernel off before the caller's value is stored: the value stands)
   if (max_substeps < 0) { h->chain_paint = false; return LBMDEM_OK; }   // (A/B: runs as before, without the rasterisation at their end)
   h->chain_max = max_substeps;
   return LBMDEM_OK;
@@ -1302,7 +1305,7 @@ int lbmdem_debug_live_memory(long* blocks, long* bytes) {
 #endif
 
 int lbmdem_set_lid(lbmdem_handle* h, double uw_h) {
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  CHECK_H(h);
   h->L.lid6 = uw_h / 6;   // the reference's commented-out expression: -uw_h/6, +uw_h/6
   return LBMDEM_OK;
 }
@@ -1364,7 +1367,8 @@ int lbmdem_move_walls(lbmdem_handle* h) {
 }
 
 int lbmdem_set_force_mode(lbmdem_handle* h, int mode) {
-  if (!h || (mode != 0 && mode != 1)) return fail(LBMDEM_EINVAL, "bad force mode");
+  CHECK_H(h);
+  if (mode != 0 && mode != 1) return fail(LBMDEM_EINVAL, "bad force mode");
   h->force_mode = mode;
   return LBMDEM_OK;
 }
@@ -1624,7 +1628,8 @@ int lbmdem_download_grain_pressure(lbmdem_handle* h, double* p) {
 long lbmdem_nbsteps(lbmdem_handle* h) { return h ? h->nbsteps : -1; }
 
 int lbmdem_set_nbsteps(lbmdem_handle* h, long n) {
-  if (!h || n < 0) return fail(LBMDEM_EINVAL, "bad argument");
+  CHECK_H(h);   // (the sub-steps asked for so far are counted from the old value, whatever a recovery has to repeat)
+  if (n < 0) return fail(LBMDEM_EINVAL, "bad argument");
   h->nbsteps = n;
   return LBMDEM_OK;
 }

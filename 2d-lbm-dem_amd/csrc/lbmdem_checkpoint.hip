@@ -334,6 +334,10 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
     }
     if (ok) ok = hipMemcpy(h->V.offsets, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) == hipSuccess &&
                  (H.nnbr == 0 || hipMemcpy(h->V.nbr, nb.data(), sizeof(int) * nb.size(), hipMemcpyHostToDevice) == hipSuccess);
+    // the per-grain counts the offsets are the running sum of (a rebuild leaves both; the last grain's total is formed from them)
+    std::vector<int> cnt((size_t)n);
+    for (int i = 0; i < n && ok; ++i) cnt[i] = off[i + 1] - off[i];
+    if (ok) ok = hipMemcpy(h->V.counts, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess;
   }
   fill(h->V.wallflags, n);
   fill(h->obst[0], sizeof(int) * (size_t)h->L.plane);

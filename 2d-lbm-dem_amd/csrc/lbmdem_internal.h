@@ -174,7 +174,7 @@ struct ObstSnap { real* xc; real* yc; real* still2; unsigned char* mode; };
 struct ObstChange { unsigned* bits; int words; int ww; int off; };
 void collide_stream_windows(int* ww, int* off);   // the fused kernel's window geometry (lbm_fused.hip)
 // test aid: counts the (row, window) pairs whose bit is clear although the two maps differ there (lbm_obst.hip)
-void launch_count_differences(const real* a, const real* b, long n, int* bad, hipStream_t st);
+void launch_count_differences(const real* a, const real* b, long n, int* bad, const int* gate, hipStream_t st);
 void launch_change_verify(const int* ob_old, const int* ob_new, const LatticeView& L, const ObstChange& chg, int windows, int* bad, hipStream_t st);
 void launch_obst_paint(int* obst, const LatticeView& L, int n, const real* x1, const real* x2, const real* r,
                        const real* rLB, const real* v1, const real* v2, const real* v3, real* xc,
@@ -372,6 +372,7 @@ struct VerletDevice {
   // symmetric CSR neighbour list, partners ascending
   int* counts;   // n
   int* offsets;  // n + 1
+  int* raw_offsets;   // [n] scratch of a rebuild: the plain exclusive sum of counts[], before k_verlet_scan<1> commits it to offsets[]
   int* nbr;      // cap
   int* own;      // cap: the grain each entry belongs to
   long cap;

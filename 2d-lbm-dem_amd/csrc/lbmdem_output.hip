@@ -100,7 +100,7 @@ int lbmdem_write_vtk(lbmdem_handle* h, const char* dir, int nfile) try {
 
 int lbmdem_set_diagnostics(lbmdem_handle* h, int always) {
   SP_UNAVAILABLE("the write_DEM diagnostics table");
-  if (!h) return fail(LBMDEM_EINVAL, "null handle");
+  CHECK_H(h);   // (always-diagnose keeps the multi-sub-step kernel out: unconfirmed launches are settled with the old setting)
   h->diag_always = always != 0;
   return LBMDEM_OK;
 }

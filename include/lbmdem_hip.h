@@ -315,7 +315,13 @@ int lbmdem_dem_chain_paints(lbmdem_handle* h, long* paints);
  * state the launch started from; the next call that is not lbmdem_run / lbmdem_run_dem (or the 256th launch since) drains
  * the stream, takes the handle back to that launch, switches the multi-sub-step kernel off for the handle and repeats the
  * sub-steps since, one launch each: the same bits. lbmdem_dem_chain_recoveries: how often that has happened (0 on a GPU of
- * its own). Distributed handles (lbmdem_dist_*) report the failure instead: a rank cannot go back alone. */
+ * its own). Distributed handles (lbmdem_dist_*) report the failure instead: a rank cannot go back alone.
+ * The setters are such calls too -- lbmdem_set_lid, lbmdem_set_force_mode, lbmdem_set_nbsteps, lbmdem_set_obst_update,
+ * lbmdem_set_change_mask, lbmdem_set_diagnostics, lbmdem_set_dem_chain, lbmdem_set_vibration: a setting takes effect at its
+ * call and never on sub-steps asked for before it, whether or not a launch among them had to be repeated.
+ * lbmdem_set_dem_chain(h, k) keeps the caller's k even when its own drain finds such a launch (the switch-off comes
+ * first); after a recovery found by any other call the kernel stays off until lbmdem_set_dem_chain is called again.
+ * A list rebuild queued behind a launch that gave up leaves the pair list alone, on a handle loaded from a checkpoint too. */
 int lbmdem_dem_chain_recoveries(lbmdem_handle* h, long* count);
 /* The grains of that kernel's workgroups ("tiles" of 64). mode 1 (default): consecutive stretches along a space-filling
  * curve over the positions at lbmdem_create (or at this call) -- compact patches of the packing whatever the numbering of the
@@ -607,6 +613,8 @@ int lbmdem_set_checkpoint_every(lbmdem_handle* h, long every_substeps, const cha
 int lbmdem_checkpoint_digest(const void* bytes, size_t n, unsigned long long* out2);      /* S1, S2 */
 int lbmdem_checkpoint_verify(const char* path, int* has_digest);
 long lbmdem_nbsteps(lbmdem_handle* h);
+/* (drains the stream when launches of the multi-sub-step kernel are unconfirmed: the sub-steps asked for before this call
+ * are counted from the old value, the ones after it from n) */
 int lbmdem_set_nbsteps(lbmdem_handle* h, long n);
 int lbmdem_get_config(lbmdem_handle* h, lbmdem_config* out);
 
