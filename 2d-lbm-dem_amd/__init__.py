@@ -176,6 +176,11 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_contacts_output.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_write_contacts_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_long, C.c_int, C.c_int]
+    L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
+    L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_write_coarse_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int]
+    L.lbmdem_set_coarse_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
@@ -335,6 +340,30 @@ def write_contacts_files(directory, nFile, r, x1, x2, fm, contacts, lx, ly, prec
     _chk(load_library(precision).lbmdem_write_contacts_files(os.fsencode(directory), int(nFile), n, _vp(cols[0]), _vp(cols[1]),
                                                              _vp(cols[2]), _vp(cols[3]), _vp(rec) if len(rec) else None,
                                                              len(rec), int(lx), int(ly)))
+
+
+# struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
+COARSE_FIELDS = ("nodes fluid_nodes grain_nodes wall_nodes sum_rho sum_jx sum_jy sum_P grains sum_m sum_mv1 sum_mv2 sum_Iw "
+                 "ke_x ke_y ke_teta sum_fhf1 sum_fhf2 sum_fhf3 sum_z sum_p M11 M12 M21 M22").split()
+COARSE_DTYPE = np.dtype([(name, np.float64) for name in COARSE_FIELDS])
+
+
+def coarse_grid(lx, ly, cw, ch, precision="f64"):
+    """(ncx, ncy) of cells of cw x ch nodes over an lx x ly lattice: (lx + cw - 1) // cw, (ly + ch - 1) // ch. Host only."""
+    ncx, ncy = C.c_int(0), C.c_int(0)
+    _chk(load_library(precision).lbmdem_coarse_grid(int(lx), int(ly), int(cw), int(ch), C.byref(ncx), C.byref(ncy)))
+    return int(ncx.value), int(ncy.value)
+
+
+def write_coarse_files(directory, nFile, lx, ly, cw, ch, cells, outside=0, contacts_valid=0, precision="f64"):
+    """coarse%.6i.dat: "# cw %d ch %d ncx %d ncy %d outside %ld contacts %d", then one line per cell, cx outer and cy inner:
+    "%d %d" and the 25 members of COARSE_DTYPE as " %le". `cells`: (ncx, ncy) of COARSE_DTYPE. Host only."""
+    ncx, ncy = coarse_grid(lx, ly, cw, ch, precision)
+    cells = np.ascontiguousarray(cells, dtype=COARSE_DTYPE)
+    if cells.shape != (ncx, ncy):
+        raise LbmDemError(-1, f"write_coarse_files: cells must have shape {(ncx, ncy)}, not {cells.shape}")
+    _chk(load_library(precision).lbmdem_write_coarse_files(os.fsencode(directory), int(nFile), int(lx), int(ly), int(cw), int(ch),
+                                                           _vp(cells), int(outside), int(contacts_valid)))
 
 
 def write_densities_host(directory, nFile, f, obst, t=0.0, rho_moy=1000.0):
@@ -755,6 +784,27 @@ class LbmDem:
     def set_contacts_output(self, on=True):
         """run_scene writes the contact files at every DEM event, right behind write_DEM / write_forces"""
         _chk(self._L.lbmdem_set_contacts_output(self._h, 1 if on else 0))
+
+    # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
+    def coarse_fields(self, cw, ch):
+        """-> (cells, outside, contacts_valid): cells a structured array of COARSE_DTYPE, shape (ncx, ncy); outside the grains
+        whose centre lies off the lattice; contacts_valid 1 when the last sub-step was a table sub-step (else sum_z .. M22 are 0)"""
+        count = C.c_long(0)
+        info = np.zeros(2, np.int64)
+        _chk(self._L.lbmdem_coarse_fields(self._h, int(cw), int(ch), None, 0, C.byref(count), _vp(info)))
+        ncx, ncy = coarse_grid(self.lx, self.ly, cw, ch)
+        cells = np.zeros((ncx, ncy), dtype=COARSE_DTYPE)
+        _chk(self._L.lbmdem_coarse_fields(self._h, int(cw), int(ch), _vp(cells), cells.size, C.byref(count), _vp(info)))
+        return cells, int(info[0]), int(info[1])
+
+    def write_coarse(self, directory=".", nFile=0, cw=16, ch=16):
+        """coarse%.6i.dat of the present state (write_coarse_files applied to coarse_fields)"""
+        _chk(self._L.lbmdem_write_coarse(self._h, os.fsencode(directory), int(nFile), int(cw), int(ch)))
+
+    def set_coarse_output(self, cw=0, ch=0):
+        """run_scene writes coarse%.6i.dat with cells of cw x ch nodes at every DEM event, behind write_DEM / write_forces and
+        the contact files; 0, 0 switches it off"""
+        _chk(self._L.lbmdem_set_coarse_output(self._h, int(cw), int(ch)))
 
     def write_densities(self, directory=".", nFile=0):
         """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""

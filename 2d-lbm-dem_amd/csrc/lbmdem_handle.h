@@ -221,6 +221,18 @@ struct lbmdem_handle {
     lbmdem_contact* rec = nullptr;        // [rec_cap]
     long rec_cap = 0;
   } cx;
+  // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
+  // allocated by the first export, grown when a finer grid needs more, freed with the handle.
+  int coarse_cw = 0, coarse_ch = 0;
+  struct CoarseStage {
+    double *cells = nullptr, *col = nullptr;   // [cell_cap][25] the records; [col_cap] column sums, [lx][7][ncy]
+    long cell_cap = 0, col_cap = 0;
+    unsigned* keys[2] = {nullptr, nullptr};    // [n] the grains' cells, unsorted and sorted (null: nothing allocated yet)
+    int* idx[2] = {nullptr, nullptr};          // [n] ... and their indices
+    long long* outside = nullptr;              // [1]
+    void* sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+  } cg;
   real* fhf = nullptr;  // [3][n]
   unsigned char* owner = nullptr;
   unsigned* mincov = nullptr;   // GrainFluidView::mincov

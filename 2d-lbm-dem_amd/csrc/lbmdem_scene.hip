@@ -171,6 +171,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
         RC_TRY(lbmdem_write_forces(h, dir, nfile));
       }
       if (!comm && h->contacts_output) RC_TRY(lbmdem_write_contacts(h, dir, nfile));   // lbmdem_set_contacts_output
+      if (!comm && h->coarse_cw > 0) RC_TRY(lbmdem_write_coarse(h, dir, nfile, h->coarse_cw, h->coarse_ch));   // lbmdem_set_coarse_output
     }
     if (cad.line(e)) {   // main.c:1884-1889
       const double* E = h->scene_energies;

@@ -496,6 +496,61 @@ int lbmdem_write_contacts(lbmdem_handle* h, const char* dir, int nfile);
 int lbmdem_set_contacts_output(lbmdem_handle* h, int on);            /* 0: off (default) */
 int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double* r, const double* x1, const double* x2,
                                 const double* fm, const lbmdem_contact* c, long count, int lx, int ly);   /* host only */
+/* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
+ * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
+ * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
+ * contract is exact arithmetic: every number is a chain of additions in a fixed order, from +0.0, that a serial loop over the
+ * downloads named below reproduces bit for bit.
+ * The grid: cw, ch >= 1 nodes per cell in x and y; ncx = (lx + cw - 1) / cw, ncy = (ly + ch - 1) / ch; cell (cx, cy) holds the nodes
+ * cx*cw <= x < min(lx, (cx+1)*cw), likewise in y (the last cells are cut at the lattice edge). Records come in host order [ncx][ncy],
+ * x slow.
+ * Node block (nodes .. sum_P), over the map and populations lbmdem_download_obst and lbmdem_download_f show -- what the last
+ * fluid step saw, not a rasterisation a run has already made for the coming one: fluid_nodes obst == -1, grain_nodes
+ * 0 <= obst < nbgrains, wall_nodes obst == nbgrains, nodes their total. Per fluid node rho = 0. + f0 + .. + f8,
+ * jx = 0. + f0*ex[0] + .. + f8*ex[8], jy likewise (lbmdem_download_macro's values), P = (1./3.) * rho_moy * (rho - 1.)
+ * (main.c:320, 533); any other node contributes +0.0. Order of additions, two levels: for each x of the cell a chain over its y
+ * ascending, then a chain over x ascending of those column sums.
+ * Grain block (grains .. sum_fhf3): a grain belongs to the cell of its centre in node coordinates as the rasteriser forms them
+ * (main.c:1009-1010), xc = (x1 - Mgx) / dx, yc = (x2 - Mby) / dx with the walls of lbmdem_get_walls: inside iff xc >= 0 && xc < lx
+ * && yc >= 0 && yc < ly (false for NaN), then cx = (int)xc / cw, cy = (int)yc / ch. The others belong to no cell and are counted
+ * in `outside` (after the first VerletWall the DEM walls lie ten times beyond the lattice). Chains over the cell's grains in
+ * ascending grain index of 1., m, m*v1, m*v2, It*v3, 0.5*m*v1*v1, 0.5*m*v2*v2, 0.5*It*v3*v3 (associated as main.c:381-383 writes
+ * them) and fhf1, fhf2, fhf3: the state of lbmdem_download_kinematics and lbmdem_download_fhf, m and It of main.c:624-626.
+ * Contact block (sum_z .. M22): the same chains over the columns z, p, M11, M12, M21, M22 of lbmdem_download_grain_table when
+ * the last sub-step was a table sub-step (that call's own condition); otherwise all six are +0.0 and contacts_valid is 0, which
+ * is no error.
+ * On the device: lanes along y stage a lattice row's values in LDS and one lane per cell segment adds them serially, a second
+ * kernel chains the column sums over x; the grains get their cell as a key, a stable radix sort keeps a cell's grains in index
+ * order and one lane per cell walks its segment. No atomics, nothing depends on launch order. Scratch is allocated by the first
+ * call and kept until lbmdem_destroy.
+ *   lbmdem_coarse_grid         host only, no handle: *ncx, *ncy
+ *   lbmdem_coarse_fields       *count = ncx * ncy; cap_cells = 0 (out may be NULL) only reports it; a buffer of fewer cells is
+ *                              refused with *count set; info2 = {outside, contacts_valid}; synchronises; changes nothing a later
+ *                              step reads
+ *   lbmdem_write_coarse_files  host only, no handle, no device: <dir>/coarse%.6i.dat -- "# cw %d ch %d ncx %d ncy %d outside %ld
+ *                              contacts %d\n", then per cell, cx outer and cy inner, "%d %d" followed by the 25 members as " %le"
+ *                              and "\n". It checks fopen.
+ *   lbmdem_write_coarse        the download, then that formatter
+ *   lbmdem_set_coarse_output   cw, ch >= 1: lbmdem_run_scene (comm == NULL) calls lbmdem_write_coarse at every DEM event with the
+ *                              event's nFile, behind write_DEM / write_forces (queued first where tables go to the background) and
+ *                              behind the contact files when those are on. 0, 0: off (the default); a checkpoint does not carry it.
+ * LBMDEM_EINVAL: cw or ch < 1 (except 0, 0 in the setter); null arguments; a strip of a decomposition or distributed grains (and
+ * lbmdem_dist_enable with the setting on); the single-precision library (the two host-only calls work there too); a directory
+ * that cannot be written ("cannot open"). Vibrating and probing handles have the export. */
+typedef struct lbmdem_coarse_cell {
+  double nodes, fluid_nodes, grain_nodes, wall_nodes;
+  double sum_rho, sum_jx, sum_jy, sum_P;
+  double grains, sum_m, sum_mv1, sum_mv2, sum_Iw, ke_x, ke_y, ke_teta;
+  double sum_fhf1, sum_fhf2, sum_fhf3;
+  double sum_z, sum_p, M11, M12, M21, M22;
+} lbmdem_coarse_cell;
+#define LBMDEM_COARSE_DOUBLES 25
+int lbmdem_coarse_grid(int lx, int ly, int cw, int ch, int* ncx, int* ncy);   /* host only */
+int lbmdem_coarse_fields(lbmdem_handle* h, int cw, int ch, lbmdem_coarse_cell* out, long cap_cells, long* count, long* info2);
+int lbmdem_write_coarse(lbmdem_handle* h, const char* dir, int nfile, int cw, int ch);
+int lbmdem_write_coarse_files(const char* dir, int nfile, int lx, int ly, int cw, int ch, const lbmdem_coarse_cell* cells,
+                              long outside, int contacts_valid);   /* host only */
+int lbmdem_set_coarse_output(lbmdem_handle* h, int cw, int ch);   /* 0, 0: off (default) */
 /* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
  * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
  * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
