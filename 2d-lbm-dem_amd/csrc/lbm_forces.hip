@@ -14,7 +14,6 @@ __global__ void k_fill_u64(unsigned long long* __restrict__ p, long count, unsig
 // hydrodynamic force and torque (main.c:1285-1333)
 // ---------------------------------------------------------------------------------------------
 
-#undef M3_LOAD_IDS
 __device__ __forceinline__ bool grain_box(const LatticeView& L, const GrainFluidView& G, int i, int& xi,
                                           int& xf, int& yi, int& yf) {
   const real xc = G.xc[i], yc = G.yc[i], rbl0 = G.rbl0[i];

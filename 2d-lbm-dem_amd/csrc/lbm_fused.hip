@@ -1,5 +1,5 @@
 // lbm_fused.hip -- the fused fluid kernels of the MI355X LBM-DEM stepper (gfx950, wave64): the PRODUCT kernels only.
-// (The experiment build adds k_cs_march3 and the per-phase timers from lbm_fused_ab.hip / lbm_march_timing.h.)
+// (The experiment build adds k_cs_march3 from lbm_fused_ab.hip.)
 //
 // What the reference does in five in-place sweeps of an AoS lattice per fluid step
 // (reinit_obst_density main.c:966-986, then collision_streaming main.c:1071-1243: collide,
@@ -25,15 +25,8 @@
 
 #include "lbm_march.h"
 #include <type_traits>
-#if defined(LBMDEM_AB) && (defined(MARCH_TIMING) || defined(MARCH_TRACE))
-#include "lbm_march_timing.h"
-#else
-#define MT_DECL
-#define MT(i)
-#define MT_FLUSH
-#endif
 
-#ifdef LBMDEM_AB
+#ifdef LBMDEM_AB   // test_experiment_build_kernel_variants_are_bit_exact: LBMDEM_MARCH=21|22 run k_cs_march3
 void launch_march3_ab(int which, int lx_template, const real* fin, real* fout, const int* obst_old, const int* obst_new,
                       const LatticeView& L, const GrainFluidView& G, const ForceSlots& S, int nstrips, int nwork, int remap,
                       int seg_rows, int seg_stride, int grid, hipStream_t st);   // lbm_fused_ab.hip
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(256) void k_collide_stream(const real* __restrict__
 // wavefront). nlev == 0: uniform segments (seg_rows / seg_stride arguments of the kernel). nlev > 0: the rows are split into
 // eight bands of band_rows rows, one per XCD (workgroup b runs on XCD b % 8), and every band is cut into rows[0] rows in
 // segments of seg[0] rows, then rows[1] rows in segments of seg[1] rows, ...: LONG SEGMENTS FIRST, SHORT ONES LAST. The
-// launch is bound by the memory system while all wave slots are busy (scripts/march_trace.py: ~390 row-equivalents per us with
+// launch is bound by the memory system while all wave slots are busy (round 4's row trace: ~390 row-equivalents per us with
 // 1 800 or with 2 040 of the 2 048 slots busy), so what a schedule can lose is its tail: with uniform 32-row segments a slot
 // idles for the last 125 us of 920 on average (14 % of the slot time); with the last rows of each band in 16- and 8-row
 // segments 4.5 %.
@@ -168,7 +161,7 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
                                            const ForceSlots& S, const ObstChange& CH, int strip, int xs, int xe,
                                            const RecRing ring,
                                            real* const pay, int* const desc, int lane, int w) {
-  (void)w;   // (the experiment build's row trace indexes its buffer with it)
+  (void)w;   // (the item's index in the launch; nothing reads it, but the kernel's prologue compiles to other code without it)
   // WW producing lanes in the middle of the window, (64 - WW) / 2 feeding lanes on either side
   constexpr int OFF = (64 - WW) / 2;
   const int y = strip * WW - OFF + lane;
@@ -233,11 +226,6 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
     if (!EDGE) return v;
     return (xl >= 0 && xl < L.nxl && ycl == y) ? v : L.n;
   };
-#if defined(LBMDEM_AB) && defined(MARCH_NO_OLD)   /* timing experiment (wrong where the maps differ): the second map is not read */
-#define MARCH_OLD(xl, same) (same)
-#else
-#define MARCH_OLD(xl, same) load_old(xl, same)
-#endif
   // off-lattice positions load a clamped neighbour's values; they are never used (pull_one tests the
   // bounds of the source node before touching its populations)
   auto load_raw = [&](int xl, real (&raw)[9]) {
@@ -270,14 +258,10 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
   int iD = load_id(xs + 1);        // row x+1
   int iE = load_id(xs + 2);        // row x+2
   {
-    int oo = MARCH_OLD(xs - 1, iB);
-#if defined(LBMDEM_AB) && defined(MARCH_NO_HALO_ROWS)   /* timing experiment (wrong results): the two rows a segment shares with its neighbours are not read */
-    load_raw(xs, Fm);
-#else
+    int oo = load_old(xs - 1, iB);
     load_raw(xs - 1, Fm);
-#endif
     make_fstar(xs - 1, Fm, oo, reinit_rec(oo), iB);
-    oo = MARCH_OLD(xs, iC);
+    oo = load_old(xs, iC);
     load_raw(xs, F0);
     make_fstar(xs, F0, oo, reinit_rec(oo), iC);
   }
@@ -287,8 +271,8 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
   ring.put(xs + 1, lane, grain_rec(iD), iD);
   ring.put(xs + 2, lane, grain_rec(iE), iE);
   int inext = load_id(xs + 3);
-  int oo1 = MARCH_OLD(xs + 1, iD);   // previous-map ids of rows x+1, x+2
-  int oo2 = MARCH_OLD(xs + 2, iE);
+  int oo1 = load_old(xs + 1, iD);   // previous-map ids of rows x+1, x+2
+  int oo2 = load_old(xs + 2, iE);
   GP rec_next = grain_rec(inext);  // owner record of row x+3, goes into the ring next iteration
   GPv gv_next = ring.getv(xs + 1, lane);
   load_raw(xs + 1, bufA);
@@ -317,17 +301,10 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
   lmask act0 = act_of(solB, solC, solD, hmax_of(iB), hmC, hmD, iB, iC, iD, xs, y);
   const lmask wmask = EDGE ? __ballot(writer) : (((lmask)1 << WW) - 1) << OFF;
 
-  MT_DECL
   // one iteration; `buf` holds row x+1 on entry and is refilled with row x+3
   auto iterate = [&](int x, real (&buf)[9]) {
-    MT(7)   // loop head
 #pragma unroll
     for (int q = 0; q < 9; ++q) Fp[q] = buf[q];
-#ifdef MARCH_TIMING   /* phase 0 = the wait for the row's populations alone */
-#pragma unroll
-    for (int q = 0; q < 9; ++q) asm volatile("" ::"v"(Fp[q]));
-    MT(0)
-#endif
     // f* of row x+1. The record of a node's PREVIOUS owner (reinit_obst_density, main.c:966-986) is the ring's record of
     // its current one except at the few nodes that have changed hands since the previous map: only a row that has such a
     // node (wave-uniform) fetches records from memory.
@@ -340,42 +317,27 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
       if (__ballot(moved) != 0) {
         if (moved) g = reinit_rec(oo1);
       }
-#if !(defined(LBMDEM_AB) && defined(MARCH_ABL_NOREINIT))   /* timing experiments (wrong results): a phase left out */
       if (re) grain_equilibrium(Lk, g, L.gx0 + x + 1, y, Fp);
-#endif
-#if !(defined(LBMDEM_AB) && defined(MARCH_ABL_NOCOLLIDE))
       if (in && iD == -1) mrt_collide(Lk, Fp);
-#endif
     }
-    MT(1)
     const int iF = inext;  // row x+3
     // ---- (1) small gathers
     oo1 = oo2;
     inext = load_id(x + 4);
-    oo2 = MARCH_OLD(x + 3, iF);
+    oo2 = load_old(x + 3, iF);
     __builtin_amdgcn_sched_barrier(0);
     // ---- (2) the big loads: populations of row x+3
     // (rows beyond xe are never consumed: the last two prefetches of a segment re-request row xe, which the wave loaded
     // one or two iterations ago, instead of two new rows -- 2 of the 36 rows a 32-row segment would read, 2 of 12 for 8 rows;
     // the loads stay unconditional so that the in-order vmcnt bookkeeping of the pipeline does not change)
-#if defined(LBMDEM_AB) && defined(MARCH_NO_HALO_ROWS)
-    load_raw(x + 3 < xe ? x + 3 : xe - 1, buf);
-#else
     load_raw(x + 3 < xe ? x + 3 : xe, buf);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-    MT(2)
     // (the column re-declared opaque: otherwise (double)(y - 1), (double)y, (double)(y + 1) of node_active's rare path are
     // hoisted out of the loop into six registers the kernel does not have, and one pair ends up in scratch -- whose reload
     // drains the row prefetch)
     int y_act = y;
     asm volatile("" : "+v"(y_act));
-#if defined(LBMDEM_AB) && defined(MARCH_ABL_NOACT)
-    const lmask actP = solD;
-#else
     const lmask actP = act_of(solC, solD, solE, hmC, hmD, hmE, iC, iD, iE, x + 1, y_act);
-#endif
-    MT(3)
 
     // the populations around P = (x, y): own row from the registers, the two column neighbours by DPP shifts
     real Fo[9], In[9];
@@ -430,18 +392,13 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
 #pragma unroll
         for (int q = 1; q < 9; ++q) T += __popcll(__ballot((ibb >> q) & 1u));
       }
-      MT(4)
       // (b) The bounce-back links of the row (typically ~20, spread over all eight directions and a few lanes) are compacted
       // into dense lanes through LDS and evaluated in ONE pass with the direction as data, instead of ~3.5
       // direction-specific divergent passes of ~130 instructions. slot of link (lane, q) = number of links in directions
       // < q + number in direction q on lower lanes. In a deep row with at most 64 links the pass leaves its results in the
       // links' slots and the lanes pick them up for the row's nine coalesced stores (`merged`); else every population but
       // the links' is stored first and the pass stores each result to the node it belongs to.
-#if defined(LBMDEM_AB) && defined(MARCH_SCATTER)   /* experiment: every result stored by the lane that evaluated it (+13 us) */
-      const bool merged = false;
-#else
       const bool merged = deep && T <= LINK_SLOTS;
-#endif
       auto store_row = [&](auto with_results) {   // the nine stores of a deep row
         if (lane_of(wm)) {
           buf_store_real<0>(Fo[0], fout_rs, fcol, so_row);
@@ -472,17 +429,9 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
       if (deep && !merged) store_row(std::false_type{});   // (a link's slot gets the streamed value as a placeholder; the stores of one
                                                // wavefront to one address keep their order, and a link whose wall distance
                                                // fires neither formula keeps exactly this value, main.c:1166-1217)
-#if defined(LBMDEM_AB) && defined(MARCH_ABL_NOPASS)
-      T = 0;
-#endif
-      MT(12)
       for (int base = 0; base < T; base += LINK_SLOTS) {  // wave-uniform; a second round only if > 64 links
         int before = 0;
-#if defined(LBMDEM_AB) && defined(MARCH_ABL_NOCOMPACT)
-        if (false) {
-#else
         if (deep) {
-#endif
 #define MARCH_COMPACT(Q)                                                                           \
           {                                                                                        \
             const lmask b = MARCH_LINK(Q);                                                         \
@@ -515,12 +464,7 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
           }
         }
         __builtin_amdgcn_wave_barrier();  // LDS operations of one wave execute in order
-        MT(10)
-#if defined(LBMDEM_AB) && defined(MARCH_ABL_NOEVALPASS)
-        if (false) {
-#else
         if (base + lane < T) {
-#endif
           const int d = desc[lane];
           const int src = d & 63;
           RtLink k;
@@ -538,33 +482,18 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
           // the record of the grain that owns S = P - e_q, and which grain that is (one round of LDS reads)
           const GP gS = ring.get(x - ex, src - ey);
           const int owner = ring.get_id(x - ex, src - ey);
-#if defined(LBMDEM_AB) && defined(MARCH_ABL_NOEVAL)
-          const real out = k.in_qo;
-#else
           const real out = ibb_eval_rt(Lk, k, Lk.wc_diag, Lk.wc_axis, gS, [&] { return ring.get(x + ex, src + ey); });
-#endif
           if (merged) pay[lane * 4] = out;   // picked up by the lane of node `src` for plane q of the row's stores
-#if !(defined(LBMDEM_AB) && defined(MARCH_ABL_NOFSTORE))
           else buf_store_real<0>(out, fout_rs, fcol_bytes(k.gy) + k.q * F_QBYTES, so_row);
-#endif
           // ... and the link's momentum-exchange sum f_new[S][opp q] + f_new[P][q] (main.c:1313-1316; the first
           // is f*[P][opp q], streamed unchanged into the solid node) to the slot table of the grain that owns S
-#if defined(LBMDEM_AB) && defined(MARCH_ABL_NOTAB)
-          if (false) {
-#else
           if (S.tab != nullptr) {
-#endif
             const int rel = slot_line(k.gx - ex, k.gy - ey, ex, ey, gS.xc, gS.yc) + S.half;
             if ((unsigned)rel < (unsigned)S.spd)
-#if defined(LBMDEM_AB) && defined(MARCH_TAB_NT)   /* experiment: the link sums past the L2's retention */
-              __builtin_nontemporal_store(k.own_qo + out, &S.tab[((long)owner * 8 + (k.q - 1)) * S.spd + rel]);
-#else
               S.tab[((long)owner * 8 + (k.q - 1)) * S.spd + rel] = k.own_qo + out;
-#endif
           }
         }
         __builtin_amdgcn_wave_barrier();
-        MT(11)
       }
       if (merged) {
         if (T > 0) store_row(std::true_type{});
@@ -574,7 +503,6 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
 #undef MARCH_HAZ
 #undef MARCH_LINK
 #undef MARCH_SRC
-      MT(5)
     }
     // row x-1 is no longer needed: its ring slot takes the owner records of row x+3; then request
     // those of row x+4 (consumed at this point of the next iteration)
@@ -588,7 +516,6 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
     solB = solC; solC = solD; solD = solE; solE = sol_of(iF);
     hmC = hmD; hmD = hmE; hmE = hmax_of(iF);
     actM = act0; act0 = actP;
-    MT(6)
   };
 
   // Both halves run unconditionally (a row >= xe stores nothing): with `if (x + 1 < xe)` around the second one the
@@ -598,14 +525,10 @@ __device__ __forceinline__ void march_item(const real* __restrict__ fin, real* _
     iterate(x, bufA);
     iterate(x + 1, bufB);
   }
-  MT_FLUSH
 }
 
 // wavefronts per workgroup of k_cs_march (they share nothing: the workgroup is the unit the dispatcher places and retires)
-#ifndef MARCH_WPB
-#define MARCH_WPB 4
-#endif
-constexpr int WPB = MARCH_WPB;
+constexpr int WPB = 4;
 
 template <int LX, int MINW, int WW, bool CHG = false>
 __global__ __launch_bounds__(64 * WPB, MINW) void k_cs_march(const real* __restrict__ fin, real* __restrict__ fout,
@@ -693,18 +616,6 @@ static void launch_cs(const real* fin, real* fout, const int* obst_old, const in
                      L, G, tiles_y, ntiles, remap);
 }
 
-#ifdef LBMDEM_AB
-// A/B builds only (make AB=1): LBMDEM_CS_VARIANT = kernel shape + 8 * xcd_remap
-static int cs_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("LBMDEM_CS_VARIANT");
-    v = e ? atoi(e) : 25;
-  }
-  return v;
-}
-#endif
-
 // rows per wave of the marching kernel: 32 (the measured optimum on a full lattice) unless that leaves fewer than two
 // rounds of resident waves; then the largest even count (the kernel works through its rows in pairs) that still gives
 // two full rounds, as short as 8. Measured on 508 rows x 66 windows (the interior of a 512-row strip), fused kernel
@@ -760,48 +671,42 @@ static MarchPlan march_plan(int rows, int nstrips, int main_seg, const int (*tai
   return P;
 }
 
+// A segment length that `rows` rows of a band can be cut into: a multiple of 8 (march_plan) that divides them.
+static constexpr bool plan_level_ok(int seg, int rows) { return seg >= 8 && seg % 8 == 0 && rows % seg == 0; }
+
 // The work order the product uses for `rows` rows of `nstrips` windows: tapered for a large range (uniform segments would be
 // 32 rows long), else none (nlev == 0: uniform segments of seg_rows rows).
 static MarchPlan product_plan(int rows, int nstrips, int seg_rows) {
-  MarchPlan P{};
-  if (seg_rows < 32) return P;
-  {
-    // Round 5: 64-row main segments and a 32-row level in front of the 16- and 8-row ones. A wavefront's rows do not get
-    // dearer with the segment length (profiles/r05_segment_length_counters.txt: wave-cycles +0.7 % at 64 rows, +2 % at 128),
-    // and every segment re-reads two prologue rows: -3 % of the read requests, fused kernel -0.4 % (interleaved A/B);
-    // 128-row segments lose 19 % to the end of the launch.
-    int main_seg = 64, ntail = 3;
-    int tail[3][2] = {{32, 64}, {16, 64}, {8, 64}};   // {rows per segment, rows of every band cut that way}
-#ifdef LBMDEM_AB   // LBMDEM_PLAN="seg:rows,seg:rows[,seg:rows]" (tail levels), LBMDEM_CS_ROWS = the main segment length
-    if (getenv("LBMDEM_CS_ROWS")) main_seg = atoi(getenv("LBMDEM_CS_ROWS"));
-    if (const char* e = getenv("LBMDEM_PLAN")) {
-      ntail = sscanf(e, "%d:%d,%d:%d,%d:%d", &tail[0][0], &tail[0][1], &tail[1][0], &tail[1][1], &tail[2][0], &tail[2][1]) / 2;
-    }
-#endif
-    bool ok = main_seg >= 8 && main_seg % 8 == 0;
-    for (int k = 0; k < ntail; ++k) ok = ok && tail[k][0] >= 8 && tail[k][0] % 8 == 0 && tail[k][1] % tail[k][0] == 0;
-    int chunk = 64;
-#ifdef LBMDEM_AB
-    if (getenv("LBMDEM_CHUNK")) chunk = atoi(getenv("LBMDEM_CHUNK"));
-#endif
-    if (chunk > 0 && chunk % main_seg != 0) chunk = 0;
-    if (ok) P = march_plan(rows, nstrips, main_seg, tail, ntail, chunk);
-  }
-  return P;
+  if (seg_rows < 32) return MarchPlan{};
+  // Round 5: 64-row main segments and a 32-row level in front of the 16- and 8-row ones. A wavefront's rows do not get
+  // dearer with the segment length (profiles/r05_segment_length_counters.txt: wave-cycles +0.7 % at 64 rows, +2 % at 128),
+  // and every segment re-reads two prologue rows: -3 % of the read requests, fused kernel -0.4 % (interleaved A/B);
+  // 128-row segments lose 19 % to the end of the launch.
+  constexpr int main_seg = 64, ntail = 3, chunk = 64;
+  static constexpr int tail[ntail][2] = {{32, 64}, {16, 64}, {8, 64}};   // {rows per segment, rows of every band cut that way}
+  static_assert(plan_level_ok(main_seg, chunk), "a chunk of a band holds whole main segments");
+  static_assert(plan_level_ok(tail[0][0], tail[0][1]) && plan_level_ok(tail[1][0], tail[1][1]) &&
+                    plan_level_ok(tail[2][0], tail[2][1]),
+                "every tail level is cut into whole segments");
+  return march_plan(rows, nstrips, main_seg, tail, ntail, chunk);
 }
 
-// which marching kernel: 2 = k_cs_march (two waves per SIMD), 3 = k_cs_march3 (three)
-#ifndef LBMDEM_MARCH_DEFAULT
-#define LBMDEM_MARCH_DEFAULT 2
-#endif
-__attribute__((unused)) static int march_kernel() {
-#ifdef LBMDEM_AB
-  static const int v = getenv("LBMDEM_MARCH") ? atoi(getenv("LBMDEM_MARCH")) : LBMDEM_MARCH_DEFAULT;
+#ifdef LBMDEM_AB   // test_experiment_build_kernel_variants_are_bit_exact: its two knobs (make AB=1 only)
+// LBMDEM_CS_VARIANT = kernel shape + 8 * xcd_remap
+static int cs_variant() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("LBMDEM_CS_VARIANT");
+    v = e ? atoi(e) : 25;
+  }
   return v;
-#else
-  return LBMDEM_MARCH_DEFAULT;
-#endif
 }
+// LBMDEM_MARCH: 2 = k_cs_march (the product's), 21 / 22 = k_cs_march3 with one / two row buffers
+static int march_kernel() {
+  static const int v = getenv("LBMDEM_MARCH") ? atoi(getenv("LBMDEM_MARCH")) : 2;
+  return v;
+}
+#endif
 
 // Producing lanes per 64-lane window. 60: a window's stores start at y = 60 k, i.e. on a 32-byte sector boundary of the
 // [y/16][q][y%16] tile rows, and cover 15 whole sectors -- with 62 (rounds 1-4) the two sectors at every window seam were
@@ -824,10 +729,6 @@ static void launch_march(const real* fin, real* fout, const int* obst_old, const
     // 256 CUs x 2 workgroups x 4 waves are resident (VGPR- and LDS-limited) and a wave takes about as long for 32
     // rows as the whole lattice takes per round, so fewer rows than two full rounds are cut into shorter segments
     seg_rows = march_segment_rows(rows, nstrips);
-#ifdef LBMDEM_AB
-    static const int env_rows = getenv("LBMDEM_CS_ROWS") ? atoi(getenv("LBMDEM_CS_ROWS")) : 0;
-    if (env_rows > 0) seg_rows = env_rows;
-#endif
   }
   const int nseg = (rows + seg_rows - 1) / seg_rows;
   int nwork = nstrips * nseg;
@@ -839,26 +740,21 @@ static void launch_march(const real* fin, real* fout, const int* obst_old, const
     nwork = 8 * P.first[P.nlev];
     grid = 8 * ((P.first[P.nlev] + WPB - 1) / WPB);
   }
-#ifdef LBMDEM_AB   // k_cs_march3 (lbm_fused_ab.hip) only exists in the experiment build
+#ifdef LBMDEM_AB   // test_experiment_build_kernel_variants_are_bit_exact[LBMDEM_MARCH=21|22]: k_cs_march3 (lbm_fused_ab.hip)
   if constexpr (WW == 62) {
     const int mk = march_kernel();
-    if (mk == 3 || mk == 21 || mk == 22) {
+    if (mk == 21 || mk == 22) {
       launch_march3_ab(mk, LX, fin, fout, obst_old, obst_new, L, G, S, nstrips, nwork, remap, seg_rows, seg_rows, grid, st);
       return;
     }
   }
 #endif
-  unsigned dyn_lds = 0;
-#ifdef LBMDEM_AB   // occupancy experiment: extra (unused) dynamic LDS so that only ONE workgroup fits a CU
-  static const int env_lds = getenv("LBMDEM_MARCH_DYNLDS") ? atoi(getenv("LBMDEM_MARCH_DYNLDS")) : 0;
-  dyn_lds = (unsigned)env_lds;
-#endif
   if (LX == 0 && chg.bits != nullptr) {
-    hipLaunchKernelGGL((k_cs_march<LX, MINW, WW, LX == 0>), dim3(grid), dim3(64 * WPB), dyn_lds, st, fin, fout, obst_old, obst_new, L, G,
+    hipLaunchKernelGGL((k_cs_march<LX, MINW, WW, LX == 0>), dim3(grid), dim3(64 * WPB), 0, st, fin, fout, obst_old, obst_new, L, G,
                        S, nstrips, nwork, remap, seg_rows, seg_rows, P, chg);
     return;
   }
-  hipLaunchKernelGGL((k_cs_march<LX, MINW, WW>), dim3(grid), dim3(64 * WPB), dyn_lds, st, fin, fout, obst_old, obst_new, L, G,
+  hipLaunchKernelGGL((k_cs_march<LX, MINW, WW>), dim3(grid), dim3(64 * WPB), 0, st, fin, fout, obst_old, obst_new, L, G,
                      S, nstrips, nwork, remap, seg_rows, seg_rows, P, chg);
 }
 
@@ -873,13 +769,6 @@ static void launch_march_two_ranges(const real* fin, real* fout, const int* obst
   const int nstrips = (L.ly + WW - 1) / WW;
   const int nwork = nstrips * 2;
   const int grid = (nwork + WPB - 1) / WPB;
-#ifdef LBMDEM_AB
-  if (march_kernel() == 3) {   // (k_cs_march3 is laid out for 62-column windows)
-    const int ns3 = (L.ly + 61) / 62, nw3 = ns3 * 2;
-    launch_march3_ab(3, 0, fin, fout, obst_old, obst_new, Ls, G, S, ns3, nw3, 0, w, hi0 - lo0, (nw3 + 3) / 4, st);
-    return;
-  }
-#endif
   hipLaunchKernelGGL((k_cs_march<0, 2, WW>), dim3(grid), dim3(64 * WPB), 0, st, fin, fout, obst_old, obst_new, Ls, G, S, nstrips,
                      nwork, 0, w, hi0 - lo0, MarchPlan{}, ObstChange{nullptr, 0, 0, 0});
 }
@@ -914,27 +803,20 @@ void collide_stream_windows(int* ww, int* off) { *ww = MARCH_WW; *off = (64 - MA
 void launch_collide_stream(const real* fin, real* fout, const int* obst_old, const int* obst_new,
                            const LatticeView& L, const GrainFluidView& G, const ForceSlots& S, hipStream_t st,
                            const ObstChange& chg) {
-#ifdef LBMDEM_AB
-  if (getenv("LBMDEM_CS_VARIANT")) {   // experiments with other kernel shapes; without the variable: the product's choice
-    int v = cs_variant();
-    const int remap = (v >> 3) & 1;
-    if (!L.reduced_lt1 && (v & ~8) >= 16) v = 1;
+#ifdef LBMDEM_AB   // test_experiment_build_kernel_variants_are_bit_exact[LBMDEM_CS_VARIANT=24|27|28|29]: other kernel shapes
+  if (getenv("LBMDEM_CS_VARIANT") && L.reduced_lt1) {   // (without the variable: the product's choice)
+    const int v = cs_variant(), remap = (v >> 3) & 1;
     switch (v & ~8) {
-      case 0: launch_cs<8, 64>(fin, fout, obst_old, obst_new, L, G, remap, st); return;
-      case 1: launch_cs<4, 64>(fin, fout, obst_old, obst_new, L, G, remap, st); return;
-      case 2: launch_cs<4, 128>(fin, fout, obst_old, obst_new, L, G, remap, st); return;
       case 16: launch_march<16, 2>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;
       case 19: launch_march<64, 2>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;
       case 20: launch_march<0, 2>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;  // one balanced round
       case 21: launch_march<32, 2, 56>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;  // 64-byte aligned stores
-      case 22: launch_march<0, 2, 62>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;   // rounds 1-4: 62 producing lanes, product work order
-      case 23: launch_march<0, 2, 56>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;   // 64-byte aligned stores, product work order
       default: launch_march<32, 2>(fin, fout, obst_old, obst_new, L, G, S, remap, st); return;
     }
   }
 #endif
   if (L.reduced_lt1) {
-#ifdef LBMDEM_AB
+#ifdef LBMDEM_AB   // test_experiment_build_kernel_variants_are_bit_exact[LBMDEM_MARCH=21|22]
     if (march_kernel() != 2) {   // k_cs_march3 (62-column windows only)
       launch_march<0, 2, 62>(fin, fout, obst_old, obst_new, L, G, S, /*xcd remap*/ 1, st);
       return;
@@ -949,8 +831,8 @@ void launch_collide_stream_edges(const real* fin, real* fout, const int* obst_ol
                                  const LatticeView& L, const GrainFluidView& G, const ForceSlots& S, int lo0, int lo1,
                                  int hi0, int hi1, hipStream_t st) {
   bool one_launch = lo1 > lo0 && hi1 > hi0 && lo1 - lo0 == hi1 - hi0 && lo1 - lo0 <= 32 && lo1 <= hi0 && L.reduced_lt1;
-#ifdef LBMDEM_AB
-  if (getenv("LBMDEM_CS_VARIANT")) one_launch = false;   // an experiment with another fused kernel
+#ifdef LBMDEM_AB   // test_experiment_build_kernel_variants_are_bit_exact[LBMDEM_CS_VARIANT=...]: that kernel for the edge rows too
+  if (getenv("LBMDEM_CS_VARIANT")) one_launch = false;
 #endif
   if (one_launch) {
     launch_march_two_ranges(fin, fout, obst_old, obst_new, L, G, S, lo0, lo1 - lo0, hi0, st);

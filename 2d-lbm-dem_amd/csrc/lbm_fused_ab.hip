@@ -1,6 +1,7 @@
 // lbm_fused_ab.hip -- EXPERIMENT BUILD ONLY (make AB=1 -> liblbmdem_hip_ab.so; nothing of this file is in the product):
 // k_cs_march3, the three-waves-per-SIMD form of the marching kernel (round 3: measured, not faster -- DESIGN.md section 4),
-// with its compile-time switches M3_DMAPOP / M3_UNIFORM / M3_MANUAL / M3_OVERFLOW, reached through LBMDEM_MARCH=3 | 21 | 22.
+// reached through LBMDEM_MARCH=21 | 22 (two waves per SIMD, one | two row buffers): the two settings that
+// tests/test_gpu_parity.py::test_experiment_build_kernel_variants_are_bit_exact holds to the golden vectors.
 #ifdef LBMDEM_AB
 
 #include "lbm_march.h"
@@ -97,75 +98,24 @@ __device__ __forceinline__ void lds_dma16_tok(const char*& gsrc, unsigned lds_ds
                : "=&s"(keep), "+v"(gsrc) : "s"(lds_dst) : "memory");
 }
 
-#ifdef M3_MANUAL
-// Loads the compiler does not see as loads (asm): it places no s_waitcnt of its own for them -- a counted wait after a
-// run of conditional stores can only assume that none of them was issued, and so drains the queue -- and the kernel
-// waits by hand with the exact number of vector-memory operations it has issued since (gfx9 retires them in order).
-typedef int m3_v4i __attribute__((ext_vector_type(4)));
-typedef int m3_v2i __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int m3_load_b32(const char* sbase, unsigned voff) {
-  int v;
-  asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
-  return v;
-}
-__device__ __forceinline__ m3_v4i m3_load_b128(const void* p) {
-  m3_v4i v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ m3_v4i m3_load_b128_16(const void* p) {
-  m3_v4i v;
-  asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ m3_v2i m3_load_b64_32(const void* p) {
-  m3_v2i v;
-  asm volatile("global_load_dwordx2 %0, %1, off offset:32" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ double m3_dbl(int lo, int hi) { return __hiloint2double(hi, lo); }
-#endif
-
-#ifdef M3_DMAPOP
-// 16 bytes per lane from (sbase + voff) to LDS byte address lds_dst (wave-uniform) + 16 * lane; the per-lane offset also
-// comes OUT of the statement so that a later ordinary load can be tied to it (issued after the DMA)
-__device__ __forceinline__ void lds_dma16_s(const char* sbase, unsigned& voff, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep), "+v"(voff) : "s"(sbase), "s"(lds_dst) : "memory");
-}
-#endif
-
 template <int LX, int MINW, int WW, int NBUF>
 __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict__ fin, real* __restrict__ fout,
                                                    const int* __restrict__ ob_old,
                                                    const int* __restrict__ ob_new, LatticeView L,
                                                    GrainFluidView G, ForceSlots S, int nstrips, int nwork,
                                                    int xcd_remap, int seg_rows, int seg_stride) {
-#ifdef M3_UNIFORM
-  int lane = threadIdx.x & 63;   // (not const: re-declared opaque in every iteration, see iterate())
-#else
   const int lane = threadIdx.x & 63;
-#endif
   int blk = blockIdx.x;
   if (xcd_remap) {
     const int per = gridDim.x >> 3;
     blk = (blk & 7) * per + (blk >> 3);
   }
-#ifdef M3_UNIFORM   /* wave-uniform, said explicitly: the row counter and the row addresses then live in scalar registers */
-  const int w = __builtin_amdgcn_readfirstlane(blk * 4 + (int)(threadIdx.x >> 6));
-#else
   const int w = blk * 4 + (threadIdx.x >> 6);
-#endif
   if (w >= nwork) return;  // whole wave
   const int strip = w % nstrips, seg = w / nstrips;
   constexpr int OFF = (64 - WW) / 2;
   static_assert(OFF >= 1, "the end lanes only feed their neighbours");
-#ifdef M3_UNIFORM
-  int y = strip * WW - OFF + lane;
-#else
   const int y = strip * WW - OFF + lane;
-#endif
   const bool yin = y >= 0 && y < L.ly;
   const bool writer = lane >= OFF && lane < OFF + WW && yin;
   const bool deep_y = strip * WW >= 2 && strip * WW + WW - 1 <= L.ly - 3;
@@ -182,54 +132,6 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
   real* const pay = sPay + wv * (64 * 4);
   int* const desc = sDesc + wv * 64;
   const unsigned lrec_lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lrec);
-#ifdef M3_DMAPOP
-  // The populations of the next row travel global -> LDS without a register landing (5 x global_load_lds_dwordx4 per
-  // row): chunk g = 64 k + lane (k = 0..4) is the 16-byte pair (y_c, y_c + 1), y_c = y0 - 1 + 2 (g % 33) (even: y0 is odd
-  // for WW = 62), of direction g / 33; it lands at staging byte 16 g, so direction q of lane l is double 66 q + l + 1.
-  static_assert(WW == 62 && NBUF == 1 && sizeof(real) == 8, "the DMA staging is laid out for the 62-column window of doubles");
-  __shared__ real sStage[4 * 640];
-  real* const stage = sStage + wv * 640;
-  const unsigned stage_lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)stage);
-  unsigned dma_off[5];   // byte offset of this lane's chunk from the first tile of the row
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    int g = 64 * k + lane;
-    if (g > 296) g = 296;
-    const int q = g / 33, c = g % 33;
-    int yc = strip * WW - OFF - 1 + 2 * c;
-    yc = yc < 0 ? 0 : (yc > L.sy - 2 ? L.sy - 2 : yc);
-    dma_off[k] = (unsigned)(((yc / LBMDEM_TILE_Y) * (9 * LBMDEM_TILE_Y) + (yc % LBMDEM_TILE_Y) + q * LBMDEM_TILE_Y) * 8);
-  }
-  typedef const int __attribute__((address_space(1))) * gint_ptr_t;
-  // request row xl (clamped like node_of); returns the probe whose arrival means the row has landed
-  auto dma_row = [&](int xl) {
-    const int xc = xl < 0 ? 0 : (xl >= L.nxl ? L.nxl - 1 : xl);
-    // (wave-uniform, but derived from threadIdx.x >> 6: say so, the DMA wants its base in scalar registers)
-    const unsigned long long rbv =
-        (unsigned long long)(reinterpret_cast<const char*>(fin) + (long)xc * (L.sy / LBMDEM_TILE_Y) * (9 * LBMDEM_TILE_Y * 8));
-    const char* rb = reinterpret_cast<const char*>(
-        ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(rbv >> 32)) << 32) |
-        (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)rbv));
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads of the previous row out of the staging are over
-    lds_dma16_s(rb, dma_off[0], stage_lds);
-    lds_dma16_s(rb, dma_off[1], stage_lds + 1024);
-    lds_dma16_s(rb, dma_off[2], stage_lds + 2048);
-    lds_dma16_s(rb, dma_off[3], stage_lds + 3072);
-    lds_dma16_s(rb, dma_off[4], stage_lds + 4096);
-#ifdef M3_MANUAL
-    return 0;
-#else
-    return *(gint_ptr_t)(unsigned long long)(rb + dma_off[4]);
-#endif
-  };
-  auto stage_read = [&](int probe, real (&f)[9]) {
-#ifndef M3_MANUAL
-    asm volatile("" ::"v"(probe) : "memory");   // the compiler's counted wait for the probe: the DMA before it has landed
-#endif
-#pragma unroll
-    for (int q = 0; q < 9; ++q) f[q] = stage[66 * q + lane + 1];
-  };
-#endif
   const real wc_diag = L.wc_diag, wc_axis = L.wc_axis;
   auto row_ok = [&](int xl) { return yin && xl >= 0 && xl < L.nxl; };
   const int ycl = y < 0 ? 0 : (y >= L.ly ? L.ly - 1 : y);
@@ -237,34 +139,7 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
     const int xc = xl < 0 ? 0 : (xl >= L.nxl ? L.nxl - 1 : xl);
     return (long)xc * L.sy + ycl;
   };
-#ifdef M3_UNIFORM
-  // scalar row base + 32-bit lane byte offset, the offset re-declared opaque at every use: otherwise the compiler folds it
-  // into a loop-invariant 64-bit per-lane pointer (two registers each, hoisted out of the loop and then spilled)
-  const int yo_ = lane == 0 ? y - 1 : (lane == 63 ? y + 1 : y);
-  const int co_ = yo_ < 0 ? 0 : (yo_ >= L.ly ? L.ly - 1 : yo_);
-  const unsigned ycl4 = 4u * (unsigned)ycl, co4 = 4u * (unsigned)co_;
-  const bool c_in = ycl == y, o_in = co_ == yo_;
-  auto opaque = [](unsigned v) { asm volatile("" : "+v"(v)); return v; };
-  auto row_of = [&](const int* ob, int xl) {
-    const int xc = xl < 0 ? 0 : (xl >= L.nxl ? L.nxl - 1 : xl);
-    return reinterpret_cast<const char*>(ob) + (long)xc * L.sy * 4;
-  };
-  auto load_old = [&](int xl) { return *reinterpret_cast<const int*>(row_of(ob_old, xl) + opaque(ycl4)); };
-  auto load_ids_row_u = [&](int xl) {
-    const bool rok = xl >= 0 && xl < L.nxl;
-    const char* row = row_of(ob_new, xl);
-    const int vc = *reinterpret_cast<const int*>(row + opaque(ycl4));
-    const int vo = *reinterpret_cast<const int*>(row + opaque(co4));
-    IdsRow r;
-    r.c = (rok && c_in) ? vc : L.n;
-    r.outer = (rok && o_in) ? vo : L.n;
-    return r;
-  };
-#define M3_LOAD_IDS(xl) load_ids_row_u(xl)
-#else
   auto load_old = [&](int xl) { return ob_old[node_of(xl)]; };
-#define M3_LOAD_IDS(xl) load_ids_row(ob_new, L, xl, y, lane)
-#endif
   auto load_raw = [&](int xl, real (&raw)[9]) {
     const long fb = fbase(node_of(xl));
 #pragma unroll
@@ -292,13 +167,13 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
 
   real Fm[9], F0[9], Fp[9], bufA[9], bufB[9];   // NBUF = 1: only bufA
 
-  IdsRow iB = M3_LOAD_IDS(xs - 1);
-  IdsRow iC = M3_LOAD_IDS(xs);
-  IdsRow iD = M3_LOAD_IDS(xs + 1);
-  IdsRow iE = M3_LOAD_IDS(xs + 2);
+  IdsRow iB = load_ids_row(ob_new, L, xs - 1, y, lane);
+  IdsRow iC = load_ids_row(ob_new, L, xs, y, lane);
+  IdsRow iD = load_ids_row(ob_new, L, xs + 1, y, lane);
+  IdsRow iE = load_ids_row(ob_new, L, xs + 2, y, lane);
   bool actm, act0;
   {
-    const IdsRow iA = M3_LOAD_IDS(xs - 2);
+    const IdsRow iA = load_ids_row(ob_new, L, xs - 2, y, lane);
     int oo = load_old(xs - 1);
     load_raw(xs - 1, Fm);
     RRec r = reinit_rec(oo);
@@ -314,60 +189,13 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
   int oo1 = load_old(xs + 1);   // previous-map ids of rows x+1, x+2
   int oo2 = load_old(xs + 2);
   RRec gre = reinit_rec(oo1);   // reinit record of row x+1
-#ifdef M3_MANUAL
-  // what is in flight across an iteration boundary: ids + previous-map id of row x+2, the reinit record of row x+1
-  int pend_c, pend_o, pend_old;
-  m3_v4i pend_ra, pend_rb;
-  m3_v2i pend_rc;
-  auto request_ids = [&](int xl) {
-    const char* row = row_of(ob_new, xl);
-    pend_c = m3_load_b32(row, opaque(ycl4));
-    pend_o = m3_load_b32(row, opaque(co4));
-    pend_old = m3_load_b32(row_of(ob_old, xl), opaque(ycl4));
-  };
-  auto request_reinit = [&](int id) {
-    const real* p = G.pk + (long)((id < 0 || id >= L.n) ? 0 : id) * 8;
-    pend_ra = m3_load_b128(p);
-    pend_rb = m3_load_b128_16(p);
-    pend_rc = m3_load_b64_32(p);
-  };
-  request_ids(xs + 2);
-  request_reinit(oo1);
-  int pop_probe = dma_row(xs + 1);
-  // everything requested so far has landed before the first iteration (the counted waits inside the loop count the
-  // operations of ONE iteration)
-  asm volatile("s_waitcnt vmcnt(0)" : "+v"(pend_c), "+v"(pend_o), "+v"(pend_old), "+v"(pend_ra), "+v"(pend_rb), "+v"(pend_rc) :: "memory");
-#elif defined(M3_DMAPOP)
-  int pop_probe = dma_row(xs + 1);
-#else
   load_raw(xs + 1, bufA);
   if (NBUF == 2) load_raw(xs + 2, bufB);
-#endif
 
   // one iteration: `buf` holds row x+1 on entry and is refilled with row x+1+NBUF
   auto iterate = [&](int x, real (&buf)[9]) {
-#ifdef M3_UNIFORM
-    // Nothing derived from the lane or the column may be hoisted out of the loop: the compiler otherwise keeps dozens of
-    // trivial loop invariants (lane | q << 8, (double)(y +- 1), per-lane pointers) in registers it does not have, and
-    // spills them to scratch -- whose reloads sit in the same in-order queue as the row prefetch.
-    asm volatile("" : "+v"(lane), "+v"(y));
-#endif
     const int gx = L.gx0 + x;
     const bool deep = deep_y && gx >= 2 && gx <= L.lx - 3;   // wave-uniform
-#ifdef M3_MANUAL
-    // The operations issued since the requests that are consumed here (ids / previous-map id of row x+2 and the
-    // populations of row x+1: at the top of the previous iteration; the reinit record: in its middle) are its nine
-    // population stores and the stores of its bounce-back pass: at most nine operations outstanding <=> all of them landed.
-    asm volatile("s_waitcnt vmcnt(9)" : "+v"(pend_c), "+v"(pend_o), "+v"(pend_old), "+v"(pend_ra), "+v"(pend_rb), "+v"(pend_rc) :: "memory");
-    {
-      const bool rok = x + 2 >= 0 && x + 2 < L.nxl;
-      iE.c = (rok && c_in) ? pend_c : L.n;
-      iE.outer = (rok && o_in) ? pend_o : L.n;
-      oo2 = pend_old;
-      gre = RRec{make_real2(m3_dbl(pend_ra.x, pend_ra.y), m3_dbl(pend_ra.z, pend_ra.w)),
-                 make_real2(m3_dbl(pend_rb.x, pend_rb.y), m3_dbl(pend_rb.z, pend_rb.w)), m3_dbl(pend_rc.x, pend_rc.y)};
-    }
-#endif
     // the old owner's velocity at (x+1, y): frees the record's registers before anything else is requested
     const real re_ux = rr_ux(gre), re_uy = rr_uy(gre, x + 1);
     int onb[9];
@@ -425,25 +253,15 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
     // once the compiler's own counted wait for `probe` is over, the records have landed.
     // (an address that comes out of an asm statement has lost its address space: say "global", or the load becomes a
     // FLAT one and the compiler falls back to vmcnt(0) everywhere)
-#ifdef M3_MANUAL
-    const int probe = 0;
-    request_ids(x + 3);
-#else
     typedef const int __attribute__((address_space(1))) * gint_ptr;
     const int probe = *(gint_ptr)(unsigned long long)rec_src;
     __builtin_amdgcn_sched_barrier(0);
     // ---- (1) 12 unconditional loads: ids of row x+3 (2), previous-map id of row x+3 (1), populations of row x+2 (9)
-    const IdsRow inext = M3_LOAD_IDS(x + 3);
+    const IdsRow inext = load_ids_row(ob_new, L, x + 3, y, lane);
     const int oo3 = load_old(x + 3);
-#endif
-#ifdef M3_DMAPOP
-    stage_read(pop_probe, Fp);
-    pop_probe = dma_row(x + 2);
-#else
 #pragma unroll
     for (int q = 0; q < 9; ++q) Fp[q] = buf[q];
     load_raw(x + 1 + NBUF, buf);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     make_fstar(x + 1, Fp, oo1, re_ux, re_uy, iD.c);
 
@@ -480,11 +298,7 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
     };
     if (T > 0) write_pay(0, In);
     // ---- (3) the reinit record of row x+2: requested late, converted at the top of the next iteration
-#ifdef M3_MANUAL
-    request_reinit(oo2);
-#else
     gre = reinit_rec(oo2);
-#endif
     // ---- (4) everything but the bounce-back links: computed and stored
     const Ids3 a3 = iC.all(), b3 = iD.all(), c3 = iE.all();   // DPP: outside the divergent &&
     const bool actp = iD.c != -1 && node_active(L, G, a3, b3, c3, L.gx0 + x + 1, y, [&] { return grain_rec(iD.c); });
@@ -506,17 +320,9 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
     }
     // ---- (5) the bounce-back links, LAST: everything the evaluation needs is in LDS, and the registers of row x-1,
     // the incoming populations and the neighbour ids are dead by now (this pass is the register peak of the loop).
-#ifndef M3_OVERFLOW
-#define M3_OVERFLOW 1
-#endif
-    for (int base = 0; base < (M3_OVERFLOW ? T : (T < 64 ? T : 64)); base += 64) {   // wave-uniform; more than one round only if the row has > 64 links
+    for (int base = 0; base < T; base += 64) {   // wave-uniform; more than one round only if the row has > 64 links
       if (base == 0) {
-#ifdef M3_MANUAL
-        // since the record DMA: 3 id loads, 5 population DMAs, 3 record loads, 9 population stores
-        asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-#else
         asm volatile("" ::"v"(probe) : "memory");   // the compiler waits for `probe` here => the records are in LDS
-#endif
       } else {
         // rare: descriptors and payloads of the next 64 links, rebuilt from what is still in registers (rows x-1, x,
         // x+1 and the ids; the cross-lane moves are repeated, in wave-uniform control flow)
@@ -566,13 +372,8 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
     }
 #pragma unroll
     for (int q = 0; q < 9; ++q) { Fm[q] = F0[q]; F0[q] = Fp[q]; }
-#ifdef M3_MANUAL
-    iB = iC; iC = iD; iD = iE;   // (iE and oo2 are decoded at the top of the next iteration)
-    oo1 = oo2;
-#else
     iB = iC; iC = iD; iD = iE; iE = inext;
     oo1 = oo2; oo2 = oo3;
-#endif
     actm = act0; act0 = actp;
   };
   if (NBUF == 1) {
@@ -588,7 +389,7 @@ __global__ __launch_bounds__(256, MINW) void k_cs_march3(const real* __restrict_
 
 }  // namespace
 
-// called by launch_march / launch_march_two_ranges (lbm_fused.hip) for LBMDEM_MARCH = 3 (three waves per SIMD), 21, 22
+// called by launch_march (lbm_fused.hip) for LBMDEM_MARCH = 21, 22
 void launch_march3_ab(int which, int lx_template, const real* fin, real* fout, const int* obst_old, const int* obst_new,
                       const LatticeView& L, const GrainFluidView& G, const ForceSlots& S, int nstrips, int nwork, int remap,
                       int seg_rows, int seg_stride, int grid, hipStream_t st) {
@@ -602,11 +403,8 @@ void launch_march3_ab(int which, int lx_template, const real* fin, real* fout, c
     case 64: M3_LAUNCH(64, MINW, NBUF); break;                                           \
     default: M3_LAUNCH(0, MINW, NBUF); break;                                            \
   }
-  if (which == 3) { M3_PICK(3, 1) }
-  else if (which == 21) { M3_PICK(2, 1) }
-#ifndef M3_DMAPOP
+  if (which == 21) { M3_PICK(2, 1) }
   else if (which == 22) { M3_PICK(2, 2) }
-#endif
 #undef M3_PICK
 #undef M3_LAUNCH
 }

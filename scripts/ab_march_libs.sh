@@ -1,5 +1,5 @@
 # A/B of several experiment builds inside ONE gpurun call: each arg = "<lib suffix>:<env assignments>", e.g.
-#   bash scripts/ab_march_libs.sh "_ab:LBMDEM_MARCH=2" "_ab_bperm:LBMDEM_MARCH=2" "_ab_m3a:LBMDEM_MARCH=3"
+#   bash scripts/ab_march_libs.sh "_ab:LBMDEM_MARCH=2" "_ab:LBMDEM_MARCH=21" "_ab_x:LBMDEM_MARCH=2"
 ROOT=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)   # the repository
 cd $GRAFT_REPO_ROOT
 P='import sys,json; d=json.loads(sys.stdin.read()); print("MLUPS", d["value"], "ms/step", d["ms_per_step"], "fused_ms", d["collide_stream_kernel_ms"], "frac", d["roofline"]["frac"])'

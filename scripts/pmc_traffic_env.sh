@@ -1,6 +1,6 @@
 # HBM traffic (FETCH_SIZE 2048 B/unit, WRITE_SIZE 1024 B/unit on gfx950, see profiles/r01_d_pmc_traffic.json) of the fused
 # kernel under several environment settings of the experiment build.
-#   usage: bash scripts/pmc_traffic_env.sh "LBMDEM_CS_VARIANT=28 LBMDEM_CS_ROWS=32" "LBMDEM_CS_VARIANT=28 LBMDEM_CS_ROWS=138"
+#   usage: bash scripts/pmc_traffic_env.sh "LBMDEM_CS_VARIANT=24" "LBMDEM_CS_VARIANT=27"
 export LBMDEM_HIP_LIBRARY=${LBMDEM_HIP_LIBRARY:-$GRAFT_REPO_ROOT/2d-lbm-dem_amd/liblbmdem_hip_ab.so}
 cd /tmp && export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out/trafficenv; rm -rf $O; mkdir -p $O
