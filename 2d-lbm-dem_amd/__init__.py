@@ -181,6 +181,12 @@ def _open_library(LIB_PATH):
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
     L.lbmdem_write_coarse_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int]
     L.lbmdem_set_coarse_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.lbmdem_flow_fields.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_flow_fields_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long]
+    L.lbmdem_flow_sums.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_write_flow.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_write_flow_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+    L.lbmdem_set_flow_output.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
@@ -364,6 +370,31 @@ def write_coarse_files(directory, nFile, lx, ly, cw, ch, cells, outside=0, conta
         raise LbmDemError(-1, f"write_coarse_files: cells must have shape {(ncx, ncy)}, not {cells.shape}")
     _chk(load_library(precision).lbmdem_write_coarse_files(os.fsencode(directory), int(nFile), int(lx), int(ly), int(cw), int(ch),
                                                            _vp(cells), int(outside), int(contacts_valid)))
+
+
+# the flow fields (LbmDem.flow_fields): the bits of the mask in plane order, LBMDEM_FLOW_*
+FLOW_NAMES = ("ux", "uy", "vort", "div", "nxx", "nxy", "gdot", "diss")
+FLOW_UX, FLOW_UY, FLOW_VORT, FLOW_DIV, FLOW_NXX, FLOW_NXY, FLOW_GDOT, FLOW_DISS = (1 << k for k in range(8))
+FLOW_ALL = 255
+FLOW_SUMS = ("n_fluid", "sum_rho", "sum_ke", "sum_diss", "sum_enstrophy", "max_u2", "max_gdot", "max_abs_div")
+
+
+def flow_plane_names(mask):
+    """the fields a mask selects, in plane order (ascending bit)"""
+    mask = int(mask)
+    if mask <= 0 or mask & ~FLOW_ALL:
+        raise LbmDemError(-1, f"flow fields: bad mask {mask}")
+    return [name for k, name in enumerate(FLOW_NAMES) if mask >> k & 1]
+
+
+def write_flow_files(directory, nFile, ux, uy, vort, gdot, diss, precision="f64"):
+    """flow%.6i.vtk from five planes (lx, ly) of doubles: the binary rectilinear-mesh format of write_vtk's files with the
+    point data fluid_velocity_lb (ux, uy, 0), vorticity, shear_rate, dissipation, each value cast to float. Host only."""
+    planes = [np.ascontiguousarray(p, dtype=np.float64) for p in (ux, uy, vort, gdot, diss)]
+    if planes[0].ndim != 2 or any(p.shape != planes[0].shape for p in planes):
+        raise LbmDemError(-1, "write_flow_files: five planes of one shape (lx, ly)")
+    lx, ly = planes[0].shape
+    _chk(load_library(precision).lbmdem_write_flow_files(os.fsencode(directory), int(nFile), lx, ly, *(_vp(p) for p in planes)))
 
 
 def write_densities_host(directory, nFile, f, obst, t=0.0, rho_moy=1000.0):
@@ -805,6 +836,46 @@ class LbmDem:
         """run_scene writes coarse%.6i.dat with cells of cw x ch nodes at every DEM event, behind write_DEM / write_forces and
         the contact files; 0, 0 switches it off"""
         _chk(self._L.lbmdem_set_coarse_output(self._h, int(cw), int(ch)))
+
+    # flow fields: composite velocity, vorticity, divergence, the collision's strain-rate moments, shear rate, dissipation
+    # (include/lbmdem_hip.h)
+    def flow_fields(self, mask=FLOW_ALL, device=False):
+        """-> {name: (lx, ly) float64 array} of the fields `mask` selects (FLOW_UX .. FLOW_DISS), lattice units. device=True:
+        torch.float64 tensors on the handle's GPU, filled by the kernel without a host copy on the handle's stream -- order
+        through set_stream or sync()."""
+        names = flow_plane_names(mask)
+        if device:
+            import torch
+            out = torch.empty((len(names), self.lx, self.ly), dtype=torch.float64, device=f"cuda:{self.cfg.device}")
+            self.flow_fields_into(mask, out)
+            return {name: out[k] for k, name in enumerate(names)}
+        count = C.c_long(0)
+        out = np.zeros((len(names), self.lx, self.ly))
+        _chk(self._L.lbmdem_flow_fields(self._h, int(mask), _vp(out), out.size, C.byref(count)))
+        return {name: out[k] for k, name in enumerate(names)}
+
+    def flow_fields_into(self, mask, tensor):
+        """the planes of `mask` into a contiguous torch.float64 CUDA tensor of at least that many elements (no synchronisation)"""
+        import torch
+        if tensor.dtype != torch.float64 or not tensor.is_cuda or not tensor.is_contiguous():
+            raise LbmDemError(-1, "flow_fields_into: a contiguous torch.float64 CUDA tensor")
+        _chk(self._L.lbmdem_flow_fields_device(self._h, int(mask), C.c_void_p(tensor.data_ptr()), int(tensor.numel())))
+
+    def flow_sums(self):
+        """-> dict of FLOW_SUMS over the fluid nodes: n_fluid, sums of rho, kinetic energy, dissipation and enstrophy, maxima of
+        u^2, the shear rate and |div| (lattice units; fixed order of additions, include/lbmdem_hip.h)"""
+        out = np.zeros(8)
+        _chk(self._L.lbmdem_flow_sums(self._h, _vp(out)))
+        return dict(zip(FLOW_SUMS, (float(v) for v in out)))
+
+    def write_flow(self, directory=".", nFile=0):
+        """flow%.6i.vtk of the present state (write_flow_files applied to flow_fields; the byte image is made on the device)"""
+        _chk(self._L.lbmdem_write_flow(self._h, os.fsencode(directory), int(nFile)))
+
+    def set_flow_output(self, on=True):
+        """run_scene writes flow%.6i.vtk at every VTK event, after the frame, and appends a line of flow_sums to flow.data at
+        every DEM event"""
+        _chk(self._L.lbmdem_set_flow_output(self._h, 1 if on else 0))
 
     def write_densities(self, directory=".", nFile=0):
         """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""

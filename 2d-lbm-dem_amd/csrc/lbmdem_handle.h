@@ -233,6 +233,18 @@ struct lbmdem_handle {
     void* sort_tmp = nullptr;
     size_t sort_bytes = 0;
   } cg;
+  // Flow fields (lbm_flow.hip). flow_output: lbmdem_set_flow_output. fl: scratch, allocated by the first call that needs it, grown
+  // when a call asks for more, freed with the handle.
+  bool flow_output = false;
+  struct FlowStage {
+    double* planes = nullptr;   // [planes_cap] the selected planes of a host export, [lx][ly] each
+    long planes_cap = 0;
+    double* part = nullptr;     // [part_cap] per (row, block of 64 y) partial sums, [lx][nb][8]; then the row sums [lx][8]
+    long part_cap = 0;
+    double* sums = nullptr;     // [8]
+    unsigned* image = nullptr;  // [image_cap] the payloads of flow%.6i.vtk in file byte order, 6 words per node
+    long image_cap = 0;
+  } fl;
   real* fhf = nullptr;  // [3][n]
   unsigned char* owner = nullptr;
   unsigned* mincov = nullptr;   // GrainFluidView::mincov
@@ -426,6 +438,7 @@ static inline VibWall vib_wall(const lbmdem_config& c) {
 // shared between the translation units
 #define LBMDEM_INTERNAL extern "C" __attribute__((visibility("hidden")))
 LBMDEM_INTERNAL int lbmdem_write_vtk_file(const char* path, int nx, int ny, const char* name, int dim, const float* data);
+LBMDEM_INTERNAL void lbmdem_vtk_put_mesh(FILE* fp, int nx, int ny);   // lbmdem_output.hip: header, mesh, CELL_DATA / POINT_DATA lines
 LBMDEM_INTERNAL void lbmdem_ps_head(FILE* fp, int n, const double* x1, const double* x2, const double* r, const double* fm,
                                     size_t stride, int lx, int ly);   // lbm_contacts.hip: header and discs of DEM%06d.ps
 LBMDEM_INTERNAL int lbmdem_verlet_build_lists(lbmdem_handle* h);

@@ -54,8 +54,8 @@ static void put_be(FILE* fp, const float* v, size_t n) {
   fwrite(buf.data(), 1, buf.size(), fp);
 }
 
-// everything in front of the variable's payload
-static void put_vtk_head(FILE* fp, int nx, int ny, const char* name, int dim) {
+// header, mesh and the CELL_DATA / POINT_DATA lines: everything in front of the first variable (also lbm_flow.hip's file)
+void lbmdem_vtk_put_mesh(FILE* fp, int nx, int ny) {
   fprintf(fp, "# vtk DataFile Version 2.0\nWritten using VisIt writer\nBINARY\n");
   fprintf(fp, "DATASET RECTILINEAR_GRID\nDIMENSIONS %d %d 1\n", nx, ny);
   // coordinates: i * (float)(1/nx) on BOTH axes, z = 0 (main.c:255-258)
@@ -68,6 +68,11 @@ static void put_vtk_head(FILE* fp, int nx, int ny, const char* name, int dim) {
   fprintf(fp, "Y_COORDINATES %d float\n", ny); put_be(fp, ys.data(), ny);
   fprintf(fp, "Z_COORDINATES 1 float\n"); put_be(fp, &z, 1);
   fprintf(fp, "CELL_DATA %d\nPOINT_DATA %d\n", (nx - 1) * (ny - 1), nx * ny);
+}
+
+// everything in front of the variable's payload
+static void put_vtk_head(FILE* fp, int nx, int ny, const char* name, int dim) {
+  lbmdem_vtk_put_mesh(fp, nx, ny);
   if (dim == 1) fprintf(fp, "SCALARS %s float\nLOOKUP_TABLE default\n", name);
   else fprintf(fp, "VECTORS %s float\n", name);
 }

@@ -104,6 +104,24 @@ int lbmdem_scene_schedule(const lbmdem_config* cfg, long nbsteps0, long n, doubl
   return LBMDEM_OK;
 }
 
+// lbmdem_set_flow_output: one line of <dir>/flow.data -- nbsteps * dt and the eight numbers of lbmdem_flow_sums -- behind a header
+// line when the file is new
+static int flow_data_line(lbmdem_handle* h, const char* dir) {
+  double s[8];
+  RC_TRY(lbmdem_flow_sums(h, s));
+  char path[4200];
+  snprintf(path, sizeof path, "%s/flow.data", *dir ? dir : ".");
+  FILE* fp = fopen(path, "a");
+  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0) fprintf(fp, "# t n_fluid sum_rho sum_ke sum_diss sum_enstrophy max_u2 max_gdot max_abs_div\n");
+  fprintf(fp, "%le", h->nbsteps * h->cfg.dt);
+  for (int k = 0; k < 8; ++k) fprintf(fp, " %le", s[k]);
+  fprintf(fp, "\n");
+  const bool bad = ferror(fp) != 0;
+  if (fclose(fp) != 0 || bad) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
+  return LBMDEM_OK;
+}
+
 static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
   CHECK_H(h);
   if (!sc || n < 0) return fail(LBMDEM_EINVAL, "bad argument");
@@ -160,6 +178,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
     s = e + 1;
     if (cad.vtk(e)) {   // write_vtk sits inside `#ifdef _FLUIDE_` (main.c:1768-1770); nFile++ does not
       if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else if (async_frames_on(h)) RC_TRY(lbmdem_write_vtk_async(h, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
+      if (dir && sc->fluid && !comm && h->flow_output) RC_TRY(lbmdem_write_flow(h, dir, nfile));   // lbmdem_set_flow_output
       nfile++;
     }
     // (with strips the sub-step before was run by rank 0 on a full replica, lbmdem_comm_run: it holds the whole table)
@@ -172,6 +191,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
       }
       if (!comm && h->contacts_output) RC_TRY(lbmdem_write_contacts(h, dir, nfile));   // lbmdem_set_contacts_output
       if (!comm && h->coarse_cw > 0) RC_TRY(lbmdem_write_coarse(h, dir, nfile, h->coarse_cw, h->coarse_ch));   // lbmdem_set_coarse_output
+      if (!comm && h->flow_output) RC_TRY(flow_data_line(h, dir));   // lbmdem_set_flow_output
     }
     if (cad.line(e)) {   // main.c:1884-1889
       const double* E = h->scene_energies;

@@ -50,6 +50,8 @@
  * its normal force. Single GPU only.
  * --coarse CWxCH: the coarse-grained fields of every DEM event next to its table (lbmdem_set_coarse_output): coarse%.6i.dat, one
  * line per cell of CW x CH lattice nodes with the sums of fluid, grains and contacts over it. Single GPU only.
+ * --flow: the flow fields (lbmdem_set_flow_output): flow%.6i.vtk next to every VTK frame -- composite velocity, vorticity, shear
+ * rate and dissipation in lattice units -- and one line of the fluid's sums in flow.data at every DEM event. Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -74,6 +76,7 @@ static int g_rank = 0, g_world = 1, g_use_comm = 0, g_dry = 0, g_vib = 0, g_run_
 static const char* g_dump_geometry = NULL;   /* --dump-geometry DIR */
 static const char* g_densities = NULL;       /* --densities DIR */
 static int g_contacts = 0;       /* --contacts */
+static int g_flow = 0;           /* --flow */
 static int g_coarse = 0, g_coarse_cw = 0, g_coarse_ch = 0;   /* --coarse CWxCH */
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
@@ -209,6 +212,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--dry")) g_dry = 1;
     if (!strcmp(argv[a], "--vib")) g_vib = 1;
     if (!strcmp(argv[a], "--contacts")) g_contacts = 1;
+    if (!strcmp(argv[a], "--flow")) g_flow = 1;
     if (!strcmp(argv[a], "--coarse")) {
       char tail = 0;
       if (a + 1 >= argc || sscanf(argv[a + 1], "%dx%d%c", &g_coarse_cw, &g_coarse_ch, &tail) != 2 || g_coarse_cw < 1 || g_coarse_ch < 1) {
@@ -251,6 +255,8 @@ int main(int argc, char** argv) {
   if (g_densities && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--densities is a single-GPU mode (write_densities needs the whole lattice on one handle)\n"); return EXIT_FAILURE; }
   if (g_contacts && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--contacts is a single-GPU mode (the contact network export needs all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_coarse && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--coarse is a single-GPU mode (the coarse-grained fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_flow && g_dry) { fprintf(stderr, "--flow cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_densities && g_dry) { fprintf(stderr, "--densities cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_async_frames && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-output is a single-GPU mode (with --gpus N rank 0 merges the strips' columns and writes the frames itself)\n"); return EXIT_FAILURE; }
   if (g_async_dem && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-dem is a single-GPU mode (with --gpus N rank 0 runs the table sub-step on a full replica and writes the tables itself)\n"); return EXIT_FAILURE; }
@@ -399,6 +405,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--dry")) {}
     else if (!strcmp(argv[a], "--vib")) {}
     else if (!strcmp(argv[a], "--contacts")) {}
+    else if (!strcmp(argv[a], "--flow")) {}
     else if (!strcmp(argv[a], "--coarse") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--async-output")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
@@ -424,7 +431,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -484,6 +491,7 @@ static int run(int argc, char** argv) {
     DIE(lbmdem_create(&cfg, r, x1, x2, &h), "create");
   }
   if (g_contacts) DIE(lbmdem_set_contacts_output(h, 1), "set_contacts_output");
+  if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");
   if (g_coarse) DIE(lbmdem_set_coarse_output(h, g_coarse_cw, g_coarse_ch), "set_coarse_output");
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */

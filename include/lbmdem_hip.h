@@ -551,6 +551,87 @@ int lbmdem_write_coarse(lbmdem_handle* h, const char* dir, int nfile, int cw, in
 int lbmdem_write_coarse_files(const char* dir, int nfile, int lx, int ly, int cw, int ch, const lbmdem_coarse_cell* cells,
                               long outside, int contacts_valid);   /* host only */
 int lbmdem_set_coarse_output(lbmdem_handle* h, int cw, int ch);   /* 0, 0: off (default) */
+/* Flow fields: what people show of the fluid in a submerged collapse -- the composite velocity of fluid and grains, its vorticity
+ * and divergence, the model's own local strain rate (the non-equilibrium stress moments the MRT collision forms at every node and
+ * throws away, main.c:1095-1106), the shear rate and the viscous dissipation -- and the fluid's line of the energy budget, made
+ * where the state lies. The reference has no such routine, so the contract is exact arithmetic: IEEE double, no contraction, every
+ * expression associated as written here; a restatement over the downloads named below reproduces every value bit for bit. Lattice
+ * units throughout.
+ * Inputs, as of the call: f = lbmdem_download_f, obst = lbmdem_download_obst, x1 x2 v1 v2 v3 = lbmdem_download_kinematics,
+ * Mgx Mby = lbmdem_get_walls, dx c s8 s9 nbgrains = lbmdem_get_config. x, y are node indices converted to double.
+ * Per node (x, y) with o = obst[x][y] and fq = f[x][y][q]:
+ *   fluid (o == -1):        rho = (((((((f0 + f1) + f2) + f3) + f4) + f5) + f6) + f7) + f8          main.c:1082
+ *                           jx  = ((((f5 + f6) + f7) - f1) - f2) - f3                                main.c:1091
+ *                           jy  = ((((f1 + f8) + f7) - f3) - f4) - f5                                main.c:1093
+ *                           pxx = ((f2 - f4) + f6) - f8        pxy = (((-f1) + f3) - f5) + f7        main.c:1095-1096
+ *                           ux = jx / rho        uy = jy / rho
+ *                           nxx = pxx - ((jx * jx) - (jy * jy)) / rho        nxy = pxy - (jx * jy) / rho      main.c:1105-1106
+ *                           D = ((-1.5 * s8) * nxx) / rho        T = ((-3. * s9) * nxy) / rho
+ *                           gdot = sqrt((D * D) + (T * T))
+ *                           diss = rho * (((nu8 * D) * D) + ((nu9 * T) * T)),  nu8 = ((1. / s8) - 0.5) / 3., nu9 likewise with s9
+ *                           (formed once on the host)
+ *   grain (0 <= o < nbgrains, i = o): ux = (v1[i] - (((y * dx) + Mby) - x2[i]) * v3[i]) / c            main.c:974
+ *                           uy = (v2[i] + (((x * dx) + Mgx) - x1[i]) * v3[i]) / c                    main.c:975
+ *                           (the grain's present kinematics and the handle's present walls: a vibrating handle's moved Mgx enters)
+ *   anything else (the lattice-edge walls, o == nbgrains, among them): ux = uy = +0.0. A lid's speed (lbmdem_set_lid) is NOT
+ *                           represented: the plate's nodes show +0.0.
+ *   nxx, nxy, gdot, diss are +0.0 at every node that is not fluid.
+ *   For 1 <= x <= lx - 2 and 1 <= y <= ly - 2:
+ *                           vort = ((uy[x+1][y] - uy[x-1][y]) * 0.5) - ((ux[x][y+1] - ux[x][y-1]) * 0.5)
+ *                           div  = ((ux[x+1][y] - ux[x-1][y]) * 0.5) + ((uy[x][y+1] - uy[x][y-1]) * 0.5)
+ *   and +0.0 on the outer ring.
+ * D and T are the model's d(ux)/dx - d(uy)/dy and d(uy)/dx + d(ux)/dy: to first order the moments are
+ * nxx = -(2 / (3 s8)) rho (dx ux - dy uy) and nxy = -(1 / (3 s9)) rho (dx uy + dy ux); they need no stencil across a grain surface.
+ * To SI units: velocities x c (m/s); vort, div, D, T, gdot / dtLB (1/s), dtLB = dx / c (lbmdem_get_config); diss is rho nu S^2 per
+ * unit volume with rho in units of rho_moy (kg/m^3), nu in dx^2 / dtLB and the rates in 1 / dtLB, so
+ * diss_SI = diss * rho_moy * dx^2 / dtLB^3 = diss * rho_moy * c^3 / dx (W/m^3); a node's kinetic energy 0.5 rho u^2 times
+ * rho_moy * c^2 is J/m^3.
+ * Planes: every selected field is one [lx][ly] plane of doubles, y fastest (the host layout of obst); the planes follow each other
+ * in ascending bit order of the mask. count = (bits set in mask) * lx * ly.
+ *   lbmdem_flow_fields          copies the planes to the host. *count is always set; cap_doubles = 0 (out may be NULL) only reports it;
+ *                               a buffer of fewer doubles is refused with *count set. Synchronises.
+ *   lbmdem_flow_fields_device   writes the same planes into the caller's DEVICE memory (cap_doubles >= count, else refused) on the
+ *                               handle's stream and does not synchronise: the route for a torch tensor (data_ptr()); order through
+ *                               lbmdem_set_stream or lbmdem_sync.
+ *   lbmdem_flow_sums            over the fluid nodes only, sums8 = { n_fluid, sum rho, sum (0.5 * rho) * ((ux * ux) + (uy * uy)),
+ *                               sum diss, sum (0.5 * vort) * vort, max ((ux * ux) + (uy * uy)), max gdot, max |div| }. A node that
+ *                               is not fluid contributes +0.0. Order of additions, three levels, each a chain from +0.0: per lattice
+ *                               row x and block of 64 consecutive y (y / 64; the last block may be short) over y ascending; per row
+ *                               over its block sums ascending; over the row sums, x ascending. Maxima start from +0.0 and are
+ *                               order-free; n_fluid is an integer in a double. No atomics, nothing depends on launch order.
+ *                               Synchronises.
+ *   lbmdem_write_flow_files     host only, no handle, no device: <dir>/flow%.6i.vtk from five planes [lx][ly] of doubles -- the
+ *                               binary rectilinear-mesh format of the files lbmdem_write_vtk_fields writes (same header, mesh and
+ *                               CELL_DATA / POINT_DATA lines, big-endian float, x fastest), then "VECTORS fluid_velocity_lb float\n"
+ *                               with (float)ux, (float)uy, 0 per node, and "SCALARS <name> float\nLOOKUP_TABLE default\n" with the
+ *                               payload for vorticity (vort), shear_rate (gdot) and dissipation (diss), back to back. lx, ly >= 2.
+ *   lbmdem_write_flow           the same file of the handle's present state; the byte image is made on the device.
+ *   lbmdem_set_flow_output      on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_flow at every VTK event of a run with
+ *                               the fluid, with the event's nFile, after the frame, and at every DEM event, after the existing
+ *                               files, appends "%le" of nbsteps * dt and " %le" of the eight sums to <dir>/flow.data (a header line
+ *                               "# t n_fluid sum_rho sum_ke sum_diss sum_enstrophy max_u2 max_gdot max_abs_div" when the file is
+ *                               created). Synchronous. 0: off (the default); a checkpoint does not carry it.
+ * Everything is off by default: nothing is allocated or launched until a call asks for it; scratch comes from the handle's pool and
+ * goes with the handle. No call changes anything a later step reads.
+ * LBMDEM_EINVAL: a mask of 0 or with bits beyond LBMDEM_FLOW_ALL; null arguments; a short buffer; a strip of a decomposition or
+ * distributed grains (and lbmdem_dist_enable with the setting on); the single-precision library (lbmdem_write_flow_files works there
+ * too); a directory that cannot be written ("cannot open"). Vibrating, probing and lid handles have the export. */
+#define LBMDEM_FLOW_UX 1
+#define LBMDEM_FLOW_UY 2
+#define LBMDEM_FLOW_VORT 4
+#define LBMDEM_FLOW_DIV 8
+#define LBMDEM_FLOW_NXX 16
+#define LBMDEM_FLOW_NXY 32
+#define LBMDEM_FLOW_GDOT 64
+#define LBMDEM_FLOW_DISS 128
+#define LBMDEM_FLOW_ALL 255
+int lbmdem_flow_fields(lbmdem_handle* h, int mask, double* out, long cap_doubles, long* count);
+int lbmdem_flow_fields_device(lbmdem_handle* h, int mask, void* dev_out, long cap_doubles);
+int lbmdem_flow_sums(lbmdem_handle* h, double* sums8);
+int lbmdem_write_flow(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_write_flow_files(const char* dir, int nfile, int lx, int ly, const double* ux, const double* uy, const double* vort,
+                            const double* gdot, const double* diss);   /* host only */
+int lbmdem_set_flow_output(lbmdem_handle* h, int on);               /* 0: off (default) */
 /* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
  * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
  * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
