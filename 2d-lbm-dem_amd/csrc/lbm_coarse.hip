@@ -17,8 +17,10 @@
 // keys by bisection and walks it serially. A cell without grains writes zeros.
 // Double-precision library only: the entry points that take a handle refuse in the float build. Grid arithmetic and the file's
 // formatter are host code and exist in both.
+// Front end, as every export's: whole_handle(), SP_REFUSE() and reader_obst() (lbmdem_handle.h) for the refusals and the map,
+// MemPool::grow (lbm_mem.h) for the scratch kept on the handle, OutFile (lbm_outfile.h) for the file.
 #include "lbm_device.h"
-#include "lbmdem_handle.h"
+#include "lbm_outfile.h"
 
 #include <errno.h>
 
@@ -202,18 +204,8 @@ int sort_bits(unsigned ncells) {   // the keys are 0 .. ncells
 int coarse_stage(lbmdem_handle* h, long ncells, long ncol, int bits) {
   auto& S = h->cg;
   const int n = h->n;
-  if (S.cell_cap < ncells) {
-    h->mem.release(S.cells);
-    S.cells = nullptr; S.cell_cap = 0;
-    HIP_TRY(h->mem.dev(&S.cells, (size_t)ncells * CG_REC));
-    S.cell_cap = ncells;
-  }
-  if (S.col_cap < ncol) {
-    h->mem.release(S.col);
-    S.col = nullptr; S.col_cap = 0;
-    HIP_TRY(h->mem.dev(&S.col, (size_t)ncol));
-    S.col_cap = ncol;
-  }
+  HIP_TRY(h->mem.grow(&S.cells, &S.cell_cap, ncells * CG_REC));
+  HIP_TRY(h->mem.grow(&S.col, &S.col_cap, ncol));
   if (!S.keys[0]) {
     HIP_TRY(h->mem.dev(&S.keys[0], (size_t)n));
     HIP_TRY(h->mem.dev(&S.keys[1], (size_t)n));
@@ -223,12 +215,7 @@ int coarse_stage(lbmdem_handle* h, long ncells, long ncol, int bits) {
   }
   size_t bytes = 0;
   HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, S.keys[0], S.keys[1], S.idx[0], S.idx[1], n, 0, bits, h->stream));
-  if (S.sort_bytes < bytes || !S.sort_tmp) {
-    h->mem.release(S.sort_tmp);
-    S.sort_tmp = nullptr; S.sort_bytes = 0;
-    HIP_TRY(h->mem.dev(&S.sort_tmp, bytes));
-    S.sort_bytes = bytes;
-  }
+  HIP_TRY(h->mem.grow(&S.sort_tmp, &S.sort_bytes, (long)bytes));
   return LBMDEM_OK;
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
@@ -256,10 +243,9 @@ int lbmdem_write_coarse_files(const char* dir, int nfile, int lx, int ly, int cw
   if (!cells) return fail(LBMDEM_EINVAL, "null buffer");
   int ncx = 0, ncy = 0;
   RC_TRY(grid_of(lx, ly, cw, ch, &ncx, &ncy));
-  char path[4200];
-  snprintf(path, sizeof path, "%s/coarse%.6i.dat", (dir && *dir) ? dir : ".", nfile);
-  FILE* fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  OutFile F;
+  RC_TRY(F.open("w", dir, "coarse%.6i.dat", nfile));
+  FILE* fp = F.fp;
   fprintf(fp, "# cw %d ch %d ncx %d ncy %d outside %ld contacts %d\n", cw, ch, ncx, ncy, outside, contacts_valid);
   for (int cx = 0; cx < ncx; ++cx)
     for (int cy = 0; cy < ncy; ++cy) {
@@ -268,26 +254,21 @@ int lbmdem_write_coarse_files(const char* dir, int nfile, int lx, int ly, int cw
       for (int k = 0; k < CG_REC; ++k) fprintf(fp, " %le", v[k]);
       fprintf(fp, "\n");
     }
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
-  return LBMDEM_OK;
+  return F.close();
 }
 
 #ifdef LBMDEM_SINGLE_PRECISION
-#define COARSE_SP_REFUSAL(h) do { if (!(h)) return fail(LBMDEM_EINVAL, "null handle"); SP_UNAVAILABLE("the coarse-grained fields export"); } while (0)
-int lbmdem_coarse_fields(lbmdem_handle* h, int, int, lbmdem_coarse_cell*, long, long*, long*) { COARSE_SP_REFUSAL(h); }
-int lbmdem_write_coarse(lbmdem_handle* h, const char*, int, int, int) { COARSE_SP_REFUSAL(h); }
-int lbmdem_set_coarse_output(lbmdem_handle* h, int, int) { COARSE_SP_REFUSAL(h); }
+int lbmdem_coarse_fields(lbmdem_handle* h, int, int, lbmdem_coarse_cell*, long, long*, long*) { SP_REFUSE(h, "the coarse-grained fields export"); }
+int lbmdem_write_coarse(lbmdem_handle* h, const char*, int, int, int) { SP_REFUSE(h, "the coarse-grained fields export"); }
+int lbmdem_set_coarse_output(lbmdem_handle* h, int, int) { SP_REFUSE(h, "the coarse-grained fields export"); }
 #else
 
 int lbmdem_coarse_fields(lbmdem_handle* h, int cw, int ch, lbmdem_coarse_cell* out, long cap_cells, long* count, long* info2) try {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
   if (!count || !info2 || cap_cells < 0 || (cap_cells > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
+  RC_TRY(whole_handle(h, "lbmdem_coarse_fields"));
   const LatticeView& L = h->L;
-  if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
-    return fail(LBMDEM_EINVAL, "lbmdem_coarse_fields needs the whole lattice and all grains on this handle (not a strip of a "
-                               "decomposition, no distributed grains)");
   int ncx = 0, ncy = 0;
   RC_TRY(grid_of(L.lx, L.ly, cw, ch, &ncx, &ncy));
   const long ncells = (long)ncx * ncy;
@@ -299,7 +280,7 @@ int lbmdem_coarse_fields(lbmdem_handle* h, int cw, int ch, lbmdem_coarse_cell* o
   auto& S = h->cg;
   CoarseJob J{};
   J.f = h->f[h->fcur];
-  J.obst = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];   // (as lbmdem_download_obst, lbmdem_write_densities)
+  J.obst = reader_obst(h);
   J.L = L;
   J.L.gate = nullptr;
   J.rho_moy = (real)h->cfg.phys.rho_moy;
@@ -326,7 +307,7 @@ int lbmdem_coarse_fields(lbmdem_handle* h, int cw, int ch, lbmdem_coarse_cell* o
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_coarse_keys, dim3((n + CG_THREADS - 1) / CG_THREADS), dim3(CG_THREADS), 0, h->stream, J);
   HIP_TRY(hipGetLastError());
-  size_t bytes = S.sort_bytes;
+  size_t bytes = (size_t)S.sort_bytes;
   HIP_TRY(hipcub::DeviceRadixSort::SortPairs(S.sort_tmp, bytes, S.keys[0], S.keys[1], S.idx[0], S.idx[1], n, 0, bits, h->stream));
   J.keys = S.keys[1]; J.idx = S.idx[1];
   hipLaunchKernelGGL(k_coarse_grains, dim3(cell_blocks), dim3(CG_THREADS), 0, h->stream, J);
@@ -358,10 +339,7 @@ int lbmdem_set_coarse_output(lbmdem_handle* h, int cw, int ch) {
   if (!h) return fail(LBMDEM_EINVAL, "null handle");
   const bool on = cw != 0 || ch != 0;
   if (on && (cw < 1 || ch < 1)) return fail(LBMDEM_EINVAL, "a coarse cell must hold at least one node each way (cw = %d, ch = %d)", cw, ch);
-  const LatticeView& L = h->L;
-  if (on && (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist))
-    return fail(LBMDEM_EINVAL, "lbmdem_set_coarse_output needs the whole lattice and all grains on this handle (not a strip of a "
-                               "decomposition, no distributed grains)");
+  if (on) RC_TRY(whole_handle(h, "lbmdem_set_coarse_output"));
   h->coarse_cw = cw;
   h->coarse_ch = ch;
   return LBMDEM_OK;

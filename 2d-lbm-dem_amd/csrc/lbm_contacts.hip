@@ -15,7 +15,9 @@
 //   k_contacts_emit   the same evaluation once more; a record's slot is the workgroup's base + the records of the rounds and
 //                     wavefronts before + the lane's rank in its wavefront's ballot.
 // Double-precision library only: the other one's entry points refuse. The files' formatter is host code and exists in both.
-#include "lbmdem_handle.h"
+// Front end, as every export's: whole_handle() and SP_REFUSE() (lbmdem_handle.h) for the refusals, MemPool::grow (lbm_mem.h) for
+// the record buffer kept on the handle, OutFile (lbm_outfile.h) for the two files.
+#include "lbm_outfile.h"
 
 #include <errno.h>
 
@@ -188,10 +190,7 @@ __global__ __launch_bounds__(CT_THREADS) void k_contacts_emit(const ContactsJob 
 
 // what the export describes: the last sub-step, when it was a table sub-step
 int contacts_job(lbmdem_handle* h, const char* who, ContactsJob* J) {
-  const LatticeView& L = h->L;
-  if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
-    return fail(LBMDEM_EINVAL, "%s needs the whole lattice and all grains on this handle (not a strip of a decomposition, no "
-                               "distributed grains)", who);
+  RC_TRY(whole_handle(h, who));
   if (!h->contacts_valid || !h->verlet_ok)
     return fail(LBMDEM_EINVAL, "%s: the last sub-step was no table sub-step, or the state it started from has been replaced since "
                                "(lbmdem_set_diagnostics(h, 1), or the sub-step that reaches a multiple of 4000)", who);
@@ -235,12 +234,6 @@ int contacts_count(lbmdem_handle* h, const ContactsJob& J) {
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
 
-int close_file(FILE* fp, const char* path) {
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
-  return LBMDEM_OK;
-}
-
 }  // namespace
 
 #pragma GCC visibility push(default)
@@ -269,17 +262,15 @@ int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double*
     if (c[k].i < 0 || c[k].i >= n || (!wall && (c[k].j < 0 || c[k].j >= n)))
       return fail(LBMDEM_EINVAL, "lbmdem_write_contacts_files: record %ld names a grain outside [0, %d) or an unknown wall", k, n);
   }
-  char path[4200];
-  snprintf(path, sizeof path, "%s/contacts%.6i.dat", (dir && *dir) ? dir : ".", nfile);
-  FILE* fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  OutFile F;
+  RC_TRY(F.open("w", dir, "contacts%.6i.dat", nfile));
+  FILE* fp = F.fp;
   fprintf(fp, "# i j dn nx ny fn ft\n");
   for (long k = 0; k < count; ++k)
     fprintf(fp, "%d %d %le %le %le %le %le\n", c[k].i, c[k].j, c[k].dn, c[k].nx, c[k].ny, c[k].fn, c[k].ft);
-  RC_TRY(close_file(fp, path));
-  snprintf(path, sizeof path, "%s/DEM%.6i_chains.ps", (dir && *dir) ? dir : ".", nfile);
-  fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  RC_TRY(F.close());
+  RC_TRY(F.open("w", dir, "DEM%.6i_chains.ps", nfile));
+  fp = F.fp;
   lbmdem_ps_head(fp, n, x1, x2, r, fm, 1, lx, ly);
   for (long k = 0; k < count; ++k) {
     if (c[k].j < 0 || !(c[k].fn > 0)) continue;   // walls have no second centre; a line of width 0 is no chain
@@ -289,15 +280,14 @@ int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double*
     fprintf(fp, "%le %le moveto \n %le %le lineto\n", x1[i] * 10000, x2[i] * 10000, x1[j] * 10000, x2[j] * 10000);
     fprintf(fp, "stroke \n");
   }
-  return close_file(fp, path);
+  return F.close();
 }
 
 #ifdef LBMDEM_SINGLE_PRECISION
-#define CONTACTS_SP_REFUSAL(h) do { if (!(h)) return fail(LBMDEM_EINVAL, "null handle"); SP_UNAVAILABLE("the contact network export"); } while (0)
-int lbmdem_contact_stats(lbmdem_handle* h, long*) { CONTACTS_SP_REFUSAL(h); }
-int lbmdem_download_contacts(lbmdem_handle* h, lbmdem_contact*, long, long*) { CONTACTS_SP_REFUSAL(h); }
-int lbmdem_write_contacts(lbmdem_handle* h, const char*, int) { CONTACTS_SP_REFUSAL(h); }
-int lbmdem_set_contacts_output(lbmdem_handle* h, int) { CONTACTS_SP_REFUSAL(h); }
+int lbmdem_contact_stats(lbmdem_handle* h, long*) { SP_REFUSE(h, "the contact network export"); }
+int lbmdem_download_contacts(lbmdem_handle* h, lbmdem_contact*, long, long*) { SP_REFUSE(h, "the contact network export"); }
+int lbmdem_write_contacts(lbmdem_handle* h, const char*, int) { SP_REFUSE(h, "the contact network export"); }
+int lbmdem_set_contacts_output(lbmdem_handle* h, int) { SP_REFUSE(h, "the contact network export"); }
 #else
 
 int lbmdem_contact_stats(lbmdem_handle* h, long* counts6) try {
@@ -341,13 +331,8 @@ int lbmdem_download_contacts(lbmdem_handle* h, lbmdem_contact* out, long cap, lo
   if (cap == 0) return LBMDEM_OK;   // (how many there are)
   if (cap < total) return fail(LBMDEM_EINVAL, "lbmdem_download_contacts: there are %lld records, the buffer holds %ld", total, cap);
   if (total == 0) return LBMDEM_OK;
-  if (X.rec_cap < total) {   // grown with some room: the count moves a little from table to table
-    h->mem.release(X.rec);
-    X.rec = nullptr; X.rec_cap = 0;
-    const long want = (long)(total + total / 8 + 64);
-    HIP_TRY(h->mem.dev(&X.rec, (size_t)want));
-    X.rec_cap = want;
-  }
+  // grown with some room: the count moves a little from table to table
+  if (X.rec_cap < total) HIP_TRY(h->mem.grow(&X.rec, &X.rec_cap, (long)(total + total / 8 + 64)));
   J.counts = X.offsets;
   J.out = X.rec;
   J.cap = total;
@@ -382,10 +367,7 @@ int lbmdem_write_contacts(lbmdem_handle* h, const char* dir, int nfile) try {
 
 int lbmdem_set_contacts_output(lbmdem_handle* h, int on) {
   if (!h) return fail(LBMDEM_EINVAL, "null handle");
-  const LatticeView& L = h->L;
-  if (on && (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist))
-    return fail(LBMDEM_EINVAL, "lbmdem_set_contacts_output needs the whole lattice and all grains on this handle (not a strip of a "
-                               "decomposition, no distributed grains)");
+  if (on) RC_TRY(whole_handle(h, "lbmdem_set_contacts_output"));
   h->contacts_output = on != 0;
   return LBMDEM_OK;
 }

@@ -15,9 +15,11 @@
 // by the staging budget (lbmdem_set_densities_staging), whatever the lattice. If a single node is refused the whole file is
 // written by the host formatter (lbmdem_write_densities_host: the reference's loops, one fprintf per value) instead.
 // Double-precision library only: the entry points that take a handle refuse in the float build.
+// Front end, as every export's: whole_handle(), SP_REFUSE() and reader_obst() (lbmdem_handle.h) for the refusals and the map,
+// OutFile (lbm_outfile.h) for the two files -- closed together, with one text for the pair; the scratch is a call's own.
 #include "lbm_device.h"
+#include "lbm_outfile.h"
 #include "lbm_text.h"
-#include "lbmdem_handle.h"
 
 #ifndef LBMDEM_SINGLE_PRECISION
 #include <hipcub/hipcub.hpp>
@@ -174,13 +176,11 @@ struct DensPlan {
 };
 
 int dens_job(lbmdem_handle* h, const char* who, DensJob* J) {
+  RC_TRY(whole_handle(h, who));
   const LatticeView& L = h->L;
-  if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
-    return fail(LBMDEM_EINVAL, "%s needs the whole lattice and all grains on this handle (not a strip of a decomposition, no "
-                               "distributed grains)", who);
   *J = DensJob{};
   J->f = h->f[h->fcur];
-  J->obst = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];   // (as lbmdem_download_vtk_fields, lbmdem_download_obst)
+  J->obst = reader_obst(h);
   J->L = L;
   J->L.gate = nullptr;
   J->rho_moy = (real)h->cfg.phys.rho_moy;
@@ -373,32 +373,22 @@ void host_body(Sink& S, Sink* press, bool head, int lx, int ly, double rho_moy, 
 
 // the two files of one call, opened together (unlike the reference, fopen is checked)
 struct DensFiles {
-  FILE *vtk = nullptr, *press = nullptr;
-  char path[2][4300];
-  ~DensFiles() { if (vtk) fclose(vtk); if (press) fclose(press); }
+  OutFile vtk, press;
   int open(const char* dir, int nfile) {
-    const char* d = (dir && *dir) ? dir : ".";
-    snprintf(path[0], sizeof path[0], "%s/densities%.6i.vtk", d, nfile);
-    snprintf(path[1], sizeof path[1], "%s/pressure_base%.6i.dat", d, nfile);
-    vtk = fopen(path[0], "w");
-    if (!vtk) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path[0]);
-    press = fopen(path[1], "w");
-    if (!press) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path[1]);
-    return LBMDEM_OK;
+    RC_TRY(vtk.open("w", dir, "densities%.6i.vtk", nfile));
+    return press.open("w", dir, "pressure_base%.6i.dat", nfile);
   }
-  int close() {
-    bool bad = ferror(vtk) != 0 || ferror(press) != 0;
-    bad |= fclose(vtk) != 0; vtk = nullptr;
-    bad |= fclose(press) != 0; press = nullptr;
-    if (bad) return fail(LBMDEM_EINVAL, "writing '%s' or '%s' failed", path[0], path[1]);
+  int close() {   // (one text for the pair)
+    const bool bad_vtk = vtk.finish(), bad_press = press.finish();
+    if (bad_vtk || bad_press) return fail(LBMDEM_EINVAL, "writing '%s' or '%s' failed", vtk.path, press.path);
     return LBMDEM_OK;
   }
 };
 
 int write_host(DensFiles& F, int lx, int ly, double t, double rho_moy, const double* f, const int* obst, long* bytes2) {
   Sink S, Sp;
-  S.fp = F.vtk;
-  Sp.fp = F.press;
+  S.fp = F.vtk.fp;
+  Sp.fp = F.press.fp;
   put_head(S, lx, ly, t);
   host_body(S, &Sp, true, lx, ly, rho_moy, f, obst, bytes2);
   return F.close();
@@ -435,11 +425,10 @@ int lbmdem_format_fixed4(const double* v, long n, char* out, long cap, long* byt
 }
 
 #ifdef LBMDEM_SINGLE_PRECISION
-#define DENS_SP_REFUSAL(h) do { if (!(h)) return fail(LBMDEM_EINVAL, "null handle"); SP_UNAVAILABLE("write_densities"); } while (0)
-int lbmdem_write_densities(lbmdem_handle* h, const char*, int) { DENS_SP_REFUSAL(h); }
-int lbmdem_download_densities_text(lbmdem_handle* h, char*, size_t, size_t*) { DENS_SP_REFUSAL(h); }
-int lbmdem_set_densities_staging(lbmdem_handle* h, size_t) { DENS_SP_REFUSAL(h); }
-int lbmdem_densities_stats(lbmdem_handle* h, long*) { DENS_SP_REFUSAL(h); }
+int lbmdem_write_densities(lbmdem_handle* h, const char*, int) { SP_REFUSE(h, "write_densities"); }
+int lbmdem_download_densities_text(lbmdem_handle* h, char*, size_t, size_t*) { SP_REFUSE(h, "write_densities"); }
+int lbmdem_set_densities_staging(lbmdem_handle* h, size_t) { SP_REFUSE(h, "write_densities"); }
+int lbmdem_densities_stats(lbmdem_handle* h, long*) { SP_REFUSE(h, "write_densities"); }
 #else
 
 int lbmdem_set_densities_staging(lbmdem_handle* h, size_t bytes) {
@@ -478,8 +467,8 @@ int lbmdem_write_densities(lbmdem_handle* h, const char* dir, int nfile) try {
     return LBMDEM_OK;
   }
   Sink S, Sp;
-  S.fp = F.vtk;
-  Sp.fp = F.press;
+  S.fp = F.vtk.fp;
+  Sp.fp = F.press.fp;
   put_head(S, lx, ly, h->cfg.phys.t);
   const long long pbytes = P.section_bytes(0, ly);
   long long done = 0;

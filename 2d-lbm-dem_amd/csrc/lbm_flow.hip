@@ -18,8 +18,10 @@
 //                 LDS as k_vtk_frame's.
 // No atomics, nothing depends on launch order. Double-precision library only: the entry points that take a handle refuse in the
 // float build; the host-only file writer exists in both.
+// Front end, as every export's: whole_handle(), SP_REFUSE() and reader_obst() (lbmdem_handle.h) for the refusals and the map,
+// MemPool::grow (lbm_mem.h) for the scratch kept on the handle, OutFile (lbm_outfile.h) for the file.
 #include "lbm_device.h"
-#include "lbmdem_handle.h"
+#include "lbm_outfile.h"
 
 #include <errno.h>
 
@@ -245,29 +247,10 @@ __global__ __launch_bounds__(256) void k_flow_image(const double* __restrict__ p
     }
 }
 
-int flow_whole(const lbmdem_handle* h, const char* who) {
-  const LatticeView& L = h->L;
-  if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
-    return fail(LBMDEM_EINVAL, "%s needs the whole lattice and all grains on this handle (not a strip of a decomposition, no "
-                               "distributed grains)", who);
-  return LBMDEM_OK;
-}
-
 int popcount8(int mask) {
   int c = 0;
   for (int b = 0; b < FL_FIELDS; ++b) c += (mask >> b) & 1;
   return c;
-}
-
-// grows one block of the handle's pool
-template <class T>
-int flow_grow(lbmdem_handle* h, T** p, long* cap, long want) {
-  if (*cap >= want && *p) return LBMDEM_OK;
-  h->mem.release(*p);
-  *p = nullptr; *cap = 0;
-  HIP_TRY(h->mem.dev(p, (size_t)want));
-  *cap = want;
-  return LBMDEM_OK;
 }
 
 // the node kernel on the handle's stream: the planes of `mask` to dev_out (device memory), the partial sums when `sums`
@@ -276,7 +259,7 @@ int flow_launch(lbmdem_handle* h, int mask, double* dev_out, bool sums) {
   const long cnt = (long)L.lx * L.ly;
   FlowJob J{};
   J.f = h->f[h->fcur];
-  J.obst = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];   // (as lbmdem_download_obst)
+  J.obst = reader_obst(h);
   J.L = L;
   J.L.gate = nullptr;
   J.K = h->kin[h->kcur];
@@ -290,7 +273,7 @@ int flow_launch(lbmdem_handle* h, int mask, double* dev_out, bool sums) {
   J.part = nullptr;
   if (sums) {
     auto& S = h->fl;
-    RC_TRY(flow_grow(h, &S.part, &S.part_cap, (long)L.lx * J.nb * FL_SUMS + (long)L.lx * FL_SUMS));
+    HIP_TRY(h->mem.grow(&S.part, &S.part_cap, (long)L.lx * J.nb * FL_SUMS + (long)L.lx * FL_SUMS));
     if (!S.sums) HIP_TRY(h->mem.dev(&S.sums, (size_t)FL_SUMS));
     J.part = S.part;
   }
@@ -310,19 +293,12 @@ int flow_launch(lbmdem_handle* h, int mask, double* dev_out, bool sums) {
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
 
-int flow_file_open(const char* dir, int nfile, char* path, size_t pathlen, FILE** fp) {
-  snprintf(path, pathlen, "%s/flow%.6i.vtk", (dir && *dir) ? dir : ".", nfile);
-  *fp = fopen(path, "w+");
-  if (!*fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
-  return LBMDEM_OK;
-}
-
 // flow%.6i.vtk from the payloads in file byte order: [ly][lx][3] words of the vector, then three scalars [ly][lx]
 int flow_write_image(const char* dir, int nfile, int lx, int ly, const unsigned* image) {
   static const char* const NAMES[3] = {"vorticity", "shear_rate", "dissipation"};
-  char path[4200];
-  FILE* fp = nullptr;
-  RC_TRY(flow_file_open(dir, nfile, path, sizeof path, &fp));
+  OutFile F;
+  RC_TRY(F.open("w+", dir, "flow%.6i.vtk", nfile));
+  FILE* fp = F.fp;
   const size_t cnt = (size_t)lx * ly;
   lbmdem_vtk_put_mesh(fp, lx, ly);
   fprintf(fp, "VECTORS fluid_velocity_lb float\n");
@@ -331,9 +307,7 @@ int flow_write_image(const char* dir, int nfile, int lx, int ly, const unsigned*
     fprintf(fp, "SCALARS %s float\nLOOKUP_TABLE default\n", NAMES[k]);
     short_write = fwrite(image + (3 + k) * cnt, 4, cnt, fp) != cnt;
   }
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad || short_write) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
-  return LBMDEM_OK;
+  return F.close(short_write);
 }
 
 inline unsigned be_float(double v) {
@@ -369,18 +343,17 @@ int lbmdem_write_flow_files(const char* dir, int nfile, int lx, int ly, const do
 }
 
 #ifdef LBMDEM_SINGLE_PRECISION
-#define FLOW_SP_REFUSAL(h) do { if (!(h)) return fail(LBMDEM_EINVAL, "null handle"); SP_UNAVAILABLE("the flow fields export"); } while (0)
-int lbmdem_flow_fields(lbmdem_handle* h, int, double*, long, long*) { FLOW_SP_REFUSAL(h); }
-int lbmdem_flow_fields_device(lbmdem_handle* h, int, void*, long) { FLOW_SP_REFUSAL(h); }
-int lbmdem_flow_sums(lbmdem_handle* h, double*) { FLOW_SP_REFUSAL(h); }
-int lbmdem_write_flow(lbmdem_handle* h, const char*, int) { FLOW_SP_REFUSAL(h); }
-int lbmdem_set_flow_output(lbmdem_handle* h, int) { FLOW_SP_REFUSAL(h); }
+int lbmdem_flow_fields(lbmdem_handle* h, int, double*, long, long*) { SP_REFUSE(h, "the flow fields export"); }
+int lbmdem_flow_fields_device(lbmdem_handle* h, int, void*, long) { SP_REFUSE(h, "the flow fields export"); }
+int lbmdem_flow_sums(lbmdem_handle* h, double*) { SP_REFUSE(h, "the flow fields export"); }
+int lbmdem_write_flow(lbmdem_handle* h, const char*, int) { SP_REFUSE(h, "the flow fields export"); }
+int lbmdem_set_flow_output(lbmdem_handle* h, int) { SP_REFUSE(h, "the flow fields export"); }
 #else
 
 int lbmdem_flow_fields_device(lbmdem_handle* h, int mask, void* dev_out, long cap_doubles) try {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
-  RC_TRY(flow_whole(h, "lbmdem_flow_fields_device"));
+  RC_TRY(whole_handle(h, "lbmdem_flow_fields_device"));
   if (mask <= 0 || (mask & ~LBMDEM_FLOW_ALL)) return fail(LBMDEM_EINVAL, "lbmdem_flow_fields_device: bad mask %d", mask);
   if (!dev_out) return fail(LBMDEM_EINVAL, "null buffer");
   const long need = (long)popcount8(mask) * h->L.lx * h->L.ly;
@@ -394,7 +367,7 @@ int lbmdem_flow_fields_device(lbmdem_handle* h, int mask, void* dev_out, long ca
 int lbmdem_flow_fields(lbmdem_handle* h, int mask, double* out, long cap_doubles, long* count) try {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
-  RC_TRY(flow_whole(h, "lbmdem_flow_fields"));
+  RC_TRY(whole_handle(h, "lbmdem_flow_fields"));
   if (mask <= 0 || (mask & ~LBMDEM_FLOW_ALL)) return fail(LBMDEM_EINVAL, "lbmdem_flow_fields: bad mask %d", mask);
   if (!count || cap_doubles < 0 || (cap_doubles > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   const long need = (long)popcount8(mask) * h->L.lx * h->L.ly;
@@ -403,7 +376,7 @@ int lbmdem_flow_fields(lbmdem_handle* h, int mask, double* out, long cap_doubles
   if (cap_doubles < need)
     return fail(LBMDEM_EINVAL, "lbmdem_flow_fields: the planes are %ld doubles, the buffer holds %ld", need, cap_doubles);
   auto& S = h->fl;
-  RC_TRY(flow_grow(h, &S.planes, &S.planes_cap, need));
+  HIP_TRY(h->mem.grow(&S.planes, &S.planes_cap, need));
   RC_TRY(flow_launch(h, mask, S.planes, false));
   HIP_TRY(hipMemcpyAsync(out, S.planes, sizeof(double) * (size_t)need, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -415,7 +388,7 @@ int lbmdem_flow_fields(lbmdem_handle* h, int mask, double* out, long cap_doubles
 int lbmdem_flow_sums(lbmdem_handle* h, double* sums8) try {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
-  RC_TRY(flow_whole(h, "lbmdem_flow_sums"));
+  RC_TRY(whole_handle(h, "lbmdem_flow_sums"));
   if (!sums8) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(flow_launch(h, 0, nullptr, true));
   HIP_TRY(hipMemcpyAsync(sums8, h->fl.sums, sizeof(double) * FL_SUMS, hipMemcpyDeviceToHost, h->stream));
@@ -428,13 +401,13 @@ int lbmdem_flow_sums(lbmdem_handle* h, double* sums8) try {
 int lbmdem_write_flow(lbmdem_handle* h, const char* dir, int nfile) try {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
-  RC_TRY(flow_whole(h, "lbmdem_write_flow"));
+  RC_TRY(whole_handle(h, "lbmdem_write_flow"));
   if (!dir) return fail(LBMDEM_EINVAL, "null directory");
   const LatticeView& L = h->L;
   const long cnt = (long)L.lx * L.ly;
   auto& S = h->fl;
-  RC_TRY(flow_grow(h, &S.planes, &S.planes_cap, 5 * cnt));
-  RC_TRY(flow_grow(h, &S.image, &S.image_cap, FL_FILE_WORDS * cnt));
+  HIP_TRY(h->mem.grow(&S.planes, &S.planes_cap, 5 * cnt));
+  HIP_TRY(h->mem.grow(&S.image, &S.image_cap, FL_FILE_WORDS * cnt));
   RC_TRY(flow_launch(h, LBMDEM_FLOW_UX | LBMDEM_FLOW_UY | LBMDEM_FLOW_VORT | LBMDEM_FLOW_GDOT | LBMDEM_FLOW_DISS, S.planes, false));
   hipLaunchKernelGGL(k_flow_image, dim3((L.lx + IM_T - 1) / IM_T, (L.ly + IM_T - 1) / IM_T), dim3(256), 0, h->stream, S.planes, cnt,
                      L.lx, L.ly, S.image);
@@ -449,7 +422,7 @@ int lbmdem_write_flow(lbmdem_handle* h, const char* dir, int nfile) try {
 
 int lbmdem_set_flow_output(lbmdem_handle* h, int on) {
   if (!h) return fail(LBMDEM_EINVAL, "null handle");
-  if (on) RC_TRY(flow_whole(h, "lbmdem_set_flow_output"));
+  if (on) RC_TRY(whole_handle(h, "lbmdem_set_flow_output"));
   h->flow_output = on != 0;
   return LBMDEM_OK;
 }

@@ -16,8 +16,10 @@
 //   an exclusive scan of the cells in file order (hipcub::DeviceScan);
 //   k_links_emit   the links of every cell once more, stored at the scanned offsets.
 // Double-precision library only (the float build has no double checker for delta): its entry points refuse.
+// Front end, as every export's: whole_handle() and SP_REFUSE() (lbmdem_handle.h) for the refusals, OutFile (lbm_outfile.h) for
+// the three files; the scratch is a call's own (a local MemPool), nothing is kept on the handle.
 #include "lbm_device.h"
-#include "lbmdem_handle.h"
+#include "lbm_outfile.h"
 
 #include <type_traits>
 
@@ -190,10 +192,8 @@ __global__ __launch_bounds__(256) void k_links_emit(const LinksJob J) {
 
 // what the export describes: the map of the most recent rasterisation and the centres it was painted from
 int geometry_job(lbmdem_handle* h, const char* who, LinksJob* J) {
+  RC_TRY(whole_handle(h, who));
   const LatticeView& L = h->L;
-  if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
-    return fail(LBMDEM_EINVAL, "%s needs the whole lattice and all grains on this handle (not a strip of a decomposition, no "
-                               "distributed grains)", who);
   if (h->geo_buf < 0)
     return fail(LBMDEM_EINVAL, "%s: the centres of the last rasterisation are gone (the grains have moved on, or the map came from "
                                "a checkpoint): the export describes a map again after the next lbmdem_obst_construction or fluid step", who);
@@ -221,17 +221,13 @@ int links_count(lbmdem_handle* h, LinksJob J, unsigned char* act_dev, unsigned l
 #endif   // !LBMDEM_SINGLE_PRECISION
 
 int put_map(const char* dir, const char* name, int lx, int ly, const int* a) {
-  char path[4200];
-  snprintf(path, sizeof path, "%s/%s", (dir && *dir) ? dir : ".", name);
-  FILE* fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  OutFile F;
+  RC_TRY(F.open("w", dir, "%s", name));
   for (int y = 0; y < ly; y++) {   // main.c:1606-1612, 1619-1624
-    for (int x = 0; x < lx; x++) fprintf(fp, "%d ", a[(size_t)x * ly + y]);
-    fprintf(fp, "\n");
+    for (int x = 0; x < lx; x++) fprintf(F.fp, "%d ", a[(size_t)x * ly + y]);
+    fprintf(F.fp, "\n");
   }
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
-  return LBMDEM_OK;
+  return F.close();
 }
 
 }  // namespace
@@ -243,24 +239,19 @@ int lbmdem_write_obst_files(const char* dir, int lx, int ly, const int* obst, co
   if (!obst || !act || (n > 0 && !links) || n < 0 || lx < 1 || ly < 1) return fail(LBMDEM_EINVAL, "bad lbmdem_write_obst_files arguments");
   RC_TRY(put_map(dir, "obst_LB.dat", lx, ly, obst));
   RC_TRY(put_map(dir, "active_nodes.dat", lx, ly, act));
-  char path[4200];
-  snprintf(path, sizeof path, "%s/links.dat", (dir && *dir) ? dir : ".");
-  FILE* fp = fopen(path, "w");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  OutFile F;
+  RC_TRY(F.open("w", dir, "links.dat"));
   for (long k = 0; k < n; k++)   // main.c:1631-1639; the list is in that order already
-    if (links[k].delta != 0) fprintf(fp, "%d  %d  %d  %f\n", links[k].x, links[k].y, links[k].q < 0 ? -links[k].q : links[k].q, links[k].delta);
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
-  return LBMDEM_OK;
+    if (links[k].delta != 0) fprintf(F.fp, "%d  %d  %d  %f\n", links[k].x, links[k].y, links[k].q < 0 ? -links[k].q : links[k].q, links[k].delta);
+  return F.close();
 }
 
 #ifdef LBMDEM_SINGLE_PRECISION
-#define LINKS_SP_REFUSAL(h) do { if (!(h)) return fail(LBMDEM_EINVAL, "null handle"); SP_UNAVAILABLE("the boundary-link export"); } while (0)
-int lbmdem_geometry_stats(lbmdem_handle* h, long*) { LINKS_SP_REFUSAL(h); }
-int lbmdem_download_act(lbmdem_handle* h, int*) { LINKS_SP_REFUSAL(h); }
-int lbmdem_download_links(lbmdem_handle* h, lbmdem_link*, long, long*) { LINKS_SP_REFUSAL(h); }
-int lbmdem_download_geometry_obst(lbmdem_handle* h, int*) { LINKS_SP_REFUSAL(h); }
-int lbmdem_write_obst(lbmdem_handle* h, const char*) { LINKS_SP_REFUSAL(h); }
+int lbmdem_geometry_stats(lbmdem_handle* h, long*) { SP_REFUSE(h, "the boundary-link export"); }
+int lbmdem_download_act(lbmdem_handle* h, int*) { SP_REFUSE(h, "the boundary-link export"); }
+int lbmdem_download_links(lbmdem_handle* h, lbmdem_link*, long, long*) { SP_REFUSE(h, "the boundary-link export"); }
+int lbmdem_download_geometry_obst(lbmdem_handle* h, int*) { SP_REFUSE(h, "the boundary-link export"); }
+int lbmdem_write_obst(lbmdem_handle* h, const char*) { SP_REFUSE(h, "the boundary-link export"); }
 #else
 
 int lbmdem_geometry_stats(lbmdem_handle* h, long* counts6) try {

@@ -23,6 +23,17 @@ class MemPool {   // not copyable; not thread-safe: one owner thread at a time
   template <class T> hipError_t dev(T** p, size_t count) { return take((void**)p, sizeof(T) * count, false); }
   template <class T> hipError_t pinned(T** p, size_t count) { return take((void**)p, sizeof(T) * count, true); }
 
+  // A device block that is kept from call to call and only grows: nothing happens while *p holds `want` elements; otherwise the
+  // old block goes and one of exactly `want` elements comes (on failure *p is null and *cap 0). The caller chooses `want`.
+  template <class T> hipError_t grow(T** p, long* cap, long want) {
+    if (*p && *cap >= want) return hipSuccess;
+    release(*p);
+    *p = nullptr; *cap = 0;
+    const hipError_t e = dev(p, (size_t)want);
+    if (e == hipSuccess) *cap = want;
+    return e;
+  }
+
   // frees and forgets ONE block; null (and a pointer the pool does not know) is a no-op
   void release(const volatile void* p) {
     for (size_t k = blocks_.size(); p && k-- > 0;)

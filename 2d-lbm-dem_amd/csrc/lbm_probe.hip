@@ -4,6 +4,8 @@
 // handle's stream right after forces_fluid of a fluid step, one short launch per sample, into a ring of records on the
 // device. The host takes no part until lbmdem_probe_read. With the probes off (the default) nothing here is reached.
 // Double-precision library only: the float build refuses lbmdem_probe_enable.
+// Unlike the exports' front ends (whole_handle(), SP_REFUSE(), lbmdem_handle.h) it refuses a strip in words of its own and
+// only where it is switched on; its buffers are released by name (lbmdem_probe_disable) and it writes no file.
 #include "lbm_device.h"
 #include "lbmdem_handle.h"
 

@@ -539,7 +539,7 @@ int lbmdem_collide_stream(lbmdem_handle* h) try {
   CHECK_NOT_SPLIT(h);
   h->cs_prepared = false;   // (a lbmdem_collide_stream_prepare that no EDGES part followed)
   const int* ob_old = h->obst[h->ocur];
-  const int* ob_new = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
+  const int* ob_new = reader_obst(h);
   hipEvent_t e1 = nullptr;
   int rc = prof_begin(h, &e1);
   if (rc != LBMDEM_OK) return rc;
@@ -619,7 +619,7 @@ static int collide_stream_part_on_impl(lbmdem_handle* h, int part, hipStream_t s
     if (hi_begin < lo_end) hi_begin = lo_end;
     h->cs_fin = h->f[h->fcur];
     h->cs_ob_old = h->obst[h->ocur];
-    h->cs_ob_new = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
+    h->cs_ob_new = reader_obst(h);
     h->cs_lo_end = lo_end; h->cs_hi_begin = hi_begin;
     if (!h->cs_prepared) {   // (a caller that hands the part to another stream has prepared before its hand-over)
       if (st != h->stream) return fail(LBMDEM_EINVAL, "lbmdem_collide_stream_prepare comes before a part on another stream");
@@ -658,7 +658,7 @@ int lbmdem_forces_fluid(lbmdem_handle* h) {
   CHECK_H(h);
   PhaseRange range_("lbmdem:forces_fluid");
   CHECK_NOT_SPLIT(h);
-  const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
+  const int* ob = reader_obst(h);
   {
     const bool cut = h->cfg.x_begin > 0 || h->cfg.x_end < h->cfg.lx;
     const int need = 2 + (int)ceil(h->rmax / h->cfg.dx);
@@ -1412,7 +1412,7 @@ int lbmdem_download_obst(lbmdem_handle* h, int* obst) {
   CHECK_H(h);
   if (!obst) return fail(LBMDEM_EINVAL, "null buffer");
   const LatticeView& L = h->L;
-  const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
+  const int* ob = reader_obst(h);
   const int rows = L.xo1 - L.xo0;
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy2D(obst + (size_t)(L.gx0 + L.xo0) * L.ly, sizeof(int) * L.ly, ob + (size_t)L.xo0 * L.sy,

@@ -405,10 +405,7 @@ int lbmdem_set_checkpoint_every(lbmdem_handle* h, long every_substeps, const cha
   if (!h) return fail(LBMDEM_EINVAL, "null handle");
   if (every_substeps < 0) return fail(LBMDEM_EINVAL, "lbmdem_set_checkpoint_every: the cadence must be >= 0, not %ld", every_substeps);
   if (every_substeps > 0) {
-    const LatticeView& L = h->L;
-    if (L.xo0 != 0 || L.xo1 != L.lx || L.gx0 != 0 || h->dist)
-      return fail(LBMDEM_EINVAL, "lbmdem_set_checkpoint_every needs the whole lattice and all grains on this handle (not a strip of a "
-                                 "decomposition, no distributed grains): there every rank saves its own file with lbmdem_checkpoint_save");
+    RC_TRY(whole_handle(h, "lbmdem_set_checkpoint_every", "there every rank saves its own file with lbmdem_checkpoint_save"));
     if (!path || !*path || strlen(path) >= sizeof h->ckpt_path) return fail(LBMDEM_EINVAL, "lbmdem_set_checkpoint_every: no path, or one that is too long");
     strcpy(h->ckpt_path, path);
   }

@@ -225,13 +225,13 @@ struct lbmdem_handle {
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;
   struct CoarseStage {
-    double *cells = nullptr, *col = nullptr;   // [cell_cap][25] the records; [col_cap] column sums, [lx][7][ncy]
+    double *cells = nullptr, *col = nullptr;   // [cell_cap] the records, 25 doubles per cell; [col_cap] column sums, [lx][7][ncy]
     long cell_cap = 0, col_cap = 0;
     unsigned* keys[2] = {nullptr, nullptr};    // [n] the grains' cells, unsorted and sorted (null: nothing allocated yet)
     int* idx[2] = {nullptr, nullptr};          // [n] ... and their indices
     long long* outside = nullptr;              // [1]
     void* sort_tmp = nullptr;
-    size_t sort_bytes = 0;
+    long sort_bytes = 0;
   } cg;
   // Flow fields (lbm_flow.hip). flow_output: lbmdem_set_flow_output. fl: scratch, allocated by the first call that needs it, grown
   // when a call asks for more, freed with the handle.
@@ -379,11 +379,24 @@ static inline hipError_t d2h_real(double* dst, const real* src, size_t n, hipStr
 #else
 #define SP_UNAVAILABLE(what) do { } while (0)
 #endif
+// the whole body of an entry point that takes a handle and exists in the double build only (the float build's stub)
+#define SP_REFUSE(h, what) do { if (!(h)) return fail(LBMDEM_EINVAL, "null handle"); SP_UNAVAILABLE(what); } while (0)
 
 static inline GrainFluidView gview(const lbmdem_handle* h) {
   const Kin& K = h->kin[h->kcur];
   return GrainFluidView{K.x1, K.x2, K.v1, K.v2, K.v3, h->xc, h->yc, h->r2, h->rbl0, h->pk, h->mincov, h->paint_epoch};
 }
+// What an export, a frame or a cadence's setter says to a handle that does not hold everything -- a strip of a decomposition,
+// distributed grains -- in the name of the entry point `who`; `instead`: what the owner of such a handle calls in its place.
+static inline int whole_handle(const lbmdem_handle* h, const char* who, const char* instead = nullptr) {
+  const LatticeView& L = h->L;
+  if (L.xo0 == 0 && L.xo1 == L.lx && L.gx0 == 0 && !h->dist) return LBMDEM_OK;
+  return fail(LBMDEM_EINVAL, "%s needs the whole lattice and all grains on this handle (not a strip of a decomposition, no "
+                             "distributed grains)%s%s", who, instead ? ": " : "", instead ? instead : "");
+}
+// The obstacle map a reader should see: the one obst_construction has made for the coming fluid step where there is one, else
+// the one the last fluid step took (lbmdem_download_obst, the frames, every export of the fluid's fields).
+static inline const int* reader_obst(const lbmdem_handle* h) { return h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur]; }
 
 static inline DemParams dem_params_of(const lbmdem_config& c) {
   const lbmdem_physics& p = c.phys;

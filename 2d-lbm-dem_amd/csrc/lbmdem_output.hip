@@ -24,9 +24,8 @@ int lbmdem_download_vtk_fields(lbmdem_handle* h, float* grain_pressure, float* g
   float* tmp = nullptr;
   HIP_TRY(scratch.dev(&tmp, cnt * 11));
   float *d_gp = tmp, *d_gv = tmp + cnt, *d_ga = tmp + 4 * cnt, *d_fp = tmp + 7 * cnt, *d_fv = tmp + 8 * cnt;
-  const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
   const Kin& K = h->kin[h->kcur];
-  launch_vtk_fields(h->f[h->fcur], ob, L, h->gp, K.v1, K.v2, K.a1, K.a2, h->cfg.phys.rho_moy, d_gp, d_gv, d_ga,
+  launch_vtk_fields(h->f[h->fcur], reader_obst(h), L, h->gp, K.v1, K.v2, K.a1, K.a2, h->cfg.phys.rho_moy, d_gp, d_gv, d_ga,
                     d_fp, d_fv, h->stream);
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipMemcpy(grain_pressure, d_gp, sizeof(float) * cnt, hipMemcpyDeviceToHost));
@@ -700,21 +699,14 @@ static int output_stats_of(lbmdem_handle* h, int kind, long* counts4, double* ms
   return LBMDEM_OK;
 }
 
-#define CHECK_WHOLE_LATTICE_OR(h, who, instead)                                                                        \
-  do {                                                                                                                 \
-    const LatticeView& L_ = (h)->L;                                                                                    \
-    if (L_.xo0 != 0 || L_.xo1 != L_.lx || L_.gx0 != 0 || (h)->dist)                                                    \
-      return fail(LBMDEM_EINVAL, who " needs the whole lattice and all grains on this handle (not a strip of a "       \
-                                     "decomposition, no distributed grains): " instead);                               \
-  } while (0)
-#define CHECK_WHOLE_LATTICE(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "use lbmdem_comm_write_vtk there")
-#define CHECK_WHOLE_TABLE(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "there rank 0 writes the tables with lbmdem_write_dem")
-#define CHECK_WHOLE_CKPT(h, who) CHECK_WHOLE_LATTICE_OR(h, who, "there every rank saves its own file with lbmdem_checkpoint_save")
+// whole_handle()'s `instead`: what the owner of a strip or of distributed grains calls for a frame, a table, a checkpoint
+#define FRAME_THERE "use lbmdem_comm_write_vtk there"
+#define TABLE_THERE "there rank 0 writes the tables with lbmdem_write_dem"
+#define CKPT_THERE "there every rank saves its own file with lbmdem_checkpoint_save"
 
 static void launch_frame(lbmdem_handle* h, void* image_dev) {
-  const int* ob = h->obst_pending ? h->obst[1 - h->ocur] : h->obst[h->ocur];
   const Kin& K = h->kin[h->kcur];
-  launch_vtk_frame(h->f[h->fcur], ob, h->L, h->gp, K.v1, K.v2, K.a1, K.a2, h->cfg.phys.rho_moy, image_dev, h->stream);
+  launch_vtk_frame(h->f[h->fcur], reader_obst(h), h->L, h->gp, K.v1, K.v2, K.a1, K.a2, h->cfg.phys.rho_moy, image_dev, h->stream);
 }
 
 size_t lbmdem_vtk_image_bytes(int lx, int ly) { return (lx > 0 && ly > 0) ? (size_t)44 * lx * ly : 0; }
@@ -730,7 +722,7 @@ int lbmdem_download_vtk_image(lbmdem_handle* h, void* image_be) {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
   if (!image_be) return fail(LBMDEM_EINVAL, "null buffer");
-  CHECK_WHOLE_LATTICE(h, "lbmdem_download_vtk_image");
+  RC_TRY(whole_handle(h, "lbmdem_download_vtk_image", FRAME_THERE));
   const size_t bytes = lbmdem_vtk_image_bytes(h->L.lx, h->L.ly);
   MemPool scratch;
   void* tmp = nullptr;
@@ -748,7 +740,7 @@ int lbmdem_set_async_output(lbmdem_handle* h, int frames) {
   CHECK_H(h);
   if (frames < 0 || frames > LBMDEM_ASYNC_MAX_FRAMES)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_output: frames must be 0..%d, not %d", LBMDEM_ASYNC_MAX_FRAMES, frames);
-  if (frames > 0) CHECK_WHOLE_LATTICE(h, "lbmdem_set_async_output");
+  if (frames > 0) RC_TRY(whole_handle(h, "lbmdem_set_async_output", FRAME_THERE));
   return lane_resize(h, ASYNC_FRAME, frames, lbmdem_vtk_image_bytes(h->L.lx, h->L.ly), "lbmdem_set_async_output", "frame");
 }
 
@@ -757,7 +749,7 @@ int lbmdem_write_vtk_async(lbmdem_handle* h, const char* dir, int nfile) {
   AsyncOut* a = h->aout;
   if (!async_frames_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: async output is off (lbmdem_set_async_output)");
   CHECK_NOT_SPLIT(h);
-  CHECK_WHOLE_LATTICE(h, "lbmdem_write_vtk_async");
+  RC_TRY(whole_handle(h, "lbmdem_write_vtk_async", FRAME_THERE));
   RC_TRY(lbmdem_async_report(h));   // an earlier frame's failure: this call queues nothing
   const char* d = (dir && *dir) ? dir : ".";
   if (strlen(d) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_write_vtk_async: directory name too long");
@@ -837,7 +829,7 @@ int lbmdem_set_async_dem(lbmdem_handle* h, int slots) {
   CHECK_H(h);
   if (slots < 0 || slots > LBMDEM_ASYNC_MAX_DEM)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_dem: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_DEM, slots);
-  if (slots > 0) CHECK_WHOLE_TABLE(h, "lbmdem_set_async_dem");
+  if (slots > 0) RC_TRY(whole_handle(h, "lbmdem_set_async_dem", TABLE_THERE));
   return lane_resize(h, ASYNC_TABLE, slots, sizeof(double) * LBMDEM_DEM_ROW_DOUBLES * (size_t)h->n, "lbmdem_set_async_dem", "table");
 #endif
 }
@@ -848,7 +840,7 @@ int lbmdem_write_dem_async(lbmdem_handle* h, const char* dir, int nfile, int wit
   CHECK_H(h);   // (a launch of k_dem_chain that gave up is undone and replayed here: the table is the confirmed one)
   if (!async_dem_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_write_dem_async: tables in the background are off (lbmdem_set_async_dem)");
   AsyncOut* a = h->aout;
-  CHECK_WHOLE_TABLE(h, "lbmdem_write_dem_async");
+  RC_TRY(whole_handle(h, "lbmdem_write_dem_async", TABLE_THERE));
   CHECK_TABLE(h);
   RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
   const char* d = (dir && *dir) ? dir : ".";
@@ -894,7 +886,7 @@ int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots) {
   CHECK_H(h);
   if (slots < 0 || slots > LBMDEM_ASYNC_MAX_CKPT)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_checkpoint: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_CKPT, slots);
-  if (slots > 0) CHECK_WHOLE_CKPT(h, "lbmdem_set_async_checkpoint");
+  if (slots > 0) RC_TRY(whole_handle(h, "lbmdem_set_async_checkpoint", CKPT_THERE));
   const CkptLayout Y = ckpt_layout(h->n, h->V.cap, h->L.plane);   // (the same whenever it is asked for: none of the three changes)
   const int rc = lane_resize(h, ASYNC_CKPT, slots, Y.total, "lbmdem_set_async_checkpoint", "checkpoint");
   if (async_ckpt_on(h)) h->aout->ckpt_layout = Y;
@@ -909,7 +901,7 @@ int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
   if (!async_ckpt_on(h)) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: checkpoints in the background are off (lbmdem_set_async_checkpoint)");
   AsyncOut* a = h->aout;
   CHECK_NOT_SPLIT(h);
-  CHECK_WHOLE_CKPT(h, "lbmdem_checkpoint_save_async");
+  RC_TRY(whole_handle(h, "lbmdem_checkpoint_save_async", CKPT_THERE));
   if (!path || !*path) return fail(LBMDEM_EINVAL, "null path");
   if (strlen(path) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: path too long");
   if (h->obst_pending) return fail(LBMDEM_EINVAL, "checkpoint between obst_construction and collide_stream");

@@ -6,7 +6,7 @@
 // lbmdem_set_checkpoint_every has one more stop that is no event of the schedule: the step counters that are multiples of its
 // cadence, where the loop saves a checkpoint behind whatever else that sub-step brings.
 
-#include "lbmdem_handle.h"
+#include "lbm_outfile.h"
 
 #include <limits.h>
 #include <time.h>
@@ -109,17 +109,14 @@ int lbmdem_scene_schedule(const lbmdem_config* cfg, long nbsteps0, long n, doubl
 static int flow_data_line(lbmdem_handle* h, const char* dir) {
   double s[8];
   RC_TRY(lbmdem_flow_sums(h, s));
-  char path[4200];
-  snprintf(path, sizeof path, "%s/flow.data", *dir ? dir : ".");
-  FILE* fp = fopen(path, "a");
-  if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
+  OutFile F;
+  RC_TRY(F.open("a", dir, "flow.data"));
+  FILE* fp = F.fp;
   if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0) fprintf(fp, "# t n_fluid sum_rho sum_ke sum_diss sum_enstrophy max_u2 max_gdot max_abs_div\n");
   fprintf(fp, "%le", h->nbsteps * h->cfg.dt);
   for (int k = 0; k < 8; ++k) fprintf(fp, " %le", s[k]);
   fprintf(fp, "\n");
-  const bool bad = ferror(fp) != 0;
-  if (fclose(fp) != 0 || bad) return fail(LBMDEM_EINVAL, "writing '%s' failed", path);
-  return LBMDEM_OK;
+  return F.close();
 }
 
 static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbmdem_scene* sc, lbmdem_scene_result* res) {
