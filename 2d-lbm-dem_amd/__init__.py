@@ -547,9 +547,12 @@ class LbmDem:
     >>> f = sim.f            # [lx][ly][9], the reference's host layout
     """
 
-    def __init__(self, lx, ly, r, x1, x2, scale=1.0, device=0, strip=None, halo=0, physics=None, precision="f64"):
+    def __init__(self, lx, ly, r, x1, x2, scale=1.0, device=0, strip=None, halo=0, physics=None, precision="f64",
+                 origin=None):
         """precision "f32": the float build of the library (the reference's -DSINGLE_PRECISION mode, main.c:34-40): same
-        methods, host arrays stay float64 (holding float values); step path and state transfers only."""
+        methods, host arrays stay float64 (holding float values); step path and state transfers only.
+        origin = (Mgx, Mby): the left and bottom walls of the config handed to lbmdem_create, where the reference's
+        initialisation has 0, 0 (a restart of a shaken box finds its left wall off zero the same way)."""
         L = load_library(precision)
         self._L = L
         self.precision = precision
@@ -564,6 +567,8 @@ class LbmDem:
         cfg.device = int(device)
         if strip is not None:
             cfg.x_begin, cfg.x_end, cfg.halo = int(strip[0]), int(strip[1]), int(halo)
+        if origin is not None:
+            cfg.Mgx, cfg.Mby = float(origin[0]), float(origin[1])
         self.cfg = cfg
         self.lx, self.ly, self.n = int(lx), int(ly), len(r)
         _chk(L.lbmdem_create(C.byref(cfg), _vp(r), _vp(x1), _vp(x2), C.byref(self._h)))

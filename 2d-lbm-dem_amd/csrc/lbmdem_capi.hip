@@ -425,9 +425,17 @@ int lbmdem_create(const lbmdem_config* cfg, const double* r, const double* x1, c
   }
   // Verlet grid over the fluid domain; grains outside are clamped into the edge cells
   {
-    // (cell edge: the float build's cell coordinates carry a relative error of ~1e-7; a hair more keeps every partner
-    // within the 3 x 3 cells that are scanned)
-    const double cs = (2 * rmax + p.distVerlet) * (sizeof(real) == 4 ? 1.001 : 1.0);
+    // Cell edge: a hair more than the widest candidate distance D = 2 rmax + distVerlet, in both precisions, so that the
+    // 3 x 3 cells that are scanned hold every partner whatever the roundings do. With u the unit roundoff of `real`:
+    //  * the candidate test (three roundings, main.c:1529) accepts no pair with |xi - xj| > D (1 + 4u);
+    //  * a cell coordinate floor((x - o) / cs) is taken from a quotient with two roundings, off by at most 2.01 u |q|,
+    //    |q| <= nc + 2 for a grain within reach of the grid (farther out both partners are clamped into one edge cell),
+    //    so two grains whose cells are two apart have |xi - xj| > cs (1 - 4.1 u (nc + 2)).
+    // With cs = 1.001 D the second exceeds the first while 4.1 u (nc + 3) < 9.9e-4: 2e12 cells across in double, 4000 in
+    // float (8192 nodes of 0.1 mm hold 630 cells of the smallest edge, 1.3 mm at the reference's radii). An edge of exactly
+    // D, as the double build had, loses pairs at the candidate test's equality: with the origin off zero about 1 in 10^4
+    // of the placements aimed at a cell boundary, with the origin at zero about 1 in 2 10^5 (tests/test_verlet_host.py).
+    const double cs = (2 * rmax + p.distVerlet) * 1.001;
     const double wx = cfg->dx * (cfg->lx - 1), wy = cfg->dx * (cfg->ly - 1);
     if (verlet_alloc(mem, h->V, n, cs, cfg->Mgx, cfg->Mby, wx, wy) != 0) return fail(LBMDEM_ENOMEM, "verlet_alloc failed");
   }
