@@ -187,6 +187,15 @@ def _open_library(LIB_PATH):
     L.lbmdem_write_flow.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_write_flow_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
     L.lbmdem_set_flow_output.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_tracer_set.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_int]
+    L.lbmdem_tracer_advance.argtypes = [C.c_void_p]
+    L.lbmdem_tracer_download.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_tracer_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.lbmdem_tracer_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_tracer_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_write_tracers.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_write_tracers_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_void_p]
+    L.lbmdem_set_tracer_output.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
@@ -395,6 +404,30 @@ def write_flow_files(directory, nFile, ux, uy, vort, gdot, diss, precision="f64"
         raise LbmDemError(-1, "write_flow_files: five planes of one shape (lx, ly)")
     lx, ly = planes[0].shape
     _chk(load_library(precision).lbmdem_write_flow_files(os.fsencode(directory), int(nFile), lx, ly, *(_vp(p) for p in planes)))
+
+
+TRACER_COUNTERS = ("tracers", "advances", "hook_advances")   # LbmDem.tracer_stats
+
+
+def write_tracers_files(directory, nFile, lx, xy, uvo, precision="f64"):
+    """tracers%.6i.vtk, legacy binary POLYDATA, from positions (n, 2) in node coordinates and their sample (n, 3) U, V, owner:
+    one vertex per tracer at the coordinates of the frames' mesh ((float)px * (float)(1 / lx), ...), the point data
+    tracer_velocity_lb and tracer_owner. n = 0 writes a valid empty file. Host only."""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    uvo = np.ascontiguousarray(uvo, dtype=np.float64).reshape(-1, 3)
+    if len(xy) != len(uvo):
+        raise LbmDemError(-1, "write_tracers_files: positions (n, 2) and their sample (n, 3)")
+    n = len(xy)
+    _chk(load_library(precision).lbmdem_write_tracers_files(os.fsencode(directory), int(nFile), int(lx), n,
+                                                            _vp(xy) if n else None, _vp(uvo) if n else None))
+
+
+class _DeviceBlock:
+    """a block of float64 device memory as torch.as_tensor reads it (the CUDA array interface): a view, nothing is copied"""
+
+    def __init__(self, ptr, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
 
 
 def write_densities_host(directory, nFile, f, obst, t=0.0, rho_moy=1000.0):
@@ -881,6 +914,66 @@ class LbmDem:
         """run_scene writes flow%.6i.vtk at every VTK event, after the frame, and appends a line of flow_sums to flow.data at
         every DEM event"""
         _chk(self._L.lbmdem_set_flow_output(self._h, 1 if on else 0))
+
+    # fluid tracers: massless particles carried by the composite velocity, one midpoint step per fluid step, on the device
+
+    def set_tracers(self, xy, automatic=True):
+        """n tracers at xy, (n, 2) node coordinates inside [0, lx - 1] x [0, ly - 1], replacing an earlier set; an empty array
+        frees it. automatic: every fluid step advances them once, behind its force kernels; else only advance_tracers does."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64)
+        if xy.size == 0:
+            xy = xy.reshape(0, 2)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise LbmDemError(-1, "set_tracers: positions of shape (n, 2)")
+        _chk(self._L.lbmdem_tracer_set(self._h, len(xy), _vp(xy) if len(xy) else None, 1 if automatic else 0))
+
+    def advance_tracers(self):
+        """one advance in the present state, on the handle's stream (no synchronisation)"""
+        _chk(self._L.lbmdem_tracer_advance(self._h))
+
+    @property
+    def tracers(self):
+        """the positions, (n, 2)"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_tracer_download(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 2), np.float64)
+        if n.value:
+            _chk(self._L.lbmdem_tracer_download(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def tracer_sample(self):
+        """(n, 3): the interpolated velocity U, V at every tracer and the owner of its nearest node"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_tracer_sample(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 3), np.float64)
+        if n.value:
+            _chk(self._L.lbmdem_tracer_sample(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def tracer_stats(self):
+        """{tracers, advances since set_tracers, hook_advances: those of them made by fluid steps}"""
+        c = np.zeros(3, np.int64)
+        _chk(self._L.lbmdem_tracer_stats(self._h, _vp(c)))
+        return dict(zip(TRACER_COUNTERS, (int(v) for v in c)))
+
+    def tracers_tensor(self):
+        """the device buffer of the positions as a torch.float64 CUDA tensor (n, 2): a view, no copy -- an advance shows in it
+        once the handle's stream has got there (sync()). Valid until the next set_tracers."""
+        import torch
+        p = C.c_void_p(None)
+        _chk(self._L.lbmdem_tracer_device(self._h, C.byref(p)))
+        n = self.tracer_stats()["tracers"]
+        if not p.value or n == 0:
+            return torch.empty((0, 2), dtype=torch.float64, device=f"cuda:{self.cfg.device}")
+        return torch.as_tensor(_DeviceBlock(p.value, (n, 2)), device=f"cuda:{self.cfg.device}")
+
+    def write_tracers(self, directory=".", nFile=0):
+        """tracers%.6i.vtk of the present positions (write_tracers_files applied to tracers and tracer_sample)"""
+        _chk(self._L.lbmdem_write_tracers(self._h, os.fsencode(directory), int(nFile)))
+
+    def set_tracer_output(self, on=True):
+        """run_scene writes tracers%.6i.vtk at every VTK event, after the frame and the flow file"""
+        _chk(self._L.lbmdem_set_tracer_output(self._h, 1 if on else 0))
 
     def write_densities(self, directory=".", nFile=0):
         """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""

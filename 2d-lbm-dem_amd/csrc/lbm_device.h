@@ -75,6 +75,33 @@ __device__ __forceinline__ real wall_uy(const LatticeView& L, const GP& g, int x
   return g.v2 + (x * L.dx + L.Mgx - g.x1) * g.v3;
 }
 
+// The composite velocity of node (x, y) of a whole lattice whose owner `o` = obst[x][y] has been read (the flow-fields block of
+// include/lbmdem_hip.h): a fluid node's j / rho from its nine populations, a grain's rigid-body velocity at the node over c, +0.0
+// anywhere else (the lattice-edge walls). The populations are read only where the node is fluid and are left in `f` for the
+// caller (the flow fields take the stress moments from them); a grain node costs five kinematics loads instead. ONE copy of the
+// formulas for the flow fields (lbm_flow.hip) and the tracers (lbm_tracers.hip).
+struct NodeVel { double ux, uy, rho, jx, jy; int fluid; };
+__device__ __forceinline__ NodeVel node_vel(const real* __restrict__ fl, int o, const LatticeView& L, const Kin& K, int x, int y,
+                                            real (&f)[9]) {
+  NodeVel V{0., 0., 0., 0., 0., 0};
+  if (o == -1) {
+    const long node = (long)x * L.sy + y;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) f[q] = fl[fidx(q, node)];
+    V.rho = f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7] + f[8];   // main.c:1082
+    V.jx = f[5] + f[6] + f[7] - f[1] - f[2] - f[3];                         // main.c:1091
+    V.jy = f[1] + f[8] + f[7] - f[3] - f[4] - f[5];                         // main.c:1093
+    V.ux = V.jx / V.rho;
+    V.uy = V.jy / V.rho;
+    V.fluid = 1;
+  } else if (o >= 0 && o < L.n) {   // wall_ux, wall_uy (main.c:974-975) over c
+    const real x1 = K.x1[o], x2 = K.x2[o], v1 = K.v1[o], v2 = K.v2[o], v3 = K.v3[o];
+    V.ux = (v1 - (y * L.dx + L.Mby - x2) * v3) / L.c;
+    V.uy = (v2 + (x * L.dx + L.Mgx - x1) * v3) / L.c;
+  }
+  return V;
+}
+
 // main.c:1082-1116, in registers
 __device__ __forceinline__ void mrt_collide(const LatticeView& L, real (&f)[9]) {
   const real a = 1. / 36;

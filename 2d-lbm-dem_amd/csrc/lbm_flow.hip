@@ -57,25 +57,12 @@ struct FlowVel { double ux, uy, rho, jx, jy, pxx, pxy; int fluid; };
 
 __device__ __forceinline__ FlowVel flow_vel(const FlowJob& J, int x, int y) {
   const LatticeView& L = J.L;
-  FlowVel V{0., 0., 0., 0., 0., 0., 0., 0};
-  const long node = (long)x * L.sy + y;
-  const int o = J.obst[node];
-  if (o == -1) {
-    real f[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) f[q] = J.f[fidx(q, node)];
-    V.rho = f[0] + f[1] + f[2] + f[3] + f[4] + f[5] + f[6] + f[7] + f[8];   // main.c:1082
-    V.jx = f[5] + f[6] + f[7] - f[1] - f[2] - f[3];                         // main.c:1091
-    V.jy = f[1] + f[8] + f[7] - f[3] - f[4] - f[5];                         // main.c:1093
-    V.pxx = f[2] - f[4] + f[6] - f[8];                                      // main.c:1095
-    V.pxy = -f[1] + f[3] - f[5] + f[7];                                     // main.c:1096
-    V.ux = V.jx / V.rho;
-    V.uy = V.jy / V.rho;
-    V.fluid = 1;
-  } else if (o >= 0 && o < L.n) {   // the grain's rigid-body velocity at the node: wall_ux, wall_uy (main.c:974-975) over c
-    const real x1 = J.K.x1[o], x2 = J.K.x2[o], v1 = J.K.v1[o], v2 = J.K.v2[o], v3 = J.K.v3[o];
-    V.ux = (v1 - (y * L.dx + L.Mby - x2) * v3) / L.c;
-    V.uy = (v2 + (x * L.dx + L.Mgx - x1) * v3) / L.c;
+  real f[9];
+  const NodeVel N = node_vel(J.f, J.obst[(long)x * L.sy + y], L, J.K, x, y, f);   // (lbm_device.h: shared with the tracers)
+  FlowVel V{N.ux, N.uy, N.rho, N.jx, N.jy, 0., 0., N.fluid};
+  if (N.fluid) {
+    V.pxx = f[2] - f[4] + f[6] - f[8];        // main.c:1095
+    V.pxy = -f[1] + f[3] - f[5] + f[7];       // main.c:1096
   }
   return V;
 }

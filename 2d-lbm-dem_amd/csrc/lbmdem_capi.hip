@@ -709,6 +709,7 @@ int lbmdem_forces_fluid(lbmdem_handle* h) {
     launch_forces_fast(h->f[h->fcur], ob, h->L, gview(h), h->fscale12, h->fscale3, h->fhf, h->owner, h->stream);
   HIP_TRY(hipGetLastError());
   if (h->probe.on) RC_TRY(lbmdem_probe_sample(h, ob));   // lbmdem_probe_enable: the sample of this fluid step
+  if (h->tracers.n > 0 && h->tracers.automatic) RC_TRY(lbmdem_tracer_launch(h, ob, true));   // lbmdem_tracer_set: this fluid step's advance
   return LBMDEM_OK;
 }
 
@@ -1156,6 +1157,7 @@ static ChainSnap chain_snapshot(const lbmdem_handle* h) {
   s.nbsteps = h->nbsteps; s.Mdx = h->cfg.Mdx; s.Mhy = h->cfg.Mhy;
   s.Mgx = h->cfg.Mgx; s.t = h->cfg.phys.t;
   s.probe_seen = h->probe.seen; s.probe_issued = h->probe.issued;
+  s.tracer_advances = h->tracers.advances; s.tracer_hook = h->tracers.hook;
   return s;
 }
 
@@ -1173,6 +1175,10 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   // the samples issued behind the failed launch found the stop word: the ring holds what it held (chain_settle_impl sets its
   // device counters to match), and the fluid steps since are counted again when they are repeated
   h->probe.seen = s.probe_seen; h->probe.issued = s.probe_issued;
+  // likewise the tracers: the advances behind the failed launch left the positions alone. The snapshot of a period is taken
+  // after that period's fluid step (run_steps: lbmdem_lbm_step, then lbmdem_dem_chain) and the replay starts behind it
+  // (`resumed`), so no fluid step's advance is made twice
+  h->tracers.advances = s.tracer_advances; h->tracers.hook = s.tracer_hook;
   // what the failed launch may have written on its way: slices of the next map's canvas, and -- by the tiles that did
   // finish -- their discs, in place. The map the next fluid step paints starts from a clean canvas again.
   const int b = 1 - s.ocur;

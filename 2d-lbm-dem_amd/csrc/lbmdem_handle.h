@@ -56,6 +56,17 @@ struct ChainSnap {
   double Mdx, Mhy;
   double Mgx, t;   // a vibrating handle's side wall and clock (lbmdem_set_vibration): with nbsteps, where its schedule stands
   long probe_seen, probe_issued;   // the probe recorder's counts (ProbeState): the ring's write and drop counters follow from them
+  long tracer_advances, tracer_hook;   // the tracers' counts (TracerState): the advances behind a failed launch did nothing
+};
+
+// Fluid tracers (lbmdem_tracer_*, lbm_tracers.hip). Nothing is allocated or launched while n == 0.
+struct TracerState {
+  long n = 0;
+  bool automatic = false;     // every fluid step advances the set once (lbmdem_forces_fluid, behind the probe sample)
+  double* xy = nullptr;       // device [n][2]: px, py in node coordinates, updated in place
+  double* uvo = nullptr;      // device [uvo_cap] scratch of lbmdem_tracer_sample and lbmdem_write_tracers: [n][3] U, V, owner
+  long uvo_cap = 0;
+  long advances = 0, hook = 0;   // advances made since lbmdem_tracer_set; those of them the fluid steps made
 };
 
 // The probe recorder (lbmdem_probe_*, lbm_probe.hip). Off unless lbmdem_probe_enable has set it up.
@@ -292,6 +303,8 @@ struct lbmdem_handle {
   int chain_giveup_at = -1;    // (experiment build: the launch, counted from 0, that is made to give up; lbmdem_debug_chain_giveup)
   long nbsteps = 0;
   ProbeState probe;
+  TracerState tracers;
+  bool tracer_output = false;   // lbmdem_set_tracer_output: lbmdem_run_scene writes tracers%.6i.vtk at every VTK event
   // write_densities (lbm_densities.hip): the staging budget in bytes (0: the default) and, of the last call, the bytes of the
   // two sections, the bands, the nodes the device refused to format (lbmdem_densities_stats)
   size_t dens_budget = 0;
@@ -461,6 +474,9 @@ LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);
 // set to what probe.issued says (after chain_restore has taken it back)
 LBMDEM_INTERNAL int lbmdem_probe_sample(lbmdem_handle* h, const int* obst);
 LBMDEM_INTERNAL int lbmdem_probe_sync_counters(lbmdem_handle* h);
+// the tracers (lbm_tracers.hip): one advance of the set in the state the stream has reached, `obst` the map to read; `hook`: made
+// by a fluid step (lbmdem_forces_fluid, behind the probe sample). Launches on the handle's stream, does not synchronise.
+LBMDEM_INTERNAL int lbmdem_tracer_launch(lbmdem_handle* h, const int* obst, bool hook);
 // background frames and tables (lbmdem_output.hip): every queued job on disk, the writer joined, everything freed (-> off); the
 // writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);

@@ -176,6 +176,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
     if (cad.vtk(e)) {   // write_vtk sits inside `#ifdef _FLUIDE_` (main.c:1768-1770); nFile++ does not
       if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else if (async_frames_on(h)) RC_TRY(lbmdem_write_vtk_async(h, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
       if (dir && sc->fluid && !comm && h->flow_output) RC_TRY(lbmdem_write_flow(h, dir, nfile));   // lbmdem_set_flow_output
+      if (dir && sc->fluid && !comm && h->tracer_output) RC_TRY(lbmdem_write_tracers(h, dir, nfile));   // lbmdem_set_tracer_output
       nfile++;
     }
     // (with strips the sub-step before was run by rank 0 on a full replica, lbmdem_comm_run: it holds the whole table)

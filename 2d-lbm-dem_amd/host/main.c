@@ -52,6 +52,9 @@
  * line per cell of CW x CH lattice nodes with the sums of fluid, grains and contacts over it. Single GPU only.
  * --flow: the flow fields (lbmdem_set_flow_output): flow%.6i.vtk next to every VTK frame -- composite velocity, vorticity, shear
  * rate and dissipation in lattice units -- and one line of the fluid's sums in flow.data at every DEM event. Single GPU only.
+ * --tracers NXxNY: fluid tracers (lbmdem_tracer_set, lbmdem_set_tracer_output): a uniform grid of NX x NY massless particles,
+ * px = (i + 0.5) * (lx - 1) / NX and py likewise, grain interiors included (those ride with their grain), advanced on the device
+ * at every fluid step; tracers%.6i.vtk next to every VTK frame. Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -77,6 +80,7 @@ static const char* g_dump_geometry = NULL;   /* --dump-geometry DIR */
 static const char* g_densities = NULL;       /* --densities DIR */
 static int g_contacts = 0;       /* --contacts */
 static int g_flow = 0;           /* --flow */
+static int g_tracers = 0, g_tracers_nx = 0, g_tracers_ny = 0;   /* --tracers NXxNY */
 static int g_coarse = 0, g_coarse_cw = 0, g_coarse_ch = 0;   /* --coarse CWxCH */
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
@@ -221,6 +225,15 @@ int main(int argc, char** argv) {
       }
       g_coarse = 1;
     }
+    if (!strcmp(argv[a], "--tracers")) {
+      char tail = 0;
+      if (a + 1 >= argc || sscanf(argv[a + 1], "%dx%d%c", &g_tracers_nx, &g_tracers_ny, &tail) != 2 || g_tracers_nx < 1 || g_tracers_ny < 1 ||
+          (long)g_tracers_nx * g_tracers_ny > 16777216L) {
+        fprintf(stderr, "--tracers NXxNY: tracers along x and y, both at least 1, at most 2^24 in all (256x256)\n");
+        return EXIT_FAILURE;
+      }
+      g_tracers = 1;
+    }
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) g_dump_geometry = argv[a + 1];
@@ -256,6 +269,8 @@ int main(int argc, char** argv) {
   if (g_contacts && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--contacts is a single-GPU mode (the contact network export needs all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_coarse && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--coarse is a single-GPU mode (the coarse-grained fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_tracers && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--tracers is a single-GPU mode (the tracers need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_tracers && g_dry) { fprintf(stderr, "--tracers cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_flow && g_dry) { fprintf(stderr, "--flow cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_densities && g_dry) { fprintf(stderr, "--densities cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_async_frames && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-output is a single-GPU mode (with --gpus N rank 0 merges the strips' columns and writes the frames itself)\n"); return EXIT_FAILURE; }
@@ -407,6 +422,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--contacts")) {}
     else if (!strcmp(argv[a], "--flow")) {}
     else if (!strcmp(argv[a], "--coarse") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--tracers") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--async-output")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--async-dem")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
@@ -431,7 +447,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -493,6 +509,19 @@ static int run(int argc, char** argv) {
   if (g_contacts) DIE(lbmdem_set_contacts_output(h, 1), "set_contacts_output");
   if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");
   if (g_coarse) DIE(lbmdem_set_coarse_output(h, g_coarse_cw, g_coarse_ch), "set_coarse_output");
+  if (g_tracers) {   /* a uniform grid over the whole domain; automatic advance, a file per frame */
+    const long nt = (long)g_tracers_nx * g_tracers_ny;
+    double* xy = (double*)malloc(sizeof(double) * 2 * (size_t)nt);
+    if (!xy) { fprintf(stderr, "--tracers: out of memory\n"); return EXIT_FAILURE; }
+    for (int i = 0; i < g_tracers_nx; ++i)
+      for (int j = 0; j < g_tracers_ny; ++j) {
+        xy[2 * ((long)i * g_tracers_ny + j)] = (i + 0.5) * (cfg.lx - 1) / g_tracers_nx;
+        xy[2 * ((long)i * g_tracers_ny + j) + 1] = (j + 0.5) * (cfg.ly - 1) / g_tracers_ny;
+      }
+    DIE(lbmdem_tracer_set(h, nt, xy, 1), "tracer_set");
+    free(xy);
+    DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");
+  }
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */
   if (g_async_dem) DIE(lbmdem_set_async_dem(h, g_async_dem), "set_async_dem");

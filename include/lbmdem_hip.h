@@ -632,6 +632,74 @@ int lbmdem_write_flow(lbmdem_handle* h, const char* dir, int nfile);
 int lbmdem_write_flow_files(const char* dir, int nfile, int lx, int ly, const double* ux, const double* uy, const double* vort,
                             const double* gdot, const double* diss);   /* host only */
 int lbmdem_set_flow_output(lbmdem_handle* h, int on);               /* 0: off (default) */
+/* Fluid tracers: the Lagrangian view the snapshots above cannot give -- massless particles carried by the composite velocity of
+ * fluid and grains, advanced on the device once per fluid step from the velocity field of that step. Pathlines of the pore fluid,
+ * of the ambient fluid a collapsing column entrains, of the fluid that rides inside the packing. The reference has no such
+ * routine, so the contract is exact arithmetic, as for the flow fields: IEEE double, no contraction, every expression associated
+ * as written here; a restatement over the downloads named in the flow-fields block reproduces every position bit for bit.
+ * Coordinates: a tracer is (px, py) in node coordinates -- node (x, y) sits at ((double)x, (double)y) -- inside the domain
+ * [0, lx - 1] x [0, ly - 1]. Tracer k of the set stays tracer k: nothing sorts or bins them.
+ * Velocity at a point (px, py) of the domain, from ux, uy of the flow-fields block (same inputs, same formulas, a lid not
+ * represented):
+ *   i = (int)px, lowered to lx - 2 if larger;  j = (int)py, lowered to ly - 2 if larger
+ *   a = px - i,  b = py - j                    (a may be exactly 1.0 on the last node, likewise b)
+ *   w00 = (1. - a) * (1. - b)    w10 = a * (1. - b)    w01 = (1. - a) * b    w11 = a * b
+ *   U = (((w00 * ux[i][j]) + (w10 * ux[i+1][j])) + (w01 * ux[i][j+1])) + (w11 * ux[i+1][j+1]),  V likewise from uy
+ * One advance is one lattice time unit, a midpoint step in the field as the call finds it:
+ *   (U0, V0) at (px, py);   qx = clamp(px + 0.5 * U0), qy = clamp(py + 0.5 * V0);   (U1, V1) at (qx, qy);
+ *   px' = clamp(px + U1), py' = clamp(py + V1)
+ *   clamp(v) on the x axis is !(v >= 0.) ? 0. : (v > (double)(lx - 1) ? (double)(lx - 1) : v), on the y axis with ly - 1: a NaN
+ *   goes to 0 and never reaches an index. (All four nodes of a cell enter with their weight, a weight of 0 included: a node
+ *   whose velocity is not finite makes U, V NaN for every point of the cells that touch it.) The lattice-edge walls hold +0.0, so
+ *   a midpoint on the last row or column sees no velocity across it.
+ * Sample at the present positions, per tracer: U, V as above and o = (double)obst[(int)(px + 0.5)][(int)(py + 0.5)], the nearest
+ * node's owner (-1: fluid, 0 .. nbgrains - 1: that grain, nbgrains: a lattice-edge wall).
+ *   lbmdem_tracer_set           n tracers from xy = n x (px, py) on the host, replacing an earlier set (whose counts start again);
+ *                               n = 0 (xy may be NULL) frees it. The buffers come from the handle's pool and go with the set or
+ *                               the handle. automatic != 0: every fluid step advances the set once, on the handle's stream behind
+ *                               the force kernels and the probe sample (lbmdem_forces_fluid; so in lbmdem_lbm_step, lbmdem_run,
+ *                               lbmdem_run_scene): it sees f after collide_stream, that step's map, and the grains as the sub-step
+ *                               before left them -- what a probe sample sees. automatic == 0: only lbmdem_tracer_advance advances.
+ *                               A position that is not finite or lies outside the domain is refused, naming the first offender;
+ *                               n is at most 2^30 / 40 (positions and the sample's scratch stay under 1 GiB). Synchronises.
+ *   lbmdem_tracer_advance       one advance in the present state (f = lbmdem_download_f, obst = lbmdem_download_obst, the present
+ *                               kinematics and walls), on the handle's stream; does not synchronise. Nothing to do without tracers.
+ *   lbmdem_tracer_download      the positions, n x (px, py). *count is always set; cap = 0 (xy may be NULL) only reports it; a buffer
+ *                               of fewer tracers is refused with *count set. Settles and synchronises.
+ *   lbmdem_tracer_device        the DEVICE address of the positions ([n][2] doubles, NULL without tracers), for a torch tensor view;
+ *                               valid until the next lbmdem_tracer_set. A position written through it is clamped as above when a
+ *                               kernel reads it. Order through lbmdem_set_stream or lbmdem_sync.
+ *   lbmdem_tracer_sample        out3 = n x (U, V, o) at the present positions; count and cap as for the download. Synchronises.
+ *   lbmdem_tracer_stats         counts3 = { tracers, advances made since lbmdem_tracer_set, those of them made by fluid steps }.
+ *   lbmdem_write_tracers_files  host only, no handle, no device: <dir>/tracers%.6i.vtk, legacy binary POLYDATA, every number
+ *                               big-endian, no separators after binary blocks: "# vtk DataFile Version 2.0\nlbmdem fluid tracers\n
+ *                               BINARY\nDATASET POLYDATA\n", "POINTS n float\n" with ((float)px * pas, (float)py * pas, 0) per tracer,
+ *                               pas = (float)(1. / lx) -- the coordinates of the frames' mesh, so the file overlays a frame --,
+ *                               "VERTICES n 2n\n" with the 32-bit integers (1, k) per tracer, "POINT_DATA n\n",
+ *                               "VECTORS tracer_velocity_lb float\n" with ((float)U, (float)V, 0) and "SCALARS tracer_owner float\n
+ *                               LOOKUP_TABLE default\n" with (float)o, from xy = n x (px, py) and uvo = n x (U, V, o). n = 0 (the
+ *                               buffers may be NULL) writes a valid empty file. lx >= 2.
+ *   lbmdem_write_tracers        the same file of the handle's present positions and their sample. Synchronises.
+ *   lbmdem_set_tracer_output    on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_tracers at every VTK event of a run with
+ *                               the fluid, with the event's nFile, after the frame and the flow file. Synchronous. 0: off (the
+ *                               default).
+ * Give-up recovery: an advance queued behind a launch of the multi-sub-step DEM kernel that gave up finds the stop word and does
+ * nothing; the replay repeats those fluid steps and advances again, once each, and the counts follow.
+ * The advance only reads the step's state and writes the tracers' own buffer: no call changes anything a later step reads. With
+ * no tracers set nothing is allocated or launched. A checkpoint does not carry tracers or the output setting: a loaded handle has
+ * none, and the file is byte for byte what a handle without tracers saves.
+ * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with tracers set or the output on); the
+ * single-precision library (lbmdem_write_tracers_files works there too); null arguments; a short buffer; a bad position or count;
+ * a directory that cannot be written ("cannot open"). Vibrating, probing and lid handles have the feature. */
+int lbmdem_tracer_set(lbmdem_handle* h, long n, const double* xy, int automatic);
+int lbmdem_tracer_advance(lbmdem_handle* h);
+int lbmdem_tracer_download(lbmdem_handle* h, double* xy, long cap, long* count);
+int lbmdem_tracer_device(lbmdem_handle* h, void** xy);
+int lbmdem_tracer_sample(lbmdem_handle* h, double* out3, long cap, long* count);
+int lbmdem_tracer_stats(lbmdem_handle* h, long* counts3);
+int lbmdem_write_tracers(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_write_tracers_files(const char* dir, int nfile, int lx, long n, const double* xy, const double* uvo);   /* host only */
+int lbmdem_set_tracer_output(lbmdem_handle* h, int on);             /* 0: off (default) */
 /* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
  * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
  * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
