@@ -196,6 +196,16 @@ def _open_library(LIB_PATH):
     L.lbmdem_write_tracers.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_write_tracers_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_void_p]
     L.lbmdem_set_tracer_output.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_scalar_set.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_int]
+    L.lbmdem_scalar_step.argtypes = [C.c_void_p]
+    L.lbmdem_scalar_download.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_scalar_download_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_scalar_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]
+    L.lbmdem_scalar_sums.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_scalar_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_write_scalar.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_write_scalar_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.lbmdem_set_scalar_output.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
@@ -420,6 +430,20 @@ def write_tracers_files(directory, nFile, lx, xy, uvo, precision="f64"):
     n = len(xy)
     _chk(load_library(precision).lbmdem_write_tracers_files(os.fsencode(directory), int(nFile), int(lx), n,
                                                             _vp(xy) if n else None, _vp(uvo) if n else None))
+
+
+SCALAR_SUMS = ("n_fluid", "sum_C", "sum_C2", "min_C", "max_C")   # LbmDem.scalar_sums
+SCALAR_COUNTERS = ("present", "steps", "hook_steps")             # LbmDem.scalar_stats
+
+
+def write_scalar_files(directory, nFile, C_plane, precision="f64"):
+    """scalar%.6i.vtk, legacy binary STRUCTURED_POINTS on the nodes of the frames' mesh, from the concentration plane [lx][ly]:
+    (float)C of every node, big-endian, x fastest (include/lbmdem_hip.h spells the layout out). Host only."""
+    plane = np.ascontiguousarray(C_plane, dtype=np.float64)
+    if plane.ndim != 2:
+        raise LbmDemError(-1, "write_scalar_files: a plane of shape (lx, ly)")
+    lx, ly = plane.shape
+    _chk(load_library(precision).lbmdem_write_scalar_files(os.fsencode(directory), int(nFile), lx, ly, _vp(plane)))
 
 
 class _DeviceBlock:
@@ -974,6 +998,71 @@ class LbmDem:
     def set_tracer_output(self, on=True):
         """run_scene writes tracers%.6i.vtk at every VTK event, after the frame and the flow file"""
         _chk(self._L.lbmdem_set_tracer_output(self._h, 1 if on else 0))
+
+    # passive scalar: a dye field advected by the fluid's velocity and diffused, five populations per node, on the device
+
+    def set_scalar(self, C_plane, tau_s=1.0, automatic=True):
+        """the dye field from the concentration plane (lx, ly): w_k * C on the fluid nodes of the present map, replacing an
+        earlier scalar; None removes it and frees its buffers. tau_s > 0.5 is the relaxation time: diffusivity (tau_s - 0.5) / 3
+        in lattice units. automatic: every fluid step steps the field once, behind its force kernels; else only step_scalar."""
+        if C_plane is None:
+            _chk(self._L.lbmdem_scalar_set(self._h, None, 0.0, 0))
+            return
+        plane = np.ascontiguousarray(C_plane, dtype=np.float64)
+        if plane.shape != (self.lx, self.ly):
+            raise LbmDemError(-1, f"set_scalar: a plane of shape ({self.lx}, {self.ly})")
+        _chk(self._L.lbmdem_scalar_set(self._h, _vp(plane), float(tau_s), 1 if automatic else 0))
+
+    def step_scalar(self):
+        """one step of the field in the present state, on the handle's stream (no synchronisation)"""
+        _chk(self._L.lbmdem_scalar_step(self._h))
+
+    @property
+    def scalar(self):
+        """the concentration plane (lx, ly), +0.0 where the scalar holds nothing"""
+        out = np.empty((self.lx, self.ly), np.float64)
+        _chk(self._L.lbmdem_scalar_download(self._h, _vp(out)))
+        return out
+
+    def scalar_state(self):
+        """-> (g, was): the populations (lx, ly, 5) and the scalar's record of the fluid nodes (lx, ly) bool"""
+        g = np.empty((self.lx, self.ly, 5), np.float64)
+        was = np.empty((self.lx, self.ly), np.uint8)
+        _chk(self._L.lbmdem_scalar_download_state(self._h, _vp(g), _vp(was)))
+        return g, was.astype(bool)
+
+    def scalar_tensor(self, refresh=True):
+        """a concentration plane on the device as a torch.float64 CUDA tensor (lx, ly): a view, no copy. refresh writes the
+        present field into it on the handle's stream (sync() before reading it); a step does not touch it. Valid until the next
+        set_scalar."""
+        import torch
+        p = C.c_void_p(None)
+        _chk(self._L.lbmdem_scalar_device(self._h, C.byref(p), 1 if refresh else 0))
+        if not p.value:
+            raise LbmDemError(-1, "scalar_tensor: no scalar is set (set_scalar first)")
+        return torch.as_tensor(_DeviceBlock(p.value, (self.lx, self.ly)), device=f"cuda:{self.cfg.device}")
+
+    def scalar_sums(self):
+        """-> dict of SCALAR_SUMS over the nodes the scalar holds: their count, the sums of C and C * C (fixed order of additions,
+        include/lbmdem_hip.h), the smallest and the largest C"""
+        out = np.zeros(5)
+        _chk(self._L.lbmdem_scalar_sums(self._h, _vp(out)))
+        return dict(zip(SCALAR_SUMS, (float(v) for v in out)))
+
+    def scalar_stats(self):
+        """{present, steps since set_scalar, hook_steps: those of them made by fluid steps}"""
+        c = np.zeros(3, np.int64)
+        _chk(self._L.lbmdem_scalar_stats(self._h, _vp(c)))
+        return dict(zip(SCALAR_COUNTERS, (int(v) for v in c)))
+
+    def write_scalar(self, directory=".", nFile=0):
+        """scalar%.6i.vtk of the present field (write_scalar_files applied to scalar)"""
+        _chk(self._L.lbmdem_write_scalar(self._h, os.fsencode(directory), int(nFile)))
+
+    def set_scalar_output(self, on=True):
+        """run_scene writes scalar%.6i.vtk at every VTK event, after the frame, and appends a line of scalar_sums to scalar.data
+        at every DEM event, while a scalar is set"""
+        _chk(self._L.lbmdem_set_scalar_output(self._h, 1 if on else 0))
 
     def write_densities(self, directory=".", nFile=0):
         """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""

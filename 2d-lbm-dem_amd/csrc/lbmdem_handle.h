@@ -57,6 +57,23 @@ struct ChainSnap {
   double Mgx, t;   // a vibrating handle's side wall and clock (lbmdem_set_vibration): with nbsteps, where its schedule stands
   long probe_seen, probe_issued;   // the probe recorder's counts (ProbeState): the ring's write and drop counters follow from them
   long tracer_advances, tracer_hook;   // the tracers' counts (TracerState): the advances behind a failed launch did nothing
+  int scalar_cur;                      // the passive scalar's ping-pong index and counts (ScalarState): likewise its steps
+  long scalar_steps, scalar_hook;
+};
+
+// The passive scalar (lbmdem_scalar_*, lbm_scalar.hip). Nothing is allocated or launched while `on` is false.
+struct ScalarState {
+  bool on = false;
+  bool automatic = false;     // every fluid step steps the field once (lbmdem_forces_fluid, behind the tracer advance)
+  double tau = 0., omega = 0.;   // omega = 1. / tau, formed once on the host
+  double* g[2] = {nullptr, nullptr};   // device [5][lx][sy] each: the populations, ping-pong; g[cur] is the present state
+  int cur = 0;
+  unsigned char* was = nullptr;   // device [lx][sy]: the nodes that were fluid when the field was last stepped or set
+  double* conc = nullptr;     // device [lx][ly]: the concentration plane of the download, the torch view and the file
+  double* part = nullptr;     // [part_cap] scratch of lbmdem_scalar_sums: per (row, block of 64 y) [lx][nb][5], then the rows [lx][5]
+  long part_cap = 0;
+  double* sums = nullptr;     // [5]
+  long steps = 0, hook = 0;   // steps made since lbmdem_scalar_set; those of them the fluid steps made
 };
 
 // Fluid tracers (lbmdem_tracer_*, lbm_tracers.hip). Nothing is allocated or launched while n == 0.
@@ -305,6 +322,8 @@ struct lbmdem_handle {
   ProbeState probe;
   TracerState tracers;
   bool tracer_output = false;   // lbmdem_set_tracer_output: lbmdem_run_scene writes tracers%.6i.vtk at every VTK event
+  ScalarState scalar;
+  bool scalar_output = false;   // lbmdem_set_scalar_output: lbmdem_run_scene writes scalar%.6i.vtk at every VTK event, a line of scalar.data at every DEM event
   // write_densities (lbm_densities.hip): the staging budget in bytes (0: the default) and, of the last call, the bytes of the
   // two sections, the bands, the nodes the device refused to format (lbmdem_densities_stats)
   size_t dens_budget = 0;
@@ -477,6 +496,11 @@ LBMDEM_INTERNAL int lbmdem_probe_sync_counters(lbmdem_handle* h);
 // the tracers (lbm_tracers.hip): one advance of the set in the state the stream has reached, `obst` the map to read; `hook`: made
 // by a fluid step (lbmdem_forces_fluid, behind the probe sample). Launches on the handle's stream, does not synchronise.
 LBMDEM_INTERNAL int lbmdem_tracer_launch(lbmdem_handle* h, const int* obst, bool hook);
+// the passive scalar (lbm_scalar.hip): one step of the field in the state the stream has reached, `obst` the map to read; `hook`:
+// made by a fluid step (lbmdem_forces_fluid, behind the tracer advance). Launches on the handle's stream, does not synchronise.
+// ... and lbmdem_set_scalar_output's line of <dir>/scalar.data (lbmdem_run_scene, at a DEM event)
+LBMDEM_INTERNAL int lbmdem_scalar_launch(lbmdem_handle* h, const int* obst, bool hook);
+LBMDEM_INTERNAL int lbmdem_scalar_data_line(lbmdem_handle* h, const char* dir);
 // background frames and tables (lbmdem_output.hip): every queued job on disk, the writer joined, everything freed (-> off); the
 // writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);

@@ -177,6 +177,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
       if (dir && sc->fluid) { if (comm) RC_TRY(lbmdem_comm_write_vtk(h, comm, dir, nfile)); else if (async_frames_on(h)) RC_TRY(lbmdem_write_vtk_async(h, dir, nfile)); else RC_TRY(lbmdem_write_vtk(h, dir, nfile)); }
       if (dir && sc->fluid && !comm && h->flow_output) RC_TRY(lbmdem_write_flow(h, dir, nfile));   // lbmdem_set_flow_output
       if (dir && sc->fluid && !comm && h->tracer_output) RC_TRY(lbmdem_write_tracers(h, dir, nfile));   // lbmdem_set_tracer_output
+      if (dir && sc->fluid && !comm && h->scalar_output && h->scalar.on) RC_TRY(lbmdem_write_scalar(h, dir, nfile));   // lbmdem_set_scalar_output
       nfile++;
     }
     // (with strips the sub-step before was run by rank 0 on a full replica, lbmdem_comm_run: it holds the whole table)
@@ -190,6 +191,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
       if (!comm && h->contacts_output) RC_TRY(lbmdem_write_contacts(h, dir, nfile));   // lbmdem_set_contacts_output
       if (!comm && h->coarse_cw > 0) RC_TRY(lbmdem_write_coarse(h, dir, nfile, h->coarse_cw, h->coarse_ch));   // lbmdem_set_coarse_output
       if (!comm && h->flow_output) RC_TRY(flow_data_line(h, dir));   // lbmdem_set_flow_output
+      if (!comm && h->scalar_output && h->scalar.on) RC_TRY(lbmdem_scalar_data_line(h, dir));   // lbmdem_set_scalar_output
     }
     if (cad.line(e)) {   // main.c:1884-1889
       const double* E = h->scene_energies;

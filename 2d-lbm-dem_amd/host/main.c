@@ -55,6 +55,10 @@
  * --tracers NXxNY: fluid tracers (lbmdem_tracer_set, lbmdem_set_tracer_output): a uniform grid of NX x NY massless particles,
  * px = (i + 0.5) * (lx - 1) / NX and py likewise, grain interiors included (those ride with their grain), advanced on the device
  * at every fluid step; tracers%.6i.vtk next to every VTK frame. Single GPU only.
+ * --dye X0,Y0,X1,Y1 [--dye-tau T]: a passive scalar (lbmdem_scalar_set, lbmdem_set_scalar_output): C = 1 at the nodes X0 <= x <= X1,
+ * Y0 <= y <= Y1 and 0 elsewhere, advected by the fluid and diffused on the device at every fluid step; scalar%.6i.vtk next to
+ * every VTK frame and a line of scalar.data at every DEM event. T is the relaxation time, diffusivity (T - 0.5) / 3 in lattice
+ * units; the default 0.53 gives 0.01, a dye that is stirred long before it spreads on its own. Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -81,6 +85,8 @@ static const char* g_densities = NULL;       /* --densities DIR */
 static int g_contacts = 0;       /* --contacts */
 static int g_flow = 0;           /* --flow */
 static int g_tracers = 0, g_tracers_nx = 0, g_tracers_ny = 0;   /* --tracers NXxNY */
+static int g_dye = 0, g_dye_box[4] = {0, 0, 0, 0};   /* --dye X0,Y0,X1,Y1 */
+static double g_dye_tau = 0.53;                      /* --dye-tau T */
 static int g_coarse = 0, g_coarse_cw = 0, g_coarse_ch = 0;   /* --coarse CWxCH */
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
@@ -234,6 +240,22 @@ int main(int argc, char** argv) {
       }
       g_tracers = 1;
     }
+    if (!strcmp(argv[a], "--dye")) {
+      char tail = 0;
+      if (a + 1 >= argc || sscanf(argv[a + 1], "%d,%d,%d,%d%c", &g_dye_box[0], &g_dye_box[1], &g_dye_box[2], &g_dye_box[3], &tail) != 4 ||
+          g_dye_box[0] < 0 || g_dye_box[1] < 0 || g_dye_box[2] < g_dye_box[0] || g_dye_box[3] < g_dye_box[1]) {
+        fprintf(stderr, "--dye X0,Y0,X1,Y1: a box of nodes, 0 <= X0 <= X1 and 0 <= Y0 <= Y1\n");
+        return EXIT_FAILURE;
+      }
+      g_dye = 1;
+    }
+    if (!strcmp(argv[a], "--dye-tau")) {
+      char tail = 0;
+      if (a + 1 >= argc || sscanf(argv[a + 1], "%lf%c", &g_dye_tau, &tail) != 1 || !(g_dye_tau > 0.5)) {
+        fprintf(stderr, "--dye-tau T: the relaxation time of the dye, larger than 0.5\n");
+        return EXIT_FAILURE;
+      }
+    }
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) g_dump_geometry = argv[a + 1];
@@ -270,6 +292,8 @@ int main(int argc, char** argv) {
   if (g_coarse && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--coarse is a single-GPU mode (the coarse-grained fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_tracers && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--tracers is a single-GPU mode (the tracers need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_dye && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dye is a single-GPU mode (the passive scalar needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_dye && g_dry) { fprintf(stderr, "--dye cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_tracers && g_dry) { fprintf(stderr, "--tracers cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_flow && g_dry) { fprintf(stderr, "--flow cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_densities && g_dry) { fprintf(stderr, "--densities cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
@@ -423,6 +447,8 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--flow")) {}
     else if (!strcmp(argv[a], "--coarse") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--tracers") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--dye") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--dye-tau") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--async-output")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--async-dem")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
@@ -447,7 +473,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -521,6 +547,15 @@ static int run(int argc, char** argv) {
     DIE(lbmdem_tracer_set(h, nt, xy, 1), "tracer_set");
     free(xy);
     DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");
+  }
+  if (g_dye) {   /* C = 1 in the box (cut to the lattice), 0 elsewhere; automatic step, a file per frame, a line per DEM event */
+    double* dye = (double*)calloc((size_t)cfg.lx * cfg.ly, sizeof(double));
+    if (!dye) { fprintf(stderr, "--dye: out of memory\n"); return EXIT_FAILURE; }
+    for (int x = g_dye_box[0]; x <= g_dye_box[2] && x < cfg.lx; ++x)
+      for (int y = g_dye_box[1]; y <= g_dye_box[3] && y < cfg.ly; ++y) dye[(size_t)x * cfg.ly + y] = 1.;
+    DIE(lbmdem_scalar_set(h, dye, g_dye_tau, 1), "scalar_set");
+    free(dye);
+    DIE(lbmdem_set_scalar_output(h, 1), "set_scalar_output");
   }
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */

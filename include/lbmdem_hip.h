@@ -700,6 +700,93 @@ int lbmdem_tracer_stats(lbmdem_handle* h, long* counts3);
 int lbmdem_write_tracers(lbmdem_handle* h, const char* dir, int nfile);
 int lbmdem_write_tracers_files(const char* dir, int nfile, int lx, long n, const double* xy, const double* uvo);   /* host only */
 int lbmdem_set_tracer_output(lbmdem_handle* h, int on);             /* 0: off (default) */
+/* Passive scalar: a dye field carried by the fluid's velocity and diffused -- what the snapshots and the tracers cannot show:
+ * mixing. How much ambient fluid a collapsing column entrains, how far the pore fluid of the packing spreads, how a dyed layer
+ * is stirred. A second lattice of five populations per node, stepped on the device once per fluid step from that step's
+ * velocity. The reference has no such routine, so the contract is exact arithmetic, as for the flow fields and the tracers:
+ * IEEE double, no contraction, every expression associated as written here; a restatement over the downloads named in the
+ * flow-fields block and lbmdem_scalar_download_state reproduces every population bit for bit.
+ * State: g_k per node, k = 0..4, on the directions q = 0, 2, 4, 6, 8 of the fluid's set (main.c:70-71):
+ *   e_0 = (0, 0), e_1 = (-1, 0), e_2 = (0, -1), e_3 = (1, 0), e_4 = (0, 1);  opp(1) = 3, opp(2) = 4, opp(3) = 1, opp(4) = 2;
+ *   w_0 = 1. / 3, w_1 .. w_4 = 1. / 6;  C = (((g_0 + g_1) + g_2) + g_3) + g_4, the concentration;
+ *   tau_s > 0.5, the relaxation time given at set time; omega = 1. / tau_s, formed once on the host;
+ *   was_fluid, the scalar's own record of the nodes that were fluid when it was last stepped or set. A node outside was_fluid
+ *   holds five +0.0, so its C reads +0.0: the field, its sums and its file live on was_fluid.
+ * Diffusivity in lattice units D = (tau_s - 0.5) / 3; to SI: D * dx^2 / dtLB = D * dx * c (m^2/s), dtLB = dx / c
+ * (lbmdem_get_config). C has the unit the caller gives it.
+ * One step, with M = lbmdem_download_obst, f = lbmdem_download_f, the kinematics and walls of the flow-fields block (what a
+ * tracer advance sees; a hooked step sees f after this fluid step's collide_stream, that step's map, the grains as the sub-step
+ * before left them). For every node n with M[n] == -1, all three stages reading the state as the stage before left it:
+ *   1. refill  if n is not in was_fluid (a grain has uncovered it): of the neighbours n + e_1, n + e_2, n + e_3, n + e_4, in that
+ *              order, those inside the lattice with M == -1 that are in was_fluid are eligible; S = +0.0, then S = S + C(neighbour)
+ *              for each eligible one with its stored C; Cf = S / (double)count, or +0.0 when none is eligible; g_k(n) = w_k * Cf.
+ *              Otherwise g_k(n) is the stored value. (Only nodes outside was_fluid are written, only nodes inside it are read.)
+ *   2. collide ux, uy of the flow-fields block at n (jx / rho, jy / rho of a fluid node); C = (((g_0 + g_1) + g_2) + g_3) + g_4;
+ *              eq_0 = w_0 * C;  eq_k = (w_k * C) * (1. + (3. * s_k)), s_1 = -ux, s_2 = -uy, s_3 = ux, s_4 = uy  (e_k . u);
+ *              g*_k = g_k - (omega * (g_k - eq_k))
+ *   3. pull    g_k(n) = g*_k(n - e_k) if n - e_k lies inside the lattice and M[n - e_k] == -1, else g*_opp(k)(n): half-way
+ *              bounce-back, no flux through grains or the lattice-edge walls. There is NO moving-wall term: a grain that moves
+ *              pushes no dye ahead of it through this rule (it does through the refill, below).
+ * Every node with M[n] != -1 holds five +0.0 afterwards, and was_fluid becomes M == -1.
+ * A node that a grain covers loses its content, and a node that a grain uncovers takes its neighbours' mean: the total of C is NOT
+ * conserved where grains move -- the treatment the reference gives the fluid's own mass in reinit_obst_density (main.c:966-986).
+ * Where no grain moves the total is conserved to rounding. lbmdem_scalar_sums lets a run watch the drift.
+ *   lbmdem_scalar_set             C = [lx][ly] doubles, y fastest: g_k = w_k * C[n] at the fluid nodes of lbmdem_download_obst,
+ *                                 five +0.0 elsewhere, was_fluid = that set, replacing an earlier scalar (whose counts start
+ *                                 again). Every value of the plane must be finite, those at other nodes (which are ignored)
+ *                                 included. C == NULL removes the scalar and frees its buffers (tau_s is not looked at). The
+ *                                 buffers -- two sets of five planes, a byte plane, a concentration plane: 89 bytes per node --
+ *                                 come from the handle's pool. automatic != 0: every fluid step steps the field once, on the
+ *                                 handle's stream behind the force kernels, the probe sample and the tracer advance
+ *                                 (lbmdem_forces_fluid; so in lbmdem_lbm_step, lbmdem_run, lbmdem_run_scene). Synchronises.
+ *   lbmdem_scalar_step            one step by hand in the present state, on the handle's stream; does not synchronise. Nothing
+ *                                 to do without a scalar.
+ *   lbmdem_scalar_download        the concentration plane C[lx][ly], +0.0 outside was_fluid. Settles and synchronises.
+ *   lbmdem_scalar_download_state  g = [lx][ly][5] and was = [lx][ly] bytes (0 or 1): what a restatement starts from.
+ *   lbmdem_scalar_device          the DEVICE address of a concentration plane ([lx][ly] doubles, NULL without a scalar) for a torch
+ *                                 tensor view, valid until the next lbmdem_scalar_set. refresh != 0 writes the present field into
+ *                                 it on the handle's stream and does not synchronise (order through lbmdem_set_stream or
+ *                                 lbmdem_sync); a step does not touch the plane. Writing into it changes nothing of the scalar.
+ *   lbmdem_scalar_sums            out5 = { nodes in was_fluid, sum C, sum C * C, min C, max C } over the nodes in was_fluid. Sums:
+ *                                 the flow sums' three levels, each a chain from +0.0 -- per lattice row x and block of 64
+ *                                 consecutive y over y ascending (a node outside was_fluid adds +0.0), per row over its blocks
+ *                                 ascending, over the rows, x ascending. Minimum and maximum are order-free (fmin, fmax from
+ *                                 +inf, -inf) and read +0.0 when was_fluid is empty. No atomics. Synchronises.
+ *   lbmdem_scalar_stats           counts3 = { 1 if a scalar is set else 0, steps made since lbmdem_scalar_set, those of them made
+ *                                 by fluid steps }.
+ *   lbmdem_write_scalar_files     host only, no handle, no device: <dir>/scalar%.6i.vtk from C[lx][ly], legacy binary
+ *                                 STRUCTURED_POINTS on the nodes of the frames' mesh, so the file overlays a frame:
+ *                                 "# vtk DataFile Version 2.0\nlbmdem passive scalar\nBINARY\nDATASET STRUCTURED_POINTS\n",
+ *                                 "DIMENSIONS lx ly 1\nORIGIN 0 0 0\nSPACING p p 1\n" with p = "%.9g" of (float)(1. / lx),
+ *                                 "POINT_DATA lx*ly\nSCALARS concentration float\nLOOKUP_TABLE default\n", then (float)C of every
+ *                                 node, big-endian, x fastest ([ly][lx]), nothing behind it. lx, ly >= 2.
+ *   lbmdem_write_scalar           the same file of the handle's present field. Synchronises.
+ *   lbmdem_set_scalar_output      on != 0: while a scalar is set lbmdem_run_scene (comm == NULL) calls lbmdem_write_scalar at every
+ *                                 VTK event of a run with the fluid, with the event's nFile, after the frame, the flow file and the
+ *                                 tracers' file, and at every DEM event, after the existing files, appends "%le" of the step
+ *                                 counter nbsteps and " %le" of the five sums to <dir>/scalar.data (a header line
+ *                                 "# step n_fluid sum_C sum_C2 min_C max_C" when the file is created). Synchronous. 0: off (the
+ *                                 default).
+ * Give-up recovery: a step queued behind a launch of the multi-sub-step DEM kernel that gave up finds the stop word and does
+ * nothing; the replay repeats those fluid steps and steps the field again, once each, and the counts follow.
+ * The step only reads the fluid's state and writes the scalar's own buffers: no call changes anything a later fluid step or DEM
+ * sub-step reads. With no scalar set nothing is allocated or launched. A checkpoint does not carry the scalar or the output
+ * setting: a loaded handle has none, and the file is byte for byte what a handle without one saves.
+ * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with a scalar set or the output on); the
+ * single-precision library (lbmdem_write_scalar_files works there too); null arguments; tau_s <= 0.5 or not finite; a value of C
+ * that is not finite; a download, the sums or the file without a scalar; a directory that cannot be written ("cannot open").
+ * Vibrating, probing, lid and tracer handles have the feature. Not built: sources, sinks and Dirichlet nodes during a run, a
+ * moving-wall flux term, a scalar that acts back on the fluid, more than one scalar. */
+int lbmdem_scalar_set(lbmdem_handle* h, const double* C, double tau_s, int automatic);
+int lbmdem_scalar_step(lbmdem_handle* h);
+int lbmdem_scalar_download(lbmdem_handle* h, double* C);
+int lbmdem_scalar_download_state(lbmdem_handle* h, double* g, unsigned char* was);
+int lbmdem_scalar_device(lbmdem_handle* h, void** C, int refresh);
+int lbmdem_scalar_sums(lbmdem_handle* h, double* out5);
+int lbmdem_scalar_stats(lbmdem_handle* h, long* counts3);
+int lbmdem_write_scalar(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_write_scalar_files(const char* dir, int nfile, int lx, int ly, const double* C);   /* host only */
+int lbmdem_set_scalar_output(lbmdem_handle* h, int on);             /* 0: off (default) */
 /* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
  * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
  * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
