@@ -206,6 +206,17 @@ def _open_library(LIB_PATH):
     L.lbmdem_write_scalar.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_write_scalar_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.lbmdem_set_scalar_output.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_mean_begin.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    for name in ("mean_sample", "mean_reset", "mean_end"):
+        getattr(L, "lbmdem_" + name).argtypes = [C.c_void_p]
+    L.lbmdem_mean_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_mean_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_mean_fields.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_mean_fields_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long]
+    L.lbmdem_mean_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
+    L.lbmdem_write_mean.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.lbmdem_write_mean_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_long] + [C.c_void_p] * 8
+    L.lbmdem_set_mean_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.lbmdem_write_densities.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.lbmdem_download_densities_text.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lbmdem_set_densities_staging.argtypes = [C.c_void_p, C.c_size_t]
@@ -444,6 +455,49 @@ def write_scalar_files(directory, nFile, C_plane, precision="f64"):
         raise LbmDemError(-1, "write_scalar_files: a plane of shape (lx, ly)")
     lx, ly = plane.shape
     _chk(load_library(precision).lbmdem_write_scalar_files(os.fsencode(directory), int(nFile), lx, ly, _vp(plane)))
+
+
+# time-averaged flow statistics (LbmDem.begin_mean ...): the accumulators of a window, the derived fields, the profile's rows
+MEAN_U, MEAN_UU, MEAN_RHO, MEAN_DISS, MEAN_GRAIN = (1 << k for k in range(5))
+MEAN_ALL = 31
+MEAN_PLANES = (("Sux", "Suy"), ("Sxx", "Sxy", "Syy"), ("Srho", "Srho2"), ("Sdiss", "Sgdot"), ("Sgux", "Sguy"))   # per bit
+MEANF_NAMES = ("phi", "solid", "mux", "muy", "rxx", "rxy", "ryy", "mrho", "vrho", "mdiss", "mgdot", "gux", "guy")
+(MEANF_PHI, MEANF_SOLID, MEANF_UX, MEANF_UY, MEANF_RXX, MEANF_RXY, MEANF_RYY, MEANF_RHO, MEANF_VRHO, MEANF_DISS, MEANF_GDOT,
+ MEANF_GUX, MEANF_GUY) = (1 << k for k in range(13))
+MEANF_ALL = 8191
+MEAN_PROFILE_ROWS = MEANF_NAMES + ("nf",)
+MEAN_COUNTERS = ("present", "mask", "samples", "hook_steps", "bytes")   # LbmDem.mean_stats
+
+
+def mean_plane_names(mask):
+    """the accumulator planes a window's mask selects, in plane order"""
+    mask = int(mask)
+    if mask <= 0 or mask & ~MEAN_ALL:
+        raise LbmDemError(-1, f"time-averaged statistics: bad mask {mask}")
+    return [name for k, group in enumerate(MEAN_PLANES) if mask >> k & 1 for name in group]
+
+
+def mean_field_names(fmask):
+    """the derived fields a field mask selects, in plane order (ascending bit)"""
+    fmask = int(fmask)
+    if fmask <= 0 or fmask & ~MEANF_ALL:
+        raise LbmDemError(-1, f"time-averaged statistics: bad field mask {fmask}")
+    return [name for k, name in enumerate(MEANF_NAMES) if fmask >> k & 1]
+
+
+def write_mean_files(directory, nFile, samples, phi, mux, muy, rxx, rxy, ryy, mrho, profile14, precision="f64"):
+    """mean%.6i.vtk (the format of flow%.6i.vtk: mean_fluid_velocity_lb, fluid_fraction, fluctuation_energy = 0.5 * (rxx + ryy),
+    reynolds_xy = rxy, mean_density) and mean_profile%.6i.dat (per y: y, samples, the thirteen profile rows over lx) from seven
+    planes (lx, ly) and the profile (14, ly). Host only."""
+    planes = [np.ascontiguousarray(p, dtype=np.float64) for p in (phi, mux, muy, rxx, rxy, ryy, mrho)]
+    if planes[0].ndim != 2 or any(p.shape != planes[0].shape for p in planes):
+        raise LbmDemError(-1, "write_mean_files: seven planes of one shape (lx, ly)")
+    lx, ly = planes[0].shape
+    prof = np.ascontiguousarray(profile14, dtype=np.float64)
+    if prof.shape != (len(MEAN_PROFILE_ROWS), ly):
+        raise LbmDemError(-1, f"write_mean_files: a profile of shape ({len(MEAN_PROFILE_ROWS)}, ly)")
+    _chk(load_library(precision).lbmdem_write_mean_files(os.fsencode(directory), int(nFile), lx, ly, int(samples),
+                                                         *(_vp(p) for p in planes), _vp(prof)))
 
 
 class _DeviceBlock:
@@ -1063,6 +1117,79 @@ class LbmDem:
         """run_scene writes scalar%.6i.vtk at every VTK event, after the frame, and appends a line of scalar_sums to scalar.data
         at every DEM event, while a scalar is set"""
         _chk(self._L.lbmdem_set_scalar_output(self._h, 1 if on else 0))
+
+    # time-averaged flow statistics: per-node sums over the fluid steps of a window, accumulated on the device
+    # (include/lbmdem_hip.h)
+    def begin_mean(self, mask=MEAN_ALL, every=1):
+        """opens a window with the accumulators of `mask` (MEAN_U .. MEAN_GRAIN), all zero, discarding an open one. every >= 1: the
+        k-th fluid step from now on is sampled when k % every == 0, behind its force kernels; every == 0: only sample_mean."""
+        _chk(self._L.lbmdem_mean_begin(self._h, int(mask), int(every)))
+
+    def sample_mean(self):
+        """one sample of the present state into the window, on the handle's stream"""
+        _chk(self._L.lbmdem_mean_sample(self._h))
+
+    def reset_mean(self):
+        """zeroes the window; the mask, `every` and the phase of the cadence stay"""
+        _chk(self._L.lbmdem_mean_reset(self._h))
+
+    def end_mean(self):
+        """closes the window and frees its memory"""
+        _chk(self._L.lbmdem_mean_end(self._h))
+
+    def mean_stats(self):
+        """{present, mask, samples, hook_steps: the fluid steps the hook has counted, bytes the window holds}"""
+        c = np.zeros(5, dtype=np.int64)
+        _chk(self._L.lbmdem_mean_stats(self._h, _vp(c)))
+        return dict(zip(MEAN_COUNTERS, (int(v) for v in c)))
+
+    def mean_accumulators(self):
+        """-> {name: (lx, ly) array}: the raw sums of the window's mask (float64, MEAN_PLANES) and n_fluid, n_grain (uint32)"""
+        names = mean_plane_names(self.mean_stats()["mask"] or MEAN_ALL)
+        planes = np.zeros((len(names), self.lx, self.ly))
+        nf, ng = np.zeros((self.lx, self.ly), np.uint32), np.zeros((self.lx, self.ly), np.uint32)
+        count = C.c_long(0)
+        _chk(self._L.lbmdem_mean_download(self._h, _vp(planes), _vp(nf), _vp(ng), planes.size, C.byref(count)))
+        out = {name: planes[k] for k, name in enumerate(names)}
+        out.update(n_fluid=nf, n_grain=ng)
+        return out
+
+    def mean_fields(self, fmask=MEANF_ALL, device=False):
+        """-> {name: (lx, ly) float64 array} of the derived fields `fmask` selects (MEANF_PHI .. MEANF_GUY), +0.0 where a node's
+        count is 0. device=True: torch.float64 tensors on the handle's GPU, filled on the handle's stream without a host copy."""
+        names = mean_field_names(fmask)
+        if device:
+            import torch
+            out = torch.empty((len(names), self.lx, self.ly), dtype=torch.float64, device=f"cuda:{self.cfg.device}")
+            self.mean_fields_into(fmask, out)
+            return {name: out[k] for k, name in enumerate(names)}
+        count = C.c_long(0)
+        out = np.zeros((len(names), self.lx, self.ly))
+        _chk(self._L.lbmdem_mean_fields(self._h, int(fmask), _vp(out), out.size, C.byref(count)))
+        return {name: out[k] for k, name in enumerate(names)}
+
+    def mean_fields_into(self, fmask, tensor):
+        """the planes of `fmask` into a contiguous torch.float64 CUDA tensor of at least that many elements (no synchronisation)"""
+        import torch
+        if tensor.dtype != torch.float64 or not tensor.is_cuda or not tensor.is_contiguous():
+            raise LbmDemError(-1, "mean_fields_into: a contiguous torch.float64 CUDA tensor")
+        _chk(self._L.lbmdem_mean_fields_device(self._h, int(fmask), C.c_void_p(tensor.data_ptr()), int(tensor.numel())))
+
+    def mean_profile(self):
+        """-> (14, ly): per y the sum over x (x ascending, from +0.0) of each derived field and of n_fluid (MEAN_PROFILE_ROWS);
+        divide by lx for the mean along x"""
+        out = np.zeros((len(MEAN_PROFILE_ROWS), self.ly))
+        _chk(self._L.lbmdem_mean_profile(self._h, _vp(out), out.size))
+        return out
+
+    def write_mean(self, directory=".", nFile=0):
+        """mean%.6i.vtk and mean_profile%.6i.dat of the window (write_mean_files applied to mean_fields and mean_profile)"""
+        _chk(self._L.lbmdem_write_mean(self._h, os.fsencode(directory), int(nFile)))
+
+    def set_mean_output(self, mask=MEAN_ALL, every=1):
+        """run_scene opens a window (mask, every) at its start, writes the two files at every VTK event and resets the window;
+        mask 0 switches it off"""
+        _chk(self._L.lbmdem_set_mean_output(self._h, int(mask), int(every)))
 
     def write_densities(self, directory=".", nFile=0):
         """write_densities (main.c:482-566): densities%.6i.vtk and pressure_base%.6i.dat, the text made on the device"""

@@ -102,6 +102,27 @@ __device__ __forceinline__ NodeVel node_vel(const real* __restrict__ fl, int o, 
   return V;
 }
 
+// The stress moments of a fluid node whose populations node_vel has left in `f`, and what the flow-fields block of
+// include/lbmdem_hip.h derives from them. ONE copy of the formulas for the flow fields (lbm_flow.hip) and the time averages
+// (lbm_mean.hip). nu8 = ((1. / s8) - 0.5) / 3. and nu9 likewise, formed once on the host.
+struct NodeMoments { double pxx, pxy; };
+__device__ __forceinline__ NodeMoments node_moments(const real (&f)[9]) {
+  return NodeMoments{f[2] - f[4] + f[6] - f[8],      // main.c:1095
+                     -f[1] + f[3] - f[5] + f[7]};    // main.c:1096
+}
+struct NodeStress { double nxx, nxy, gdot, diss; };
+__device__ __forceinline__ NodeStress node_stress(const LatticeView& L, double nu8, double nu9, double pxx, double pxy, double rho,
+                                                  double jx, double jy) {
+  NodeStress S;
+  S.nxx = pxx - (jx * jx - jy * jy) / rho;   // main.c:1105
+  S.nxy = pxy - jx * jy / rho;               // main.c:1106
+  const double D = -1.5 * L.s8 * S.nxx / rho;
+  const double T = -3. * L.s9 * S.nxy / rho;
+  S.gdot = sqrt(D * D + T * T);
+  S.diss = rho * (nu8 * D * D + nu9 * T * T);
+  return S;
+}
+
 // main.c:1082-1116, in registers
 __device__ __forceinline__ void mrt_collide(const LatticeView& L, real (&f)[9]) {
   const real a = 1. / 36;

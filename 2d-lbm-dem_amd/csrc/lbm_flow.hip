@@ -61,8 +61,9 @@ __device__ __forceinline__ FlowVel flow_vel(const FlowJob& J, int x, int y) {
   const NodeVel N = node_vel(J.f, J.obst[(long)x * L.sy + y], L, J.K, x, y, f);   // (lbm_device.h: shared with the tracers)
   FlowVel V{N.ux, N.uy, N.rho, N.jx, N.jy, 0., 0., N.fluid};
   if (N.fluid) {
-    V.pxx = f[2] - f[4] + f[6] - f[8];        // main.c:1095
-    V.pxy = -f[1] + f[3] - f[5] + f[7];       // main.c:1096
+    const NodeMoments P = node_moments(f);   // (lbm_device.h: shared with the time averages)
+    V.pxx = P.pxx;
+    V.pxy = P.pxy;
   }
   return V;
 }
@@ -100,12 +101,11 @@ __global__ __launch_bounds__(FL_THREADS) void k_flow_nodes(const FlowJob J) {
       if (xr >= xa && xr < xb) {   // a row of the segment: its local fields
         double nxx = 0., nxy = 0.;
         if (V.fluid) {
-          nxx = V.pxx - (V.jx * V.jx - V.jy * V.jy) / V.rho;   // main.c:1105
-          nxy = V.pxy - V.jx * V.jy / V.rho;                   // main.c:1106
-          const double D = -1.5 * L.s8 * nxx / V.rho;
-          const double T = -3. * L.s9 * nxy / V.rho;
-          nx.gdot = sqrt(D * D + T * T);
-          nx.diss = V.rho * (J.nu8 * D * D + J.nu9 * T * T);
+          const NodeStress S = node_stress(L, J.nu8, J.nu9, V.pxx, V.pxy, V.rho, V.jx, V.jy);   // (lbm_device.h, likewise)
+          nxx = S.nxx;
+          nxy = S.nxy;
+          nx.gdot = S.gdot;
+          nx.diss = S.diss;
           nx.u2 = V.ux * V.ux + V.uy * V.uy;
           nx.ke = 0.5 * V.rho * nx.u2;
           nx.rho = V.rho;

@@ -711,6 +711,7 @@ int lbmdem_forces_fluid(lbmdem_handle* h) {
   if (h->probe.on) RC_TRY(lbmdem_probe_sample(h, ob));   // lbmdem_probe_enable: the sample of this fluid step
   if (h->tracers.n > 0 && h->tracers.automatic) RC_TRY(lbmdem_tracer_launch(h, ob, true));   // lbmdem_tracer_set: this fluid step's advance
   if (h->scalar.on && h->scalar.automatic) RC_TRY(lbmdem_scalar_launch(h, ob, true));   // lbmdem_scalar_set: this fluid step's step
+  if (h->mean.every > 0) RC_TRY(lbmdem_mean_hook(h, ob));   // lbmdem_mean_begin: this fluid step's sample, when it is due
   return LBMDEM_OK;
 }
 
@@ -1160,6 +1161,7 @@ static ChainSnap chain_snapshot(const lbmdem_handle* h) {
   s.probe_seen = h->probe.seen; s.probe_issued = h->probe.issued;
   s.tracer_advances = h->tracers.advances; s.tracer_hook = h->tracers.hook;
   s.scalar_cur = h->scalar.cur; s.scalar_steps = h->scalar.steps; s.scalar_hook = h->scalar.hook;
+  s.mean_samples = h->mean.samples; s.mean_hook = h->mean.hook;
   return s;
 }
 
@@ -1183,6 +1185,9 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   h->tracers.advances = s.tracer_advances; h->tracers.hook = s.tracer_hook;
   // ... and the passive scalar: its two kernels are gated, so both buffers and was_fluid hold what they held; the index goes back
   h->scalar.cur = s.scalar_cur; h->scalar.steps = s.scalar_steps; h->scalar.hook = s.scalar_hook;
+  // ... and the time averages: the sample kernel is gated and adds in place, so the window holds what it held; the counts go back
+  // and the replay makes those fluid steps' samples again, once each
+  h->mean.samples = s.mean_samples; h->mean.hook = s.mean_hook;
   // what the failed launch may have written on its way: slices of the next map's canvas, and -- by the tiles that did
   // finish -- their discs, in place. The map the next fluid step paints starts from a clean canvas again.
   const int b = 1 - s.ocur;

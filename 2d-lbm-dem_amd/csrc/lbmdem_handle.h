@@ -59,6 +59,20 @@ struct ChainSnap {
   long tracer_advances, tracer_hook;   // the tracers' counts (TracerState): the advances behind a failed launch did nothing
   int scalar_cur;                      // the passive scalar's ping-pong index and counts (ScalarState): likewise its steps
   long scalar_steps, scalar_hook;
+  long mean_samples, mean_hook;        // the time averages' counts (MeanState): the samples behind a failed launch added nothing
+};
+
+// Time-averaged flow statistics (lbmdem_mean_*, lbm_mean.hip). Nothing is allocated or launched while no window is open; `every`
+// is 0 then, which is all lbmdem_forces_fluid looks at.
+struct MeanState {
+  bool on = false;
+  int mask = 0, every = 0;    // LBMDEM_MEAN_* of the window; every >= 1: the k-th fluid step since the window opened is sampled when k % every == 0
+  int nsel = 0;               // planes of doubles the mask selects
+  unsigned* cnt = nullptr;    // device [2][lx][sy]: n_fluid, n_grain
+  double* S = nullptr;        // device [nsel][lx][sy]: the selected planes in table order
+  long samples = 0, hook = 0; // samples in the window; fluid steps the hook has counted (lbmdem_mean_reset keeps it modulo `every`)
+  double* out = nullptr;      // [out_cap] scratch of lbmdem_mean_fields and lbmdem_mean_profile
+  long out_cap = 0;
 };
 
 // The passive scalar (lbmdem_scalar_*, lbm_scalar.hip). Nothing is allocated or launched while `on` is false.
@@ -328,6 +342,8 @@ struct lbmdem_handle {
   // two sections, the bands, the nodes the device refused to format (lbmdem_densities_stats)
   size_t dens_budget = 0;
   long dens_stats[4] = {0, 0, 0, 0};
+  MeanState mean;
+  int mean_output_mask = 0, mean_output_every = 0;   // lbmdem_set_mean_output: lbmdem_run_scene opens a window and writes mean%.6i.vtk, mean_profile%.6i.dat at every VTK event
   AsyncOut* aout = nullptr;   // null: frames, tables and checkpoints are written synchronously (the default)
   // lbmdem_set_checkpoint_every: lbmdem_run_scene saves to ckpt_path whenever the step counter reaches a multiple (0: never)
   long ckpt_every = 0;
@@ -501,6 +517,10 @@ LBMDEM_INTERNAL int lbmdem_tracer_launch(lbmdem_handle* h, const int* obst, bool
 // ... and lbmdem_set_scalar_output's line of <dir>/scalar.data (lbmdem_run_scene, at a DEM event)
 LBMDEM_INTERNAL int lbmdem_scalar_launch(lbmdem_handle* h, const int* obst, bool hook);
 LBMDEM_INTERNAL int lbmdem_scalar_data_line(lbmdem_handle* h, const char* dir);
+// the time averages (lbm_mean.hip): the hook of a fluid step (lbmdem_forces_fluid, behind the scalar step; called only while a
+// window with every >= 1 is open) counts the step and launches its sample when it is due, `obst` the map to read. Launches on the
+// handle's stream, does not synchronise.
+LBMDEM_INTERNAL int lbmdem_mean_hook(lbmdem_handle* h, const int* obst);
 // background frames and tables (lbmdem_output.hip): every queued job on disk, the writer joined, everything freed (-> off); the
 // writer's first unreported failure, if any, as this thread's error (LBMDEM_OK when there is none)
 LBMDEM_INTERNAL void lbmdem_async_release(lbmdem_handle* h);

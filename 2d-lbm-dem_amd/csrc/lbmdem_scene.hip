@@ -142,6 +142,8 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
     return sc->fluid ? lbmdem_run(h, k) : lbmdem_run_dem(h, k);
   };
   const long ck = comm ? 0 : h->ckpt_every;   // lbmdem_set_checkpoint_every: single-domain runs
+  const bool mean_out = dir && sc->fluid && !comm && h->mean_output_mask != 0;   // lbmdem_set_mean_output
+  if (mean_out) RC_TRY(lbmdem_mean_begin(h, h->mean_output_mask, h->mean_output_every));
   for (long s = first; s < end && !stopped;) {
     long e = cad.next(s, end);
     if (ck > 0) {   // the sub-step that brings the counter to the next multiple of the cadence ends a stretch as well
@@ -178,6 +180,10 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
       if (dir && sc->fluid && !comm && h->flow_output) RC_TRY(lbmdem_write_flow(h, dir, nfile));   // lbmdem_set_flow_output
       if (dir && sc->fluid && !comm && h->tracer_output) RC_TRY(lbmdem_write_tracers(h, dir, nfile));   // lbmdem_set_tracer_output
       if (dir && sc->fluid && !comm && h->scalar_output && h->scalar.on) RC_TRY(lbmdem_write_scalar(h, dir, nfile));   // lbmdem_set_scalar_output
+      if (mean_out && h->mean.samples > 0) {   // (the writers above have settled the handle: the count is that of the samples made)
+        RC_TRY(lbmdem_write_mean(h, dir, nfile));
+        RC_TRY(lbmdem_mean_reset(h));
+      }
       nfile++;
     }
     // (with strips the sub-step before was run by rank 0 on a full replica, lbmdem_comm_run: it holds the whole table)

@@ -85,6 +85,7 @@ int lbmdem_dist_enable(lbmdem_handle* h, int margin_rows) try {
   if (h->flow_output) return fail(LBMDEM_EINVAL, "the flow fields export is not available with distributed grains (lbmdem_set_flow_output(h, 0) first)");
   if (h->tracers.n > 0 || h->tracer_output) return fail(LBMDEM_EINVAL, "fluid tracers are not available with distributed grains (lbmdem_tracer_set(h, 0, NULL, 0) and lbmdem_set_tracer_output(h, 0) first)");
   if (h->scalar.on || h->scalar_output) return fail(LBMDEM_EINVAL, "the passive scalar is not available with distributed grains (lbmdem_scalar_set(h, NULL, 0, 0) and lbmdem_set_scalar_output(h, 0) first)");
+  if (h->mean.on || h->mean_output_mask) return fail(LBMDEM_EINVAL, "time averaging is not available with distributed grains (lbmdem_mean_end(h) and lbmdem_set_mean_output(h, 0, 0) first)");
   if (h->vib) return fail(LBMDEM_EINVAL, "vibrating walls are not available with distributed grains");
   if (h->probe.on) return fail(LBMDEM_EINVAL, "probes are not available with distributed grains (lbmdem_probe_disable first)");
   if (async_frames_on(h)) return fail(LBMDEM_EINVAL, "frames in the background are not available with distributed grains (lbmdem_set_async_output(h, 0) first)");

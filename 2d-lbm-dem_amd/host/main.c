@@ -59,6 +59,9 @@
  * Y0 <= y <= Y1 and 0 elsewhere, advected by the fluid and diffused on the device at every fluid step; scalar%.6i.vtk next to
  * every VTK frame and a line of scalar.data at every DEM event. T is the relaxation time, diffusivity (T - 0.5) / 3 in lattice
  * units; the default 0.53 gives 0.01, a dye that is stirred long before it spreads on its own. Single GPU only.
+ * --mean [EVERY]: time-averaged flow statistics (lbmdem_set_mean_output, every accumulator): every EVERY-th fluid step (default 1)
+ * is sampled on the device; mean%.6i.vtk -- mean fluid velocity, fluid fraction, fluctuation energy, Reynolds shear stress, mean
+ * density -- and mean_profile%.6i.dat next to every VTK frame, each over the fluid steps since the frame before. Single GPU only.
  * --gpus N: one process per GPU, rank k on device K + k; --devices a,b,c names the device of every rank instead (the
  * same device may appear twice: that is how the tests run several ranks on a one-GPU box, see tests/rccl_shim).
  */
@@ -87,6 +90,7 @@ static int g_flow = 0;           /* --flow */
 static int g_tracers = 0, g_tracers_nx = 0, g_tracers_ny = 0;   /* --tracers NXxNY */
 static int g_dye = 0, g_dye_box[4] = {0, 0, 0, 0};   /* --dye X0,Y0,X1,Y1 */
 static double g_dye_tau = 0.53;                      /* --dye-tau T */
+static int g_mean = 0;           /* --mean [EVERY] */
 static int g_coarse = 0, g_coarse_cw = 0, g_coarse_ch = 0;   /* --coarse CWxCH */
 static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
@@ -184,7 +188,7 @@ static int check_decomposition(int argc, char** argv, int gpus) {
     else if (!strcmp(argv[a], "--ly") && a + 1 < argc) ly = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--scale") && a + 1 < argc) scale = atof(argv[++a]);
     else if (argv[a][0] == '-' && argv[a][1] == '-' && strcmp(argv[a], "--comm") && strcmp(argv[a], "--dry") &&
-             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && strcmp(argv[a], "--async-output") && strcmp(argv[a], "--async-dem") && strcmp(argv[a], "--async-checkpoint") && a + 1 < argc) ++a;
+             strcmp(argv[a], "--vib") && strcmp(argv[a], "--run-stats") && strcmp(argv[a], "--async-output") && strcmp(argv[a], "--async-dem") && strcmp(argv[a], "--async-checkpoint") && strcmp(argv[a], "--mean") && a + 1 < argc) ++a;
     else if (argv[a][0] != '-' && !sample) sample = argv[a];
   }
   if (!sample) return 0;   /* run() prints the usage line */
@@ -256,6 +260,10 @@ int main(int argc, char** argv) {
         return EXIT_FAILURE;
       }
     }
+    if (!strcmp(argv[a], "--mean")) {
+      g_mean = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 1;
+      if (g_mean < 1) { fprintf(stderr, "--mean [EVERY]: every EVERY-th fluid step is sampled, EVERY at least 1\n"); return EXIT_FAILURE; }
+    }
     if (!strcmp(argv[a], "--run-stats")) g_run_stats = 1;
     if (!strcmp(argv[a], "--probes")) probes = 1;
     if (!strcmp(argv[a], "--dump-geometry") && a + 1 < argc) g_dump_geometry = argv[a + 1];
@@ -293,6 +301,8 @@ int main(int argc, char** argv) {
   if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_tracers && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--tracers is a single-GPU mode (the tracers need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_dye && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dye is a single-GPU mode (the passive scalar needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_mean && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--mean is a single-GPU mode (the time-averaged statistics need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_mean && g_dry) { fprintf(stderr, "--mean cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_dye && g_dry) { fprintf(stderr, "--dye cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_tracers && g_dry) { fprintf(stderr, "--tracers cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_flow && g_dry) { fprintf(stderr, "--flow cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
@@ -449,6 +459,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--tracers") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--dye") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--dye-tau") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--mean")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--run-stats")) {}
     else if (!strcmp(argv[a], "--async-output")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--async-dem")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
@@ -473,7 +484,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -557,6 +568,7 @@ static int run(int argc, char** argv) {
     free(dye);
     DIE(lbmdem_set_scalar_output(h, 1), "set_scalar_output");
   }
+  if (g_mean) DIE(lbmdem_set_mean_output(h, LBMDEM_MEAN_ALL, g_mean), "set_mean_output");
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */
   if (g_async_dem) DIE(lbmdem_set_async_dem(h, g_async_dem), "set_async_dem");

@@ -787,6 +787,122 @@ int lbmdem_scalar_stats(lbmdem_handle* h, long* counts3);
 int lbmdem_write_scalar(lbmdem_handle* h, const char* dir, int nfile);
 int lbmdem_write_scalar_files(const char* dir, int nfile, int lx, int ly, const double* C);   /* host only */
 int lbmdem_set_scalar_output(lbmdem_handle* h, int on);             /* 0: off (default) */
+/* Time-averaged flow statistics: what a run of this model is reported as -- the mean velocity field of a collapse or a slope
+ * flow, the fluctuation energy and the Reynolds shear stress around that mean, the mean density (pore pressure), how much of the
+ * time a node lies inside a grain. Every export above is an instant; these are sums over hundreds of fluid steps, accumulated
+ * on the device, one pass per sample. The reference has no such routine, so the contract is exact arithmetic, as for the flow
+ * fields: IEEE double, no contraction, every expression associated as written here; a restatement over the downloads named in
+ * the flow-fields block and lbmdem_mean_download reproduces every accumulator bit for bit.
+ * A window is a set of per-node accumulators, all +0.0 / 0 when it opens:
+ *   always            n_fluid[x][y], n_grain[x][y]  32-bit unsigned counts;  samples, a count on the host
+ *   LBMDEM_MEAN_U     Sux, Suy          a fluid node adds ux, uy
+ *   LBMDEM_MEAN_UU    Sxx, Sxy, Syy     a fluid node adds ux * ux, ux * uy, uy * uy (each product rounded, then added)
+ *   LBMDEM_MEAN_RHO   Srho, Srho2       a fluid node adds rho, rho * rho
+ *   LBMDEM_MEAN_DISS  Sdiss, Sgdot      a fluid node adds diss, gdot
+ *   LBMDEM_MEAN_GRAIN Sgux, Sguy        a grain's node adds ux, uy of the composite velocity (the grain's rigid-body velocity)
+ * planes of doubles; those outside the window's mask do not exist. rho, ux, uy, gdot, diss are those of the flow-fields block
+ * above: same inputs (f, obst, the present kinematics and walls; a hooked sample sees what a probe sample sees), same formulas,
+ * a lid not represented.
+ * One sample: at every node exactly one of three things happens. o == -1: n_fluid = n_fluid + 1 and S = S + v for every selected
+ * fluid plane. 0 <= o < nbgrains: n_grain = n_grain + 1 and Sgux = Sgux + ux, Sguy = Sguy + uy if selected. Anything else (the
+ * lattice-edge walls): nothing. A plane outside the node's class is left untouched (the same bits as adding +0.0: a chain from
+ * +0.0 never holds -0.0). A value that is not finite is accumulated as it comes. Then samples = samples + 1.
+ * Derived fields, planes [lx][ly] of doubles in ascending bit order of the field mask, count = (bits set) * lx * ly, with
+ * N = (double)samples, nf = (double)n_fluid[x][y], ng = (double)n_grain[x][y]:
+ *   LBMDEM_MEANF_PHI   phi   = nf / N                      LBMDEM_MEANF_SOLID solid = ng / N
+ *   LBMDEM_MEANF_UX    mux   = Sux / nf                    LBMDEM_MEANF_UY    muy   = Suy / nf
+ *   LBMDEM_MEANF_RXX   rxx   = (Sxx / nf) - (mux * mux)    LBMDEM_MEANF_RXY   rxy   = (Sxy / nf) - (mux * muy)
+ *   LBMDEM_MEANF_RYY   ryy   = (Syy / nf) - (muy * muy)
+ *   LBMDEM_MEANF_RHO   mrho  = Srho / nf                   LBMDEM_MEANF_VRHO  vrho  = (Srho2 / nf) - (mrho * mrho)
+ *   LBMDEM_MEANF_DISS  mdiss = Sdiss / nf                  LBMDEM_MEANF_GDOT  mgdot = Sgdot / nf
+ *   LBMDEM_MEANF_GUX   gux   = Sgux / ng                   LBMDEM_MEANF_GUY   guy   = Sguy / ng
+ * and +0.0 wherever the divisor count is 0. (rxx, ryy, vrho are differences of rounded numbers: they may come out a few ulp of the
+ * mean square below zero.) To SI units as in the flow-fields block; mean pore pressure P = (1. / 3.) * rho_moy * (mrho - 1.) * c^2.
+ * Profile: out[14][ly]; row k < 13 is, for every y, the chain from +0.0 over x ascending of derived field k (bit k above), row 13
+ * that of nf. A field whose accumulators the window does not hold gives a row of +0.0. The division by lx is left to the caller.
+ *   lbmdem_mean_begin           opens a window with the planes of `mask`. An open window is discarded; its memory is kept when
+ *                               the mask is the same and given back and allocated anew when it differs. The memory -- 8 bytes
+ *                               of counts and 8 per selected plane for every node of the padded lattice -- comes from the
+ *                               handle's pool. every >= 1: the k-th fluid step after this call, k = 1, 2, ..., is sampled when
+ *                               k % every == 0, on the handle's stream behind the force kernels, the probe sample, the tracer
+ *                               advance and the scalar step (lbmdem_forces_fluid; so in lbmdem_lbm_step, lbmdem_run,
+ *                               lbmdem_run_scene), from the map that step took. every == 0: samples by hand only.
+ *   lbmdem_mean_sample          one sample of the present state (f = lbmdem_download_f, obst = lbmdem_download_obst, the present
+ *                               kinematics and walls: what lbmdem_tracer_advance reads), on the handle's stream; does not
+ *                               synchronise.
+ *   lbmdem_mean_reset           zeroes the window: accumulators, counts, samples. The mask, `every` and the count of hooked fluid
+ *                               steps modulo `every` stay, so the cadence goes on as if nothing had happened.
+ *   lbmdem_mean_end             closes the window and gives the memory back. Nothing to do without one.
+ *   lbmdem_mean_stats           out5 = { 1 if a window is open else 0, its mask, samples, hook_steps: the fluid steps the hook has
+ *                               counted since lbmdem_mean_begin (after a reset: modulo every), bytes the window holds }.
+ *   lbmdem_mean_download        the raw accumulators: the selected planes as [lx][ly] in the order of the table above
+ *                               (*count = planes * lx * ly doubles, always set; a buffer of fewer is refused), n_fluid and n_grain
+ *                               as [lx][ly]. Settles and synchronises.
+ *   lbmdem_mean_fields          copies the derived planes of `fmask` to the host; *count, cap_doubles as lbmdem_flow_fields.
+ *                               A field whose accumulators are not in the window's mask is refused by name; a window without a
+ *                               sample is refused ("no sample has been taken"). Synchronises.
+ *   lbmdem_mean_fields_device   the same planes into the caller's DEVICE memory on the handle's stream; does not synchronise.
+ *   lbmdem_mean_profile         out[14][ly] (cap_doubles >= 14 * ly). Synchronises.
+ *   lbmdem_write_mean_files     host only, no handle, no device: <dir>/mean%.6i.vtk -- the binary rectilinear-mesh format of
+ *                               flow%.6i.vtk (same header, mesh and CELL_DATA / POINT_DATA lines, big-endian float, x fastest),
+ *                               "VECTORS mean_fluid_velocity_lb float\n" with (float)mux, (float)muy, 0 per node, then
+ *                               "SCALARS <name> float\nLOOKUP_TABLE default\n" with the payload for fluid_fraction (phi),
+ *                               fluctuation_energy (0.5 * (rxx + ryy)), reynolds_xy (rxy) and mean_density (mrho) -- and
+ *                               <dir>/mean_profile%.6i.dat: the line
+ *                               "# y samples phi solid mux muy rxx rxy ryy mrho vrho mdiss mgdot gux guy\n", then per y "%d %ld"
+ *                               of y and samples and thirteen " %le" of p / (double)lx for the profile's rows 0..12, "\n".
+ *                               Planes [lx][ly], profile14 = [14][ly]. lx, ly >= 2.
+ *   lbmdem_write_mean           the same two files of the handle's window (the planes downloaded, the image made on the host);
+ *                               a plane the window cannot give is +0.0, as its row of the profile is. Synchronises.
+ *   lbmdem_set_mean_output      mask != 0 (every >= 1): lbmdem_run_scene (comm == NULL) with the fluid and a directory opens a
+ *                               window (mask, every) at its start and, at every VTK event, after the frame and the other exports'
+ *                               files, provided samples > 0, calls lbmdem_write_mean with the event's nFile and resets the
+ *                               window: each file holds the averages since the event before. Synchronous. mask == 0: off (the
+ *                               default).
+ * Give-up recovery: a sample queued behind a launch of the multi-sub-step DEM kernel that gave up finds the stop word and adds
+ * nothing; the replay repeats those fluid steps and samples again, once each; samples and hook_steps follow.
+ * A sample only reads the step's state and writes the window: no call changes anything a later step reads. With no window open a
+ * fluid step pays one comparison on the host; nothing is allocated or launched. A checkpoint does not carry a window or the
+ * output setting: a loaded handle has none, and the file is byte for byte what a handle without one saves.
+ * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with a window open or the output on);
+ * the single-precision library (lbmdem_write_mean_files works there too); a mask of 0 or with bits beyond LBMDEM_MEAN_ALL /
+ * LBMDEM_MEANF_ALL; every < 0; null arguments; a short buffer; a sample, a reset or a read without a window; a directory that
+ * cannot be written ("cannot open"). Vibrating, probing, lid, tracer and scalar handles have the feature. Not built: windows on
+ * strips or in checkpoints, averages of vorticity or of the dye, weighted or several simultaneous windows, a device image kernel. */
+#define LBMDEM_MEAN_U 1
+#define LBMDEM_MEAN_UU 2
+#define LBMDEM_MEAN_RHO 4
+#define LBMDEM_MEAN_DISS 8
+#define LBMDEM_MEAN_GRAIN 16
+#define LBMDEM_MEAN_ALL 31
+#define LBMDEM_MEANF_PHI 1
+#define LBMDEM_MEANF_SOLID 2
+#define LBMDEM_MEANF_UX 4
+#define LBMDEM_MEANF_UY 8
+#define LBMDEM_MEANF_RXX 16
+#define LBMDEM_MEANF_RXY 32
+#define LBMDEM_MEANF_RYY 64
+#define LBMDEM_MEANF_RHO 128
+#define LBMDEM_MEANF_VRHO 256
+#define LBMDEM_MEANF_DISS 512
+#define LBMDEM_MEANF_GDOT 1024
+#define LBMDEM_MEANF_GUX 2048
+#define LBMDEM_MEANF_GUY 4096
+#define LBMDEM_MEANF_ALL 8191
+int lbmdem_mean_begin(lbmdem_handle* h, int mask, int every);
+int lbmdem_mean_sample(lbmdem_handle* h);
+int lbmdem_mean_reset(lbmdem_handle* h);
+int lbmdem_mean_end(lbmdem_handle* h);
+int lbmdem_mean_stats(lbmdem_handle* h, long* out5);
+int lbmdem_mean_download(lbmdem_handle* h, double* planes, unsigned* n_fluid, unsigned* n_grain, long cap_doubles, long* count);
+int lbmdem_mean_fields(lbmdem_handle* h, int fmask, double* out, long cap_doubles, long* count);
+int lbmdem_mean_fields_device(lbmdem_handle* h, int fmask, void* dev_out, long cap_doubles);
+int lbmdem_mean_profile(lbmdem_handle* h, double* out, long cap_doubles);
+int lbmdem_write_mean(lbmdem_handle* h, const char* dir, int nfile);
+int lbmdem_write_mean_files(const char* dir, int nfile, int lx, int ly, long samples, const double* phi, const double* mux,
+                            const double* muy, const double* rxx, const double* rxy, const double* ryy, const double* mrho,
+                            const double* profile14);   /* host only */
+int lbmdem_set_mean_output(lbmdem_handle* h, int mask, int every);   /* mask 0: off (default) */
 /* write_densities (main.c:482-566), the reference's ASCII, ParaView-readable dump of the fluid fields masked by the obstacle
  * map: <dir>/densities%.6i.vtk -- the reference's header ("Outfile domain LB t: %e" with the handle's clock, coordinates
  * (float)i * (1./lx) printed "%e " on both axes), a SCALARS Pressure section of "%.4lf\n" lines and a VECTORS VecVelocity
