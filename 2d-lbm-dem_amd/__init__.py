@@ -232,6 +232,8 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_checkpoint_every.argtypes = [C.c_void_p, C.c_long, C.c_char_p]
     L.lbmdem_checkpoint_digest.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
     L.lbmdem_checkpoint_verify.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+    L.lbmdem_set_checkpoint_contents.argtypes = [C.c_void_p, C.c_int]
+    L.lbmdem_checkpoint_contents.argtypes = [C.c_char_p, C.c_void_p]
     L.lbmdem_set_force_mode.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_set_dem_chain.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_dem_chain_paints.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
@@ -467,6 +469,9 @@ MEANF_NAMES = ("phi", "solid", "mux", "muy", "rxx", "rxy", "ryy", "mrho", "vrho"
 MEANF_ALL = 8191
 MEAN_PROFILE_ROWS = MEANF_NAMES + ("nf",)
 MEAN_COUNTERS = ("present", "mask", "samples", "hook_steps", "bytes")   # LbmDem.mean_stats
+# LBMDEM_CKPT_*: the optional state a checkpoint carries (LbmDem.set_checkpoint_contents, LbmDem.checkpoint_contents)
+CKPT_TRACERS, CKPT_SCALAR, CKPT_MEAN, CKPT_ALL = 1, 2, 4, 7
+CKPT_CONTENTS = ("mask", "tracers", "scalar_steps", "mean_mask", "mean_samples")
 
 
 def mean_plane_names(mask):
@@ -736,6 +741,20 @@ class LbmDem:
         has = C.c_int(0)
         _chk(load_library().lbmdem_checkpoint_verify(os.fsencode(path), C.byref(has)))
         return bool(has.value)
+
+    def set_checkpoint_contents(self, mask=CKPT_ALL):
+        """Every save of this handle (checkpoint_save, checkpoint_save_async, run_scene's cadence) adds what of CKPT_TRACERS |
+        CKPT_SCALAR | CKPT_MEAN it has at that moment; checkpoint_load restores whatever a file holds. 0: off (the default),
+        and then, or with nothing selected present, the file is the plain file byte for byte."""
+        _chk(self._L.lbmdem_set_checkpoint_contents(self._h, int(mask)))
+
+    @staticmethod
+    def checkpoint_contents(path):
+        """dict: what a checkpoint file carries beyond the plain state -- mask (CKPT_*), tracers, scalar_steps, mean_mask,
+        mean_samples; all 0 for a plain file. Host only, no device."""
+        out = np.zeros(5, np.int64)
+        _chk(load_library().lbmdem_checkpoint_contents(os.fsencode(path), _vp(out)))
+        return dict(zip(CKPT_CONTENTS, (int(v) for v in out)))
 
     @staticmethod
     def checkpoint_digest(data):

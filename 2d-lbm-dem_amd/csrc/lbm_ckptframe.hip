@@ -1,7 +1,8 @@
 // lbm_ckptframe.hip -- one checkpoint as the file holds it: the device-resident sections lbmdem_checkpoint_save dumps one by
 // one -- r, kin[kcur] (9n), fhf (3n), gp, V.offsets (n + 1 ints), V.nbr (offsets[n] ints, read here), V.wallflags (n bytes),
-// obst[ocur], the nine planes of f[fcur] -- gathered into a slot's staging by ONE launch on the handle's stream, with every
-// section's digest added up in the same pass (lbmdem_checkpoint_save_async; layout: CkptFrameJob, lbmdem_internal.h).
+// obst[ocur], the nine planes of f[fcur], and behind them the optional state a handle was told to save
+// (lbmdem_set_checkpoint_contents): the tracers' xy, the scalar's g[cur] and was, the window's cnt and S -- gathered into a
+// slot's staging by ONE launch on the handle's stream, with every section's digest added up in the same pass (lbmdem_checkpoint_save_async; layout: CkptFrameJob, lbmdem_internal.h).
 // Double-precision library only: the float build has no checkpoints.
 #include "lbmdem_internal.h"
 
@@ -102,13 +103,19 @@ __global__ __launch_bounds__(CKPT_BLOCK) void k_ckpt_frame(const CkptFrameJob J)
   ckpt_section<CKPT_WALLFLAGS>(J, J.bytes[CKPT_WALLFLAGS], part);
   ckpt_section<CKPT_OBST>(J, J.bytes[CKPT_OBST], part);
   ckpt_section<CKPT_F>(J, J.bytes[CKPT_F], part);
+  // the optional state: length 0 (nothing read, nothing written, no atomic) where the file does not carry it
+  ckpt_section<CKPT_TRACERS>(J, J.bytes[CKPT_TRACERS], part);
+  ckpt_section<CKPT_SCALAR_G>(J, J.bytes[CKPT_SCALAR_G], part);
+  ckpt_section<CKPT_SCALAR_WAS>(J, J.bytes[CKPT_SCALAR_WAS], part);
+  ckpt_section<CKPT_MEAN_CNT>(J, J.bytes[CKPT_MEAN_CNT], part);
+  ckpt_section<CKPT_MEAN_S>(J, J.bytes[CKPT_MEAN_S], part);
 }
 
 }  // namespace
 
 void launch_ckpt_frame(const CkptFrameJob& J, hipStream_t st) {
   size_t most = 1;
-  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) {
+  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) {   // all fourteen: the scalar's or the window's planes may be the longest
     const size_t chunks = (J.bytes[s] + 15) / 16;
     if (chunks > most) most = chunks;
   }

@@ -418,6 +418,7 @@ int lbmdem_mean_begin(lbmdem_handle* h, int mask, int every) try {
   M.every = every;
   M.samples = 0;
   M.hook = 0;
+  M.resumed = false;   // (a window begun by hand is no loaded one; lbmdem_checkpoint_load sets the mark behind this call)
   return mean_zero_launch(h);
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");

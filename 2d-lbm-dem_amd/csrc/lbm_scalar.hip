@@ -420,7 +420,12 @@ int lbmdem_scalar_set(lbmdem_handle* h, const double* C, double tau_s, int autom
   S.tau = tau_s;
   S.omega = 1. / tau_s;
   h->scalar = S;   // (from here on scalar_free gives everything back)
-  hipError_t e = hipMemcpyAsync(S.conc, C, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, h->stream);
+  // the padding columns (y >= ly) are written by no kernel: zero, so that the sections of a checkpoint that carries the scalar
+  // (lbmdem_set_checkpoint_contents) do not depend on what the allocations held before
+  hipError_t e = hipMemsetAsync(S.g[0], 0, sizeof(double) * (size_t)(SC_K * plane), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S.g[1], 0, sizeof(double) * (size_t)(SC_K * plane), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(S.was, 0, (size_t)plane, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(S.conc, C, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_scalar_init, sc_node_grid(L), dim3(SC_THREADS), 0, h->stream, S.conc, reader_obst(h), L.lx, L.ly, L.sy, plane,
                        S.g[0], S.was);

@@ -22,8 +22,7 @@
 namespace {
 
 #ifndef LBMDEM_SINGLE_PRECISION
-// positions (2 doubles) and the sample's scratch (3 doubles) of a set stay under 1 GiB together
-constexpr long TRACER_MAX = ((long)1 << 30) / (long)(5 * sizeof(double));
+// (TRACER_MAX, lbmdem_handle.h: positions, 2 doubles, and the sample's scratch, 3 doubles, of a set stay under 1 GiB together)
 constexpr int TR_THREADS = 256;
 
 struct TracerJob {

@@ -73,6 +73,9 @@ struct MeanState {
   long samples = 0, hook = 0; // samples in the window; fluid steps the hook has counted (lbmdem_mean_reset keeps it modulo `every`)
   double* out = nullptr;      // [out_cap] scratch of lbmdem_mean_fields and lbmdem_mean_profile
   long out_cap = 0;
+  // one shot: the window came out of a checkpoint (lbmdem_checkpoint_load) and nothing has been run on it since.
+  // lbmdem_run_scene goes on with such a window instead of opening a new one when it is the window it would open.
+  bool resumed = false;
 };
 
 // The passive scalar (lbmdem_scalar_*, lbm_scalar.hip). Nothing is allocated or launched while `on` is false.
@@ -91,6 +94,8 @@ struct ScalarState {
 };
 
 // Fluid tracers (lbmdem_tracer_*, lbm_tracers.hip). Nothing is allocated or launched while n == 0.
+// positions (2 doubles) and the sample's scratch (3 doubles) of a set stay under 1 GiB together
+constexpr long TRACER_MAX = ((long)1 << 30) / (long)(5 * sizeof(double));
 struct TracerState {
   long n = 0;
   bool automatic = false;     // every fluid step advances the set once (lbmdem_forces_fluid, behind the probe sample)
@@ -119,11 +124,30 @@ struct ProbeState {
 // slot's pinned buffer on the copy stream behind an event, and written by the writer thread once the copy's event has completed.
 // A slot is free again when its files are closed: staging and pinned buffer are never overwritten while anything reads them.
 // Nothing of this exists while the three features are off.
+// The header of a checkpoint's extension (lbmdem_set_checkpoint_contents; the byte layout is in include/lbmdem_hip.h): what the
+// host knows of the optional state the file carries. The five sections it announces follow it -- tracers (16 tr_n bytes),
+// scalar_g (40 plane), scalar_was (plane), mean_cnt (8 plane), mean_S (8 mn_nsel plane) --, each absent (length 0) when its bit
+// of `mask` is clear.
+struct CkptExtra {
+  char magic[8];       // "LBMXTRA1"
+  int mask, pad0;      // LBMDEM_CKPT_* of what follows
+  long plane;          // sanity: lx * sy of the writer
+  long tr_n;           // tracers: TracerState's n, automatic, advances, hook
+  int tr_automatic, pad1;
+  long tr_advances, tr_hook;
+  double sc_tau;       // scalar: ScalarState's tau, automatic, steps, hook (omega is formed from tau again)
+  int sc_automatic, pad2;
+  long sc_steps, sc_hook;
+  int mn_mask, mn_every, mn_nsel, pad3;   // window: MeanState's mask, every, nsel, samples, hook
+  long mn_samples, mn_hook;
+};
+static_assert(sizeof(CkptExtra) == 120, "the extension header has the documented layout");
 struct CkptShot {      // the host's side of a checkpoint's header as it stood when the checkpoint was queued. The pair list's
   lbmdem_config cfg;   // length, the carries and the sections' digests come back with the copy (the staging's word area).
   long nbsteps = 0, plane = 0;   // (cfg: incl. the clock and the walls)
   double lid6 = 0;
   int force_mode = 0, diag_always = 0, verlet_ok = 0, vib = 0;
+  CkptExtra xtra{};    // mask == 0: the file has no extension
 };
 struct AsyncSlot {
   void* staging = nullptr;   // device, AsyncLane::bytes
@@ -135,7 +159,10 @@ struct AsyncSlot {
   // when the event was queued, the checkpoint's header
   int nfile = 0, with_forces = 0;
   double stats22[22];
+  // a checkpoint is laid out job by job: optional state can appear or vanish between two queued checkpoints
   CkptShot shot;
+  CkptLayout ckpt_layout{};   // where the job's sections lie in staging and pinned buffer
+  size_t ckpt_bytes = 0;      // the job's copy: ckpt_layout.total, never more than AsyncLane::bytes
 };
 // The counters of lbmdem_output_stats / lbmdem_output_stats_dem / lbmdem_output_stats_checkpoint: each kind has its own set,
 // reset when its slots change
@@ -167,7 +194,6 @@ struct AsyncOut {
   AsyncLane lane[ASYNC_KINDS];
   double* dem_scratch = nullptr;             // device: the addends of the ten sums [10][n], then the 22 numbers (k_dem_stats)
   double* dem_stats_host = nullptr;          // pinned [22]
-  CkptLayout ckpt_layout{};                  // of the handle: n grains, the pair list at its capacity, the slab
   hipStream_t copy_stream = nullptr;
   std::thread writer;
   std::mutex mu;
@@ -348,6 +374,7 @@ struct lbmdem_handle {
   // lbmdem_set_checkpoint_every: lbmdem_run_scene saves to ckpt_path whenever the step counter reaches a multiple (0: never)
   long ckpt_every = 0;
   char ckpt_path[4096] = "";
+  int ckpt_contents = 0;   // lbmdem_set_checkpoint_contents: the LBMDEM_CKPT_* every save adds where the handle has them (0: none)
   // KE, PE, SE, IFR, WF, INCE, TSLIP, TRW of the last write_DEM of lbmdem_run_scene: its "steps" line prints them (main.c:1885-1889)
   double scene_energies[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int force_mode = 0;
@@ -533,9 +560,12 @@ static inline bool async_ckpt_on(const lbmdem_handle* h) { return lane_on(h, ASY
 // lbmdem_checkpoint.hip, for the background writer (lbmdem_output.hip): what a slot's launch reads, and the file of a slot
 // whose copy has arrived -- header, sections, digest trailer to `<path>.tmp`, then renamed onto `<path>`; on failure the text
 // goes to `msg`, the .tmp file is removed and `<path>` is not touched
+// lbmdem_ckpt_extra: the extension header of the handle as it stands -- what lbmdem_set_checkpoint_contents selects and the handle
+// has (X->mask == 0: none) -- and the layout of a file with it, the pair list at its capacity
+LBMDEM_INTERNAL CkptLayout lbmdem_ckpt_extra(const lbmdem_handle* h, CkptExtra* X);
 LBMDEM_INTERNAL void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned char* staging, CkptFrameJob* J);
 LBMDEM_INTERNAL int lbmdem_ckpt_save_replacing(lbmdem_handle* h, const char* path);
-LBMDEM_INTERNAL int lbmdem_ckpt_write_slot(const AsyncSlot* S, const CkptLayout* Y, char* msg, size_t msglen);
+LBMDEM_INTERNAL int lbmdem_ckpt_write_slot(const AsyncSlot* S, char* msg, size_t msglen);
 LBMDEM_INTERNAL int lbmdem_async_report(lbmdem_handle* h);
 // the next obst_construction will update obst[1 - ocur] in place: nobody resets that canvas beforehand
 static inline bool obst_update_planned(const lbmdem_handle* h) {

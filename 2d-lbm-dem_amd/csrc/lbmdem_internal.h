@@ -325,34 +325,43 @@ void launch_dem_frame(const DemTableView& T, double* rows, double* addends, hipS
 // the 22 numbers of the stats.data line from the table and the addends ([0], the time, is left 0 for the host)
 void launch_dem_stats(const DemTableView& T, const double* addends, double* stats22, hipStream_t st);
 // lbm_ckptframe.hip (double build): the device-resident sections of a checkpoint gathered into one staging buffer by ONE launch,
-// in the order lbmdem_checkpoint_save dumps them -- r, kin, fhf, gp, V.offsets, V.nbr, V.wallflags, obst, f -- with each
-// section's digest (S1 = sum of its little-endian 64-bit words, S2 = sum of (index + 1) * word, both mod 2^64, the last word
-// zero-padded) added up in the same pass. The staging starts with a word area of CKPT_WORDS_BYTES: 64-bit words [0] the pair
-// list's length offsets[n], [1..3] the three carries, [4 + 2 s], [5 + 2 s] S1, S2 of section s; the area must be zero when
-// the launch begins. Section s follows at at[s], a multiple of 16.
-constexpr int CKPT_DEV_SECTIONS = 9;
-enum : int { CKPT_R = 0, CKPT_KIN, CKPT_FHF, CKPT_GP, CKPT_OFFSETS, CKPT_NBR, CKPT_WALLFLAGS, CKPT_OBST, CKPT_F };
+// in the order lbmdem_checkpoint_save dumps them -- r, kin, fhf, gp, V.offsets, V.nbr, V.wallflags, obst, f, then the five
+// sections of the optional state (lbmdem_set_checkpoint_contents): the tracers' xy, the scalar's g[cur] and was, the window's
+// cnt and S, each of length 0 where the file does not carry it -- with each section's digest (S1 = sum of its little-endian
+// 64-bit words, S2 = sum of (index + 1) * word, both mod 2^64, the last word zero-padded) added up in the same pass. The staging
+// starts with a word area of CKPT_WORDS_BYTES: 64-bit words [0] the pair list's length offsets[n], [1..3] the three carries,
+// [4 + 2 s], [5 + 2 s] S1, S2 of section s; the area must be zero when the launch begins. Section s follows at at[s], a multiple
+// of 16.
+constexpr int CKPT_DEV_SECTIONS = 9;     // the sections of every file
+constexpr int CKPT_XTRA_SECTIONS = 5;    // ... and those of the optional state
+constexpr int CKPT_ALL_SECTIONS = CKPT_DEV_SECTIONS + CKPT_XTRA_SECTIONS;
+enum : int { CKPT_R = 0, CKPT_KIN, CKPT_FHF, CKPT_GP, CKPT_OFFSETS, CKPT_NBR, CKPT_WALLFLAGS, CKPT_OBST, CKPT_F,
+             CKPT_TRACERS, CKPT_SCALAR_G, CKPT_SCALAR_WAS, CKPT_MEAN_CNT, CKPT_MEAN_S };
+// The word area is exactly full: 4 + 2 * 14 = 32 words of 8 bytes. A fifteenth section needs a larger area.
 constexpr size_t CKPT_WORDS_BYTES = 256;
+static_assert(8 * (4 + 2 * CKPT_ALL_SECTIONS) == CKPT_WORDS_BYTES, "the word area holds the digests of every section");
 struct CkptLayout {
-  size_t bytes[CKPT_DEV_SECTIONS];   // section lengths as the file holds them (CKPT_NBR: at the list's capacity)
-  size_t at[CKPT_DEV_SECTIONS];      // where each starts in the staging
+  size_t bytes[CKPT_ALL_SECTIONS];   // section lengths as the file holds them (CKPT_NBR: at the list's capacity)
+  size_t at[CKPT_ALL_SECTIONS];      // where each starts in the staging
   size_t total;                      // staging bytes
 };
-static inline CkptLayout ckpt_layout(int n, long nbr_cap, long plane) {
+// `xtra`: the lengths of the five sections of the optional state (null: a file without them)
+static inline CkptLayout ckpt_layout(int n, long nbr_cap, long plane, const size_t* xtra = nullptr) {
   CkptLayout Y;
   const size_t N = (size_t)n;
   Y.bytes[CKPT_R] = 8 * N; Y.bytes[CKPT_KIN] = 72 * N; Y.bytes[CKPT_FHF] = 24 * N; Y.bytes[CKPT_GP] = 8 * N;
   Y.bytes[CKPT_OFFSETS] = 4 * (N + 1); Y.bytes[CKPT_NBR] = 4 * (size_t)nbr_cap; Y.bytes[CKPT_WALLFLAGS] = N;
   Y.bytes[CKPT_OBST] = 4 * (size_t)plane; Y.bytes[CKPT_F] = 72 * (size_t)plane;
+  for (int s = 0; s < CKPT_XTRA_SECTIONS; ++s) Y.bytes[CKPT_DEV_SECTIONS + s] = xtra ? xtra[s] : 0;
   size_t at = CKPT_WORDS_BYTES;
-  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) { Y.at[s] = at; at += (Y.bytes[s] + 15) / 16 * 16; }
+  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) { Y.at[s] = at; at += (Y.bytes[s] + 15) / 16 * 16; }
   Y.total = at;
   return Y;
 }
 struct CkptFrameJob {
-  const void* src[CKPT_DEV_SECTIONS];   // null: the section is all zero (the offsets of a handle without a pair list)
-  size_t bytes[CKPT_DEV_SECTIONS];      // (CKPT_NBR: the capacity; the launch itself takes 4 * *nnbr, never more than this)
-  size_t at[CKPT_DEV_SECTIONS];
+  const void* src[CKPT_ALL_SECTIONS];   // null: the section is all zero (the offsets of a handle without a pair list)
+  size_t bytes[CKPT_ALL_SECTIONS];      // (CKPT_NBR: the capacity; the launch itself takes 4 * *nnbr, never more than this)
+  size_t at[CKPT_ALL_SECTIONS];
   const int* nnbr;                      // &V.offsets[n]; null: no pair list, 0 entries
   const double* carry;                  // [3]
   unsigned char* staging;

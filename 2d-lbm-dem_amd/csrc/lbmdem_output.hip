@@ -474,7 +474,7 @@ static void async_writer(AsyncOut* a) {
         break;
 #ifndef LBMDEM_SINGLE_PRECISION
       case ASYNC_CKPT:
-        code = lbmdem_ckpt_write_slot(&S, &a->ckpt_layout, msg, sizeof msg);
+        code = lbmdem_ckpt_write_slot(&S, msg, sizeof msg);   // (from the slot's own layout)
         break;
 #endif
     }
@@ -592,11 +592,11 @@ static void async_release_if_unused(lbmdem_handle* h) {
   lbmdem_async_release(h);
 }
 
-// A kind's number of slots changes (`who`: the setter, `noun`: what a slot holds). The request is carried out first: everything
-// queued is written, the old slots are freed, the new ones made, `bytes` of device staging and of pinned host memory each; a
-// failure of the writer that nobody has been told about is taken out beforehand and is what the call then returns.
+// A kind's number of slots changes, or their size (`who`: the setter, `noun`: what a slot holds). The request is carried out
+// first: everything queued is written, the old slots are freed, the new ones made, `bytes` of device staging and of pinned host
+// memory each; a failure of the writer that nobody has been told about is taken out beforehand and is what the call then returns.
 static int lane_resize(lbmdem_handle* h, int kind, int slots, size_t bytes, const char* who, const char* noun) {
-  if ((h->aout ? h->aout->lane[kind].slots : 0) == slots) return LBMDEM_OK;
+  if ((h->aout ? h->aout->lane[kind].slots : 0) == slots && (slots == 0 || h->aout->lane[kind].bytes == bytes)) return LBMDEM_OK;
   int old_code = LBMDEM_OK, old_kind = ASYNC_FRAME;
   char old_msg[sizeof AsyncOut::err_msg];
   if (AsyncOut* a = h->aout) {
@@ -887,10 +887,11 @@ int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots) {
   if (slots < 0 || slots > LBMDEM_ASYNC_MAX_CKPT)
     return fail(LBMDEM_EINVAL, "lbmdem_set_async_checkpoint: slots must be 0..%d, not %d", LBMDEM_ASYNC_MAX_CKPT, slots);
   if (slots > 0) RC_TRY(whole_handle(h, "lbmdem_set_async_checkpoint", CKPT_THERE));
-  const CkptLayout Y = ckpt_layout(h->n, h->V.cap, h->L.plane);   // (the same whenever it is asked for: none of the three changes)
-  const int rc = lane_resize(h, ASYNC_CKPT, slots, Y.total, "lbmdem_set_async_checkpoint", "checkpoint");
-  if (async_ckpt_on(h)) h->aout->ckpt_layout = Y;
-  return rc;
+  // the file of the handle as it stands: with the optional state lbmdem_set_checkpoint_contents selects, where the handle has
+  // it now (lbmdem_checkpoint_save_async makes the slots larger when a later checkpoint needs more)
+  CkptExtra X;
+  const CkptLayout Y = lbmdem_ckpt_extra(h, &X);
+  return lane_resize(h, ASYNC_CKPT, slots, Y.total, "lbmdem_set_async_checkpoint", "checkpoint");
 #endif
 }
 
@@ -906,21 +907,36 @@ int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
   if (strlen(path) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: path too long");
   if (h->obst_pending) return fail(LBMDEM_EINVAL, "checkpoint between obst_construction and collide_stream");
   RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
+  // the layout is the job's: optional state may have appeared or gone since the last checkpoint was queued
+  CkptExtra X;
+  const CkptLayout Y = lbmdem_ckpt_extra(h, &X);
+  if (Y.total > a->lane[ASYNC_CKPT].bytes) {   // the state has outgrown the slots: as many, larger ones (drains the lane first)
+    const int slots = a->lane[ASYNC_CKPT].slots;
+    AsyncCounters kept;
+    { std::unique_lock<std::mutex> lk(a->mu); async_wait_idle(a, lk); kept = a->lane[ASYNC_CKPT].c; }
+    const int rc = lane_resize(h, ASYNC_CKPT, slots, Y.total, "lbmdem_checkpoint_save_async", "checkpoint");
+    a = h->aout;   // (LBMDEM_ENOMEM: the lane is as lane_resize leaves it, off, and `a` may be gone with it)
+    if (async_ckpt_on(h)) { std::lock_guard<std::mutex> lk(a->mu); a->lane[ASYNC_CKPT].c = kept; }   // the counters are the feature's, not the slots'
+    RC_TRY(rc);
+  }
   const int s = lane_acquire(a, ASYNC_CKPT);
   const auto t_hold = std::chrono::steady_clock::now();
   AsyncSlot& S = a->lane[ASYNC_CKPT].slot[s];
   strcpy(S.path, path);
+  S.ckpt_layout = Y;
+  S.ckpt_bytes = Y.total;
+  S.shot.xtra = X;
   // the host's side of the header, as of now: the run goes on behind this call
   S.shot.cfg = h->cfg; S.shot.nbsteps = h->nbsteps; S.shot.plane = h->L.plane; S.shot.lid6 = h->L.lid6;
   S.shot.force_mode = h->force_mode; S.shot.diag_always = h->diag_always ? 1 : 0; S.shot.verlet_ok = h->verlet_ok ? 1 : 0;
   S.shot.vib = h->vib ? 1 : 0;
   if (h->carry_from < h->substep_seq) launch_carry_resolve(h->ct, h->carry_from, h->stream);   // as lbmdem_checkpoint_save
   CkptFrameJob J;
-  lbmdem_ckpt_frame_job(h, a->ckpt_layout, static_cast<unsigned char*>(S.staging), &J);
+  lbmdem_ckpt_frame_job(h, S.ckpt_layout, static_cast<unsigned char*>(S.staging), &J);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemsetAsync(S.staging, 0, CKPT_WORDS_BYTES, h->stream);   // the digests are sums: from zero
   if (e == hipSuccess) { launch_ckpt_frame(J, h->stream); e = hipGetLastError(); }
-  if (e == hipSuccess) e = slot_copy_behind(h, a, S, a->lane[ASYNC_CKPT].bytes);
+  if (e == hipSuccess) e = slot_copy_behind(h, a, S, S.ckpt_bytes);   // the job's bytes, not the lane's capacity
   if (e != hipSuccess) {
     lane_abandon(a, S);
     HIP_TRY(e);

@@ -143,7 +143,12 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
   };
   const long ck = comm ? 0 : h->ckpt_every;   // lbmdem_set_checkpoint_every: single-domain runs
   const bool mean_out = dir && sc->fluid && !comm && h->mean_output_mask != 0;   // lbmdem_set_mean_output
-  if (mean_out) RC_TRY(lbmdem_mean_begin(h, h->mean_output_mask, h->mean_output_every));
+  {   // a window that has just come out of a checkpoint goes on where it was when it is the window this call would open
+    const bool resume = mean_out && h->mean.on && h->mean.resumed && h->mean.mask == h->mean_output_mask &&
+                        h->mean.every == h->mean_output_every;
+    h->mean.resumed = false;   // (one shot, whatever this call does)
+    if (mean_out && !resume) RC_TRY(lbmdem_mean_begin(h, h->mean_output_mask, h->mean_output_every));
+  }
   for (long s = first; s < end && !stopped;) {
     long e = cad.next(s, end);
     if (ck > 0) {   // the sub-step that brings the counter to the next multiple of the cadence ends a stretch as well

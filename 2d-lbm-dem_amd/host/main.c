@@ -96,6 +96,7 @@ static int g_async_frames = 0;   /* --async-output [N] */
 static int g_async_dem = 0;      /* --async-dem [N] */
 static int g_async_ckpt = 0;     /* --async-checkpoint [N] */
 static long g_ckpt_every = 0;    /* --checkpoint-every N */
+static int g_ckpt_state = 0;     /* --checkpoint-state */
 /* the optional count behind --async-output: all digits */
 static int is_count(const char* s) {
   if (!s || !*s) return 0;
@@ -272,6 +273,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--async-dem")) g_async_dem = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 2;
     if (!strcmp(argv[a], "--async-checkpoint")) g_async_ckpt = (a + 1 < argc && is_count(argv[a + 1])) ? atoi(argv[a + 1]) : 1;
     if (!strcmp(argv[a], "--checkpoint-every") && a + 1 < argc) g_ckpt_every = atol(argv[a + 1]);
+    if (!strcmp(argv[a], "--checkpoint-state")) g_ckpt_state = 1;
     if (!strcmp(argv[a], "--verify-checkpoint") && a + 1 < argc) {   /* host only: no device is touched */
       int has = 0;
       if (lbmdem_checkpoint_verify(argv[a + 1], &has) != LBMDEM_OK) { fprintf(stderr, "verify-checkpoint: %s\n", lbmdem_last_error()); return EXIT_FAILURE; }
@@ -311,6 +313,7 @@ int main(int argc, char** argv) {
   if (g_async_dem && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--async-dem is a single-GPU mode (with --gpus N rank 0 runs the table sub-step on a full replica and writes the tables itself)\n"); return EXIT_FAILURE; }
   if ((g_async_ckpt || g_ckpt_every) && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--checkpoint-every and --async-checkpoint are single-GPU modes (with --gpus N every rank saves its own file at the end)\n"); return EXIT_FAILURE; }
   if (g_ckpt_every < 0) { fprintf(stderr, "--checkpoint-every N: a number of DEM steps\n"); return EXIT_FAILURE; }
+  if (g_ckpt_state && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--checkpoint-state is a single-GPU mode (a strip's checkpoint holds the strip and nothing else)\n"); return EXIT_FAILURE; }
   if (gpus <= 1) return run(argc, argv);
   g_world = gpus; g_use_comm = 1;
   { /* every strip must be at least one margin wide (lbmdem_dist_enable would refuse on the ranks whose strip is one
@@ -465,6 +468,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--async-dem")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--async-checkpoint")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--checkpoint-every") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--checkpoint-state")) {}
     else if (!strcmp(argv[a], "--vib-freq") && a + 1 < argc) vib_freq = atof(argv[++a]);
     else if (!strcmp(argv[a], "--vib-amp") && a + 1 < argc) vib_amp = atof(argv[++a]);
     else if (!strcmp(argv[a], "--probes") && a + 1 < argc) probe_path = argv[++a];
@@ -484,7 +488,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -531,6 +535,7 @@ static int run(int argc, char** argv) {
   }
   lbmdem_handle* h = NULL;
   long nbsteps = 0;
+  int got_tracers = 0, got_dye = 0;   /* --restart: the file carried them, and they are not seeded again */
   if (ckpt_in) {
     DIE(lbmdem_checkpoint_load(ckpt_in, cfg.device, &h), "checkpoint_load");
     DIE(lbmdem_get_config(h, &cfg), "get_config");
@@ -540,13 +545,28 @@ static int run(int argc, char** argv) {
     }
     nbsteps = lbmdem_nbsteps(h);
     SAY("Restarted from %s at step %ld\n", ckpt_in, nbsteps);
+    if (!g_use_comm) {   /* what of the optional state came back with the file (--checkpoint-state of the run that wrote it) */
+      long tr[3], sc[3], mn[5];
+      DIE(lbmdem_tracer_stats(h, tr), "tracer_stats");
+      DIE(lbmdem_scalar_stats(h, sc), "scalar_stats");
+      DIE(lbmdem_mean_stats(h, mn), "mean_stats");
+      got_tracers = tr[0] > 0; got_dye = sc[0] != 0;
+      if (got_tracers || got_dye || mn[0]) {
+        SAY("Restored with it:");
+        if (got_tracers) SAY(" %ld tracers (%ld advances)", tr[0], tr[1]);
+        if (got_dye) SAY(" the dye (%ld steps)", sc[1]);
+        if (mn[0]) SAY(" an averaging window (mask %ld, %ld samples)", mn[1], mn[2]);
+        SAY("\n");
+      }
+    }
   } else {
     DIE(lbmdem_create(&cfg, r, x1, x2, &h), "create");
   }
   if (g_contacts) DIE(lbmdem_set_contacts_output(h, 1), "set_contacts_output");
   if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");
   if (g_coarse) DIE(lbmdem_set_coarse_output(h, g_coarse_cw, g_coarse_ch), "set_coarse_output");
-  if (g_tracers) {   /* a uniform grid over the whole domain; automatic advance, a file per frame */
+  if (g_tracers && got_tracers) DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");   /* the loaded set goes on: tracer k stays tracer k */
+  else if (g_tracers) {   /* a uniform grid over the whole domain; automatic advance, a file per frame */
     const long nt = (long)g_tracers_nx * g_tracers_ny;
     double* xy = (double*)malloc(sizeof(double) * 2 * (size_t)nt);
     if (!xy) { fprintf(stderr, "--tracers: out of memory\n"); return EXIT_FAILURE; }
@@ -559,7 +579,8 @@ static int run(int argc, char** argv) {
     free(xy);
     DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");
   }
-  if (g_dye) {   /* C = 1 in the box (cut to the lattice), 0 elsewhere; automatic step, a file per frame, a line per DEM event */
+  if (g_dye && got_dye) DIE(lbmdem_set_scalar_output(h, 1), "set_scalar_output");   /* the loaded field goes on */
+  else if (g_dye) {   /* C = 1 in the box (cut to the lattice), 0 elsewhere; automatic step, a file per frame, a line per DEM event */
     double* dye = (double*)calloc((size_t)cfg.lx * cfg.ly, sizeof(double));
     if (!dye) { fprintf(stderr, "--dye: out of memory\n"); return EXIT_FAILURE; }
     for (int x = g_dye_box[0]; x <= g_dye_box[2] && x < cfg.lx; ++x)
@@ -568,7 +589,8 @@ static int run(int argc, char** argv) {
     free(dye);
     DIE(lbmdem_set_scalar_output(h, 1), "set_scalar_output");
   }
-  if (g_mean) DIE(lbmdem_set_mean_output(h, LBMDEM_MEAN_ALL, g_mean), "set_mean_output");
+  if (g_mean) DIE(lbmdem_set_mean_output(h, LBMDEM_MEAN_ALL, g_mean), "set_mean_output");   /* (a loaded window with this mask and cadence goes on: lbmdem_run_scene) */
+  if (g_ckpt_state) DIE(lbmdem_set_checkpoint_contents(h, LBMDEM_CKPT_ALL), "set_checkpoint_contents");   /* every save below */
   if (g_vib) DIE(lbmdem_set_vibration(h, 1), "set_vibration");   /* (a restarted vibrating run vibrates anyway) */
   if (g_async_frames) DIE(lbmdem_set_async_output(h, g_async_frames), "set_async_output");   /* set-up, like create: before the clock starts */
   if (g_async_dem) DIE(lbmdem_set_async_dem(h, g_async_dem), "set_async_dem");

@@ -687,7 +687,8 @@ int lbmdem_set_flow_output(lbmdem_handle* h, int on);               /* 0: off (d
  * nothing; the replay repeats those fluid steps and advances again, once each, and the counts follow.
  * The advance only reads the step's state and writes the tracers' own buffer: no call changes anything a later step reads. With
  * no tracers set nothing is allocated or launched. A checkpoint does not carry tracers or the output setting: a loaded handle has
- * none, and the file is byte for byte what a handle without tracers saves.
+ * none, and the file is byte for byte what a handle without tracers saves -- unless lbmdem_set_checkpoint_contents has
+ * LBMDEM_CKPT_TRACERS on: then the positions and the two counts are in the file and come back with it (never the output setting).
  * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with tracers set or the output on); the
  * single-precision library (lbmdem_write_tracers_files works there too); null arguments; a short buffer; a bad position or count;
  * a directory that cannot be written ("cannot open"). Vibrating, probing and lid handles have the feature. */
@@ -771,7 +772,9 @@ int lbmdem_set_tracer_output(lbmdem_handle* h, int on);             /* 0: off (d
  * nothing; the replay repeats those fluid steps and steps the field again, once each, and the counts follow.
  * The step only reads the fluid's state and writes the scalar's own buffers: no call changes anything a later fluid step or DEM
  * sub-step reads. With no scalar set nothing is allocated or launched. A checkpoint does not carry the scalar or the output
- * setting: a loaded handle has none, and the file is byte for byte what a handle without one saves.
+ * setting: a loaded handle has none, and the file is byte for byte what a handle without one saves -- unless
+ * lbmdem_set_checkpoint_contents has LBMDEM_CKPT_SCALAR on: then the populations, the fluid flags of the last step, tau_s and the
+ * counts are in the file and come back with it (never the output setting).
  * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with a scalar set or the output on); the
  * single-precision library (lbmdem_write_scalar_files works there too); null arguments; tau_s <= 0.5 or not finite; a value of C
  * that is not finite; a download, the sums or the file without a scalar; a directory that cannot be written ("cannot open").
@@ -863,12 +866,14 @@ int lbmdem_set_scalar_output(lbmdem_handle* h, int on);             /* 0: off (d
  * nothing; the replay repeats those fluid steps and samples again, once each; samples and hook_steps follow.
  * A sample only reads the step's state and writes the window: no call changes anything a later step reads. With no window open a
  * fluid step pays one comparison on the host; nothing is allocated or launched. A checkpoint does not carry a window or the
- * output setting: a loaded handle has none, and the file is byte for byte what a handle without one saves.
+ * output setting: a loaded handle has none, and the file is byte for byte what a handle without one saves -- unless
+ * lbmdem_set_checkpoint_contents has LBMDEM_CKPT_MEAN on: then the window's mask, `every`, accumulators and counts are in the file
+ * and come back with it, hook_steps included, so that the k-th-step rule goes on in phase (never the output setting).
  * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with a window open or the output on);
  * the single-precision library (lbmdem_write_mean_files works there too); a mask of 0 or with bits beyond LBMDEM_MEAN_ALL /
  * LBMDEM_MEANF_ALL; every < 0; null arguments; a short buffer; a sample, a reset or a read without a window; a directory that
  * cannot be written ("cannot open"). Vibrating, probing, lid, tracer and scalar handles have the feature. Not built: windows on
- * strips or in checkpoints, averages of vorticity or of the dye, weighted or several simultaneous windows, a device image kernel. */
+ * strips, averages of vorticity or of the dye, weighted or several simultaneous windows, a device image kernel. */
 #define LBMDEM_MEAN_U 1
 #define LBMDEM_MEAN_UU 2
 #define LBMDEM_MEAN_RHO 4
@@ -1011,7 +1016,45 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out);
  * behind their slot. LBMDEM_EINVAL: slots outside 0..2, lbmdem_checkpoint_save_async while off, a strip of a decomposition or
  * distributed grains (and lbmdem_dist_enable on a handle that has either setting on), the single-precision library (it has no
  * checkpoints). LBMDEM_ENOMEM: the slots cannot be had (then the feature is off). Vibrating and probing handles have it. A
- * checkpoint carries neither setting. */
+ * checkpoint carries neither setting.
+ *
+ * The optional state. lbmdem_set_checkpoint_contents(h, mask), mask an OR of LBMDEM_CKPT_TRACERS, LBMDEM_CKPT_SCALAR,
+ * LBMDEM_CKPT_MEAN (0: off, the default), makes every save of the handle -- lbmdem_checkpoint_save, lbmdem_checkpoint_save_async,
+ * the cadence of lbmdem_run_scene -- add what of the three the handle has at that moment: the tracers (positions, `automatic`,
+ * both counts), the passive scalar (populations, the fluid flags `was`, tau_s, `automatic`, both counts; omega is formed from
+ * tau_s again, scratch buffers are not stored) and the open averaging window (mask, `every`, n_fluid, n_grain, the selected
+ * planes, samples and hook_steps). lbmdem_checkpoint_load needs no setting: it restores whatever the file holds, through the same
+ * allocations as lbmdem_tracer_set, lbmdem_scalar_set and lbmdem_mean_begin, and a run continued from the file is bit-identical
+ * in all three to the uninterrupted one. With the mask 0, or with nothing of the mask present on the handle, the file is the
+ * plain file byte for byte and its trailer "LBMCKSM1". The setting is not stored in the file, nor are the per-frame output
+ * settings or the probes' ring. lbmdem_run_scene, which opens a new window on entry (lbmdem_set_mean_output), goes on with a
+ * window that has just been loaded instead -- once -- when its mask and `every` are those of the output setting.
+ * Layout. Behind section f, and only in a file of a whole handle (has_dist == 0), the extension: a header of 120 bytes, little
+ * endian -- "LBMXTRA1"; int32 mask, int32 0; int64 lx * sy (a sanity value; sy: the row pitch, ly rounded up to 16);
+ * tracers: int64 n, int32 automatic, int32 0, int64 advances, int64 hook_advances; scalar: float64 tau_s, int32 automatic,
+ * int32 0, int64 steps, int64 hook_steps; window: int32 mask, int32 every, int32 nsel (planes of doubles), int32 0, int64
+ * samples, int64 hook_steps; the values of a state the mask does not name are 0 -- then five sections in this order, each of
+ * length 0 when its bit is clear: tracers (16 n bytes: x, y per tracer), scalar_g (five planes of lx * sy doubles, device
+ * layout [x][sy]), scalar_was (lx * sy bytes, each 0 or 1), mean_cnt (two planes of lx * sy uint32), mean_S (nsel planes of lx *
+ * sy doubles). A background file with an extension ends in the trailer "LBMCKSM2" instead of "LBMCKSM1": the same form with
+ * always 16 entries -- the ten above, then extras (the extension header), tracers, scalar_g, scalar_was, mean_cnt, mean_S; an
+ * absent section has bytes, S1 and S2 of 0 --, so either trailer is found at the very end of a file. lbmdem_checkpoint_verify
+ * and the loader accept both and name the section that fails. The loader trusts nothing of the extension: lengths against the
+ * file's size, n within the tracers' limit and every position inside the lattice (NaN refused), tau_s finite and > 0.5, `was`
+ * bytes 0 or 1, the window's mask, nsel and counters; a file whose extension fails is refused as a whole. A library from before
+ * the extension loads such a file as a plain one: it stops reading behind f (and does not see the trailer "LBMCKSM2" of a
+ * background file, whose digests it therefore does not check).
+ * lbmdem_checkpoint_contents(path, out5) (host only, no device): what a file carries -- out5 = {mask, tracers, the scalar's
+ * steps, the window's mask, the window's samples}; all 0 for a plain file.
+ * LBMDEM_EINVAL: bits beyond LBMDEM_CKPT_ALL; a non-zero mask on a strip of a decomposition or with distributed grains; the
+ * single-precision library. lbmdem_checkpoint_save_async makes its slots larger (as many, after draining them) when the state has
+ * outgrown them; LBMDEM_ENOMEM from that leaves checkpoints in the background off. */
+#define LBMDEM_CKPT_TRACERS 1
+#define LBMDEM_CKPT_SCALAR 2
+#define LBMDEM_CKPT_MEAN 4
+#define LBMDEM_CKPT_ALL 7
+int lbmdem_set_checkpoint_contents(lbmdem_handle* h, int mask);   /* 0: off (default) */
+int lbmdem_checkpoint_contents(const char* path, long* out5);
 #define LBMDEM_ASYNC_MAX_CKPT 2
 int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots);     /* 0: off (default) */
 int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path);
