@@ -82,8 +82,8 @@ int mean_write_files(const char* dir, int nfile, int lx, int ly, long samples, c
 #ifndef LBMDEM_SINGLE_PRECISION
 constexpr int MN_PLANES = 11;    // Sux Suy | Sxx Sxy Syy | Srho Srho2 | Sdiss Sgdot | Sgux Sguy
 constexpr int MN_ROWS = MN_FIELDS + 1;   // the profile's rows: the thirteen fields, then n_fluid
-// the planes of each bit of the window's mask, in table order
-constexpr int MN_BIT_FIRST[5] = {0, 2, 5, 7, 9}, MN_BIT_COUNT[5] = {2, 3, 2, 2, 2};
+// the first plane of each bit of the window's mask, in table order (their counts: MEAN_BIT_PLANES, lbmdem_handle.h)
+constexpr int MN_BIT_FIRST[5] = {0, 2, 5, 7, 9};
 // the accumulators each derived field needs
 constexpr int MN_NEEDS[MN_FIELDS] = {0, 0, LBMDEM_MEAN_U, LBMDEM_MEAN_U, LBMDEM_MEAN_U | LBMDEM_MEAN_UU, LBMDEM_MEAN_U | LBMDEM_MEAN_UU,
                                      LBMDEM_MEAN_U | LBMDEM_MEAN_UU, LBMDEM_MEAN_RHO, LBMDEM_MEAN_RHO, LBMDEM_MEAN_DISS,
@@ -92,11 +92,6 @@ const char* const MN_FIELD_NAMES[MN_FIELDS] = {"phi", "solid", "mux", "muy", "rx
                                                "gux", "guy"};
 
 int mn_popcount(int mask) { return __builtin_popcount((unsigned)mask); }
-int mn_planes_of(int mask) {
-  int c = 0;
-  for (int b = 0; b < 5; ++b) c += ((mask >> b) & 1) ? MN_BIT_COUNT[b] : 0;
-  return c;
-}
 
 constexpr int MN_THREADS = 256;   // columns of a window
 constexpr int MN_SEG = 16;        // rows of a segment
@@ -240,7 +235,7 @@ void mn_offsets(const lbmdem_handle* h, long (&off)[MN_PLANES]) {
   for (int k = 0; k < MN_PLANES; ++k) off[k] = -1;
   for (int b = 0; b < 5; ++b)
     if ((h->mean.mask >> b) & 1)
-      for (int k = 0; k < MN_BIT_COUNT[b]; ++k) off[MN_BIT_FIRST[b] + k] = (long)(at++) * mn_plane(h);
+      for (int k = 0; k < MEAN_BIT_PLANES[b]; ++k) off[MN_BIT_FIRST[b] + k] = (long)(at++) * mn_plane(h);
 }
 MeanView mn_view(const lbmdem_handle* h) {
   const MeanState& M = h->mean;
@@ -403,7 +398,7 @@ int lbmdem_mean_begin(lbmdem_handle* h, int mask, int every) try {
   }
   if (!M.on) {
     const long plane = mn_plane(h);
-    const int nsel = mn_planes_of(mask);
+    const int nsel = mean_planes_of(mask);
     MeanState N{};
     if (h->mem.dev(&N.cnt, (size_t)(2 * plane)) != hipSuccess || h->mem.dev(&N.S, (size_t)(nsel * plane)) != hipSuccess) {
       h->mem.release(N.cnt); h->mem.release(N.S);

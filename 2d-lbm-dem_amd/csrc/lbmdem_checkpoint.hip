@@ -54,8 +54,9 @@ typedef unsigned long long u64;
 constexpr int CKSM_SECTIONS = 1 + CKPT_DEV_SECTIONS;
 constexpr int CKSM2_SECTIONS = CKSM_SECTIONS + 1 + CKPT_XTRA_SECTIONS;
 constexpr int CKSM_EXTRAS = CKSM_SECTIONS;   // the extension header's entry
-static const char* const CKSM_NAMES[CKSM2_SECTIONS] = {"header", "r", "kin", "fhf", "gp", "offsets", "nbr", "wallflags", "obst", "f",
-                                                       "extras", "tracers", "scalar_g", "scalar_was", "mean_cnt", "mean_S"};
+// a trailer's entries are the two headers and CKPT_TABLE's sections: "header", the nine, "extras", the five
+static int cksm_entry(int s) { return s < CKPT_DEV_SECTIONS ? 1 + s : 2 + s; }
+static const char* cksm_name(int e) { return e == 0 ? "header" : e == CKSM_EXTRAS ? "extras" : CKPT_TABLE[e < CKSM_EXTRAS ? e - 1 : e - 2].name; }
 struct CksmEntry { u64 bytes, s1, s2; };
 struct CksmTrailer {    // "LBMCKSM1"
   char magic[8];
@@ -70,21 +71,6 @@ struct CksmTrailer2 {   // "LBMCKSM2"
 static_assert(sizeof(CksmTrailer) == 16 + 24 * CKSM_SECTIONS && sizeof(CksmTrailer2) == 16 + 24 * CKSM2_SECTIONS, "the trailers have no padding");
 
 // ---- the extension ("LBMXTRA1", CkptExtra: lbmdem_handle.h) -----------------------------------------------------------------
-constexpr int MEAN_BIT_PLANES[5] = {2, 3, 2, 2, 2};   // planes of doubles per bit of a window's mask (lbm_mean.hip's table)
-static int mean_planes_of(int mask) {
-  int c = 0;
-  for (int b = 0; b < 5; ++b) c += ((mask >> b) & 1) ? MEAN_BIT_PLANES[b] : 0;
-  return c;
-}
-// the lengths of the five sections an extension header announces
-static void extra_lengths(const CkptExtra& X, u64 len[CKPT_XTRA_SECTIONS]) {
-  const u64 plane = (u64)X.plane;
-  len[0] = (X.mask & LBMDEM_CKPT_TRACERS) ? 16 * (u64)X.tr_n : 0;
-  len[1] = (X.mask & LBMDEM_CKPT_SCALAR) ? 40 * plane : 0;
-  len[2] = (X.mask & LBMDEM_CKPT_SCALAR) ? plane : 0;
-  len[3] = (X.mask & LBMDEM_CKPT_MEAN) ? 8 * plane : 0;
-  len[4] = (X.mask & LBMDEM_CKPT_MEAN) ? 8 * (u64)X.mn_nsel * plane : 0;
-}
 // Nothing of an extension header is trusted: every number is checked here before a length is formed or anything allocated
 // from it. `plane`: lx * sy by the file's own header. null: plausible, else what is wrong with it.
 static const char* extra_implausible(const CkptExtra& X, long plane) {
@@ -127,11 +113,76 @@ static void digest_add(const void* bytes, size_t nbytes, u64 first_word, u64 acc
   acc[0] = s1; acc[1] = s2;
 }
 
-// the lengths of the ten sections of a file with this header
-static void section_lengths(const CkptHeader& H, u64 len[CKSM_SECTIONS]) {
-  const CkptLayout Y = ckpt_layout(H.cfg.nbgrains, H.nnbr, H.plane);
-  len[0] = sizeof(CkptHeader);
-  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) len[1 + s] = Y.bytes[s];
+// the numbers of a file's two headers that its sections' lengths follow from (X null: a file without an extension)
+static CkptDims ckpt_dims(const CkptHeader& H, const CkptExtra* X) {
+  return CkptDims{(size_t)H.cfg.nbgrains, (size_t)H.nnbr, (size_t)H.plane, X ? (size_t)X->tr_n : 0, X ? (size_t)X->mn_nsel : 0, X ? X->mask : 0};
+}
+// the lengths of a file's sections as its trailer lists them (X null: the last six are 0) -> their sum
+static u64 section_lengths(const CkptHeader& H, const CkptExtra* X, u64 len[CKSM2_SECTIONS]) {
+  const CkptDims D = ckpt_dims(H, X);
+  len[0] = sizeof H;
+  len[CKSM_EXTRAS] = X ? sizeof *X : 0;
+  u64 sum = len[0] + len[CKSM_EXTRAS];
+  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) sum += len[cksm_entry(s)] = ckpt_section_bytes(s, D);
+  return sum;
+}
+
+// The extension behind f (never in a strip's file): `at` is the offset behind f, `size` the file's, `plane` lx * sy by the file's
+// header. XTRA_NONE: what follows f, if anything, is no extension (a trailer, also one cut within the three letters both magics
+// begin with). XTRA_OK: *X, checked. XTRA_REFUSED: *X holds *why (extra_implausible), or with *why null is cut short or unreadable.
+enum { XTRA_NONE, XTRA_OK, XTRA_REFUSED };
+static int read_extension(FILE* fp, u64 at, u64 size, long plane, CkptExtra* X, const char** why) {
+  memset(X, 0, sizeof *X);
+  *why = nullptr;
+  if (size <= at) return XTRA_NONE;
+  const size_t k = size - at < sizeof *X ? (size_t)(size - at) : sizeof *X;
+  if (fseeko(fp, (off_t)at, SEEK_SET) != 0 || !rd(fp, X, k)) return XTRA_REFUSED;
+  if (memcmp(X->magic, "LBMXTRA1", k < 8 ? k : 8) != 0 || (k < 8 && memcmp(X->magic, "LBMCKSM1", k) == 0)) return XTRA_NONE;
+  if (k < sizeof *X) return XTRA_REFUSED;
+  *why = extra_implausible(*X, plane);
+  return *why ? XTRA_REFUSED : XTRA_OK;
+}
+// the refusal's message of the paths that read without a trailer (the loader, lbmdem_checkpoint_contents)
+static int extension_refused(const char* path, const char* why) {
+  if (!why) return fail(LBMDEM_EINVAL, "checkpoint '%s': its extension header is cut short", path);
+  return fail(LBMDEM_EINVAL, "checkpoint '%s': its extension holds %s", path, why);
+}
+
+// CkptHeader from the host's side as it stood, the pair list's length and the three carries; has_dist stays 0
+static void ckpt_header(CkptHeader* H, const CkptShot& C, int nnbr, const void* carry3) {
+  memset(H, 0, sizeof *H);
+  memcpy(H->magic, "LBMDEMC5", 8);
+  H->lid6 = C.lid6;
+  H->layout = CKPT_LAYOUT; H->force_mode = C.force_mode; H->diag_always = C.diag_always;
+  H->has_carry = 1;
+  memcpy(H->carry, carry3, sizeof H->carry);
+  H->cfg = C.cfg; H->nbsteps = C.nbsteps; H->verlet_ok = C.verlet_ok; H->nnbr = nnbr; H->plane = C.plane;
+  H->vib = C.vib;
+}
+
+// where a section's bytes lie on a handle (a section of length 0 is never read: its place may be anything)
+static void* ckpt_where(const lbmdem_handle* h, int s) {
+  switch (s) {
+    case CKPT_R: return h->r;                 case CKPT_KIN: return h->kin[h->kcur].x1;
+    case CKPT_FHF: return h->fhf;             case CKPT_GP: return h->gp;
+    case CKPT_OFFSETS: return h->V.offsets;   case CKPT_NBR: return h->V.nbr;   // (zero offsets in the file without a pair list)
+    case CKPT_WALLFLAGS: return h->V.wallflags;
+    case CKPT_OBST: return h->obst[h->ocur];  case CKPT_F: return h->f[h->fcur];
+    case CKPT_TRACERS: return h->tracers.xy;
+    case CKPT_SCALAR_G: return h->scalar.g[h->scalar.cur];   case CKPT_SCALAR_WAS: return h->scalar.was;
+    case CKPT_MEAN_CNT: return h->mean.cnt;   default: return h->mean.S;
+  }
+}
+// `bytes` between the device and the file in pieces of at most `piece`: bounded host staging
+static bool ckpt_copy(FILE* fp, void* dev, size_t bytes, size_t piece, bool to_file) {
+  std::vector<char> buf(bytes < piece ? bytes : piece);
+  for (size_t done = 0; done < bytes; done += buf.size()) {
+    const size_t k = bytes - done < buf.size() ? bytes - done : buf.size();
+    char* at = static_cast<char*>(dev) + done;
+    if (to_file ? hipMemcpy(buf.data(), at, k, hipMemcpyDeviceToHost) != hipSuccess || !wr(fp, buf.data(), k)
+                : !rd(fp, buf.data(), k) || hipMemcpy(at, buf.data(), k, hipMemcpyHostToDevice) != hipSuccess) return false;
+  }
+  return true;
 }
 
 // lbmdem_checkpoint_verify. A trailer is looked for where a complete file has it, at the very end: its presence does not hang
@@ -176,25 +227,15 @@ static int verify_file(const char* path, int* has_digest, bool lenient) {
   }
   if (!have_header || memcmp(H.magic, "LBMDEMC5", 8) != 0 || H.layout != CKPT_LAYOUT || !header_plausible(H))
     return lenient && !at_end ? LBMDEM_OK : fail(LBMDEM_EINVAL, "'%s' is not a checkpoint of this library version", path);
-  u64 len[CKSM2_SECTIONS], fixed = 0;
-  memset(len, 0, sizeof len);
-  section_lengths(H, len);
-  for (int s = 0; s < CKSM_SECTIONS; ++s) fixed += len[s];
+  u64 len[CKSM2_SECTIONS];
+  u64 fixed = section_lengths(H, nullptr, len);
   // the extension, where the file has one: right behind f, never in a strip's file
   CkptExtra X;
-  memset(&X, 0, sizeof X);
-  bool have_extra = false;
-  if (H.has_dist == 0 && size > fixed) {
-    const u64 rest = size - fixed;
-    const size_t k = rest < sizeof X ? (size_t)rest : sizeof X;
-    if (fseeko(fp, (off_t)fixed, SEEK_SET) != 0 || !rd(fp, &X, k)) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot read behind its sections", path);
-    // (a file cut within the three letters both magics begin with is taken for one cut inside its trailer, as ever)
-    if (memcmp(X.magic, "LBMXTRA1", k < 8 ? k : 8) == 0 && !(k < 8 && memcmp(X.magic, "LBMCKSM1", k) == 0)) {
-      if (k < sizeof X)
-        return lenient && !at_end ? LBMDEM_OK : fail(LBMDEM_EINVAL, "checkpoint '%s': its extension header is cut short (%llu of %zu bytes)", path, rest, sizeof X);
-      have_extra = true;
-    }
-  }
+  const char* why = nullptr;
+  const int xr = H.has_dist == 0 ? read_extension(fp, fixed, size, H.plane, &X, &why) : XTRA_NONE;
+  if (xr == XTRA_REFUSED && !why)
+    return lenient && !at_end ? LBMDEM_OK : fail(LBMDEM_EINVAL, "checkpoint '%s': its extension header is cut short (%llu of %zu bytes)", path, size - fixed, sizeof X);
+  const bool have_extra = xr != XTRA_NONE;
   if (two && !have_extra) return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'extras' is missing behind section 'f' (the file is torn or corrupted)", path);
   if (have_extra) {
     if (at_end && two) {   // the extension header against its digest before anything is taken from it
@@ -203,11 +244,8 @@ static int verify_file(const char* path, int* has_digest, bool lenient) {
       if (T.e[CKSM_EXTRAS].bytes != sizeof X || acc[0] != T.e[CKSM_EXTRAS].s1 || acc[1] != T.e[CKSM_EXTRAS].s2)
         return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'extras' does not match its digest (the file is torn or corrupted)", path);
     }
-    if (const char* why = extra_implausible(X, H.plane))
-      return lenient && !at_end ? LBMDEM_OK : fail(LBMDEM_EINVAL, "checkpoint '%s': section 'extras' holds %s", path, why);
-    len[CKSM_EXTRAS] = sizeof X;
-    extra_lengths(X, len + CKSM_EXTRAS + 1);
-    for (int s = CKSM_EXTRAS; s < CKSM2_SECTIONS; ++s) fixed += len[s];
+    if (why) return lenient && !at_end ? LBMDEM_OK : fail(LBMDEM_EINVAL, "checkpoint '%s': section 'extras' holds %s", path, why);
+    fixed = section_lengths(H, &X, len);
   }
   const int nsec = have_extra ? CKSM2_SECTIONS : CKSM_SECTIONS;
   if (!at_end) {
@@ -231,23 +269,26 @@ static int verify_file(const char* path, int* has_digest, bool lenient) {
   for (int s = 1; s < nsec; ++s) {
     if (T.e[s].bytes != len[s])
       return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' is %llu bytes long by the header and %llu by the digest trailer", path,
-                  CKSM_NAMES[s], len[s], T.e[s].bytes);
+                  cksm_name(s), len[s], T.e[s].bytes);
     u64 acc[2] = {0, 0};
     for (u64 done = 0; done < len[s];) {
       const size_t piece = len[s] - done < buf.size() ? (size_t)(len[s] - done) : buf.size();
-      if (!rd(fp, buf.data(), piece)) return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' cannot be read", path, CKSM_NAMES[s]);
+      if (!rd(fp, buf.data(), piece)) return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' cannot be read", path, cksm_name(s));
       digest_add(buf.data(), piece, done / 8, acc);
       done += piece;
     }
     if (acc[0] != T.e[s].s1 || acc[1] != T.e[s].s2)
-      return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' does not match its digest (the file is torn or corrupted)", path, CKSM_NAMES[s]);
+      return fail(LBMDEM_EINVAL, "checkpoint '%s': section '%s' does not match its digest (the file is torn or corrupted)", path, cksm_name(s));
   }
   return LBMDEM_OK;
 }
 }  // namespace
 
 // ---- what a save adds to the file: the optional state lbmdem_set_checkpoint_contents selects, where the handle has it ----------
-CkptLayout lbmdem_ckpt_extra(const lbmdem_handle* h, CkptExtra* X) {
+CkptLayout lbmdem_ckpt_shot(const lbmdem_handle* h, CkptShot* C) {
+  C->cfg = h->cfg; C->nbsteps = h->nbsteps; C->plane = h->L.plane; C->lid6 = h->L.lid6;
+  C->force_mode = h->force_mode; C->diag_always = h->diag_always ? 1 : 0; C->verlet_ok = h->verlet_ok ? 1 : 0; C->vib = h->vib ? 1 : 0;
+  CkptExtra* X = &C->xtra;
   memset(X, 0, sizeof *X);
   const TracerState& T = h->tracers;
   const ScalarState& S = h->scalar;
@@ -265,25 +306,20 @@ CkptLayout lbmdem_ckpt_extra(const lbmdem_handle* h, CkptExtra* X) {
     X->mask |= LBMDEM_CKPT_MEAN;
     X->mn_mask = M.mask; X->mn_every = M.every; X->mn_nsel = M.nsel; X->mn_samples = M.samples; X->mn_hook = M.hook;
   }
-  if (!X->mask) return ckpt_layout(h->n, h->V.cap, h->L.plane);
-  memcpy(X->magic, "LBMXTRA1", 8);
-  X->plane = (long)h->L.lx * h->L.sy;
-  u64 len[CKPT_XTRA_SECTIONS];
-  extra_lengths(*X, len);
-  size_t xb[CKPT_XTRA_SECTIONS];
-  for (int s = 0; s < CKPT_XTRA_SECTIONS; ++s) xb[s] = (size_t)len[s];
-  return ckpt_layout(h->n, h->V.cap, h->L.plane, xb);
+  if (X->mask) {
+    memcpy(X->magic, "LBMXTRA1", 8);
+    X->plane = (long)h->L.lx * h->L.sy;
+  }
+  // (a slot holds CKPT_NBR at the list's capacity: its length is known only on the device when the slot is laid out)
+  return ckpt_layout(CkptDims{(size_t)h->n, (size_t)h->V.cap, (size_t)h->L.plane, (size_t)X->tr_n, (size_t)X->mn_nsel, X->mask});
 }
 
 #ifndef LBMDEM_SINGLE_PRECISION
 // ---- checkpoints in the background: the two ends of a slot's way (the middle is lbmdem_output.hip's) --------------------------
 void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned char* staging, CkptFrameJob* J) {
-  // (a section of length 0 is never read: its source may be anything)
-  const void* src[CKPT_ALL_SECTIONS] = {h->r, h->kin[h->kcur].x1, h->fhf, h->gp, h->verlet_ok ? h->V.offsets : nullptr,
-                                        h->V.nbr, h->V.wallflags, h->obst[h->ocur], h->f[h->fcur],
-                                        h->tracers.xy, h->scalar.g[h->scalar.cur], h->scalar.was, h->mean.cnt, h->mean.S};
-  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) { J->src[s] = src[s]; J->bytes[s] = Y.bytes[s]; J->at[s] = Y.at[s]; }
-  J->nnbr = h->verlet_ok ? h->V.offsets + h->n : nullptr;   // (lbmdem_checkpoint_save: zero offsets, no entries without a list)
+  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) { J->src[s] = ckpt_where(h, s); J->bytes[s] = Y.bytes[s]; J->at[s] = Y.at[s]; }
+  if (!h->verlet_ok) J->src[CKPT_OFFSETS] = nullptr;        // without a pair list: zero offsets, no entries (as lbmdem_checkpoint_save)
+  J->nnbr = h->verlet_ok ? h->V.offsets + h->n : nullptr;
   J->carry = h->ct.carry;
   J->staging = staging;
   J->gate = h->L.gate;
@@ -293,48 +329,34 @@ int lbmdem_ckpt_write_slot(const AsyncSlot* S, char* msg, size_t msglen) {
   const CkptLayout* Y = &S->ckpt_layout;
   const unsigned char* image = static_cast<const unsigned char*>(S->pinned);
   const u64* words = reinterpret_cast<const u64*>(image);
-  const CkptShot& C = S->shot;
   CkptHeader H;
-  memset(&H, 0, sizeof H);
-  memcpy(H.magic, "LBMDEMC5", 8);
-  H.lid6 = C.lid6;
-  H.layout = CKPT_LAYOUT; H.force_mode = C.force_mode; H.diag_always = C.diag_always;
-  H.has_carry = 1;
-  memcpy(H.carry, words + 1, sizeof H.carry);
-  H.cfg = C.cfg; H.nbsteps = C.nbsteps; H.verlet_ok = C.verlet_ok; H.nnbr = (int)words[0]; H.plane = C.plane;
-  H.has_dist = 0;
-  H.vib = C.vib;
-  const CkptExtra& X = C.xtra;
+  ckpt_header(&H, S->shot, (int)words[0], words + 1);
+  const CkptExtra& X = S->shot.xtra;
   const bool extra = X.mask != 0;   // then "LBMCKSM2" with all its entries, else the trailer of every file so far
   CksmTrailer2 T;
   memset(&T, 0, sizeof T);
   memcpy(T.magic, extra ? "LBMCKSM2" : "LBMCKSM1", 8);
   T.nsections = extra ? CKSM2_SECTIONS : CKSM_SECTIONS;
   const size_t tsize = extra ? sizeof(CksmTrailer2) : sizeof(CksmTrailer);
-  {
-    u64 acc[2] = {0, 0};
-    digest_add(&H, sizeof H, 0, acc);
-    T.e[0] = CksmEntry{sizeof H, acc[0], acc[1]};
-  }
-  for (int s = 0; s < CKPT_DEV_SECTIONS; ++s) {
-    const u64 bytes = s == CKPT_NBR ? 4 * (u64)H.nnbr : Y->bytes[s];
-    T.e[1 + s] = CksmEntry{bytes, words[4 + 2 * s], words[5 + 2 * s]};
-  }
-  if (extra) {
-    u64 acc[2] = {0, 0};
-    digest_add(&X, sizeof X, 0, acc);
-    T.e[CKSM_EXTRAS] = CksmEntry{sizeof X, acc[0], acc[1]};
-    for (int s = CKPT_DEV_SECTIONS; s < CKPT_ALL_SECTIONS; ++s)   // (a section of length 0 has added nothing: digests 0)
-      T.e[CKSM_EXTRAS + 1 + s - CKPT_DEV_SECTIONS] = CksmEntry{Y->bytes[s], words[4 + 2 * s], words[5 + 2 * s]};
-  }
+  const int nsec = extra ? CKPT_ALL_SECTIONS : CKPT_DEV_SECTIONS;
+  u64 len[CKSM2_SECTIONS];   // the file's lengths: CKPT_NBR at 4 * nnbr, not at the capacity the slot holds it at
+  (void)section_lengths(H, extra ? &X : nullptr, len);
+  u64 acc[4] = {0, 0, 0, 0};
+  digest_add(&H, sizeof H, 0, acc);
+  T.e[0] = CksmEntry{sizeof H, acc[0], acc[1]};
+  if (extra) digest_add(&X, sizeof X, 0, acc + 2);
+  if (extra) T.e[CKSM_EXTRAS] = CksmEntry{sizeof X, acc[2], acc[3]};
+  for (int s = 0; s < nsec; ++s)   // (a section of length 0 has added nothing: digests 0)
+    T.e[cksm_entry(s)] = CksmEntry{len[cksm_entry(s)], words[4 + 2 * s], words[5 + 2 * s]};
   char tmp[sizeof S->path + 8];
   snprintf(tmp, sizeof tmp, "%s.tmp", S->path);
   FILE* fp = fopen(tmp, "wb");
   if (!fp) { snprintf(msg, msglen, "cannot open '%s' for writing: %s", tmp, strerror(errno)); return LBMDEM_EINVAL; }
   bool ok = wr(fp, &H, sizeof H);
-  for (int s = 0; s < CKPT_DEV_SECTIONS && ok; ++s) ok = wr(fp, image + Y->at[s], (size_t)T.e[1 + s].bytes);   // exact lengths
-  if (extra && ok) ok = wr(fp, &X, sizeof X);
-  for (int s = CKPT_DEV_SECTIONS; s < CKPT_ALL_SECTIONS && extra && ok; ++s) ok = wr(fp, image + Y->at[s], Y->bytes[s]);
+  for (int s = 0; s < nsec && ok; ++s) {
+    if (s == CKPT_DEV_SECTIONS) ok = wr(fp, &X, sizeof X);
+    if (ok) ok = wr(fp, image + Y->at[s], (size_t)len[cksm_entry(s)]);
+  }
   if (ok) ok = wr(fp, &T, tsize);
   int err = errno;
   if (fclose(fp) != 0) { if (ok) err = errno; ok = false; }
@@ -358,64 +380,41 @@ int lbmdem_checkpoint_save(lbmdem_handle* h, const char* path) try {
   // capacities: one file per rank; the carries must have been agreed over the ranks first, lbmdem_comm_sync_carries)
   HIP_TRY(hipStreamSynchronize(h->stream));
   const int n = h->n;
-  std::vector<int> off(n + 1, 0);
+  std::vector<int> off(n + 1, 0);   // (the offsets of a handle without a pair list are zeros in the file)
   if (h->verlet_ok) HIP_TRY(hipMemcpy(off.data(), h->V.offsets, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
-  CkptExtra X;   // the handle has settled and its stream is idle: the counters are those of the state on the device
-  (void)lbmdem_ckpt_extra(h, &X);
-  CkptHeader H;
-  memset(&H, 0, sizeof H);
-  memcpy(H.magic, "LBMDEMC5", 8);
-  H.lid6 = h->L.lid6;
-  H.layout = CKPT_LAYOUT; H.force_mode = h->force_mode; H.diag_always = h->diag_always ? 1 : 0;
-  H.has_carry = 1;
+  CkptShot C;   // the handle has settled and its stream is idle: the counters are those of the state on the device
+  (void)lbmdem_ckpt_shot(h, &C);
+  const CkptExtra& X = C.xtra;
   if (!h->dist && h->carry_from < h->substep_seq) {
     launch_carry_resolve(h->ct, h->carry_from, h->stream);
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
-  HIP_TRY(hipMemcpy(H.carry, h->ct.carry, sizeof H.carry, hipMemcpyDeviceToHost));
-  H.cfg = h->cfg; H.nbsteps = h->nbsteps; H.verlet_ok = h->verlet_ok ? 1 : 0; H.nnbr = off[n]; H.plane = h->L.plane;
+  double carry[3];
+  HIP_TRY(hipMemcpy(carry, h->ct.carry, sizeof carry, hipMemcpyDeviceToHost));
+  CkptHeader H;
+  ckpt_header(&H, C, off[n], carry);
   H.has_dist = h->dist ? 1 : 0;
-  H.vib = h->vib ? 1 : 0;
+  const CkptDims D = ckpt_dims(H, &X);
+  const size_t piece = sizeof(double) * D.plane;   // f and the extension's sections of several planes go plane by plane
   FILE* fp = fopen(path, "wb");
   if (!fp) return fail(LBMDEM_EINVAL, "cannot open '%s' for writing", path);
   bool ok = wr(fp, &H, sizeof H);
-  auto dump = [&](const void* dev, size_t bytes) {
-    if (!ok || bytes == 0) return;
-    std::vector<char> buf(bytes);
-    if (hipMemcpy(buf.data(), dev, bytes, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; return; }
-    ok = wr(fp, buf.data(), bytes);
-  };
-  dump(h->r, sizeof(double) * n);
-  dump(h->kin[h->kcur].x1, sizeof(double) * 9 * n);
-  dump(h->fhf, sizeof(double) * 3 * n);
-  dump(h->gp, sizeof(double) * n);
-  dump(h->V.offsets, sizeof(int) * (n + 1));
-  dump(h->V.nbr, sizeof(int) * (size_t)H.nnbr);
-  dump(h->V.wallflags, n);
-  dump(h->obst[h->ocur], sizeof(int) * (size_t)h->L.plane);
-  for (int q = 0; q < 9 && ok; ++q)  // the lattice (device layout) in nine chunks: bounded host staging
-    dump(h->f[h->fcur] + (size_t)q * h->L.plane, sizeof(double) * (size_t)h->L.plane);
-  if (h->dist && ok) {   // optional trailing section
-    CkptDist D;
-    memset(&D, 0, sizeof D);
-    memcpy(D.magic, "LBMDIST1", 8);
-    D.margin = h->dist_margin; D.cap_g = h->dd.cap_g; D.cap_t = h->dd.cap_t; D.cap_l = h->dd.cap_l;
-    D.poison = h->dist_poison ? 1 : 0;
-    ok = wr(fp, &D, sizeof D);
-    dump(h->dd.active, n); dump(h->dd.fluidmask, n); dump(h->owner, n);
-  }
-  if (X.mask && ok) {   // the extension: its header, then the five sections, plane by plane (bounded host staging)
-    const size_t plane = (size_t)X.plane;
-    ok = wr(fp, &X, sizeof X);
-    if (X.mask & LBMDEM_CKPT_TRACERS) dump(h->tracers.xy, 16 * (size_t)X.tr_n);
-    if (X.mask & LBMDEM_CKPT_SCALAR) {
-      for (int k = 0; k < 5; ++k) dump(h->scalar.g[h->scalar.cur] + k * plane, sizeof(double) * plane);
-      dump(h->scalar.was, plane);
+  for (int s = 0; s < CKPT_ALL_SECTIONS && ok; ++s) {
+    if (s == CKPT_DEV_SECTIONS) {   // behind f: a strip's own part, or the extension (never both), or nothing
+      if (h->dist) {
+        CkptDist Q;
+        memset(&Q, 0, sizeof Q);
+        memcpy(Q.magic, "LBMDIST1", 8);
+        Q.margin = h->dist_margin; Q.cap_g = h->dd.cap_g; Q.cap_t = h->dd.cap_t; Q.cap_l = h->dd.cap_l;
+        Q.poison = h->dist_poison ? 1 : 0;
+        ok = wr(fp, &Q, sizeof Q) && ckpt_copy(fp, h->dd.active, n, piece, true) && ckpt_copy(fp, h->dd.fluidmask, n, piece, true) &&
+             ckpt_copy(fp, h->owner, n, piece, true);
+      }
+      if (!X.mask) break;
+      ok = wr(fp, &X, sizeof X);
     }
-    if (X.mask & LBMDEM_CKPT_MEAN) {
-      for (int k = 0; k < 2; ++k) dump(h->mean.cnt + k * plane, sizeof(unsigned) * plane);
-      for (int k = 0; k < X.mn_nsel; ++k) dump(h->mean.S + k * plane, sizeof(double) * plane);
-    }
+    const size_t bytes = ckpt_section_bytes(s, D);
+    if (ok) ok = s == CKPT_OFFSETS ? wr(fp, off.data(), bytes) : ckpt_copy(fp, ckpt_where(h, s), bytes, piece, true);
   }
   ok = (fclose(fp) == 0) && ok;
   if (!ok) return fail(LBMDEM_EHIP, "writing checkpoint '%s' failed", path);
@@ -426,37 +425,29 @@ int lbmdem_checkpoint_save(lbmdem_handle* h, const char* path) try {
   return fail(LBMDEM_EINVAL, "unexpected C++ exception");
 }
 
-// The extension of the file, where it has one: `fp` stands behind f. Everything is checked before it is used: the header's
-// numbers, the sections' lengths against the file, the positions (lbmdem_tracer_set's own test), the bytes of `was`. The states
-// are then set up the way their setters do it -- lbmdem_tracer_set, lbmdem_scalar_set (which forms omega = 1. / tau),
-// lbmdem_mean_begin -- and filled with the file's sections and counters.
-static int load_extra(const char* path, FILE* fp, lbmdem_handle* h) {
-  const off_t at0 = ftello(fp);
-  struct stat stt{};
-  if (at0 < 0 || fstat(fileno(fp), &stt) != 0) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot take its size", path);
-  const u64 rest = (u64)stt.st_size - (u64)at0;
+// section s of the file, at which `fp` stands, to its place on the handle, a plane's worth at a time; len: section_lengths
+static bool fill_section(FILE* fp, lbmdem_handle* h, int s, const u64* len) {
+  return ckpt_copy(fp, ckpt_where(h, s), (size_t)len[cksm_entry(s)], sizeof(double) * (size_t)h->L.plane, false);
+}
+
+// The extension of the file, where it has one: `at` is the offset behind f, `size` the file's. Everything is checked before it
+// is used: the header's numbers, the sections' lengths against the file, the positions (lbmdem_tracer_set's own test), the bytes
+// of `was`. The states are then set up the way their setters do it -- lbmdem_tracer_set, lbmdem_scalar_set (which forms omega =
+// 1. / tau), lbmdem_mean_begin -- and filled with the file's sections and counters.
+static int load_extra(const char* path, FILE* fp, u64 at, u64 size, const CkptHeader& H, lbmdem_handle* h) {
   CkptExtra X;
-  if (rest < 8 || !rd(fp, X.magic, 8) || memcmp(X.magic, "LBMXTRA1", 8) != 0) return LBMDEM_OK;   // a plain file (or its trailer)
-  if (rest < sizeof X || !rd(fp, reinterpret_cast<char*>(&X) + 8, sizeof X - 8))
-    return fail(LBMDEM_EINVAL, "checkpoint '%s': its extension header is cut short", path);
-  const LatticeView& L = h->L;
-  const size_t plane = (size_t)L.lx * L.sy;
-  if (const char* why = extra_implausible(X, (long)plane)) return fail(LBMDEM_EINVAL, "checkpoint '%s': its extension holds %s", path, why);
-  u64 len[CKPT_XTRA_SECTIONS], need = sizeof X;
-  extra_lengths(X, len);
-  for (int s = 0; s < CKPT_XTRA_SECTIONS; ++s) need += len[s];
+  const char* why = nullptr;
+  const int xr = read_extension(fp, at, size, H.plane, &X, &why);
+  if (xr == XTRA_NONE) return LBMDEM_OK;   // a plain file (or its trailer)
+  if (xr == XTRA_REFUSED) return extension_refused(path, why);
+  u64 len[CKSM2_SECTIONS];
+  const u64 need = section_lengths(H, &X, len) - at, rest = size - at;
   if (rest < need)
     return fail(LBMDEM_EINVAL, "checkpoint '%s' is shorter than its extension claims (%llu of at least %llu bytes behind section 'f')", path, rest, need);
   bool ok = true;
-  std::vector<char> buf;
-  auto fill = [&](void* dev, size_t bytes) {   // (lbmdem_checkpoint_load's: one piece of bounded size at a time)
-    if (!ok || bytes == 0) return;
-    buf.resize(bytes);
-    ok = rd(fp, buf.data(), bytes) && hipMemcpy(dev, buf.data(), bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
   if (X.mask & LBMDEM_CKPT_TRACERS) {
-    std::vector<double> xy(2 * (size_t)X.tr_n);   // (16 tr_n bytes are in the file)
-    if (!rd(fp, xy.data(), sizeof(double) * xy.size())) return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'tracers' cannot be read", path);
+    std::vector<double> xy(2 * (size_t)X.tr_n);
+    if (!rd(fp, xy.data(), (size_t)len[cksm_entry(CKPT_TRACERS)])) return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'tracers' cannot be read", path);
     RC_TRY(lbmdem_tracer_set(h, X.tr_n, xy.data(), X.tr_automatic));   // refuses a position outside the lattice, NaN included
     h->tracers.advances = X.tr_advances;
     h->tracers.hook = X.tr_hook;
@@ -464,28 +455,26 @@ static int load_extra(const char* path, FILE* fp, lbmdem_handle* h) {
   if (X.mask & LBMDEM_CKPT_SCALAR) {
     {   // `was` lies behind the populations: looked at first, nothing is allocated for a file whose flags are not flags
       const off_t at_g = ftello(fp);
-      std::vector<unsigned char> was(plane);
-      if (at_g < 0 || fseeko(fp, at_g + (off_t)len[1], SEEK_SET) != 0 || !rd(fp, was.data(), plane) || fseeko(fp, at_g, SEEK_SET) != 0)
+      std::vector<unsigned char> was((size_t)len[cksm_entry(CKPT_SCALAR_WAS)]);
+      if (at_g < 0 || fseeko(fp, at_g + (off_t)len[cksm_entry(CKPT_SCALAR_G)], SEEK_SET) != 0 || !rd(fp, was.data(), was.size()) ||
+          fseeko(fp, at_g, SEEK_SET) != 0)
         return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'scalar_was' cannot be read", path);
-      for (size_t k = 0; k < plane; ++k)
+      for (size_t k = 0; k < was.size(); ++k)
         if (was[k] > 1) return fail(LBMDEM_EINVAL, "checkpoint '%s': section 'scalar_was' holds the byte %d at %zu (0 or 1 expected)", path, was[k], k);
     }
     {
-      const std::vector<double> zero((size_t)L.lx * L.ly, 0.);
+      const std::vector<double> zero((size_t)h->L.lx * h->L.ly, 0.);
       RC_TRY(lbmdem_scalar_set(h, zero.data(), X.sc_tau, X.sc_automatic));
     }
-    ScalarState& S = h->scalar;
-    for (int k = 0; k < 5; ++k) fill(S.g[S.cur] + k * plane, sizeof(double) * plane);
-    fill(S.was, plane);
-    S.steps = X.sc_steps;
-    S.hook = X.sc_hook;
+    ok = fill_section(fp, h, CKPT_SCALAR_G, len) && fill_section(fp, h, CKPT_SCALAR_WAS, len);
+    h->scalar.steps = X.sc_steps;
+    h->scalar.hook = X.sc_hook;
   }
   if (X.mask & LBMDEM_CKPT_MEAN) {
     RC_TRY(lbmdem_mean_begin(h, X.mn_mask, X.mn_every));
     MeanState& M = h->mean;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(LBMDEM_EHIP, "checkpoint: the window could not be set up");   // (its zeroing)
-    for (int k = 0; k < 2; ++k) fill(M.cnt + k * plane, sizeof(unsigned) * plane);
-    for (int k = 0; k < M.nsel; ++k) fill(M.S + k * plane, sizeof(double) * plane);
+    ok = ok && fill_section(fp, h, CKPT_MEAN_CNT, len) && fill_section(fp, h, CKPT_MEAN_S, len);
     M.samples = X.mn_samples;
     M.hook = X.mn_hook;
     M.resumed = true;
@@ -514,17 +503,14 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
     return fail(LBMDEM_EINVAL, "checkpoint '%s': implausible header (grains %d, lattice %d x %d, rows [%d, %d))", path,
                 hc.nbgrains, hc.lx, hc.ly, hc.x_begin, hc.x_end);
   const int n = H.cfg.nbgrains;
-  {   // nothing is allocated from a header the file itself cannot back: the fixed part alone is this long
-    struct stat stt{};
-    const long long need = (long long)sizeof H + (long long)sizeof(double) * 14 * n + (long long)sizeof(int) * (n + 1) +
-                           (long long)sizeof(int) * H.nnbr + n + (long long)(sizeof(int) + 9 * sizeof(double)) * H.plane;
-    if (fstat(fileno(fp), &stt) != 0) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot take its size (at least %lld bytes needed)", path, need);
-    if ((long long)stt.st_size < need)
-      return fail(LBMDEM_EINVAL, "checkpoint '%s' is shorter than its header claims (%lld of at least %lld bytes)", path,
-                  (long long)stt.st_size, need);
-  }
+  u64 len[CKSM2_SECTIONS];
+  const u64 need = section_lengths(H, nullptr, len);   // nothing is allocated from a header the file itself cannot back
+  struct stat stt{};
+  if (fstat(fileno(fp), &stt) != 0) return fail(LBMDEM_EINVAL, "checkpoint '%s': cannot take its size (at least %llu bytes needed)", path, need);
+  if ((u64)stt.st_size < need)
+    return fail(LBMDEM_EINVAL, "checkpoint '%s' is shorter than its header claims (%llu of at least %llu bytes)", path, (u64)stt.st_size, need);
   std::vector<double> r(n), kin(9 * (size_t)n);
-  if (!rd(fp, r.data(), sizeof(double) * n) || !rd(fp, kin.data(), sizeof(double) * 9 * n)) return fail(LBMDEM_EINVAL, "checkpoint truncated");
+  if (!rd(fp, r.data(), (size_t)len[cksm_entry(CKPT_R)]) || !rd(fp, kin.data(), (size_t)len[cksm_entry(CKPT_KIN)])) return fail(LBMDEM_EINVAL, "checkpoint truncated");
   lbmdem_config cfg = H.cfg;
   cfg.device = device;
   lbmdem_handle* h = nullptr;
@@ -535,45 +521,41 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
     ~HandleGuard() { if (h) lbmdem_destroy(h); }
   } guard{h};
   bool ok = h->L.plane == H.plane && H.nnbr <= h->V.cap;
-  auto fill = [&](void* dev, size_t bytes) {
-    if (!ok || bytes == 0) return;
-    std::vector<char> buf(bytes);
-    ok = rd(fp, buf.data(), bytes) && hipMemcpy(dev, buf.data(), bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  if (ok) ok = hipMemcpy(h->kin[0].x1, kin.data(), sizeof(double) * 9 * n, hipMemcpyHostToDevice) == hipSuccess;
-  h->kcur = 0;
-  fill(h->fhf, sizeof(double) * 3 * n);
-  fill(h->gp, sizeof(double) * n);
-  {   // the pair list goes straight into kernels that index with it: checked here, on the host
-    std::vector<int> off((size_t)n + 1), nb((size_t)H.nnbr);
-    if (ok) ok = rd(fp, off.data(), sizeof(int) * off.size()) && rd(fp, nb.data(), sizeof(int) * nb.size());
-    if (ok && H.verlet_ok) {
-      ok = off[0] == 0 && off[n] == H.nnbr;
-      for (int i = 0; i < n && ok; ++i) ok = off[i] <= off[i + 1];
-      for (long k = 0; k < H.nnbr && ok; ++k) ok = nb[k] >= 0 && nb[k] < n;
-      if (!ok) return fail(LBMDEM_EINVAL, "checkpoint '%s': the pair list is inconsistent", path);
-    }
-    if (ok) ok = hipMemcpy(h->V.offsets, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) == hipSuccess &&
-                 (H.nnbr == 0 || hipMemcpy(h->V.nbr, nb.data(), sizeof(int) * nb.size(), hipMemcpyHostToDevice) == hipSuccess);
-    // the per-grain counts the offsets are the running sum of (a rebuild leaves both; the last grain's total is formed from them)
-    std::vector<int> cnt((size_t)n);
-    for (int i = 0; i < n && ok; ++i) cnt[i] = off[i + 1] - off[i];
-    if (ok) ok = hipMemcpy(h->V.counts, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess;
-  }
-  fill(h->V.wallflags, n);
-  fill(h->obst[0], sizeof(int) * (size_t)h->L.plane);
-  h->ocur = 0; h->obst_pending = false;
+  h->kcur = h->ocur = h->fcur = 0;   // where ckpt_where puts kin, obst and f
+  h->obst_pending = false;
   h->chg_state[0] = h->chg_state[1] = 0;
   h->snap_ok[0] = h->snap_ok[1] = false;   // (the loaded map is not the picture lbmdem_create has just painted)
   h->geo_buf = -1;                         // (... nor do the centres of that paint describe it)
-  for (int q = 0; q < 9 && ok; ++q) fill(h->f[0] + (size_t)q * h->L.plane, sizeof(double) * (size_t)h->L.plane);
-  h->fcur = 0;
+  for (int s = CKPT_KIN; s < CKPT_DEV_SECTIONS && ok; ++s) {   // (r went into lbmdem_create, which derives the rest of a grain from it)
+    if (s == CKPT_KIN) {
+      ok = hipMemcpy(ckpt_where(h, s), kin.data(), (size_t)len[cksm_entry(s)], hipMemcpyHostToDevice) == hipSuccess;
+    } else if (s == CKPT_OFFSETS) {   // with CKPT_NBR: the pair list goes straight into kernels that index with it, checked here, on the host
+      std::vector<int> off((size_t)n + 1), nb((size_t)H.nnbr);
+      ok = rd(fp, off.data(), sizeof(int) * off.size()) && rd(fp, nb.data(), sizeof(int) * nb.size());
+      if (ok && H.verlet_ok) {
+        ok = off[0] == 0 && off[n] == H.nnbr;
+        for (int i = 0; i < n && ok; ++i) ok = off[i] <= off[i + 1];
+        for (long k = 0; k < H.nnbr && ok; ++k) ok = nb[k] >= 0 && nb[k] < n;
+        if (!ok) return fail(LBMDEM_EINVAL, "checkpoint '%s': the pair list is inconsistent", path);
+      }
+      if (ok) ok = hipMemcpy(h->V.offsets, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                   (H.nnbr == 0 || hipMemcpy(h->V.nbr, nb.data(), sizeof(int) * nb.size(), hipMemcpyHostToDevice) == hipSuccess);
+      // the per-grain counts the offsets are the running sum of (a rebuild leaves both; the last grain's total is formed from them)
+      std::vector<int> cnt((size_t)n);
+      for (int i = 0; i < n && ok; ++i) cnt[i] = off[i + 1] - off[i];
+      if (ok) ok = hipMemcpy(h->V.counts, cnt.data(), sizeof(int) * cnt.size(), hipMemcpyHostToDevice) == hipSuccess;
+    } else if (s != CKPT_NBR) {
+      ok = fill_section(fp, h, s, len);
+    }
+  }
   if (ok && H.has_dist) {   // a strip with distributed grains: masks and message capacities as the writer had them. A
     CkptDist D;             // missing or short section fails the load HERE, not later inside a collective on one rank
+    const size_t piece = sizeof(double) * (size_t)H.plane;
     ok = rd(fp, &D, sizeof D) && memcmp(D.magic, "LBMDIST1", 8) == 0 && D.margin > 0 && D.cap_g > 0 && D.cap_t > 0 &&
          D.cap_l > 0 && D.cap_g <= n && D.cap_t <= n && D.cap_l <= n &&
-         lbmdem_dist_enable_caps(h, D.margin, D.cap_g, D.cap_t, D.cap_l) == LBMDEM_OK;
-    if (ok) { fill(h->dd.active, n); fill(h->dd.fluidmask, n); fill(h->owner, n); h->dist_poison = D.poison != 0; }
+         lbmdem_dist_enable_caps(h, D.margin, D.cap_g, D.cap_t, D.cap_l) == LBMDEM_OK &&
+         ckpt_copy(fp, h->dd.active, n, piece, false) && ckpt_copy(fp, h->dd.fluidmask, n, piece, false) && ckpt_copy(fp, h->owner, n, piece, false);
+    if (ok) h->dist_poison = D.poison != 0;
   }
   if (!ok) return fail(LBMDEM_EINVAL, "checkpoint '%s' is truncated or from a different decomposition", path);
   h->cfg = cfg;  // wall positions as saved
@@ -596,7 +578,7 @@ int lbmdem_checkpoint_load(const char* path, int device, lbmdem_handle** out) tr
     launch_tile_halo(h->V, n, h->stream);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(LBMDEM_EHIP, "k_fill_own failed");
   }
-  if (!H.has_dist) RC_TRY(load_extra(path, fp, h));   // (a refusal leaves through the guard: the file is refused as a whole)
+  if (!H.has_dist) RC_TRY(load_extra(path, fp, need, (u64)stt.st_size, H, h));   // (a refusal leaves through the guard: the file is refused as a whole)
   guard.h = nullptr;
   *out = h;
   return LBMDEM_OK;
@@ -656,17 +638,14 @@ int lbmdem_checkpoint_contents(const char* path, long* out5) {
   if (fstat(fileno(fp), &stt) != 0 || !rd(fp, &H, sizeof H) || memcmp(H.magic, "LBMDEMC5", 8) != 0 || H.layout != CKPT_LAYOUT ||
       !header_plausible(H))
     return fail(LBMDEM_EINVAL, "'%s' is not a checkpoint of this library version", path);
-  u64 len[CKSM_SECTIONS], fixed = 0;
-  section_lengths(H, len);
-  for (int s = 0; s < CKSM_SECTIONS; ++s) fixed += len[s];
-  const u64 size = (u64)stt.st_size;
+  u64 len[CKSM2_SECTIONS];
+  const u64 fixed = section_lengths(H, nullptr, len), size = (u64)stt.st_size;
   if (size < fixed) return fail(LBMDEM_EINVAL, "checkpoint '%s' is shorter than its header claims (%llu of at least %llu bytes)", path, size, fixed);
   CkptExtra X;
-  if (H.has_dist || size - fixed < 8 || fseeko(fp, (off_t)fixed, SEEK_SET) != 0 || !rd(fp, X.magic, 8) || memcmp(X.magic, "LBMXTRA1", 8) != 0)
-    return LBMDEM_OK;   // a plain file
-  if (size - fixed < sizeof X || !rd(fp, reinterpret_cast<char*>(&X) + 8, sizeof X - 8))
-    return fail(LBMDEM_EINVAL, "checkpoint '%s': its extension header is cut short", path);
-  if (const char* why = extra_implausible(X, H.plane)) return fail(LBMDEM_EINVAL, "checkpoint '%s': its extension holds %s", path, why);
+  const char* why = nullptr;
+  const int xr = H.has_dist ? XTRA_NONE : read_extension(fp, fixed, size, H.plane, &X, &why);
+  if (xr == XTRA_NONE) return LBMDEM_OK;   // a plain file
+  if (xr == XTRA_REFUSED) return extension_refused(path, why);
   out5[0] = X.mask; out5[1] = X.tr_n; out5[2] = X.sc_steps; out5[3] = X.mn_mask; out5[4] = X.mn_samples;
   return LBMDEM_OK;
 }

@@ -77,6 +77,13 @@ struct MeanState {
   // lbmdem_run_scene goes on with such a window instead of opening a new one when it is the window it would open.
   bool resumed = false;
 };
+// planes of doubles per bit of a window's mask, in table order (Sux Suy | Sxx Sxy Syy | Srho Srho2 | Sdiss Sgdot | Sgux Sguy)
+constexpr int MEAN_BIT_PLANES[5] = {2, 3, 2, 2, 2};
+static inline int mean_planes_of(int mask) {
+  int c = 0;
+  for (int b = 0; b < 5; ++b) c += ((mask >> b) & 1) ? MEAN_BIT_PLANES[b] : 0;
+  return c;
+}
 
 // The passive scalar (lbmdem_scalar_*, lbm_scalar.hip). Nothing is allocated or launched while `on` is false.
 struct ScalarState {
@@ -125,9 +132,8 @@ struct ProbeState {
 // A slot is free again when its files are closed: staging and pinned buffer are never overwritten while anything reads them.
 // Nothing of this exists while the three features are off.
 // The header of a checkpoint's extension (lbmdem_set_checkpoint_contents; the byte layout is in include/lbmdem_hip.h): what the
-// host knows of the optional state the file carries. The five sections it announces follow it -- tracers (16 tr_n bytes),
-// scalar_g (40 plane), scalar_was (plane), mean_cnt (8 plane), mean_S (8 mn_nsel plane) --, each absent (length 0) when its bit
-// of `mask` is clear.
+// host knows of the optional state the file carries. The five sections it announces follow it (CKPT_TABLE, lbmdem_internal.h),
+// each absent (length 0) when its bit of `mask` is clear.
 struct CkptExtra {
   char magic[8];       // "LBMXTRA1"
   int mask, pad0;      // LBMDEM_CKPT_* of what follows
@@ -560,9 +566,9 @@ static inline bool async_ckpt_on(const lbmdem_handle* h) { return lane_on(h, ASY
 // lbmdem_checkpoint.hip, for the background writer (lbmdem_output.hip): what a slot's launch reads, and the file of a slot
 // whose copy has arrived -- header, sections, digest trailer to `<path>.tmp`, then renamed onto `<path>`; on failure the text
 // goes to `msg`, the .tmp file is removed and `<path>` is not touched
-// lbmdem_ckpt_extra: the extension header of the handle as it stands -- what lbmdem_set_checkpoint_contents selects and the handle
-// has (X->mask == 0: none) -- and the layout of a file with it, the pair list at its capacity
-LBMDEM_INTERNAL CkptLayout lbmdem_ckpt_extra(const lbmdem_handle* h, CkptExtra* X);
+// lbmdem_ckpt_shot: the host's side of the header of the handle as it stands, with the extension header -- what
+// lbmdem_set_checkpoint_contents selects and the handle has (C->xtra.mask == 0: none) -- and the layout of that file in a slot
+LBMDEM_INTERNAL CkptLayout lbmdem_ckpt_shot(const lbmdem_handle* h, CkptShot* C);
 LBMDEM_INTERNAL void lbmdem_ckpt_frame_job(const lbmdem_handle* h, const CkptLayout& Y, unsigned char* staging, CkptFrameJob* J);
 LBMDEM_INTERNAL int lbmdem_ckpt_save_replacing(lbmdem_handle* h, const char* path);
 LBMDEM_INTERNAL int lbmdem_ckpt_write_slot(const AsyncSlot* S, char* msg, size_t msglen);

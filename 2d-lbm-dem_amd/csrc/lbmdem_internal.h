@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/lbmdem_hip.h"
 #include "lbm_mem.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -325,36 +326,56 @@ void launch_dem_frame(const DemTableView& T, double* rows, double* addends, hipS
 // the 22 numbers of the stats.data line from the table and the addends ([0], the time, is left 0 for the host)
 void launch_dem_stats(const DemTableView& T, const double* addends, double* stats22, hipStream_t st);
 // lbm_ckptframe.hip (double build): the device-resident sections of a checkpoint gathered into one staging buffer by ONE launch,
-// in the order lbmdem_checkpoint_save dumps them -- r, kin, fhf, gp, V.offsets, V.nbr, V.wallflags, obst, f, then the five
-// sections of the optional state (lbmdem_set_checkpoint_contents): the tracers' xy, the scalar's g[cur] and was, the window's
-// cnt and S, each of length 0 where the file does not carry it -- with each section's digest (S1 = sum of its little-endian
-// 64-bit words, S2 = sum of (index + 1) * word, both mod 2^64, the last word zero-padded) added up in the same pass. The staging
-// starts with a word area of CKPT_WORDS_BYTES: 64-bit words [0] the pair list's length offsets[n], [1..3] the three carries,
-// [4 + 2 s], [5 + 2 s] S1, S2 of section s; the area must be zero when the launch begins. Section s follows at at[s], a multiple
-// of 16.
+// in file order (CKPT_TABLE below) -- each of length 0 where the file does not carry it -- with each section's digest (S1 = sum of
+// its little-endian 64-bit words, S2 = sum of (index + 1) * word, both mod 2^64, the last word zero-padded) added up in the same
+// pass. The staging starts with a word area of CKPT_WORDS_BYTES: 64-bit words [0] the pair list's length offsets[n], [1..3] the
+// three carries, [4 + 2 s], [5 + 2 s] S1, S2 of section s; the area must be zero when the launch begins. Section s follows at
+// at[s], a multiple of 16.
 constexpr int CKPT_DEV_SECTIONS = 9;     // the sections of every file
-constexpr int CKPT_XTRA_SECTIONS = 5;    // ... and those of the optional state
+constexpr int CKPT_XTRA_SECTIONS = 5;    // ... and those of the optional state (lbmdem_set_checkpoint_contents)
 constexpr int CKPT_ALL_SECTIONS = CKPT_DEV_SECTIONS + CKPT_XTRA_SECTIONS;
 enum : int { CKPT_R = 0, CKPT_KIN, CKPT_FHF, CKPT_GP, CKPT_OFFSETS, CKPT_NBR, CKPT_WALLFLAGS, CKPT_OBST, CKPT_F,
              CKPT_TRACERS, CKPT_SCALAR_G, CKPT_SCALAR_WAS, CKPT_MEAN_CNT, CKPT_MEAN_S };
 // The word area is exactly full: 4 + 2 * 14 = 32 words of 8 bytes. A fifteenth section needs a larger area.
 constexpr size_t CKPT_WORDS_BYTES = 256;
 static_assert(8 * (4 + 2 * CKPT_ALL_SECTIONS) == CKPT_WORDS_BYTES, "the word area holds the digests of every section");
+// THE format of a checkpoint's sections, which both saves, the loader and the verifier walk: one entry per section in file
+// order. A length follows from the numbers of the file's two headers -- CkptHeader's grains, pair-list entries and nodes (nxl *
+// sy), CkptExtra's mask, tracers and planes of the window. Where a section lies on a handle: ckpt_where, lbmdem_checkpoint.hip.
+struct CkptDims { size_t n, nnbr, plane, tr_n, mn_nsel; int mask; };   // mask: LBMDEM_CKPT_*, 0 in a file without an extension
+enum : int { CKPT_PER_GRAIN, CKPT_PER_GRAIN_AND_ONE, CKPT_PER_PAIR_ENTRY, CKPT_PER_NODE, CKPT_PER_TRACER, CKPT_PER_MEAN_PLANE_NODE };
+struct CkptSection {
+  const char* name;   // as the digest trailer's messages use it
+  int id;             // CKPT_*: its index here, in CkptLayout, in CkptFrameJob and in the word area
+  int bit;            // the LBMDEM_CKPT_* it belongs to; 0: one of the nine of every file
+  int unit, per;      // bytes per CKPT_PER_*
+};
+constexpr CkptSection CKPT_TABLE[CKPT_ALL_SECTIONS] = {
+    {"r", CKPT_R, 0, 8, CKPT_PER_GRAIN}, {"kin", CKPT_KIN, 0, 72, CKPT_PER_GRAIN}, {"fhf", CKPT_FHF, 0, 24, CKPT_PER_GRAIN},
+    {"gp", CKPT_GP, 0, 8, CKPT_PER_GRAIN}, {"offsets", CKPT_OFFSETS, 0, 4, CKPT_PER_GRAIN_AND_ONE},
+    {"nbr", CKPT_NBR, 0, 4, CKPT_PER_PAIR_ENTRY}, {"wallflags", CKPT_WALLFLAGS, 0, 1, CKPT_PER_GRAIN},
+    {"obst", CKPT_OBST, 0, 4, CKPT_PER_NODE}, {"f", CKPT_F, 0, 72, CKPT_PER_NODE},
+    {"tracers", CKPT_TRACERS, LBMDEM_CKPT_TRACERS, 16, CKPT_PER_TRACER},
+    {"scalar_g", CKPT_SCALAR_G, LBMDEM_CKPT_SCALAR, 40, CKPT_PER_NODE}, {"scalar_was", CKPT_SCALAR_WAS, LBMDEM_CKPT_SCALAR, 1, CKPT_PER_NODE},
+    {"mean_cnt", CKPT_MEAN_CNT, LBMDEM_CKPT_MEAN, 8, CKPT_PER_NODE}, {"mean_S", CKPT_MEAN_S, LBMDEM_CKPT_MEAN, 8, CKPT_PER_MEAN_PLANE_NODE}};
+constexpr bool ckpt_table_in_order(int s = 0) { return s == CKPT_ALL_SECTIONS || (CKPT_TABLE[s].id == s && ckpt_table_in_order(s + 1)); }
+static_assert(ckpt_table_in_order(), "CKPT_TABLE is in the order of the CKPT_* enum, which is the file's");
+static inline size_t ckpt_section_bytes(int s, const CkptDims& D) {
+  const CkptSection& T = CKPT_TABLE[s];
+  if (T.bit && !(D.mask & T.bit)) return 0;   // a section of the optional state the file does not carry
+  const size_t count[] = {D.n, D.n + 1, D.nnbr, D.plane, D.tr_n, D.mn_nsel * D.plane};
+  return T.unit * count[T.per];
+}
 struct CkptLayout {
   size_t bytes[CKPT_ALL_SECTIONS];   // section lengths as the file holds them (CKPT_NBR: at the list's capacity)
   size_t at[CKPT_ALL_SECTIONS];      // where each starts in the staging
   size_t total;                      // staging bytes
 };
-// `xtra`: the lengths of the five sections of the optional state (null: a file without them)
-static inline CkptLayout ckpt_layout(int n, long nbr_cap, long plane, const size_t* xtra = nullptr) {
+// (the staging holds CKPT_NBR at the list's capacity: D.nnbr is V.cap here, the file's own 4 * nnbr comes with the copy)
+static inline CkptLayout ckpt_layout(const CkptDims& D) {
   CkptLayout Y;
-  const size_t N = (size_t)n;
-  Y.bytes[CKPT_R] = 8 * N; Y.bytes[CKPT_KIN] = 72 * N; Y.bytes[CKPT_FHF] = 24 * N; Y.bytes[CKPT_GP] = 8 * N;
-  Y.bytes[CKPT_OFFSETS] = 4 * (N + 1); Y.bytes[CKPT_NBR] = 4 * (size_t)nbr_cap; Y.bytes[CKPT_WALLFLAGS] = N;
-  Y.bytes[CKPT_OBST] = 4 * (size_t)plane; Y.bytes[CKPT_F] = 72 * (size_t)plane;
-  for (int s = 0; s < CKPT_XTRA_SECTIONS; ++s) Y.bytes[CKPT_DEV_SECTIONS + s] = xtra ? xtra[s] : 0;
   size_t at = CKPT_WORDS_BYTES;
-  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) { Y.at[s] = at; at += (Y.bytes[s] + 15) / 16 * 16; }
+  for (int s = 0; s < CKPT_ALL_SECTIONS; ++s) { Y.bytes[s] = ckpt_section_bytes(s, D); Y.at[s] = at; at += (Y.bytes[s] + 15) / 16 * 16; }
   Y.total = at;
   return Y;
 }

@@ -889,8 +889,8 @@ int lbmdem_set_async_checkpoint(lbmdem_handle* h, int slots) {
   if (slots > 0) RC_TRY(whole_handle(h, "lbmdem_set_async_checkpoint", CKPT_THERE));
   // the file of the handle as it stands: with the optional state lbmdem_set_checkpoint_contents selects, where the handle has
   // it now (lbmdem_checkpoint_save_async makes the slots larger when a later checkpoint needs more)
-  CkptExtra X;
-  const CkptLayout Y = lbmdem_ckpt_extra(h, &X);
+  CkptShot C;
+  const CkptLayout Y = lbmdem_ckpt_shot(h, &C);
   return lane_resize(h, ASYNC_CKPT, slots, Y.total, "lbmdem_set_async_checkpoint", "checkpoint");
 #endif
 }
@@ -907,9 +907,10 @@ int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
   if (strlen(path) >= sizeof AsyncSlot::path) return fail(LBMDEM_EINVAL, "lbmdem_checkpoint_save_async: path too long");
   if (h->obst_pending) return fail(LBMDEM_EINVAL, "checkpoint between obst_construction and collide_stream");
   RC_TRY(lbmdem_async_report(h));   // an earlier job's failure: this call queues nothing
-  // the layout is the job's: optional state may have appeared or gone since the last checkpoint was queued
-  CkptExtra X;
-  const CkptLayout Y = lbmdem_ckpt_extra(h, &X);
+  // the layout is the job's: optional state may have appeared or gone since the last checkpoint was queued. The host's side of
+  // the header is taken as of now: the run goes on behind this call
+  CkptShot C;
+  const CkptLayout Y = lbmdem_ckpt_shot(h, &C);
   if (Y.total > a->lane[ASYNC_CKPT].bytes) {   // the state has outgrown the slots: as many, larger ones (drains the lane first)
     const int slots = a->lane[ASYNC_CKPT].slots;
     AsyncCounters kept;
@@ -925,11 +926,7 @@ int lbmdem_checkpoint_save_async(lbmdem_handle* h, const char* path) {
   strcpy(S.path, path);
   S.ckpt_layout = Y;
   S.ckpt_bytes = Y.total;
-  S.shot.xtra = X;
-  // the host's side of the header, as of now: the run goes on behind this call
-  S.shot.cfg = h->cfg; S.shot.nbsteps = h->nbsteps; S.shot.plane = h->L.plane; S.shot.lid6 = h->L.lid6;
-  S.shot.force_mode = h->force_mode; S.shot.diag_always = h->diag_always ? 1 : 0; S.shot.verlet_ok = h->verlet_ok ? 1 : 0;
-  S.shot.vib = h->vib ? 1 : 0;
+  S.shot = C;
   if (h->carry_from < h->substep_seq) launch_carry_resolve(h->ct, h->carry_from, h->stream);   // as lbmdem_checkpoint_save
   CkptFrameJob J;
   lbmdem_ckpt_frame_job(h, S.ckpt_layout, static_cast<unsigned char*>(S.staging), &J);
