@@ -9,6 +9,7 @@ reference's source.
 
     python tests/golden/make_golden.py            # regenerate every fixture
     python tests/golden/make_golden.py --shapes   # only the odd-shape cases S_* (fp64 and float) and vtk_S_61x59/
+    python tests/golden/make_golden.py --packed   # only the packed case P_tri_127x121 (fp64 and float)
 
 Each case runs in its own process (the reference keeps its state in file-scope globals).
 Large arrays are stored as a strided sample plus the SHA-256 of the full little-endian float64
@@ -96,6 +97,14 @@ def cases():
         elif lx >= 60:
             x[0], y[1], x[2], y[3] = 0.35, 0.35, 0.1 * lx - 0.35, 0.1 * ly - 0.35
         c[f"S_{lx}x{ly}"] = dict(kind="shape", lx=lx, ly=ly, r_mm=r, x_mm=x, y_mm=y, seed=7, dumps=SHAPE_DUMPS)
+    # P: a two-dimensional packing (tests/packing_util.py: a jittered triangular lattice, 156 grains numbered at random), run and
+    # dumped like the S cases. Rows never touch each other; here more than half of the grains carry three or more non-zero
+    # contact forces and two thirds of the contact normals are steep: the sums of force_grains' `double fn, ft` over several
+    # partners, in both precisions.
+    import packing_util
+    r, x, y = packing_util.tri_packing(127, 121, 0.5, shuffle=True)
+    c["P_tri_127x121"] = dict(kind="shape", lx=127, ly=121, r_mm=r, x_mm=x, y_mm=y, seed=7, dumps=SHAPE_DUMPS,
+                              file_max=58405)      # no larger than the largest S_*.npz (S_98x119)
     return c
 
 
@@ -378,10 +387,10 @@ def make_real_fixtures(only=None):
         print("wrote", name, {k: str(v)[:20] for k, v in res.items() if k.startswith(("sha_f", "mass"))})
 
 
-def make_case_fixtures(sp=False, kinds=None):
-    """<case>.npz / <case>_f32.npz for every case (of these kinds) that is stored as one file"""
+def make_case_fixtures(sp=False, kinds=None, prefix=""):
+    """<case>.npz / <case>_f32.npz for every case (of these kinds, with this prefix) that is stored as one file"""
     for name, case in cases().items():
-        if case["kind"] == "output" or (kinds is not None and case["kind"] not in kinds):
+        if case["kind"] == "output" or (kinds is not None and case["kind"] not in kinds) or not name.startswith(prefix):
             continue
         q = mp.Queue()
         p = mp.Process(target=_generate, args=(name, case, q, sp))
@@ -391,10 +400,11 @@ def make_case_fixtures(sp=False, kinds=None):
         path = os.path.join(HERE, name + ("_f32" if sp else "") + ".npz")
         packed = pack(name, case, res)
         np.savez_compressed(path, **packed)
-        if case["kind"] == "shape" and os.path.getsize(path) >= SHAPE_FILE_MAX:      # does not fit: without the f sample
+        file_max = case.get("file_max", SHAPE_FILE_MAX)
+        if case["kind"] == "shape" and os.path.getsize(path) >= file_max:      # does not fit: without the f sample
             packed = pack(name, case, res, f_sample=False)
             np.savez_compressed(path, **packed)
-            assert os.path.getsize(path) < SHAPE_FILE_MAX, (path, os.path.getsize(path))
+            assert os.path.getsize(path) < file_max, (path, os.path.getsize(path))
         print("wrote", os.path.basename(path), os.path.getsize(path), {k: getattr(v, "shape", None) for k, v in packed.items()})
 
 
@@ -422,11 +432,15 @@ def main():
         make_f32_fixtures()
         return
     if len(sys.argv) > 1 and sys.argv[1] == "--shapes":     # only the S_* cases, both precisions, and their VTK frame
-        make_case_fixtures(kinds=("shape",))
-        make_f32_fixtures(kinds=("shape",))
+        make_case_fixtures(kinds=("shape",), prefix="S_")
+        make_case_fixtures(sp=True, kinds=("shape",), prefix="S_")
         p = mp.Process(target=make_vtk_shape_fixture)
         p.start()
         p.join()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "--packed":
+        make_case_fixtures(prefix="P_")
+        make_case_fixtures(sp=True, prefix="P_")
         return
     if len(sys.argv) > 1 and sys.argv[1] == "--dry":
         make_dry_output_fixture()
