@@ -176,6 +176,16 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_contacts_output.argtypes = [C.c_void_p, C.c_int]
     L.lbmdem_write_contacts_files.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_long, C.c_int, C.c_int]
+    L.lbmdem_cluster_compute.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+    L.lbmdem_download_cluster_grains.argtypes = [C.c_void_p] + [C.c_void_p] * 4
+    L.lbmdem_cluster_grains_device.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4
+    L.lbmdem_download_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_cluster_rounds.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_write_clusters.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_int]
+    L.lbmdem_set_clusters_output.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int]
+    L.lbmdem_write_clusters_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 5 +
+                                              [C.c_long, C.c_double, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_int,
+                                               C.c_int])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -380,6 +390,36 @@ def write_contacts_files(directory, nFile, r, x1, x2, fm, contacts, lx, ly, prec
                                                              len(rec), int(lx), int(ly)))
 
 
+# struct lbmdem_cluster: one component of two or more grains of the contact net (LbmDem.cluster_table), 56 bytes
+CLUSTER_DTYPE = np.dtype([("label", np.int32), ("size", np.int32), ("contacts", np.int64), ("walls", np.int32), ("core", np.int32),
+                          ("xmin", np.float64), ("xmax", np.float64), ("ymin", np.float64), ("ymax", np.float64)])
+CLUSTER_COUNTERS = ("selected_pairs", "selected_walls", "clusters", "largest_size", "largest_label", "isolated_grains",
+                    "core_grains", "core_pairs", "core_walls", "spanning")
+
+
+def write_clusters_files(directory, nFile, r, x1, x2, fm, contacts, label, degree, core, walls, table, fmin, relative, zmin, thr,
+                         counts, t, lx, ly, precision="f64"):
+    """clusters%.6i.dat, cluster_table%.6i.dat, DEM%.6i_clusters.ps and one appended line of clusters.data (include/lbmdem_hip.h
+    spells the four formats out) from per-grain r, x1, x2, fm, a record list (CONTACT_DTYPE), the four per-grain results, the
+    table (CLUSTER_DTYPE), the three parameters, the threshold, the ten counts (a dict of CLUSTER_COUNTERS or a sequence) and
+    the time of the line. Host only."""
+    cols = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (r, x1, x2, fm)]
+    ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (label, degree, core, walls)]
+    rec = np.ascontiguousarray(contacts, dtype=CONTACT_DTYPE).reshape(-1)
+    tab = np.ascontiguousarray(table, dtype=CLUSTER_DTYPE).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in CLUSTER_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    n = len(cols[0])
+    if any(len(a) != n for a in cols + ints) or len(cnt) != len(CLUSTER_COUNTERS):
+        raise LbmDemError(-1, "write_clusters_files: r, x1, x2, fm, label, degree, core and walls must have one value per grain, "
+                              "counts ten")
+    _chk(load_library(precision).lbmdem_write_clusters_files(
+        os.fsencode(directory), int(nFile), n, *(_vp(a) for a in cols), _vp(rec) if len(rec) else None, len(rec),
+        *(_vp(a) for a in ints), _vp(tab) if len(tab) else None, len(tab), float(fmin), int(bool(relative)), int(zmin), float(thr),
+        _vp(cnt), float(t), int(lx), int(ly)))
+
+
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
 COARSE_FIELDS = ("nodes fluid_nodes grain_nodes wall_nodes sum_rho sum_jx sum_jy sum_P grains sum_m sum_mv1 sum_mv2 sum_Iw "
                  "ke_x ke_y ke_teta sum_fhf1 sum_fhf2 sum_fhf3 sum_z sum_p M11 M12 M21 M22").split()
@@ -506,10 +546,11 @@ def write_mean_files(directory, nFile, samples, phi, mux, muy, rxx, rxy, ryy, mr
 
 
 class _DeviceBlock:
-    """a block of float64 device memory as torch.as_tensor reads it (the CUDA array interface): a view, nothing is copied"""
+    """a block of device memory -- float64, or int32 with typestr "<i4" -- as torch.as_tensor reads it (the CUDA array interface):
+    a view, nothing is copied"""
 
-    def __init__(self, ptr, shape):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f8", "data": (int(ptr), False), "version": 2,
+    def __init__(self, ptr, shape, typestr="<f8"):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2,
                                          "strides": None}
 
 
@@ -950,6 +991,55 @@ class LbmDem:
     def set_contacts_output(self, on=True):
         """run_scene writes the contact files at every DEM event, right behind write_DEM / write_forces"""
         _chk(self._L.lbmdem_set_contacts_output(self._h, 1 if on else 0))
+
+    # force chains: clusters, coordination and rattlers of the contact net of the last table sub-step (include/lbmdem_hip.h)
+    def clusters(self, fmin=1.0, relative=True, zmin=2):
+        """the cluster analysis of the records at or above the threshold -- fmin, or fmin times the mean of the positive pair
+        forces when relative -- with the core that is left when grains of fewer than zmin contacts are removed over and over
+        -> (dict of CLUSTER_COUNTERS, the threshold)"""
+        c = np.zeros(len(CLUSTER_COUNTERS), np.int64)
+        thr = C.c_double(0.0)
+        _chk(self._L.lbmdem_cluster_compute(self._h, float(fmin), int(bool(relative)), int(zmin), _vp(c), C.byref(thr)))
+        return dict(zip(CLUSTER_COUNTERS, (int(v) for v in c))), float(thr.value)
+
+    def cluster_grains(self):
+        """-> dict of the per-grain results of the last clusters(): label (the smallest grain of the component), degree, core
+        (1: not removed), walls (bit 0 .. 3: a selected contact with the bottom, top, left, right wall); int32 arrays [n]"""
+        out = {k: np.zeros(self.n, np.int32) for k in ("label", "degree", "core", "walls")}
+        _chk(self._L.lbmdem_download_cluster_grains(self._h, *(_vp(out[k]) for k in ("label", "degree", "core", "walls"))))
+        return out
+
+    def cluster_grains_tensors(self):
+        """the same four as torch.int32 views of the handle's device memory, good until the next clusters()"""
+        import torch
+        p = [C.c_void_p() for _ in range(4)]
+        _chk(self._L.lbmdem_cluster_grains_device(self._h, *(C.byref(q) for q in p)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(q.value, (self.n,), "<i4"), device=dev)
+                for k, q in zip(("label", "degree", "core", "walls"), p)}
+
+    def cluster_table(self):
+        """structured array of CLUSTER_DTYPE: the components of two or more grains of the last clusters(), ascending label"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_clusters(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=CLUSTER_DTYPE)
+        if n.value:
+            _chk(self._L.lbmdem_download_clusters(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def cluster_rounds(self):
+        """(rounds of the component loop, rounds of the core loop that removed a grain) of the last clusters()"""
+        r = np.zeros(2, np.int32)
+        _chk(self._L.lbmdem_cluster_rounds(self._h, _vp(r)))
+        return int(r[0]), int(r[1])
+
+    def write_clusters(self, directory=".", nFile=0, fmin=1.0, relative=True, zmin=2):
+        """clusters%.6i.dat, cluster_table%.6i.dat, DEM%.6i_clusters.ps and a line of clusters.data of the last table sub-step"""
+        _chk(self._L.lbmdem_write_clusters(self._h, os.fsencode(directory), int(nFile), float(fmin), int(bool(relative)), int(zmin)))
+
+    def set_clusters_output(self, on=True, fmin=1.0, relative=True, zmin=2):
+        """run_scene writes the cluster files at every DEM event, behind the contact files"""
+        _chk(self._L.lbmdem_set_clusters_output(self._h, 1 if on else 0, float(fmin), int(bool(relative)), int(zmin)))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

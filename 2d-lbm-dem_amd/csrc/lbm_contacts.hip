@@ -14,6 +14,8 @@
 //   an exclusive scan of the per-workgroup counts, all pair counts first, then all wall counts (hipcub::DeviceScan);
 //   k_contacts_emit   the same evaluation once more; a record's slot is the workgroup's base + the records of the rounds and
 //                     wavefronts before + the lane's rank in its wavefront's ballot.
+// lbmdem_contacts_records is these three steps for whoever wants the records on the device: the download below, and the cluster
+// analysis (lbm_clusters.hip), which never copies them to the host.
 // Double-precision library only: the other one's entry points refuse. The files' formatter is host code and exists in both.
 // Front end, as every export's: whole_handle() and SP_REFUSE() (lbmdem_handle.h) for the refusals, MemPool::grow (lbm_mem.h) for
 // the record buffer kept on the handle, OutFile (lbm_outfile.h) for the two files.
@@ -290,6 +292,40 @@ int lbmdem_write_contacts(lbmdem_handle* h, const char*, int) { SP_REFUSE(h, "th
 int lbmdem_set_contacts_output(lbmdem_handle* h, int) { SP_REFUSE(h, "the contact network export"); }
 #else
 
+// count, scan, total and -- when the records fit into `room` -- emit: the records of the last table sub-step in h->cx.rec, on the
+// device, the *npairs pair records first (lbmdem_download_contacts, and lbm_clusters.hip with room = LONG_MAX). Synchronises once,
+// for the total; the emit is left on the stream.
+int lbmdem_contacts_records(lbmdem_handle* h, const char* who, long room, long* npairs, long* total) {
+  ContactsJob J;
+  RC_TRY(contacts_job(h, who, &J));
+  RC_TRY(contacts_stage(h, J.nwg));
+  auto& X = h->cx;
+  const int items = 2 * J.nwg + 1;
+  J.census = X.census;
+  J.counts = X.counts;
+  // (the item behind the last workgroup is an empty one: its offset is the number of records)
+  HIP_TRY(hipMemsetAsync(X.counts + items - 1, 0, sizeof(long long), h->stream));
+  RC_TRY(contacts_count(h, J));
+  size_t bytes = X.scan_bytes;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(X.scan_tmp, bytes, X.counts, X.offsets, items, h->stream));
+  long long ends[2] = {0, 0};   // the offset of the first wall record, and of the item behind the last
+  HIP_TRY(hipMemcpyAsync(&ends[0], X.offsets + J.nwg, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(&ends[1], X.offsets + items - 1, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  *npairs = (long)ends[0];
+  *total = (long)ends[1];
+  if (ends[1] == 0 || room < ends[1]) return LBMDEM_OK;
+  // grown with some room: the count moves a little from table to table
+  if (X.rec_cap < ends[1]) HIP_TRY(h->mem.grow(&X.rec, &X.rec_cap, (long)(ends[1] + ends[1] / 8 + 64)));
+  J.counts = X.offsets;
+  J.out = X.rec;
+  J.cap = ends[1];
+  if (h->contacts_film) hipLaunchKernelGGL(k_contacts_emit<true>, dim3(J.nwg), dim3(CT_THREADS), 0, h->stream, J);
+  else hipLaunchKernelGGL(k_contacts_emit<false>, dim3(J.nwg), dim3(CT_THREADS), 0, h->stream, J);
+  HIP_TRY(hipGetLastError());
+  return LBMDEM_OK;
+}
+
 int lbmdem_contact_stats(lbmdem_handle* h, long* counts6) try {
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
@@ -312,34 +348,13 @@ int lbmdem_download_contacts(lbmdem_handle* h, lbmdem_contact* out, long cap, lo
   CHECK_H(h);
   CHECK_NOT_SPLIT(h);
   if (!count || (cap > 0 && !out) || cap < 0) return fail(LBMDEM_EINVAL, "null buffer");
-  ContactsJob J;
-  RC_TRY(contacts_job(h, "lbmdem_download_contacts", &J));
-  RC_TRY(contacts_stage(h, J.nwg));
-  auto& X = h->cx;
-  const int items = 2 * J.nwg + 1;
-  J.census = X.census;
-  J.counts = X.counts;
-  // (the item behind the last workgroup is an empty one: its offset is the number of records)
-  HIP_TRY(hipMemsetAsync(X.counts + items - 1, 0, sizeof(long long), h->stream));
-  RC_TRY(contacts_count(h, J));
-  size_t bytes = X.scan_bytes;
-  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(X.scan_tmp, bytes, X.counts, X.offsets, items, h->stream));
-  long long total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, X.offsets + items - 1, sizeof total, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  *count = (long)total;
+  long npairs = 0, total = 0;
+  RC_TRY(lbmdem_contacts_records(h, "lbmdem_download_contacts", cap, &npairs, &total));
+  *count = total;
   if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < total) return fail(LBMDEM_EINVAL, "lbmdem_download_contacts: there are %lld records, the buffer holds %ld", total, cap);
+  if (cap < total) return fail(LBMDEM_EINVAL, "lbmdem_download_contacts: there are %ld records, the buffer holds %ld", total, cap);
   if (total == 0) return LBMDEM_OK;
-  // grown with some room: the count moves a little from table to table
-  if (X.rec_cap < total) HIP_TRY(h->mem.grow(&X.rec, &X.rec_cap, (long)(total + total / 8 + 64)));
-  J.counts = X.offsets;
-  J.out = X.rec;
-  J.cap = total;
-  if (h->contacts_film) hipLaunchKernelGGL(k_contacts_emit<true>, dim3(J.nwg), dim3(CT_THREADS), 0, h->stream, J);
-  else hipLaunchKernelGGL(k_contacts_emit<false>, dim3(J.nwg), dim3(CT_THREADS), 0, h->stream, J);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, X.rec, sizeof(lbmdem_contact) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(out, h->cx.rec, sizeof(lbmdem_contact) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {

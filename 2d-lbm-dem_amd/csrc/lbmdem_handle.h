@@ -295,6 +295,29 @@ struct lbmdem_handle {
     lbmdem_contact* rec = nullptr;        // [rec_cap]
     long rec_cap = 0;
   } cx;
+  // The cluster analysis of the contact net (lbm_clusters.hip). cl: scratch and results, allocated by the first
+  // lbmdem_cluster_compute, grown with the record count, freed with the handle. The results describe the table sub-step whose
+  // sequence number is `seq`: the readers ask for contacts_valid and seq == substep_seq. clusters_*: lbmdem_set_clusters_output.
+  bool clusters_output = false;
+  double clusters_fmin = 0.;
+  int clusters_relative = 0, clusters_zmin = 0;
+  struct ClusterStage {
+    bool valid = false;
+    long long seq = -1;
+    int* ints = nullptr;                  // the per-grain and per-root planes, the scan's flags and positions (null: nothing allocated yet)
+    unsigned long long* words = nullptr;  // [5][n] per root: selected pair records, the box's four keys
+    unsigned long long* census = nullptr; // [10], then the words of the loops: changed, error
+    double* thr = nullptr;                // [1]
+    double* partial = nullptr;            // [partial_cap] the block partials of S, then (as long long) the blocks' counts
+    long partial_cap = 0;
+    unsigned char* sel = nullptr;         // [sel_cap] a record is selected
+    long sel_cap = 0;
+    lbmdem_cluster* table = nullptr;      // [n / 2 + 1]
+    void* scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    long nclusters = 0, npairs = 0, nrec = 0;   // of the last compute
+    int rounds_cc = 0, rounds_core = 0;         // rounds the two loops took in the last compute
+  } cl;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;
@@ -535,6 +558,8 @@ LBMDEM_INTERNAL int lbmdem_write_vtk_file(const char* path, int nx, int ny, cons
 LBMDEM_INTERNAL void lbmdem_vtk_put_mesh(FILE* fp, int nx, int ny);   // lbmdem_output.hip: header, mesh, CELL_DATA / POINT_DATA lines
 LBMDEM_INTERNAL void lbmdem_ps_head(FILE* fp, int n, const double* x1, const double* x2, const double* r, const double* fm,
                                     size_t stride, int lx, int ly);   // lbm_contacts.hip: header and discs of DEM%06d.ps
+// lbm_contacts.hip: count, scan, total and -- when the records fit into `room` -- emit, the records left in h->cx.rec on the device
+LBMDEM_INTERNAL int lbmdem_contacts_records(lbmdem_handle* h, const char* who, long room, long* npairs, long* total);
 LBMDEM_INTERNAL int lbmdem_verlet_build_lists(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_chain_settle(lbmdem_handle* h);
 LBMDEM_INTERNAL int lbmdem_dem_tiles_by_index(lbmdem_handle* h);

@@ -496,6 +496,85 @@ int lbmdem_write_contacts(lbmdem_handle* h, const char* dir, int nfile);
 int lbmdem_set_contacts_output(lbmdem_handle* h, int on);            /* 0: off (default) */
 int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double* r, const double* x1, const double* x2,
                                 const double* fm, const lbmdem_contact* c, long count, int lx, int ly);   /* host only */
+/* Force chains: the contact net above read as a graph, on the device, so that nobody has to download 48 bytes per contact and run
+ * a union-find at every DEM event. Which contacts: the records of lbmdem_download_contacts, in that call's order, under that
+ * call's validity condition. Nodes are the grains 0 .. n-1; walls are no nodes. Every result is an integer, or a minimum or a
+ * maximum, that does not depend on the order of evaluation; a serial restatement over lbmdem_download_contacts and columns 0 and 1
+ * of lbmdem_download_grain_table reproduces every number exactly, thr on the bits.
+ * 1. Selection. A record is selected iff fn >= thr (never, then, when fn is a NaN). relative == 0: thr = fmin. relative != 0:
+ *    thr = fmin * (S / m), where m is the number of grain-grain records with fn > 0 -- converted to double -- and S their sum in this
+ *    association: the grain-grain records k = 0, 1, .. in record order are cut into blocks of 1024 consecutive records
+ *    (block b holds 1024 b <= k < 1024 (b + 1), the last block may be short); per block a partial, started from +0.0, to which the
+ *    block's fn > 0 are added one by one, k ascending (any other record is skipped); S, started from +0.0, to which the partials are
+ *    added one by one, b ascending. IEEE double, no contraction. When m == 0: thr = +infinity if fmin > 0, thr = 0 if fmin == 0.
+ *    fmin must be finite and >= 0.
+ * 2. degree[i]: the selected records that name grain i as i or as j, wall records (j < 0) included. walls[i]: the OR of
+ *    1 << (-j - 1) over grain i's selected wall records (LBMDEM_WALL_B 1, _T 2, _L 4, _R 8).
+ * 3. label[i]: the smallest grain index in i's connected component over the selected grain-grain records; a grain without a selected
+ *    pair is its own label.
+ * 4. core[i]: repeat until nothing changes: remove every grain whose remaining degree is < zmin, the remaining degree being the
+ *    grain's selected wall records plus its selected pair records whose other end has not been removed. 1 for the survivors, 0
+ *    otherwise; the outcome does not depend on the order of removal. zmin lies in 0 .. 6; 0 removes nothing.
+ * 5. The cluster table: one lbmdem_cluster per component of size >= 2, ascending label. size: its grains; contacts: the selected pair
+ *    records inside it; walls: the OR of its members' walls; core: its members with core == 1; xmin .. ymax: minimum and maximum of
+ *    its members' centres, columns 0 and 1 of lbmdem_download_grain_table, under the total order of the bit patterns (-0.0 below
+ *    +0.0, a NaN beyond the infinity of its sign). The members of the struct take 56 bytes.
+ * 6. counts10, in order: selected pair records; selected wall records; components of size >= 2; size of the largest component (1 if
+ *    none has two grains); label of the largest component, the smallest label among equals; grains of degree 0; core grains; selected
+ *    pair records with both ends in the core; selected wall records at core grains; the spanning mask -- bit 0: one component has
+ *    both LBMDEM_WALL_L and LBMDEM_WALL_R among its walls, bit 1: both LBMDEM_WALL_B and LBMDEM_WALL_T.
+ * On the device: one lane per block forms the partials of S and one lane adds them; degree and walls by atomics; the components by
+ * min-label hooking (atomicMin on the larger root: a node's parent is never larger than the node, so no cycle can form) and pointer
+ * jumping in rounds of kernel launches, the core by rounds that remove and then subtract. Each round raises a device flag when it
+ * changed something; the host stops at the first quiet round and gives up, with LBMDEM_EINVAL, after n + 1 rounds. No workgroup
+ * waits for another, every device loop has a bound. Scratch comes from the handle's pool with the first call and goes with the
+ * handle; everything runs on the handle's stream.
+ *   lbmdem_cluster_compute          the analysis of the last table sub-step; counts10 and *thr. Synchronises; changes nothing a
+ *                                   later step reads.
+ *   lbmdem_download_cluster_grains  label, degree, core, walls, [n] ints each; any pointer may be NULL
+ *   lbmdem_cluster_grains_device    the same four as device pointers into the handle's scratch (for a torch view), good until the
+ *                                   next compute or lbmdem_destroy; any pointer may be NULL
+ *   lbmdem_download_clusters        the table; cap = 0 (out may be NULL) only reports *count; a buffer of fewer than *count entries
+ *                                   is refused with *count set
+ *   lbmdem_cluster_rounds           rounds2 = the rounds the component loop took (the quiet one included; 0 without a pair record),
+ *                                   the rounds of the core loop that removed a grain
+ *   These four are refused, with LBMDEM_EINVAL and a sentence that names lbmdem_cluster_compute, when no compute has been made
+ *   for the last table sub-step.
+ *   lbmdem_write_clusters_files     host only, no handle, no device. Four files in <dir>:
+ *                                   clusters%.6i.dat -- "# fmin %le relative %d zmin %d threshold %le\n", "# i label degree core
+ *                                   walls\n", then n lines "%d %d %d %d %d\n";
+ *                                   cluster_table%.6i.dat -- "%d %d %ld %d %d %le %le %le %le\n" per entry, the members in order;
+ *                                   DEM%.6i_clusters.ps -- header and one arc per grain as lbmdem_write_forces prints them, then per
+ *                                   selected grain-grain record (fn >= thr) the four lines of DEM%.6i_chains.ps with
+ *                                   " <r> <g> <b> setrgbcolor \n" in the place of " 0.0 setgray \n", the colour palette[label[i] % 8]
+ *                                   of: "0.894 0.102 0.110", "0.216 0.494 0.722", "0.302 0.686 0.290", "0.596 0.306 0.639",
+ *                                   "1.000 0.498 0.000", "0.651 0.337 0.157", "0.969 0.506 0.749", "0.400 0.400 0.400";
+ *                                   clusters.data -- one line appended: "%le %le" of t and thr, " %ld" of each of the ten counts,
+ *                                   "\n"; when the file is created, first the line "# t threshold selected_pairs selected_walls
+ *                                   clusters largest_size largest_label isolated_grains core_grains core_pairs core_walls spanning".
+ *                                   It checks fopen; records that name a grain outside [0, n) or an unknown wall, and labels
+ *                                   outside [0, n), are refused before anything is written.
+ *   lbmdem_write_clusters           the compute, the downloads, then that formatter with r, x1, x2, fm of
+ *                                   lbmdem_download_grain_table and t = nbsteps * dt
+ *   lbmdem_set_clusters_output      on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_clusters(dir, nFile, fmin, relative,
+ *                                   zmin) at every DEM event, behind the contact files. Off by default; a checkpoint does not
+ *                                   carry it.
+ * LBMDEM_EINVAL: fmin negative or not finite, zmin outside 0 .. 6; a strip of a decomposition or distributed grains (and
+ * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers; a
+ * directory that cannot be written ("cannot open"). */
+typedef struct lbmdem_cluster { int label, size; long contacts; int walls, core; double xmin, xmax, ymin, ymax; } lbmdem_cluster;
+#define LBMDEM_CLUSTER_COUNTS 10
+int lbmdem_cluster_compute(lbmdem_handle* h, double fmin, int relative, int zmin, long* counts10, double* thr);
+int lbmdem_download_cluster_grains(lbmdem_handle* h, int* label, int* degree, int* core, int* walls);
+int lbmdem_cluster_grains_device(lbmdem_handle* h, const int** label, const int** degree, const int** core, const int** walls);
+int lbmdem_download_clusters(lbmdem_handle* h, lbmdem_cluster* out, long cap, long* count);
+int lbmdem_cluster_rounds(lbmdem_handle* h, int* rounds2);
+int lbmdem_write_clusters(lbmdem_handle* h, const char* dir, int nfile, double fmin, int relative, int zmin);
+int lbmdem_set_clusters_output(lbmdem_handle* h, int on, double fmin, int relative, int zmin);   /* 0: off (default) */
+int lbmdem_write_clusters_files(const char* dir, int nfile, int n, const double* r, const double* x1, const double* x2,
+                                const double* fm, const lbmdem_contact* c, long count, const int* label, const int* degree,
+                                const int* core, const int* walls, const lbmdem_cluster* table, long nclusters, double fmin,
+                                int relative, int zmin, double thr, const long* counts10, double t, int lx, int ly);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
