@@ -186,6 +186,16 @@ def _open_library(LIB_PATH):
     L.lbmdem_write_clusters_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 5 +
                                               [C.c_long, C.c_double, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_int,
                                                C.c_int])
+    L.lbmdem_structure_edges.argtypes = [C.c_double, C.c_int, C.c_void_p]
+    L.lbmdem_structure_compute.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_long, C.c_void_p]
+    L.lbmdem_download_structure_grains.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+    L.lbmdem_structure_grains_device.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6
+    L.lbmdem_download_structure_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.lbmdem_download_structure_neighbours.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_write_structure.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_double]
+    L.lbmdem_set_structure_output.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double]
+    L.lbmdem_write_structure_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int, C.c_double] +
+                                               [C.c_void_p] * 2 + [C.c_double] * 3)
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -418,6 +428,38 @@ def write_clusters_files(directory, nFile, r, x1, x2, fm, contacts, label, degre
         os.fsencode(directory), int(nFile), n, *(_vp(a) for a in cols), _vp(rec) if len(rec) else None, len(rec),
         *(_vp(a) for a in ints), _vp(tab) if len(tab) else None, len(tab), float(fmin), int(bool(relative)), int(zmin), float(thr),
         _vp(cnt), float(t), int(lx), int(ly)))
+
+
+# the per-grain results of LbmDem.structure() (LbmDem.structure_grains), and the names of its eight counts
+STRUCTURE_DTYPE = np.dtype([("nb", np.int32), ("bonds", np.int32), ("c6", np.float64), ("s6", np.float64), ("c2", np.float64),
+                            ("s2", np.float64)])
+STRUCTURE_COUNTERS = ("entries", "pairs", "bonded_pairs", "max_neighbours", "lone_grains", "six_bonds", "coincident_pairs",
+                      "nonfinite_grains")
+
+
+def structure_edges(rcut, nbins, precision="f64"):
+    """the squared bin edges of the pair histogram, e2[nbins + 1] (include/lbmdem_hip.h: the table alone decides a bin). Host only."""
+    e2 = np.zeros(max(int(nbins), 0) + 1, np.float64)
+    _chk(load_library(precision).lbmdem_structure_edges(float(rcut), int(nbins), _vp(e2)))
+    return e2
+
+
+def write_structure_files(directory, nFile, grains, rcut, nbins, shell, hist, counts, t, W, H, precision="f64"):
+    """structure%.6i.dat, gr%.6i.dat and one appended line of structure.data (include/lbmdem_hip.h spells the three formats out) from
+    the per-grain results (STRUCTURE_DTYPE), the parameters, the histogram, the eight counts (a dict of STRUCTURE_COUNTERS or a
+    sequence), the time of the line and the box's extent. Host only."""
+    g = np.ascontiguousarray(grains, dtype=STRUCTURE_DTYPE).reshape(-1)
+    ints = [np.ascontiguousarray(g[k]) for k in ("nb", "bonds")]
+    dbl = [np.ascontiguousarray(g[k]) for k in ("c6", "s6", "c2", "s2")]
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in STRUCTURE_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    hh = np.ascontiguousarray(hist, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(STRUCTURE_COUNTERS) or len(hh) != int(nbins):
+        raise LbmDemError(-1, "write_structure_files: counts must have eight values, hist one per bin")
+    _chk(load_library(precision).lbmdem_write_structure_files(
+        os.fsencode(directory), int(nFile), len(g), *(_vp(a) for a in ints), *(_vp(a) for a in dbl), float(rcut), int(nbins),
+        float(shell), _vp(hh), _vp(cnt), float(t), float(W), float(H)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1040,6 +1082,58 @@ class LbmDem:
     def set_clusters_output(self, on=True, fmin=1.0, relative=True, zmin=2):
         """run_scene writes the cluster files at every DEM event, behind the contact files"""
         _chk(self._L.lbmdem_set_clusters_output(self._h, 1 if on else 0, float(fmin), int(bool(relative)), int(zmin)))
+
+    # packing structure: neighbour shells, g(r) and bond order of the grains where they are now (include/lbmdem_hip.h)
+    def structure(self, rcut, nbins=64, shell=1.2, max_entries=2 ** 31 - 1):
+        """the fixed-radius neighbour list within rcut, the pair histogram of nbins bins, the bonds within shell times the sum of
+        two radii and the bond-order and fabric sums; max_entries = 0: counts and histogram only -> dict of STRUCTURE_COUNTERS"""
+        c = np.zeros(len(STRUCTURE_COUNTERS), np.int64)
+        _chk(self._L.lbmdem_structure_compute(self._h, float(rcut), int(nbins), float(shell), int(max_entries), _vp(c)))
+        return dict(zip(STRUCTURE_COUNTERS, (int(v) for v in c)))
+
+    def structure_grains(self):
+        """structured array [n] of STRUCTURE_DTYPE of the last structure(): neighbours, bonds and the unnormalised sums c6, s6
+        (psi6) and c2, s2 (fabric) over the bonded neighbours"""
+        cols = {k: np.zeros(self.n, STRUCTURE_DTYPE[k]) for k in STRUCTURE_DTYPE.names}
+        _chk(self._L.lbmdem_download_structure_grains(self._h, *(_vp(cols[k]) for k in STRUCTURE_DTYPE.names)))
+        out = np.zeros(self.n, STRUCTURE_DTYPE)
+        for k in STRUCTURE_DTYPE.names:
+            out[k] = cols[k]
+        return out
+
+    def structure_tensors(self):
+        """the same six as torch views (int32, float64) of the handle's device memory, good until the next structure()"""
+        import torch
+        p = [C.c_void_p() for _ in range(6)]
+        _chk(self._L.lbmdem_structure_grains_device(self._h, *(C.byref(q) for q in p)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(q.value, (self.n,), "<i4" if STRUCTURE_DTYPE[k] == np.int32 else "<f8"), device=dev)
+                for k, q in zip(STRUCTURE_DTYPE.names, p)}
+
+    def structure_hist(self):
+        """int64 [nbins]: the unordered neighbour pairs per bin of the last structure()"""
+        nb = C.c_int(0)
+        _chk(self._L.lbmdem_download_structure_hist(self._h, None, 0, C.byref(nb)))
+        out = np.zeros(nb.value, np.int64)
+        _chk(self._L.lbmdem_download_structure_hist(self._h, _vp(out), nb.value, C.byref(nb)))
+        return out
+
+    def structure_neighbours(self):
+        """-> (offsets int32 [n + 1], nbr int32 [entries]): the symmetric list of the last structure(), every grain's neighbours
+        ascending by index"""
+        cnt = C.c_long(0)
+        _chk(self._L.lbmdem_download_structure_neighbours(self._h, None, None, 0, C.byref(cnt)))
+        off, nbr = np.zeros(self.n + 1, np.int32), np.zeros(cnt.value, np.int32)
+        _chk(self._L.lbmdem_download_structure_neighbours(self._h, _vp(off), _vp(nbr) if cnt.value else None, cnt.value, C.byref(cnt)))
+        return off, nbr
+
+    def write_structure(self, directory=".", nFile=0, rcut=0.0, nbins=64, shell=1.2):
+        """structure%.6i.dat, gr%.6i.dat and a line of structure.data of the grains where they are now"""
+        _chk(self._L.lbmdem_write_structure(self._h, os.fsencode(directory), int(nFile), float(rcut), int(nbins), float(shell)))
+
+    def set_structure_output(self, on=True, rcut=0.0, nbins=64, shell=1.2):
+        """run_scene writes the structure files at every DEM event, behind the cluster files"""
+        _chk(self._L.lbmdem_set_structure_output(self._h, 1 if on else 0, float(rcut), int(nbins), float(shell)))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

@@ -1562,6 +1562,7 @@ int lbmdem_upload_kinematics(lbmdem_handle* h, const double* k9) try {
   HIP_TRY(hipMemcpy(h->kin[h->kcur].x1, soa.data(), sizeof(real) * 9 * n, hipMemcpyHostToDevice));
   h->verlet_tracks_positions = false;   // the pair list no longer bounds which discs can meet (obst_construction: atomics)
   h->contacts_valid = false;
+  h->grains_moved++;   // (what lbmdem_structure_compute has made describes other centres)
   drop_chain_paint(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {

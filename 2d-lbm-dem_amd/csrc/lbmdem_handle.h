@@ -318,6 +318,34 @@ struct lbmdem_handle {
     long nclusters = 0, npairs = 0, nrec = 0;   // of the last compute
     int rounds_cc = 0, rounds_core = 0;         // rounds the two loops took in the last compute
   } cl;
+  // The packing structure beyond contacts (lbm_structure.hip): neighbour shells, g(r), bond order. st: scratch and results,
+  // allocated by the first lbmdem_structure_compute, grown with the entries, freed with the handle. The results describe the
+  // centres as of sub-step `seq` and upload `moved`: the readers ask for seq == substep_seq and moved == grains_moved (every
+  // sub-step raises the one, lbmdem_upload_kinematics the other; a checkpoint load makes a new handle). structure_*:
+  // lbmdem_set_structure_output.
+  long long grains_moved = 0;
+  bool structure_output = false;
+  double structure_rcut = 0., structure_shell = 0.;
+  int structure_nbins = 0;
+  struct StructureStage {
+    bool valid = false, listed = false;   // a compute has been made; it made the list, bonds and the four sums too
+    long long seq = -1, moved = -1;
+    unsigned long long* words = nullptr;  // [ST_WORDS] bounds' keys and the census (null: nothing allocated yet)
+    void* grid = nullptr;                 // the cell grid's origin, sides and counts, made on the device
+    unsigned* keys = nullptr;             // [2][n] a grain's cell, unsorted and sorted
+    int* idx = nullptr;                   // [2][n] the grains, by index and by cell
+    double* sorted = nullptr;             // [3][n] x, y, r by cell
+    int* ints = nullptr;                  // nb [n + 1], bonds [n], offsets [n + 1]
+    double* sums = nullptr;               // [4][n] c6, s6, c2, s2
+    double* e2 = nullptr;                 // [4097]
+    unsigned long long* hist = nullptr;   // [4096]
+    int* nbr = nullptr;                   // [nbr_cap] twice the entries: as emitted, then ascending
+    long nbr_cap = 0;
+    char* tmp = nullptr;                  // hipcub's scratch, sorts and scan
+    long tmp_bytes = 0;
+    long entries = 0;                     // of the last compute
+    int nbins = 0;
+  } st;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -575,6 +575,89 @@ int lbmdem_write_clusters_files(const char* dir, int nfile, int n, const double*
                                 const double* fm, const lbmdem_contact* c, long count, const int* label, const int* degree,
                                 const int* core, const int* walls, const lbmdem_cluster* table, long nclusters, double fmin,
                                 int relative, int zmin, double thr, const long* counts10, double t, int lx, int ly);   /* host only */
+/* Packing structure: what a packing looks like beyond touching partners -- the fixed-radius neighbour list in index order, the pair
+ * histogram behind g(r), the bonds of the first shell and the unnormalised bond-order (psi6) and fabric sums -- on the device, so
+ * that nobody has to download the centres and run an all-pairs or k-d-tree job at every DEM event. Results are integers wherever
+ * possible; where they are floating point, each is a chain of IEEE double operations in the order stated here, which a numpy
+ * restatement reproduces on the bits (tests/structure_util.py).
+ * Inputs: the current centres x_i, y_i (columns 0 and 1 of lbmdem_download_grain_table, as they are once the handle is settled) and
+ * radii r_i (column 9) of the n grains; rcut, finite and > 0, in the unit of the kinematics; nbins in 1 .. 4096; shell, finite and
+ * >= 1; max_entries in 0 .. 2^31 - 1. All arithmetic is IEEE double without contraction.
+ * 1. Neighbours. dx = x_j - x_i, dy = y_j - y_i, d2 = dx*dx + dy*dy (two products, then one addition), rc2 = rcut*rcut. j is a
+ *    neighbour of i iff j != i and d2 <= rc2 -- never, then, with a NaN, and never with an infinite centre; coincident centres are
+ *    neighbours. The list is symmetric CSR: offsets[n + 1] ints and nbr[], each grain's neighbours ascending by index.
+ * 2. Pair histogram. dr = rcut / nbins; e2[k] = (k*dr)*(k*dr) for k = 0 .. nbins - 1, k converted to double; e2[nbins] = rc2.
+ *    hist[k] is the 64-bit count of the unordered neighbour pairs i < j with e2[k] <= d2, and d2 < e2[k + 1] for k < nbins - 1: the
+ *    last bin takes everything up to and including rc2. The table alone decides a bin (where neighbouring edges are equal, the last
+ *    bin k with e2[k] <= d2); the device guesses with sqrt(d2)/dr and corrects the guess against the table.
+ *    lbmdem_structure_edges returns the table, e2[nbins + 1] (host only).
+ * 3. Bonds. A neighbour is bonded iff d2 <= b*b with b = shell * (r_i + r_j). bonds[i] is their number.
+ * 4. Bond order and fabric. c6[i], s6[i], c2[i], s2[i] start from +0.0; the bonded neighbours with d2 > 0 are added one by one, j
+ *    ascending: d = sqrt(d2), nx = dx/d, ny = dy/d; a2 = nx*nx - ny*ny, b2 = 2.*nx*ny; a4 = a2*a2 - b2*b2, b4 = 2.*a2*b2;
+ *    a6 = a4*a2 - b4*b2, b6 = b4*a2 + a4*b2; c2 += a2; s2 += b2; c6 += a6; s6 += b6. Unnormalised: |psi6| = sqrt(c6^2 + s6^2) / bonds
+ *    and the fabric anisotropy are divisions the caller makes.
+ * 5. counts8, in order: list entries (2 x pairs); pairs; bonded pairs (i < j); the largest offsets[i + 1] - offsets[i]; grains
+ *    without a neighbour; grains with exactly six bonds; coincident pairs (d2 == 0, i < j); grains with a non-finite centre.
+ * Capacity: when the entries exceed max_entries > 0 the compute fails with LBMDEM_EINVAL and a sentence that carries both numbers,
+ * and nothing is allocated for the list. max_entries == 0 asks for the counts and the histogram only: the list, bonds and the four
+ * sums are not produced and their readers refuse.
+ * On the device, all on the handle's stream: a cell grid of the analysis' own over the current centres -- bounds from a min/max over
+ * the finite centres, the cell side per axis max(rcut, extent / 1024) and 2^-20 of it more (so that the rounding of a cell index
+ * cannot separate two grains at exactly rcut by two cells), the non-finite centres in one cell of their own; the grains ordered by
+ * cell with a radix sort; count, scan, emit over the 3 x 3 cells with the candidates staged in LDS 256 at a time (a cell may hold any
+ * number of grains); the histogram per workgroup in LDS as 32-bit integers, flushed with 64-bit atomics; a segmented sort for the
+ * index order; one lane per grain for the chains of 4. No floating-point atomic, no workgroup waits for another, every loop has a
+ * bound. The Verlet list and its grid are not touched. Scratch comes from the handle's pool with the first call.
+ *   lbmdem_structure_compute              the compute; counts8. Synchronises; changes nothing a later step reads.
+ *   lbmdem_download_structure_grains      nb (= offsets[i + 1] - offsets[i]) and bonds, [n] ints; c6, s6, c2, s2, [n] doubles; any
+ *                                         pointer may be NULL
+ *   lbmdem_structure_grains_device        the same six as device pointers into the handle's scratch (for a torch view), good until
+ *                                         the next compute or lbmdem_destroy; any pointer may be NULL
+ *   lbmdem_download_structure_hist        hist[nbins] of the last compute; cap = 0 only reports *nbins; a buffer of fewer bins is
+ *                                         refused with *nbins set
+ *   lbmdem_download_structure_neighbours  offsets[n + 1] (may be NULL) and nbr[]; cap = 0 leaves nbr alone and reports *count, the
+ *                                         entries; a buffer of fewer than *count entries is refused with *count set
+ *   These readers are refused, with LBMDEM_EINVAL and a sentence that names lbmdem_structure_compute, until a compute has been
+ *   made, and again after anything that moves grains: a sub-step (every kind of step makes some), lbmdem_upload_kinematics; a
+ *   checkpoint load gives a new handle, on which no compute has been made. After a compute with max_entries == 0 every reader but
+ *   the histogram's refuses.
+ *   lbmdem_write_structure_files          host only, no handle, no device. Three files in <dir>:
+ *                                         structure%.6i.dat -- "# rcut %le nbins %d shell %le\n", "# i neighbours bonds c6 s6 c2
+ *                                         s2\n", then n lines "%d %d %d %le %le %le %le\n" of i, nb, bonds, c6, s6, c2, s2;
+ *                                         gr%.6i.dat -- "# rcut %le nbins %d n %d W %le H %le\n", a second "#" line that states g,
+ *                                         then per bin "%d %le %le %ld %le\n" of k, sqrt(e2[k]), sqrt(e2[k + 1]), hist[k] and
+ *                                         g = hist[k] / ideal, ideal = ((npairs_all * pi) * (e2[k + 1] - e2[k])) / (W * H) in
+ *                                         this association, npairs_all = ((double)n * (double)(n - 1)) / 2., pi =
+ *                                         3.141592653589793; g = 0 where ideal is no positive number. No edge correction;
+ *                                         structure.data -- one line appended: "%le" of t, " %ld" of each of the eight counts,
+ *                                         " %le %le\n" of psi6 and fabric. psi6: the sum, from +0.0 and by index, of
+ *                                         sqrt(c6*c6 + s6*s6) / bonds over the grains with bonds, divided by their number (0
+ *                                         without one); fabric: sqrt(C2*C2 + S2*S2) / B with C2, S2 the sums of c2, s2 from +0.0
+ *                                         by index and B the sum of bonds (0 when B is 0). When the file is created, first the line
+ *                                         "# t entries pairs bonded_pairs max_neighbours lone_grains six_bonds coincident_pairs
+ *                                         nonfinite_grains psi6 fabric". It checks fopen; nb outside [0, n), bonds outside
+ *                                         [0, nb] and a negative bin are refused before anything is written.
+ *   lbmdem_write_structure                the compute with max_entries = 2^31 - 1, the downloads, then that formatter with
+ *                                         t = nbsteps * dt, W = Mdx - Mgx and H = Mhy - Mby, where the walls stand
+ *   lbmdem_set_structure_output           on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_structure(dir, nFile, rcut,
+ *                                         nbins, shell) at every DEM event, behind the cluster files. Off by default; a checkpoint
+ *                                         does not carry it.
+ * Single-domain fp64 handles; vibrating, probing, lid, tracer, scalar and mean handles included. LBMDEM_EINVAL: a parameter outside
+ * its range; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the single-precision
+ * library (the two host-only functions exist there too); null buffers; a directory that cannot be written ("cannot open"). */
+#define LBMDEM_STRUCTURE_COUNTS 8
+int lbmdem_structure_edges(double rcut, int nbins, double* e2);   /* host only */
+int lbmdem_structure_compute(lbmdem_handle* h, double rcut, int nbins, double shell, long max_entries, long* counts8);
+int lbmdem_download_structure_grains(lbmdem_handle* h, int* nb, int* bonds, double* c6, double* s6, double* c2, double* s2);
+int lbmdem_structure_grains_device(lbmdem_handle* h, const int** nb, const int** bonds, const double** c6, const double** s6,
+                                   const double** c2, const double** s2);
+int lbmdem_download_structure_hist(lbmdem_handle* h, long* hist, int cap, int* nbins);
+int lbmdem_download_structure_neighbours(lbmdem_handle* h, int* offsets, int* nbr, long cap, long* count);
+int lbmdem_write_structure(lbmdem_handle* h, const char* dir, int nfile, double rcut, int nbins, double shell);
+int lbmdem_set_structure_output(lbmdem_handle* h, int on, double rcut, int nbins, double shell);   /* 0: off (default) */
+int lbmdem_write_structure_files(const char* dir, int nfile, int n, const int* nb, const int* bonds, const double* c6,
+                                 const double* s6, const double* c2, const double* s2, double rcut, int nbins, double shell,
+                                 const long* hist, const long* counts8, double t, double W, double H);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
