@@ -196,6 +196,14 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_structure_output.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double]
     L.lbmdem_write_structure_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double, C.c_int, C.c_double] +
                                                [C.c_void_p] * 2 + [C.c_double] * 3)
+    L.lbmdem_voronoi_compute.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_download_voronoi_grains.argtypes = [C.c_void_p] + [C.c_void_p] * 8
+    L.lbmdem_voronoi_grains_device.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 8
+    L.lbmdem_download_voronoi_faces.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_write_voronoi.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_double]
+    L.lbmdem_set_voronoi_output.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    L.lbmdem_write_voronoi_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_double, C.c_void_p] +
+                                             [C.c_double] * 3)
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -460,6 +468,29 @@ def write_structure_files(directory, nFile, grains, rcut, nbins, shell, hist, co
     _chk(load_library(precision).lbmdem_write_structure_files(
         os.fsencode(directory), int(nFile), len(g), *(_vp(a) for a in ints), *(_vp(a) for a in dbl), float(rcut), int(nbins),
         float(shell), _vp(hh), _vp(cnt), float(t), float(W), float(H)))
+
+
+# the per-grain results of LbmDem.voronoi() (LbmDem.voronoi_grains), the names of its eight counts, and the bits of `flags`
+VORONOI_DTYPE = np.dtype([("area", np.float64), ("perimeter", np.float64), ("phi", np.float64), ("R2", np.float64),
+                          ("faces", np.int32), ("walls", np.int32), ("nverts", np.int32), ("flags", np.int32)])
+VORONOI_COUNTERS = ("cells", "complete", "empty", "overflowed", "nonfinite_grains", "grain_faces", "wall_faces", "max_faces")
+VOR_MAXV = 32
+VOR_COMPLETE, VOR_EMPTY, VOR_OVERFLOW, VOR_NONFINITE = 1, 2, 4, 8
+
+
+def write_voronoi_files(directory, nFile, grains, rcut, counts, t, W, H, precision="f64"):
+    """voronoi%.6i.dat and one appended line of voronoi.data (include/lbmdem_hip.h spells the two formats out) from the per-grain
+    results (VORONOI_DTYPE), the cutoff, the eight counts (a dict of VORONOI_COUNTERS or a sequence), the time of the line and the
+    box's extent. Host only."""
+    g = np.ascontiguousarray(grains, dtype=VORONOI_DTYPE).reshape(-1)
+    cols = [np.ascontiguousarray(g[k]) for k in ("area", "perimeter", "phi", "faces", "walls", "nverts", "flags")]
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in VORONOI_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(VORONOI_COUNTERS):
+        raise LbmDemError(-1, "write_voronoi_files: counts must have eight values")
+    _chk(load_library(precision).lbmdem_write_voronoi_files(
+        os.fsencode(directory), int(nFile), len(g), *(_vp(a) for a in cols), float(rcut), _vp(cnt), float(t), float(W), float(H)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1134,6 +1165,53 @@ class LbmDem:
     def set_structure_output(self, on=True, rcut=0.0, nbins=64, shell=1.2):
         """run_scene writes the structure files at every DEM event, behind the cluster files"""
         _chk(self._L.lbmdem_set_structure_output(self._h, 1 if on else 0, float(rcut), int(nbins), float(shell)))
+
+    # Voronoi cells: the radical tessellation on top of the last structure()'s neighbour list (include/lbmdem_hip.h)
+    def voronoi(self, rcut=None):
+        """the cells of the grains where they are now, from the neighbour list of the last structure(); with rcut that compute is
+        made first, structure(rcut, 1, 1.0) -> dict of VORONOI_COUNTERS"""
+        if rcut is not None:
+            self.structure(rcut, 1, 1.0)
+        c = np.zeros(len(VORONOI_COUNTERS), np.int64)
+        _chk(self._L.lbmdem_voronoi_compute(self._h, _vp(c)))
+        return dict(zip(VORONOI_COUNTERS, (int(v) for v in c)))
+
+    def voronoi_grains(self):
+        """structured array [n] of VORONOI_DTYPE of the last voronoi(): a cell's area, perimeter, local solid fraction and largest
+        squared vertex distance, its grain faces, wall bits, vertices and flags (VOR_COMPLETE, ...)"""
+        cols = {k: np.zeros(self.n, VORONOI_DTYPE[k]) for k in VORONOI_DTYPE.names}
+        _chk(self._L.lbmdem_download_voronoi_grains(self._h, *(_vp(cols[k]) for k in VORONOI_DTYPE.names)))
+        out = np.zeros(self.n, VORONOI_DTYPE)
+        for k in VORONOI_DTYPE.names:
+            out[k] = cols[k]
+        return out
+
+    def voronoi_tensors(self):
+        """the same eight as torch views (float64, int32) of the handle's device memory, good until the next voronoi()"""
+        import torch
+        p = [C.c_void_p() for _ in range(8)]
+        _chk(self._L.lbmdem_voronoi_grains_device(self._h, *(C.byref(q) for q in p)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(q.value, (self.n,), "<i4" if VORONOI_DTYPE[k] == np.int32 else "<f8"), device=dev)
+                for k, q in zip(VORONOI_DTYPE.names, p)}
+
+    def voronoi_faces(self):
+        """-> (foff int32 [n + 1], fsrc int32 [faces], flen float64 [faces]): every cell's faces in polygon order, the neighbour
+        behind each (or -1 .. -4: the bottom, right, top and left wall) and its length"""
+        cnt = C.c_long(0)
+        _chk(self._L.lbmdem_download_voronoi_faces(self._h, None, None, None, 0, C.byref(cnt)))
+        off, src, length = np.zeros(self.n + 1, np.int32), np.zeros(cnt.value, np.int32), np.zeros(cnt.value, np.float64)
+        _chk(self._L.lbmdem_download_voronoi_faces(self._h, _vp(off), _vp(src) if cnt.value else None,
+                                                   _vp(length) if cnt.value else None, cnt.value, C.byref(cnt)))
+        return off, src, length
+
+    def write_voronoi(self, directory=".", nFile=0, rcut=0.0):
+        """voronoi%.6i.dat and a line of voronoi.data of the grains where they are now"""
+        _chk(self._L.lbmdem_write_voronoi(self._h, os.fsencode(directory), int(nFile), float(rcut)))
+
+    def set_voronoi_output(self, on=True, rcut=0.0):
+        """run_scene writes the Voronoi files at every DEM event, behind the structure files"""
+        _chk(self._L.lbmdem_set_voronoi_output(self._h, 1 if on else 0, float(rcut)))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

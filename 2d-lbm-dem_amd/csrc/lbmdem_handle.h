@@ -346,6 +346,27 @@ struct lbmdem_handle {
     long entries = 0;                     // of the last compute
     int nbins = 0;
   } st;
+  // Voronoi cells (lbm_voronoi.hip): the radical tessellation on top of st's neighbour list. vo: scratch and results, allocated by
+  // the first lbmdem_voronoi_compute, the face arrays grown with the faces, freed with the handle. The kernels read st and the
+  // kinematics and write here only. seq, moved: as st's, and the readers ask the same of them. voronoi_*: lbmdem_set_voronoi_output.
+  bool voronoi_output = false;
+  double voronoi_rcut = 0.;
+  struct VoronoiStage {
+    bool valid = false;
+    long long seq = -1, moved = -1;
+    unsigned long long* words = nullptr;  // [VO_WORDS] the census (null: nothing allocated yet)
+    double* dbl = nullptr;                // [4][n] area, perimeter, phi, R2
+    int* ints = nullptr;                  // [4][n] faces, walls, nverts, flags; then nf [n + 1] and foff [n + 1]
+    int* rsrc = nullptr;                  // [VOR_MAXV][n] a grain's faces as the cell pass leaves them, face k of grain i at k*n + i
+    double* rlen = nullptr;               // [VOR_MAXV][n]
+    int* fsrc = nullptr;                  // [fsrc_cap] the faces as CSR
+    double* flen = nullptr;               // [flen_cap]
+    long fsrc_cap = 0, flen_cap = 0;
+    char* tmp = nullptr;                  // hipcub's scratch, the scan
+    long tmp_bytes = 0;
+    long nfaces = 0;                      // of the last compute
+    double rcut = 0.;                     // the structure compute's, as the last compute recovered it
+  } vo;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -658,6 +658,92 @@ int lbmdem_set_structure_output(lbmdem_handle* h, int on, double rcut, int nbins
 int lbmdem_write_structure_files(const char* dir, int nfile, int n, const int* nb, const int* bonds, const double* c6,
                                  const double* s6, const double* c2, const double* s2, double rcut, int nbins, double shell,
                                  const long* hist, const long* counts8, double t, double W, double H);   /* host only */
+/* Voronoi cells: how much space a grain has -- the radical (power, Laguerre) tessellation of the discs inside the four walls, on the
+ * device and on top of the neighbour list the structure analysis leaves there: per grain the cell's area, perimeter and local solid
+ * fraction, its topological neighbour count and the walls it touches, and the cells' faces as CSR -- the Delaunay graph with the
+ * length of every face. Every floating-point result is a chain of IEEE double operations in the order stated here, which a Python
+ * restatement reproduces on the bits (tests/voronoi_util.py).
+ * Inputs: the centres x_i, y_i and radii r_i as the structure analysis reads them; the four walls where they stand now, Mgx, Mdx,
+ * Mby, Mhy of lbmdem_get_config (on a vibrating handle the moved walls); offsets, nbr and rcut of the most recent
+ * lbmdem_structure_compute, which must still be valid and must have made a list (the handle keeps rcut*rcut, the last edge of
+ * that compute's table; squaring is one-to-one on doubles with a normal square, so rcut is the one double whose square rounds to
+ * it, and a compute whose rcut*rcut is no normal number is refused); rmax, the largest r_i (a max is exact in any order). All
+ * arithmetic is IEEE double without contraction, the operations in the order written here.
+ * 1. The cell of grain i is a convex polygon of at most LBMDEM_VOR_MAXV = 32 vertices; vertex k carries (vx, vy) and src, the source
+ *    of the edge that leaves it towards vertex k + 1 (cyclically): a grain's index, or -1 .. -4 for the bottom, right, top and left
+ *    wall. It starts as the box, counter-clockwise: (Mgx, Mby, -1) (Mdx, Mby, -2) (Mdx, Mhy, -3) (Mgx, Mhy, -4). A grain with a
+ *    non-finite centre starts with no vertices.
+ * 2. The polygon is clipped by each neighbour j of the list, in list order (ascending index), while it has vertices:
+ *    dx = x_j - x_i, dy = y_j - y_i, d2 = dx*dx + dy*dy; j is skipped unless d2 > 0. h = 0.5*((d2 + r_i*r_i) - r_j*r_j). For every
+ *    vertex s = ((vx - x_i)*dx + (vy - y_i)*dy) - h; the vertex is inside iff s <= 0. The edges a -> b are walked in order: if a is
+ *    inside, a is emitted with its own src; if exactly one of a, b is inside, t = sa/(sa - sb) and the vertex
+ *    (a.vx + t*(b.vx - a.vx), a.vy + t*(b.vy - a.vy)) is emitted with src = j when a is inside, else a.src. A line that cuts nothing
+ *    (every vertex inside) leaves the polygon as it was -- the device may therefore pass over a j of which a bound shows that
+ *    every s is negative. A clip that would leave more than 32 vertices overflows the cell: no vertices, flag OVERFLOW.
+ * 3. Measures, one walk over the final polygon, sums from +0.0: with ax = a.vx - x_i, ay = a.vy - y_i and bx, by alike,
+ *    A2 += ax*by - bx*ay and area = 0.5*A2; with ex = b.vx - a.vx, ey = b.vy - a.vy, len = sqrt(ex*ex + ey*ey) and
+ *    perimeter += len; R2 = max(ax*ax + ay*ay), from 0. An edge is a face iff its two endpoints differ in either coordinate,
+ *    compared on values (lattices make edges of no length, and those must not count). faces counts the faces with src >= 0, walls
+ *    is the OR of 1 << (-src - 1) over the faces with src < 0, nverts the vertices. phi = ((pi*r_i)*r_i)/area where area > 0, else
+ *    0, pi = 3.141592653589793. A cell without vertices has zeros in every measure.
+ * 4. flags: LBMDEM_VOR_EMPTY -- no vertices left and not overflowed (a non-finite centre too); LBMDEM_VOR_OVERFLOW;
+ *    LBMDEM_VOR_NONFINITE -- the centre; LBMDEM_VOR_COMPLETE -- with bound = 0.5*(rcut + (r_i*r_i - rmax*rmax)/rcut), set iff
+ *    nverts > 0 && bound > 0 && R2 <= bound*bound. Then no grain beyond the cutoff could cut the cell: a point p of the cell has
+ *    |p - x_i| <= bound =: b, a grain j outside the list has |x_j - x_i| > rcut, hence |p - x_j| > rcut - b, and j's power
+ *    (rcut - b)^2 - rmax^2 = b^2 - r_i^2 + (rcut^2 - 2 rcut b - rmax^2 + r_i^2) = b^2 - r_i^2 is no smaller than i's own.
+ * 5. Faces as CSR: foff[n + 1] is the scan of the number of faces of either kind; per face, in polygon order, fsrc (the neighbour,
+ *    or -1 .. -4) and flen (len above). j is a Delaunay neighbour of i where j is in i's segment of fsrc.
+ * 6. counts8, in order: cells with area > 0; complete cells; empty cells; overflowed cells; grains with a non-finite centre; grain
+ *    faces, counted from both sides; wall faces; the largest faces.
+ * On the device, on the handle's stream: one lane per grain clips its own cell serially, the polygon (twice: the one it clips, the
+ * one it makes) in an LDS slice of its own; the faces go to rows, a scan makes foff, an emit fills the CSR; the census is integer
+ * atomics. No floating-point atomic, no workgroup waits for another, every loop has a bound. The kernels read the structure
+ * analysis' list and the kinematics and write to scratch of their own, taken from the handle's pool with the first call.
+ *   lbmdem_voronoi_compute          the compute; counts8. Synchronises; changes nothing a later step reads. Refused with a sentence
+ *                                   that names lbmdem_structure_compute when no such compute describes the grains where they are now,
+ *                                   or when the last one had max_entries == 0.
+ *   lbmdem_download_voronoi_grains  area, perimeter, phi, R2, [n] doubles; faces, walls, nverts, flags, [n] ints; any pointer may
+ *                                   be NULL
+ *   lbmdem_voronoi_grains_device    the same eight as device pointers into the handle's scratch (for a torch view), good until the
+ *                                   next compute or lbmdem_destroy; any pointer may be NULL
+ *   lbmdem_download_voronoi_faces   foff[n + 1] (may be NULL), fsrc[] and flen[] (either may be NULL); cap = 0 leaves both alone and
+ *                                   reports *count, the faces; buffers of fewer than *count faces are refused with *count set
+ *   These readers are refused, with LBMDEM_EINVAL and a sentence that names lbmdem_voronoi_compute, until a compute has been made,
+ *   and again after anything that moves grains, exactly as the structure readers are.
+ *   lbmdem_write_voronoi_files      host only, no handle, no device. Two files in <dir>: voronoi%.6i.dat -- "# rcut %le\n",
+ *                                   "# i area perimeter phi faces walls nverts flags\n", then n lines "%d %le %le %le %d %d %d %d\n";
+ *                                   voronoi.data -- one line appended: "%le" of t, " %ld" of each of the eight counts,
+ *                                   " %le %le %le %le\n" of the sum of area from +0.0 by index, W*H, the mean phi over the complete
+ *                                   cells with area > 0 (their phi added from +0.0 by index, divided by their number; 0 without
+ *                                   one) and the mean faces over the same cells (faces converted to double, added and divided
+ *                                   alike). When the file is created, first the line "# t cells complete empty overflowed
+ *                                   nonfinite_grains grain_faces wall_faces max_faces sum_area box_area mean_phi mean_faces". It
+ *                                   checks fopen; nverts outside [0, 32] and faces outside [0, nverts] are refused before anything
+ *                                   is written.
+ *   lbmdem_write_voronoi            lbmdem_structure_compute(rcut, 1, 1.0, 2^31 - 1), the Voronoi compute, the downloads, then that
+ *                                   formatter with t = nbsteps * dt, W = Mdx - Mgx and H = Mhy - Mby, where the walls stand
+ *   lbmdem_set_voronoi_output       on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_voronoi(dir, nFile, rcut) at every
+ *                                   DEM event, behind the structure files. Off by default; a checkpoint does not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL: rcut not finite and > 0; a strip of a decomposition or distributed grains (and
+ * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers;
+ * a directory that cannot be written ("cannot open"). */
+#define LBMDEM_VORONOI_COUNTS 8
+#define LBMDEM_VOR_MAXV 32
+#define LBMDEM_VOR_COMPLETE 1
+#define LBMDEM_VOR_EMPTY 2
+#define LBMDEM_VOR_OVERFLOW 4
+#define LBMDEM_VOR_NONFINITE 8
+int lbmdem_voronoi_compute(lbmdem_handle* h, long* counts8);
+int lbmdem_download_voronoi_grains(lbmdem_handle* h, double* area, double* perimeter, double* phi, double* R2, int* faces, int* walls,
+                                   int* nverts, int* flags);
+int lbmdem_voronoi_grains_device(lbmdem_handle* h, const double** area, const double** perimeter, const double** phi,
+                                 const double** R2, const int** faces, const int** walls, const int** nverts, const int** flags);
+int lbmdem_download_voronoi_faces(lbmdem_handle* h, int* foff, int* fsrc, double* flen, long cap, long* count);
+int lbmdem_write_voronoi(lbmdem_handle* h, const char* dir, int nfile, double rcut);
+int lbmdem_set_voronoi_output(lbmdem_handle* h, int on, double rcut);   /* 0: off (default) */
+int lbmdem_write_voronoi_files(const char* dir, int nfile, int n, const double* area, const double* perimeter, const double* phi,
+                               const int* faces, const int* walls, const int* nverts, const int* flags, double rcut,
+                               const long* counts8, double t, double W, double H);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
