@@ -204,6 +204,16 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_voronoi_output.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.lbmdem_write_voronoi_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_double, C.c_void_p] +
                                              [C.c_double] * 3)
+    L.lbmdem_pore_compute.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.lbmdem_download_pore_labels.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_pore_labels_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.lbmdem_download_pores.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_pore_grains.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+    L.lbmdem_pore_grains_device.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+    L.lbmdem_write_pores.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_set_pores_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_write_pore_files.argtypes = ([C.c_char_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_long, C.c_int] +
+                                          [C.c_void_p] * 4 + [C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -491,6 +501,37 @@ def write_voronoi_files(directory, nFile, grains, rcut, counts, t, W, H, precisi
         raise LbmDemError(-1, "write_voronoi_files: counts must have eight values")
     _chk(load_library(precision).lbmdem_write_voronoi_files(
         os.fsencode(directory), int(nFile), len(g), *(_vp(a) for a in cols), float(rcut), _vp(cnt), float(t), float(W), float(H)))
+
+
+# struct lbmdem_pore: one connected component of the fluid phase (LbmDem.pore_table), 56 bytes; the names of the ten counts of
+# LbmDem.pores()
+PORE_DTYPE = np.dtype([("label", np.int32), ("walls", np.int32), ("nodes", np.int64), ("grain_links", np.int64),
+                       ("wall_links", np.int64), ("mass_q32", np.int64), ("xmin", np.int32), ("xmax", np.int32), ("ymin", np.int32),
+                       ("ymax", np.int32)])
+PORE_COUNTERS = ("fluid_nodes", "components", "largest_nodes", "largest_label", "trapped_nodes", "single_nodes", "spanning",
+                 "throat_grains", "dry_grains", "unaccumulated")
+
+
+def write_pore_files(directory, nFile, conn, lx, ly, table, wet, pore_min, pore_max, counts, t, label=None, precision="f64"):
+    """pore_table%.6i.dat, pore_grains%.6i.dat, one appended line of pores.data and, with a label plane (lx, ly),
+    pores%.6i.vtk (include/lbmdem_hip.h spells the four formats out) from the table (PORE_DTYPE), the three per-grain results,
+    the ten counts (a dict of PORE_COUNTERS or a sequence) and the time of the line. Host only."""
+    tab = np.ascontiguousarray(table, dtype=PORE_DTYPE).reshape(-1)
+    ints = [np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (wet, pore_min, pore_max)]
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in PORE_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    n = len(ints[0])
+    if any(len(a) != n for a in ints) or len(cnt) != len(PORE_COUNTERS):
+        raise LbmDemError(-1, "write_pore_files: wet, pore_min and pore_max must have one value per grain, counts ten")
+    lab = None
+    if label is not None:
+        lab = np.ascontiguousarray(label, dtype=np.int32)
+        if lab.shape != (int(lx), int(ly)):
+            raise LbmDemError(-1, "write_pore_files: a label plane of shape (lx, ly)")
+    _chk(load_library(precision).lbmdem_write_pore_files(
+        os.fsencode(directory), int(nFile), int(conn), int(lx), int(ly), 0 if lab is None else 1, None if lab is None else _vp(lab),
+        _vp(tab) if len(tab) else None, len(tab), n, *(_vp(a) for a in ints), _vp(cnt), float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1212,6 +1253,66 @@ class LbmDem:
     def set_voronoi_output(self, on=True, rcut=0.0):
         """run_scene writes the Voronoi files at every DEM event, behind the structure files"""
         _chk(self._L.lbmdem_set_voronoi_output(self._h, 1 if on else 0, float(rcut)))
+
+    # pore space: the connected components of the fluid phase of the map as it is now (include/lbmdem_hip.h)
+    def pores(self, conn=8, map=None):
+        """labels the fluid nodes of the handle's map -- or of `map`, (lx, ly) ints: -1 fluid, a grain's index, n the wall -- into
+        components joined along 4 or 8 directions -> dict of PORE_COUNTERS"""
+        c = np.zeros(len(PORE_COUNTERS), np.int64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "pores: a map of shape (lx, ly)")
+        _chk(self._L.lbmdem_pore_compute(self._h, int(conn), None if m is None else _vp(m), _vp(c)))
+        return dict(zip(PORE_COUNTERS, (int(v) for v in c)))
+
+    def pore_labels(self):
+        """int32 (lx, ly) of the last pores(): the smallest index x * ly + y of a fluid node's component, -1 off the fluid"""
+        out = np.empty((self.lx, self.ly), np.int32)
+        _chk(self._L.lbmdem_download_pore_labels(self._h, _vp(out)))
+        return out
+
+    def pore_labels_tensor(self):
+        """the same plane as a torch.int32 view (lx, sy) of the handle's device memory, sy the device's row pitch: node (x, y) at
+        [x, y], the columns from ly on hold -1. Good until the next pores()."""
+        import torch
+        p, sy = C.c_void_p(), C.c_int(0)
+        _chk(self._L.lbmdem_pore_labels_device(self._h, C.byref(p), C.byref(sy)))
+        return torch.as_tensor(_DeviceBlock(p.value, (self.lx, sy.value), "<i4"), device=f"cuda:{self.cfg.device}")
+
+    def pore_table(self):
+        """structured array of PORE_DTYPE: the components of the last pores(), ascending label"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_pores(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=PORE_DTYPE)
+        if n.value:
+            _chk(self._L.lbmdem_download_pores(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def pore_grains(self):
+        """-> dict of the per-grain results of the last pores(): wet (links into fluid), pore_min and pore_max (the smallest and
+        largest label a grain borders, -1 without one); int32 arrays [n]"""
+        out = {k: np.zeros(self.n, np.int32) for k in ("wet", "pore_min", "pore_max")}
+        _chk(self._L.lbmdem_download_pore_grains(self._h, *(_vp(out[k]) for k in ("wet", "pore_min", "pore_max"))))
+        return out
+
+    def pore_grains_tensors(self):
+        """the same three as torch.int32 views of the handle's device memory, good until the next pores()"""
+        import torch
+        p = [C.c_void_p() for _ in range(3)]
+        _chk(self._L.lbmdem_pore_grains_device(self._h, *(C.byref(q) for q in p)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(q.value, (self.n,), "<i4"), device=dev)
+                for k, q in zip(("wet", "pore_min", "pore_max"), p)}
+
+    def write_pores(self, directory=".", nFile=0, conn=8, plane=False):
+        """pore_table%.6i.dat, pore_grains%.6i.dat, a line of pores.data and (plane) pores%.6i.vtk of the map as it is now"""
+        _chk(self._L.lbmdem_write_pores(self._h, os.fsencode(directory), int(nFile), int(conn), 1 if plane else 0))
+
+    def set_pores_output(self, on=True, conn=8, plane=False):
+        """run_scene writes the pore files at every DEM event, behind the Voronoi files"""
+        _chk(self._L.lbmdem_set_pores_output(self._h, 1 if on else 0, int(conn), 1 if plane else 0))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

@@ -503,6 +503,7 @@ int lbmdem_obst_construction(lbmdem_handle* h) {
   if (h->dist && !h->dist_period_open)
     return fail(LBMDEM_EINVAL, "distributed grains: lbmdem_dist_begin_period comes before the fluid step");
   if (h->cs_interior_pending) return fail(LBMDEM_EINVAL, "lbmdem_collide_stream_part(LBMDEM_CS_INTERIOR) has not been called after LBMDEM_CS_EDGES");
+  h->lattice_seq++;   // (what lbmdem_pore_compute has made describes another map)
   int rc = paint_into(h, h->obst[1 - h->ocur]);
   if (rc == LBMDEM_OK) h->obst_pending = true;
   return rc;
@@ -573,6 +574,7 @@ int lbmdem_collide_stream(lbmdem_handle* h) try {
   h->slots_valid = h->fs.tab != nullptr;
   HIP_TRY(hipGetLastError());
   h->fcur = 1 - h->fcur;
+  h->lattice_seq++;
   if (h->obst_pending) { h->ocur = 1 - h->ocur; h->obst_pending = false; h->obst_reset_rows = 0; }
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -641,6 +643,7 @@ static int collide_stream_part_on_impl(lbmdem_handle* h, int part, hipStream_t s
     if (h->prof_this && h->ev_used > 0) { HIP_TRY(hipEventRecord(h->ev2[h->ev_used - 1], st)); h->ev2_set[h->ev_used - 1] = 1; }
     HIP_TRY(hipGetLastError());
     h->fcur = 1 - h->fcur;
+    h->lattice_seq++;
     if (h->obst_pending) { h->ocur = 1 - h->ocur; h->obst_pending = false; h->obst_reset_rows = 0; }
     h->cs_interior_pending = true;
     return LBMDEM_OK;
@@ -1410,6 +1413,7 @@ int lbmdem_upload_f(lbmdem_handle* h, const double* f_aos) {
   real* tmp = nullptr;
   HIP_TRY(scratch.dev(&tmp, cnt));
   h->slots_valid = false;  // the populations the link sums were formed from are being replaced
+  h->lattice_seq++;
   HIP_TRY(h2d_real(tmp, f_aos + (size_t)L.gx0 * L.ly * 9, cnt, h->stream));
   launch_aos_to_soa(tmp, h->f[h->fcur], L, h->stream);
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -367,6 +367,30 @@ struct lbmdem_handle {
     long nfaces = 0;                      // of the last compute
     double rcut = 0.;                     // the structure compute's, as the last compute recovered it
   } vo;
+  // The pore space (lbm_pores.hip): the fluid phase labelled into connected components. po: scratch and results, allocated by the
+  // first lbmdem_pore_compute, the table grown with the components, freed with the handle. The kernels read the map and f and
+  // write here only. The results describe the map and f as of sub-step `seq`, upload `moved` and lattice change `fluid`: the
+  // readers ask for seq == substep_seq, moved == grains_moved and fluid == lattice_seq (a rasterisation, a fluid step and
+  // lbmdem_upload_f raise the last). pores_*: lbmdem_set_pores_output.
+  long long lattice_seq = 0;
+  bool pores_output = false;
+  int pores_conn = 8, pores_plane = 0;
+  struct PoreStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    unsigned long long* words = nullptr;  // [PO_WORDS] the census (null: nothing allocated yet)
+    int* parent = nullptr;                // [lx][sy] the union-find: a fluid node's parent, a device node no larger than itself; else -1
+    int* label = nullptr;                 // [lx][sy] the result: the smallest host index of the node's component, else -1
+    int* rank = nullptr;                  // [lx][sy] at a root: its place in the table (written and read at roots only)
+    int* map = nullptr;                   // [lx][sy] a caller's map in device layout (allocated by the first compute that brings one)
+    int* cnt = nullptr;                   // [2][nblocks + 1] roots per block of the flatten pass, and their scan
+    int* grains = nullptr;                // [3][n] wet, pore_min, pore_max
+    lbmdem_pore* table = nullptr;         // [table_cap]
+    long table_cap = 0;
+    char* tmp = nullptr;                  // hipcub's scratch, the scan
+    long tmp_bytes = 0;
+    long ncomp = 0;                       // of the last compute
+  } po;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -744,6 +744,86 @@ int lbmdem_set_voronoi_output(lbmdem_handle* h, int on, double rcut);   /* 0: of
 int lbmdem_write_voronoi_files(const char* dir, int nfile, int n, const double* area, const double* perimeter, const double* phi,
                                const int* faces, const int* walls, const int* nverts, const int* flags, double rcut,
                                const long* counts8, double t, double W, double H);   /* host only */
+/* Pore space: is the fluid connected? In two dimensions touching discs close the gaps between them, and whether a reductionR, a
+ * lattice resolution and a packing leave one percolating pore space or a set of sealed pockets decides whether the pore pressures
+ * mean anything. The fluid phase of the obstacle map is labelled into connected components on the device; per component its size,
+ * extent, the walls it touches, its wetted links and its fluid mass; per grain the pores it borders -- a grain that borders two
+ * different pores plugs a throat. Every result is an integer and the labels are canonical, so nothing depends on the algorithm; a
+ * numpy restatement reproduces everything exactly (tests/pore_util.py).
+ * Inputs, as of the call: the map M, lbmdem_download_obst's [lx][ly] or a caller's map of that shape, and f, lbmdem_download_f's.
+ * Node (x, y) has the index k = x*ly + y. lx*ly (and lx times the device's row pitch, ly rounded up to 16) must be below 2^31. A
+ * node is fluid iff M == -1, a grain node iff 0 <= M < nbgrains, a wall node iff M == nbgrains; a caller's map with any other value
+ * is refused before any result exists, the sentence names the first offending index.
+ * 1. Components. conn is 4 or 8. Two fluid nodes are joined when they differ by one of the directions q = 1..8 of the D2Q9 set
+ *    (conn == 4: the axis directions q = 2, 4, 6, 8 only). With conn == 8 a diagonal step joins them whatever the other two nodes
+ *    of the square are: exactly what streaming lets a population cross. label[x][y] is the smallest index k of the node's
+ *    component, -1 where the node is not fluid.
+ * 2. Table: one lbmdem_pore per component, ascending by label. nodes; xmin, xmax, ymin, ymax over its nodes; grain_links and
+ *    wall_links: the pairs (fluid node of the component, q in 1..8 -- always all eight) whose neighbour is a grain node, or is a wall
+ *    node or lies outside the lattice; walls: for every such wall or outside neighbour (nx, ny) bit 0 (B) if ny <= 0, bit 1 (T)
+ *    if ny >= ly - 1, bit 2 (L) if nx <= 0, bit 3 (R) if nx >= lx - 1; mass_q32: per fluid node rho = 0. + f0 + .. + f8
+ *    (lbmdem_download_macro's value); where rho is finite and |rho| < 2^20 the node adds (long)rint(rho * 4294967296.), ties to
+ *    even, in 64-bit two's-complement arithmetic that wraps; otherwise it adds 0 and is counted under 4. Fixed point: the sum does
+ *    not depend on the order and needs integer atomics only.
+ * 3. Per grain, [n] ints each: wet, the pairs (node of grain i, q in 1..8) whose neighbour lies inside the lattice and is fluid;
+ *    pore_min and pore_max, the smallest and the largest label among those neighbours, both -1 when there is none. With a caller's
+ *    map grain i's nodes are that map's.
+ * 4. counts10, in order: fluid nodes; components; nodes of the largest component (0 if none); its label (the smallest among equals,
+ *    -1 if none); fluid nodes outside the largest component (the trapped ones); components of exactly one node; spanning mask: bit
+ *    0 when a component carries both L and R, bit 1 when one carries both B and T; grains with pore_min != pore_max; grains with
+ *    wet == 0; fluid nodes whose rho was not accumulated.
+ * On the device, on the handle's stream, in the device layout (node = x*sy + y, the same order as k): k_po_local labels a tile of
+ * 16 x 64 nodes in LDS by a union-find and stores per fluid node the tile's smallest node of its component; k_po_seam joins across
+ * the tiles' borders, one lane per border node, by atomicMin on the larger root; k_po_flatten sets every node to its root and
+ * counts the roots, a scan and k_po_emit rank them in ascending order; k_po_table accumulates table and grain outputs with integer
+ * atomics behind a reduction over the lanes of a wavefront that share a label and an LDS slot per workgroup. A parent is never
+ * larger than its node: a find walks strictly downward, no cycle can form, a union retries only when another lane has lowered
+ * the same root. Single launches, no workgroup waits for another, no floating-point atomic. Scratch comes from the handle's pool
+ * with the first call and goes with the handle.
+ *   lbmdem_pore_compute          the compute; map NULL: the handle's; counts10. Synchronises; changes nothing a later step reads.
+ *   lbmdem_download_pore_labels  label[lx][ly]
+ *   lbmdem_pore_labels_device    the label plane where it lies on the device, node (x, y) at x * *sy + y (for a torch view), good
+ *                                until the next compute or lbmdem_destroy
+ *   lbmdem_download_pores        the table; cap = 0 leaves `out` alone and reports *count; a buffer of fewer than *count entries is
+ *                                refused with *count set and nothing written
+ *   lbmdem_download_pore_grains  wet, pore_min, pore_max, [n] ints; any pointer may be NULL
+ *   lbmdem_pore_grains_device    the same three as device pointers; any pointer may be NULL
+ *   These readers are refused, with LBMDEM_EINVAL and a sentence that names lbmdem_pore_compute, until a compute has been made, and
+ *   again after anything that changes the map or f: any kind of step or sub-step, lbmdem_upload_f, lbmdem_upload_kinematics.
+ *   lbmdem_write_pore_files      host only, no handle, no device. In <dir>: pore_table%.6i.dat -- "# conn %d lx %d ly %d\n",
+ *                                "# label nodes xmin xmax ymin ymax grain_links wall_links walls mass_q32\n", then per entry
+ *                                "%d %ld %d %d %d %d %ld %ld %d %ld\n"; pore_grains%.6i.dat -- "# i wet pore_min pore_max\n", then n
+ *                                lines "%d %d %d %d\n"; pores.data -- one line appended, "%le" of t and " %ld" of each of the ten
+ *                                counts; when the file is created, first the line "# t fluid_nodes components largest_nodes
+ *                                largest_label trapped_nodes single_nodes spanning throat_grains dry_grains unaccumulated";
+ *                                pores%.6i.vtk, only when plane != 0 -- the label plane as legacy STRUCTURED_POINTS on the frames'
+ *                                mesh, lbmdem_write_scalar_files' header with the title "lbmdem pore labels" and "SCALARS pore int
+ *                                1", then the labels as big-endian 32-bit integers, x fastest. It checks fopen ("cannot open");
+ *                                labels outside [-1, lx*ly) and table entries not ascending by label are refused before anything
+ *                                is written. label may be NULL when plane == 0, table when ntable == 0.
+ *   lbmdem_write_pores           the compute on the handle's map, the downloads, then that formatter with t = nbsteps * dt
+ *   lbmdem_set_pores_output      on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_pores(dir, nFile, conn, plane) at
+ *                                every DEM event, behind the Voronoi files. Off by default; a checkpoint does not carry it.
+ * Single-domain fp64 handles, vibrating, probing, lid, tracer, scalar and mean handles included. LBMDEM_EINVAL: conn other than 4 or
+ * 8; null arguments; a lattice of 2^31 nodes or more; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with
+ * the setting on); the single-precision library (the host-only formatter exists there too); a directory that cannot be written. */
+typedef struct lbmdem_pore {
+  int label, walls;
+  long nodes, grain_links, wall_links, mass_q32;
+  int xmin, xmax, ymin, ymax;
+} lbmdem_pore;
+#define LBMDEM_PORE_COUNTS 10
+int lbmdem_pore_compute(lbmdem_handle* h, int conn, const int* map /* NULL: the handle's */, long* counts10);
+int lbmdem_download_pore_labels(lbmdem_handle* h, int* label);   /* [lx][ly], host layout */
+int lbmdem_pore_labels_device(lbmdem_handle* h, const int** label, int* sy);   /* device layout, pitch sy */
+int lbmdem_download_pores(lbmdem_handle* h, lbmdem_pore* out, long cap, long* count);
+int lbmdem_download_pore_grains(lbmdem_handle* h, int* wet, int* pore_min, int* pore_max);   /* any may be NULL */
+int lbmdem_pore_grains_device(lbmdem_handle* h, const int** wet, const int** pore_min, const int** pore_max);
+int lbmdem_write_pores(lbmdem_handle* h, const char* dir, int nfile, int conn, int plane);
+int lbmdem_set_pores_output(lbmdem_handle* h, int on, int conn, int plane);   /* 0: off (default) */
+int lbmdem_write_pore_files(const char* dir, int nfile, int conn, int lx, int ly, int plane, const int* label,
+                            const lbmdem_pore* table, long ntable, int n, const int* wet, const int* pore_min,
+                            const int* pore_max, const long* counts10, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
