@@ -214,6 +214,17 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_pores_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.lbmdem_write_pore_files.argtypes = ([C.c_char_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_long, C.c_int] +
                                           [C.c_void_p] * 4 + [C.c_double])
+    L.lbmdem_clearance_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+    L.lbmdem_download_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_clearance_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.lbmdem_download_clearance_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_clearance_owners.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_clearance_owners_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.lbmdem_download_throats.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_write_clearance.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
+    L.lbmdem_set_clearance_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.lbmdem_write_clearance_files.argtypes = ([C.c_char_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_long, C.c_void_p, C.c_long, C.c_int] +
+                                               [C.c_void_p] * 3 + [C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -532,6 +543,40 @@ def write_pore_files(directory, nFile, conn, lx, ly, table, wet, pore_min, pore_
     _chk(load_library(precision).lbmdem_write_pore_files(
         os.fsencode(directory), int(nFile), int(conn), int(lx), int(ly), 0 if lab is None else 1, None if lab is None else _vp(lab),
         _vp(tab) if len(tab) else None, len(tab), n, *(_vp(a) for a in ints), _vp(cnt), float(t)))
+
+
+# struct lbmdem_throat: the ridge between the regions of two owners (LbmDem.throat_table), 20 bytes; the names of the ten counts
+# of LbmDem.clearance()
+THROAT_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("edges", np.int32), ("c_min", np.int32), ("node", np.int32)])
+CLEARANCE_COUNTERS = ("fluid_nodes", "d2_max", "d2_max_node", "sum_d2", "ridge_edges", "throats", "grain_throats", "narrowest_c",
+                      "ownerless_grains", "kmax")
+
+
+def write_clearance_files(directory, nFile, lx, ly, table, hist, owned, d2max, counts, t, d2=None, owner=None, precision="f64"):
+    """throats%.6i.dat, clearance_hist%.6i.dat, clearance_owners%.6i.dat, one appended line of clearance.data and, with the two
+    planes (lx, ly), clearance%.6i.vtk (include/lbmdem_hip.h spells the five formats out) from the throat table (THROAT_DTYPE),
+    the histogram, the two per-owner results [n + 1], the ten counts (a dict of CLEARANCE_COUNTERS or a sequence) and the time
+    of the line. Host only."""
+    tab = np.ascontiguousarray(table, dtype=THROAT_DTYPE).reshape(-1)
+    hs = np.ascontiguousarray(hist, dtype=np.int64).reshape(-1)
+    ow = np.ascontiguousarray(owned, dtype=np.int64).reshape(-1)
+    dm = np.ascontiguousarray(d2max, dtype=np.int32).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in CLEARANCE_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(ow) != len(dm) or len(ow) < 2 or len(cnt) != len(CLEARANCE_COUNTERS):
+        raise LbmDemError(-1, "write_clearance_files: owned and d2max must have one value per grain and one for the wall, counts ten")
+    if (d2 is None) != (owner is None):
+        raise LbmDemError(-1, "write_clearance_files: d2 and owner come together")
+    planes = None
+    if d2 is not None:
+        planes = [np.ascontiguousarray(a, dtype=np.int32) for a in (d2, owner)]
+        if any(a.shape != (int(lx), int(ly)) for a in planes):
+            raise LbmDemError(-1, "write_clearance_files: planes of shape (lx, ly)")
+    _chk(load_library(precision).lbmdem_write_clearance_files(
+        os.fsencode(directory), int(nFile), int(lx), int(ly), 0 if planes is None else 1, None if planes is None else _vp(planes[0]),
+        None if planes is None else _vp(planes[1]), _vp(tab) if len(tab) else None, len(tab), _vp(hs) if len(hs) else None, len(hs),
+        len(ow) - 1, _vp(ow), _vp(dm), _vp(cnt), float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1313,6 +1358,78 @@ class LbmDem:
     def set_pores_output(self, on=True, conn=8, plane=False):
         """run_scene writes the pore files at every DEM event, behind the Voronoi files"""
         _chk(self._L.lbmdem_set_pores_output(self._h, 1 if on else 0, int(conn), 1 if plane else 0))
+
+    # pore clearance: the exact distance map of the map as it is now, its owners, the pore sizes and the throats (include/lbmdem_hip.h)
+    def clearance(self, map=None, max_edges=0):
+        """the squared distance from every fluid node of the handle's map -- or of `map`, (lx, ly) ints: -1 fluid, a grain's index,
+        n the wall -- to the nearest position that is not fluid, with its owner, the histogram, the owners' table and the throats.
+        max_edges: the most ridge edges to hold records for, 0: no limit -> dict of CLEARANCE_COUNTERS"""
+        c = np.zeros(len(CLEARANCE_COUNTERS), np.int64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "clearance: a map of shape (lx, ly)")
+        _chk(self._L.lbmdem_clearance_compute(self._h, None if m is None else _vp(m), int(max_edges), _vp(c)))
+        return dict(zip(CLEARANCE_COUNTERS, (int(v) for v in c)))
+
+    def clearance_planes(self):
+        """(d2, owner), int32 (lx, ly) each, of the last clearance(): the squared distance (0 off the fluid) and the nearest
+        position's owner (the map itself off the fluid)"""
+        d2, owner = np.empty((self.lx, self.ly), np.int32), np.empty((self.lx, self.ly), np.int32)
+        _chk(self._L.lbmdem_download_clearance(self._h, _vp(d2), _vp(owner)))
+        return d2, owner
+
+    def clearance_tensors(self):
+        """the same two planes as torch.int32 views (lx, sy) of the handle's device memory, sy the device's row pitch: node (x, y)
+        at [x, y], the columns from ly on hold 0 (d2) and -1 (owner). Good until the next clearance()."""
+        import torch
+        p, q, sy = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        _chk(self._L.lbmdem_clearance_device(self._h, C.byref(p), C.byref(q), C.byref(sy)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(a.value, (self.lx, sy.value), "<i4"), device=dev) for k, a in (("d2", p), ("owner", q))}
+
+    def clearance_hist(self):
+        """int64 [kmax + 1] of the last clearance(): the fluid nodes per isqrt(d2), the pore-size distribution"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_clearance_hist(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.int64)
+        _chk(self._L.lbmdem_download_clearance_hist(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def clearance_owners(self):
+        """-> dict of the per-owner results of the last clearance(), [n + 1] each, entry n the wall: owned (int64, the fluid nodes
+        the owner has) and d2max (int32, the largest d2 among them, -1 without one)"""
+        out = {"owned": np.zeros(self.n + 1, np.int64), "d2max": np.zeros(self.n + 1, np.int32)}
+        _chk(self._L.lbmdem_download_clearance_owners(self._h, _vp(out["owned"]), _vp(out["d2max"])))
+        return out
+
+    def clearance_owner_tensors(self):
+        """the same two as torch views (int64, int32) of the handle's device memory, good until the next clearance()"""
+        import torch
+        p, q = C.c_void_p(), C.c_void_p()
+        _chk(self._L.lbmdem_clearance_owners_device(self._h, C.byref(p), C.byref(q)))
+        dev = f"cuda:{self.cfg.device}"
+        return {"owned": torch.as_tensor(_DeviceBlock(p.value, (self.n + 1,), "<i8"), device=dev),
+                "d2max": torch.as_tensor(_DeviceBlock(q.value, (self.n + 1,), "<i4"), device=dev)}
+
+    def throat_table(self):
+        """structured array of THROAT_DTYPE: the throats of the last clearance(), ascending (lo, hi)"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_throats(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=THROAT_DTYPE)
+        if n.value:
+            _chk(self._L.lbmdem_download_throats(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def write_clearance(self, directory=".", nFile=0, plane=False):
+        """throats%.6i.dat, clearance_hist%.6i.dat, clearance_owners%.6i.dat, a line of clearance.data and (plane)
+        clearance%.6i.vtk of the map as it is now"""
+        _chk(self._L.lbmdem_write_clearance(self._h, os.fsencode(directory), int(nFile), 1 if plane else 0))
+
+    def set_clearance_output(self, on=True, plane=False):
+        """run_scene writes the clearance files at every DEM event, behind the pore files"""
+        _chk(self._L.lbmdem_set_clearance_output(self._h, 1 if on else 0, 1 if plane else 0))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

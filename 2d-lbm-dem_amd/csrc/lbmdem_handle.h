@@ -391,6 +391,38 @@ struct lbmdem_handle {
     long tmp_bytes = 0;
     long ncomp = 0;                       // of the last compute
   } po;
+  // The pore clearance (lbm_clearance.hip): the exact squared distance from every fluid node to the nearest position that is not
+  // fluid, that position's owner, the histogram, the owners' table and the throats. clr: scratch and results, allocated by the
+  // first lbmdem_clearance_compute, the ridge records and the throat table grown with their counts, freed with the handle. The
+  // kernels read the map and write here only. Valid under the pores' guard: seq, moved and fluid as in PoreStage.
+  // clearance_*: lbmdem_set_clearance_output.
+  bool clearance_output = false;
+  int clearance_plane = 0;
+  struct ClearanceStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    unsigned long long* words = nullptr;  // [CE_WORDS] the census (null: nothing allocated yet)
+    unsigned long long* key = nullptr;    // [lx][sy] the row pass: (distance along y)^2 << 32 | owner
+    int* d2 = nullptr;                    // [lx][sy] the result: the squared distance, 0 off the fluid and in the pad columns
+    int* owner = nullptr;                 // [lx][sy] the result: the nearest position's owner, the map off the fluid, -1 in the pad columns
+    int* map = nullptr;                   // [lx][sy] a caller's map in device layout (allocated by the first compute that brings one)
+    unsigned long long* hist = nullptr;   // [hbins] fluid nodes per isqrt(d2)
+    int hbins = 0;                        // (min(lx, ly) + 1) / 2 + 2: no isqrt(d2) reaches it
+    unsigned long long* owned = nullptr;  // [n + 1] fluid nodes per owner
+    int* d2max = nullptr;                 // [n + 1] the largest d2 among them, -1 without one
+    unsigned long long* cnt = nullptr;    // [2][nblocks + 1] ridge edges per block of the count pass, and their scan
+    unsigned long long* rec = nullptr;    // [4][rec_cap] the ridge records: pair keys and values, each with the sort's second buffer
+    unsigned long long* uniq = nullptr;   // [rec_cap] the distinct pair keys
+    int* runs = nullptr;                  // [2][rec_cap] their run lengths, and the scan of those
+    long rec_cap = 0;
+    int* nruns = nullptr;                 // [1] the run-length encode's count
+    lbmdem_throat* table = nullptr;       // [table_cap]
+    long table_cap = 0;
+    char* tmp = nullptr;                  // hipcub's scratch: the scans, the sorts, the encode
+    long tmp_bytes = 0;
+    long nedges = 0, nthroats = 0;        // of the last compute
+    int kmax = 0;
+  } clr;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -824,6 +824,96 @@ int lbmdem_set_pores_output(lbmdem_handle* h, int on, int conn, int plane);   /*
 int lbmdem_write_pore_files(const char* dir, int nfile, int conn, int lx, int ly, int plane, const int* label,
                             const lbmdem_pore* table, long ntable, int n, const int* wet, const int* pore_min,
                             const int* pore_max, const long* counts10, double t);   /* host only */
+/* Pore clearance: how WIDE is the pore space? The pore-size distribution, the narrowest gap between every two neighbouring grains
+ * -- the throat that sets the permeability and closes first -- and the grain every fluid node belongs to, all from one exact
+ * integer object: the squared Euclidean distance from each fluid node to the nearest position that is not fluid, with that
+ * position's owner. Every result is an integer and every tie has a rule, so nothing depends on the algorithm; a numpy restatement
+ * reproduces everything exactly (tests/clearance_util.py) and its distances are scipy.ndimage.distance_transform_edt's.
+ * Input, as of the call: the map M, lbmdem_download_obst's [lx][ly] or a caller's map of that shape: -1 fluid, 0 .. n-1 a grain,
+ * n = nbgrains the wall; a caller's map with any other value is refused before any result exists, the sentence names the first
+ * offending index (lbmdem_pore_compute's sentence). Node (x, y) has the index k = x*ly + y. Every position outside the lattice
+ * counts as a wall node, owner n. lx and ly are at most 32768, so that d2 < 2^31.
+ * 1. d2[x][y], int: for a fluid node the minimum over all positions (x', y') that are not fluid, those outside the lattice
+ *    included, of (x-x')^2 + (y-y')^2; 0 off the fluid.
+ * 2. owner[x][y], int: for a fluid node the smallest map value among the non-fluid positions at distance exactly d2 -- a grain
+ *    before the wall, the smaller grain index among grains; off the fluid M itself.
+ * 3. hist[k], long, k = 0 .. kmax: the fluid nodes with isqrt(d2) == k, isqrt the integer square root rounded down,
+ *    kmax = isqrt(the largest d2): the pore-size distribution. (hist[0] is 0.)
+ * 4. Per owner 0 .. n, entry n the wall: owned, long, the fluid nodes that have this owner; d2max, int, the largest d2 among them,
+ *    -1 without one.
+ * 5. Ridge edges: the pairs of fluid nodes p < q, q = p + 1 in the same row x or q = p + ly, with owner[p] != owner[q]. An edge's
+ *    pair is (lo, hi) = (min, max) of the two owners, its clearance c = max(d2[p], d2[q]). The throat table: one lbmdem_throat per
+ *    distinct pair, ascending by (lo, hi): edges, the number of the pair's edges (the length of the ridge between the two); c_min,
+ *    the smallest clearance among them; node, the smallest p among the edges with c == c_min. Two discs whose nearest nodes are an
+ *    even g apart have c_min = (g/2)^2.
+ * 6. counts10, in order: fluid_nodes; d2_max, the largest d2 of the lattice (0 without fluid); d2_max_node, the smallest index k
+ *    with d2 == d2_max; sum_d2, the sum over all nodes; ridge_edges; throats, the table's entries; grain_throats, those with
+ *    hi < n; narrowest_c, the smallest c_min of those, -1 without one; ownerless_grains, the grains 0 .. n-1 with owned == 0;
+ *    kmax.
+ * On the device, on the handle's stream, in the device layout (node = x*sy + y): one packed key per node, d2 << 32 | owner, whose
+ * minimum is the rule of 1 and 2. k_ce_row, a wavefront per row x, finds the nearest non-fluid position of the row below and
+ * above every y by running maxima and minima over the lanes (the positions -1 and ly seed them) and stores g^2 << 32 | owner;
+ * k_ce_col, lanes along y, lets every node walk x' = x -+ 1, x -+ 2, .. over the rows' keys, rows outside the lattice counting as
+ * dx^2 << 32 | n, until dx^2 exceeds the best distance -- exact, because the nearest non-fluid position within row x' is that
+ * row's nearest along y -- writes d2 and owner and accumulates the histogram and the owners' table (lanes of a wavefront that
+ * share a bin or an owner first, then LDS, then 64-bit integer atomics); k_ce_count, a scan and k_ce_emit list the ridge edges
+ * as (pair, c, p) records, two stable radix sorts order them by pair, c and p, a run-length encode finds the pairs and
+ * k_ce_throats reads each run's first record; k_ce_census makes the counts. Single launches, integer atomics only, no floating
+ * point. Scratch comes from the handle's pool with the first call and goes with the handle; the ridge records are allocated for
+ * the edges there are.
+ *   lbmdem_clearance_compute        the compute; map NULL: the handle's; max_edges: the most ridge edges the caller is prepared to
+ *                                   hold records for (40 bytes each while the compute runs), 0: no limit below 2^31 - 1. A ridge
+ *                                   of more edges fails with "lbmdem_clearance_compute: the ridge has %llu edges, max_edges is
+ *                                   %ld" and leaves no result. counts10. Synchronises; changes nothing a later step reads.
+ *   lbmdem_download_clearance       d2[lx][ly] and owner[lx][ly]; either may be NULL, not both
+ *   lbmdem_clearance_device         the two planes where they lie on the device, node (x, y) at x * *sy + y (for a torch view);
+ *                                   the pad columns ly .. *sy - 1 hold 0 (d2) and -1 (owner); good until the next compute or
+ *                                   lbmdem_destroy
+ *   lbmdem_download_clearance_hist  the histogram, kmax + 1 longs; cap = 0 leaves `hist` alone and reports *count; a buffer of
+ *                                   fewer than *count entries is refused with *count set and nothing written
+ *   lbmdem_download_clearance_owners, lbmdem_clearance_owners_device   owned [n + 1] longs and d2max [n + 1] ints, on the host and
+ *                                   as device pointers; any pointer may be NULL
+ *   lbmdem_download_throats         the table; sized as lbmdem_download_pores is: cap = 0 reports *count, a short buffer is
+ *                                   refused ("there are %ld throats, the buffer holds %ld") with *count set and nothing written
+ *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_clearance_compute has been made for the map as it is now",
+ *   until a compute has been made, after a refused compute, and after anything the pore readers are refused after: any kind of
+ *   step or sub-step, lbmdem_upload_f, lbmdem_upload_kinematics.
+ *   lbmdem_write_clearance_files    host only, no handle, no device. In <dir>: throats%.6i.dat -- "# lx %d ly %d n %d\n",
+ *                                   "# lo hi edges c_min node\n", then per entry "%d %d %d %d %d\n"; clearance_hist%.6i.dat --
+ *                                   "# k nodes\n", then nhist lines "%ld %ld\n" of k and hist[k]; clearance_owners%.6i.dat --
+ *                                   "# owner owned d2max\n", then n + 1 lines "%d %ld %d\n"; clearance.data -- one line appended,
+ *                                   "%le" of t and " %ld" of each of the ten counts; when the file is created, first the line
+ *                                   "# t fluid_nodes d2_max d2_max_node sum_d2 ridge_edges throats grain_throats narrowest_c
+ *                                   ownerless_grains kmax"; clearance%.6i.vtk, only when plane != 0 -- legacy STRUCTURED_POINTS
+ *                                   on the frames' mesh, lbmdem_write_pore_files' header with the title "lbmdem pore clearance"
+ *                                   up to "POINT_DATA %ld\n", then twice, for d2 and for owner: "SCALARS d2 int 1\nLOOKUP_TABLE
+ *                                   default\n" ("SCALARS owner int 1 .."), the plane as big-endian 32-bit integers, x fastest,
+ *                                   and "\n". It checks fopen ("cannot open"); a negative d2, an owner outside [0, n] and table
+ *                                   entries that do not ascend by (lo, hi) with 0 <= lo < hi <= n are refused before anything is
+ *                                   written. d2 and owner may be NULL when plane == 0, table when ntable == 0.
+ *   lbmdem_write_clearance          the compute on the handle's map (max_edges 0), the downloads, then that formatter with
+ *                                   t = nbsteps * dt
+ *   lbmdem_set_clearance_output     on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_clearance(dir, nFile, plane) at
+ *                                   every DEM event, behind the pore files. Off by default; a checkpoint does not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL: null arguments; a side above 32768; max_edges outside 0 .. 2^31 - 1; a strip of a
+ * decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the single-precision library (the host-only
+ * formatter exists there too); a directory that cannot be written. */
+typedef struct lbmdem_throat {
+  int lo, hi, edges, c_min, node;
+} lbmdem_throat;
+#define LBMDEM_CLEARANCE_COUNTS 10
+int lbmdem_clearance_compute(lbmdem_handle* h, const int* map /* NULL: the handle's */, long max_edges, long* counts10);
+int lbmdem_download_clearance(lbmdem_handle* h, int* d2, int* owner);   /* [lx][ly], host layout; either may be NULL */
+int lbmdem_clearance_device(lbmdem_handle* h, const int** d2, const int** owner, int* sy);   /* device layout, pitch sy */
+int lbmdem_download_clearance_hist(lbmdem_handle* h, long* hist, long cap, long* count);
+int lbmdem_download_clearance_owners(lbmdem_handle* h, long* owned, int* d2max);   /* [n + 1]; any may be NULL */
+int lbmdem_clearance_owners_device(lbmdem_handle* h, const long** owned, const int** d2max);
+int lbmdem_download_throats(lbmdem_handle* h, lbmdem_throat* out, long cap, long* count);
+int lbmdem_write_clearance(lbmdem_handle* h, const char* dir, int nfile, int plane);
+int lbmdem_set_clearance_output(lbmdem_handle* h, int on, int plane);   /* 0: off (default) */
+int lbmdem_write_clearance_files(const char* dir, int nfile, int lx, int ly, int plane, const int* d2, const int* owner,
+                                 const lbmdem_throat* table, long ntable, const long* hist, long nhist, int n, const long* owned,
+                                 const int* d2max, const long* counts10, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
