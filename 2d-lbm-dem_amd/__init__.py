@@ -225,6 +225,16 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_clearance_output.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.lbmdem_write_clearance_files.argtypes = ([C.c_char_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_long, C.c_void_p, C.c_long, C.c_int] +
                                                [C.c_void_p] * 3 + [C.c_double])
+    L.lbmdem_network_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p]
+    L.lbmdem_download_network.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_network_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.lbmdem_download_network_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_network_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_network_links.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_write_network.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_set_network_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_write_network_files.argtypes = ([C.c_char_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_long, C.c_void_p, C.c_long, C.c_void_p,
+                                              C.c_long, C.c_void_p, C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -577,6 +587,43 @@ def write_clearance_files(directory, nFile, lx, ly, table, hist, owned, d2max, c
         os.fsencode(directory), int(nFile), int(lx), int(ly), 0 if planes is None else 1, None if planes is None else _vp(planes[0]),
         None if planes is None else _vp(planes[1]), _vp(tab) if len(tab) else None, len(tab), _vp(hs) if len(hs) else None, len(hs),
         len(ow) - 1, _vp(ow), _vp(dm), _vp(cnt), float(t)))
+
+
+# struct lbmdem_net_body, lbmdem_net_link, lbmdem_net_group: the records of the pore network (LbmDem.network_bodies,
+# network_links, network_groups), 32, 20 and 32 bytes; the names of the ten counts of LbmDem.network()
+NET_BODY_DTYPE = np.dtype([("node", np.int32), ("d2", np.int32), ("nodes", np.int64), ("degree", np.int32), ("parent", np.int32),
+                           ("group", np.int32)], align=True)
+NET_LINK_DTYPE = np.dtype([("lo", np.int32), ("hi", np.int32), ("edges", np.int32), ("saddle", np.int32), ("node", np.int32)])
+NET_GROUP_DTYPE = np.dtype([("body", np.int32), ("bodies", np.int32), ("nodes", np.int64), ("d2", np.int32), ("node", np.int32),
+                            ("degree", np.int32)], align=True)
+NETWORK_COUNTERS = ("fluid_nodes", "bodies", "body_links", "body_edges", "groups", "group_links", "group_edges", "isolated_groups",
+                    "largest_group_nodes", "narrowest_saddle")
+
+
+def write_network_files(directory, nFile, lx, ly, n, merge, bodies, groups, links, counts, t, body=None, group=None, precision="f64"):
+    """network_bodies%.6i.dat, network_links%.6i.dat, network_groups%.6i.dat, one appended line of network.data and, with the two
+    planes (lx, ly), network%.6i.vtk (include/lbmdem_hip.h spells the five formats out) from the body table (NET_BODY_DTYPE), the
+    group table (NET_GROUP_DTYPE), the links between the groups (NET_LINK_DTYPE), the ten counts (a dict of NETWORK_COUNTERS or a
+    sequence) and the time of the line; n: the grain count of the first lines. Host only."""
+    bo = np.ascontiguousarray(bodies, dtype=NET_BODY_DTYPE).reshape(-1)
+    gr = np.ascontiguousarray(groups, dtype=NET_GROUP_DTYPE).reshape(-1)
+    li = np.ascontiguousarray(links, dtype=NET_LINK_DTYPE).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in NETWORK_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(NETWORK_COUNTERS):
+        raise LbmDemError(-1, "write_network_files: ten counts")
+    if (body is None) != (group is None):
+        raise LbmDemError(-1, "write_network_files: body and group come together")
+    planes = None
+    if body is not None:
+        planes = [np.ascontiguousarray(a, dtype=np.int32) for a in (body, group)]
+        if any(a.shape != (int(lx), int(ly)) for a in planes):
+            raise LbmDemError(-1, "write_network_files: planes of shape (lx, ly)")
+    _chk(load_library(precision).lbmdem_write_network_files(
+        os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(merge), 0 if planes is None else 1,
+        None if planes is None else _vp(planes[0]), None if planes is None else _vp(planes[1]), _vp(bo) if len(bo) else None, len(bo),
+        _vp(gr) if len(gr) else None, len(gr), _vp(li) if len(li) else None, len(li), _vp(cnt), float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1430,6 +1477,65 @@ class LbmDem:
     def set_clearance_output(self, on=True, plane=False):
         """run_scene writes the clearance files at every DEM event, behind the pore files"""
         _chk(self._L.lbmdem_set_clearance_output(self._h, 1 if on else 0, 1 if plane else 0))
+
+    # pore network: the watershed of the clearance map -- bodies, links with their saddles, merged groups (include/lbmdem_hip.h)
+    def network(self, map=None, merge=-1, max_edges=0):
+        """the pore bodies of the handle's map -- or of `map`, (lx, ly) ints as clearance() takes them --, the links between them,
+        the groups that bodies whose pass lies within `merge` of the lower summit's radius form (-1: no merging) and the links
+        between those. Runs clearance() first where its result is not there. max_edges: the most edges between bodies to hold
+        records for, 0: no limit -> dict of NETWORK_COUNTERS"""
+        c = np.zeros(len(NETWORK_COUNTERS), np.int64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "network: a map of shape (lx, ly)")
+        _chk(self._L.lbmdem_network_compute(self._h, None if m is None else _vp(m), int(merge), int(max_edges), _vp(c)))
+        return dict(zip(NETWORK_COUNTERS, (int(v) for v in c)))
+
+    def network_planes(self):
+        """(body, group), int32 (lx, ly) each, of the last network(): the body's number and the group's root body, -1 off the fluid"""
+        body, group = np.empty((self.lx, self.ly), np.int32), np.empty((self.lx, self.ly), np.int32)
+        _chk(self._L.lbmdem_download_network(self._h, _vp(body), _vp(group)))
+        return body, group
+
+    def network_tensors(self):
+        """the same two planes as torch.int32 views (lx, sy) of the handle's device memory, sy the device's row pitch: node (x, y)
+        at [x, y], the columns from ly on hold -1. Good until the next network()."""
+        import torch
+        p, q, sy = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        _chk(self._L.lbmdem_network_device(self._h, C.byref(p), C.byref(q), C.byref(sy)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(a.value, (self.lx, sy.value), "<i4"), device=dev) for k, a in (("body", p), ("group", q))}
+
+    def _network_table(self, call, dtype, *lead):
+        n = C.c_long(0)
+        _chk(call(self._h, *lead, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=dtype)
+        if n.value:
+            _chk(call(self._h, *lead, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def network_bodies(self):
+        """structured array of NET_BODY_DTYPE: the bodies of the last network(), ascending by peak node"""
+        return self._network_table(self._L.lbmdem_download_network_bodies, NET_BODY_DTYPE)
+
+    def network_groups(self):
+        """structured array of NET_GROUP_DTYPE: the groups of the last network(), ascending by root body"""
+        return self._network_table(self._L.lbmdem_download_network_groups, NET_GROUP_DTYPE)
+
+    def network_links(self, level=1):
+        """structured array of NET_LINK_DTYPE: the links between bodies (level 0) or groups (1), ascending (lo, hi)"""
+        return self._network_table(self._L.lbmdem_download_network_links, NET_LINK_DTYPE, int(level))
+
+    def write_network(self, directory=".", nFile=0, merge=-1, plane=False):
+        """network_bodies%.6i.dat, network_links%.6i.dat, network_groups%.6i.dat, a line of network.data and (plane)
+        network%.6i.vtk of the map as it is now"""
+        _chk(self._L.lbmdem_write_network(self._h, os.fsencode(directory), int(nFile), int(merge), 1 if plane else 0))
+
+    def set_network_output(self, on=True, merge=-1, plane=False):
+        """run_scene writes the network files at every DEM event, behind the clearance files"""
+        _chk(self._L.lbmdem_set_network_output(self._h, 1 if on else 0, int(merge), 1 if plane else 0))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

@@ -422,7 +422,34 @@ struct lbmdem_handle {
     long tmp_bytes = 0;
     long nedges = 0, nthroats = 0;        // of the last compute
     int kmax = 0;
+    bool own = false;                     // the last compute was of the handle's map, not of a caller's (lbm_network.hip reuses d2 then)
   } clr;
+  // The pore network (lbm_network.hip): a watershed of clr.d2 -- per fluid node the body (the local maximum it climbs to) and the
+  // group its body merges into, the body and group records and the links of both levels. net: planes and block counts allocated by
+  // the first lbmdem_network_compute, the per-body arrays and the tables grown with their counts, freed with the handle; the sort
+  // records of a call live in a pool of that call. The kernels read clr.d2 and write here only. Valid under the clearance's guard.
+  // network_*: lbmdem_set_network_output.
+  bool network_output = false;
+  int network_merge = -1, network_plane = 0;
+  struct NetworkStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    unsigned long long* words = nullptr;  // [NW_WORDS] the census (null: nothing allocated yet)
+    int* par = nullptr;                   // [lx][sy] the ascent: a higher node of the same basin, in the end the peak; -1 off the fluid
+    int* body = nullptr;                  // [lx][sy] the result: the body's number, -1 off the fluid and in the pad columns
+    int* group = nullptr;                 // [lx][sy] the result: the group's root body; before that the peaks' numbers
+    unsigned long long* cnt = nullptr;    // [2][nblocks + 1] peaks, then edges, per block of nodes, and their scan
+    int* nruns = nullptr;                 // [1] the run-length encode's count
+    lbmdem_net_body* bodies = nullptr;    // [body_cap]
+    int* barr = nullptr;                  // [5][body_cap + 1] per body: group, degree of either level, root flag and its scan
+    unsigned long long* best = nullptr;   // [body_cap] per body the merge candidate, saddle << 32 | ~partner
+    long body_cap = 0;
+    lbmdem_net_group* groups = nullptr;   // [group_cap]
+    long group_cap = 0;
+    lbmdem_net_link* links[2] = {nullptr, nullptr};   // [link_cap[level]]
+    long link_cap[2] = {0, 0};
+    long nbodies = 0, ngroups = 0, nlinks[2] = {0, 0};   // of the last compute
+  } net;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -69,6 +69,11 @@
  * length of the ridge and its narrowest place in throats%.6i.dat, the pore-size distribution in clearance_hist%.6i.dat, per owner
  * its fluid nodes in clearance_owners%.6i.dat, a line of clearance.data (how narrow is the narrowest throat?) and, with
  * --clearance-plane, the two planes in clearance%.6i.vtk. Single GPU only.
+ * --network [MERGE] [--network-plane]: the pore network of every DEM event (lbmdem_set_network_output): the watershed of the
+ * clearance map -- per pore body its peak, size and neighbours in network_bodies%.6i.dat, the groups that bodies whose pass lies
+ * within MERGE of the lower summit's radius form (default: no merging) in network_groups%.6i.dat, the links between the groups
+ * with their saddles in network_links%.6i.dat, a line of network.data (how many pores? how narrow is the narrowest constriction?)
+ * and, with --network-plane, the body and group planes in network%.6i.vtk. Single GPU only.
  * --coarse CWxCH: the coarse-grained fields of every DEM event next to its table (lbmdem_set_coarse_output): coarse%.6i.dat, one
  * line per cell of CW x CH lattice nodes with the sums of fluid, grains and contacts over it. Single GPU only.
  * --flow: the flow fields (lbmdem_set_flow_output): flow%.6i.vtk next to every VTK frame -- composite velocity, vorticity, shear
@@ -116,6 +121,7 @@ static int g_voronoi = 0;        /* --voronoi RCUT */
 static double g_voronoi_rcut = 0.;
 static int g_pores = 0, g_pores_conn = 8, g_pores_plane = 0;   /* --pores [4|8], --pores-plane */
 static int g_clearance = 0, g_clearance_plane = 0;   /* --clearance, --clearance-plane */
+static int g_network = 0, g_network_merge = -1, g_network_plane = 0;   /* --network [MERGE], --network-plane */
 static int g_tracers = 0, g_tracers_nx = 0, g_tracers_ny = 0;   /* --tracers NXxNY */
 static int g_dye = 0, g_dye_box[4] = {0, 0, 0, 0};   /* --dye X0,Y0,X1,Y1 */
 static double g_dye_tau = 0.53;                      /* --dye-tau T */
@@ -298,6 +304,11 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[a], "--pores-plane")) g_pores_plane = 1;
     if (!strcmp(argv[a], "--clearance")) g_clearance = 1;
     if (!strcmp(argv[a], "--clearance-plane")) g_clearance_plane = 1;
+    if (!strcmp(argv[a], "--network")) {
+      g_network = 1;
+      if (a + 1 < argc && is_count(argv[a + 1])) g_network_merge = atoi(argv[a + 1]);
+    }
+    if (!strcmp(argv[a], "--network-plane")) g_network_plane = 1;
     if (!strcmp(argv[a], "--structure-bins")) {
       if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) < 1 || atoi(argv[a + 1]) > 4096) { fprintf(stderr, "--structure-bins N: the bins of the pair histogram, 1 .. 4096\n"); return EXIT_FAILURE; }
       g_structure_bins = atoi(argv[a + 1]);
@@ -386,6 +397,9 @@ int main(int argc, char** argv) {
   if (g_clearance_plane && !g_clearance) { fprintf(stderr, "--clearance-plane needs --clearance\n"); return EXIT_FAILURE; }
   if (g_clearance && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--clearance is a single-GPU mode (the pore clearance analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_clearance && g_dry) { fprintf(stderr, "--clearance cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
+  if (g_network_plane && !g_network) { fprintf(stderr, "--network-plane needs --network\n"); return EXIT_FAILURE; }
+  if (g_network && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--network is a single-GPU mode (the pore network analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_network && g_dry) { fprintf(stderr, "--network cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_tracers && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--tracers is a single-GPU mode (the tracers need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_dye && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dye is a single-GPU mode (the passive scalar needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
@@ -553,6 +567,8 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--pores-plane")) {}
     else if (!strcmp(argv[a], "--clearance")) {}
     else if (!strcmp(argv[a], "--clearance-plane")) {}
+    else if (!strcmp(argv[a], "--network")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
+    else if (!strcmp(argv[a], "--network-plane")) {}
     else if (!strcmp(argv[a], "--structure-bins") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--structure-shell") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--coarse") && a + 1 < argc) ++a;
@@ -585,7 +601,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -665,6 +681,7 @@ static int run(int argc, char** argv) {
   if (g_voronoi) DIE(lbmdem_set_voronoi_output(h, 1, g_voronoi_rcut), "set_voronoi_output");
   if (g_pores) DIE(lbmdem_set_pores_output(h, 1, g_pores_conn, g_pores_plane), "set_pores_output");
   if (g_clearance) DIE(lbmdem_set_clearance_output(h, 1, g_clearance_plane), "set_clearance_output");
+  if (g_network) DIE(lbmdem_set_network_output(h, 1, g_network_merge, g_network_plane), "set_network_output");
   if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");
   if (g_coarse) DIE(lbmdem_set_coarse_output(h, g_coarse_cw, g_coarse_ch), "set_coarse_output");
   if (g_tracers && got_tracers) DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");   /* the loaded set goes on: tracer k stays tracer k */

@@ -914,6 +914,108 @@ int lbmdem_set_clearance_output(lbmdem_handle* h, int on, int plane);   /* 0: of
 int lbmdem_write_clearance_files(const char* dir, int nfile, int lx, int ly, int plane, const int* d2, const int* owner,
                                  const lbmdem_throat* table, long ntable, const long* hist, long nhist, int n, const long* owned,
                                  const int* d2max, const long* counts10, double t);   /* host only */
+/* Pore network: WHICH pores are there, and how are they joined? The pore bodies (the wide places), the constrictions between them,
+ * how many neighbours a pore has and how large the constriction is that a front must pass -- the graph that permeability
+ * estimates, invasion percolation and clogging studies start from. It is a watershed of the clearance analysis' d2: every fluid
+ * node climbs to the local maximum of d2 it belongs to. Every result is an integer and every tie has a rule, so nothing depends on
+ * the algorithm; a numpy restatement reproduces everything exactly (tests/network_util.py).
+ * Input, as of the call: the map M, lbmdem_download_obst's [lx][ly] or a caller's map of that shape, validated as
+ * lbmdem_clearance_compute validates it (the sentence under this function's name); behind it that analysis' d2. Node (x, y) has
+ * the index k = x*ly + y, N = lx*ly. Two nodes are ADJACENT when they differ by at most 1 in both x and y (8 neighbours: a
+ * diagonal step between two solid corners counts). p is HIGHER than q, p > q below, when d2[p] > d2[q], or d2[p] == d2[q] and
+ * p < q: a strict total order on the fluid nodes.
+ * 1. Ascent. up(p) is the highest node among p and its adjacent fluid nodes. A fluid node with up(p) == p is a peak; peak(p) is
+ *    where repeated up ends (up(p) > p off the peaks).
+ * 2. Bodies. The peaks are numbered 0 .. B-1 ascending by node index. body[x][y], int: the number of peak(p), -1 off the fluid.
+ *    lbmdem_net_body: node, the peak's index; d2, the peak's d2, the body's largest; nodes, long; degree, the number of level-0
+ *    links it is in; parent and group, rule 4.
+ * 3. Links, level 0. An edge is a pair of adjacent fluid nodes p < q with different bodies -- q one of p + 1, p + ly - 1, p + ly,
+ *    p + ly + 1, inside the lattice and in the same or the next row as adjacency demands. Its height is min(d2[p], d2[q]). One
+ *    lbmdem_net_link per distinct pair (lo, hi), lo < hi, of bodies, ascending by (lo, hi): edges; saddle, the largest height
+ *    among the pair's edges; node, the smallest p among the edges of that height.
+ * 4. Merge, parameter merge (int). merge == -1: parent[a] = a for all a. merge >= 0: the candidates of body a are its links
+ *    whose partner b has a peak higher than a's and isqrt(d2 of a's peak) - isqrt(saddle) <= merge, isqrt rounded down as in the
+ *    clearance block. parent[a] is the candidate with the largest saddle, among equal saddles the smaller b; without a
+ *    candidate a. group[a] is where repeated parent ends (parents are strictly higher: no cycle). ONE round by definition,
+ *    not iterated after merging. group[x][y], int: group[body[x][y]], -1 off the fluid.
+ * 5. Groups. One lbmdem_net_group per root, ascending by body number: body, the root's number; bodies; nodes, long; d2 and
+ *    node, the root's; degree, its level-1 links.
+ * 6. Links, level 1: rule 3 with group in place of body; lo and hi are root body numbers.
+ * 7. counts10, in order: fluid_nodes; bodies; body_links; body_edges; groups; group_links; group_edges; isolated_groups
+ *    (degree 0); largest_group_nodes; narrowest_saddle, the smallest level-1 saddle, -1 without a link.
+ * Identities: the bodies' nodes sum to fluid_nodes; with merge == -1 level 1 equals level 0; a map without solid nodes has one
+ * body; no body or group spans two 8-connected pores -- every lbmdem_pore_compute(conn 8) component is a union of groups; a link's
+ * saddle is at most both peaks' d2.
+ * On the device (lbm_network.hip), on the handle's stream, single launches: the clearance compute first where it is needed --
+ * with map == NULL and a clearance result of the handle's map that its guard still calls valid, that result's d2 plane is
+ * reused; otherwise lbmdem_clearance_compute runs on the map with no edge cap, and its readers are valid afterwards as if the
+ * caller had called it. Then the ascent over the key d2 << 32 | (N-1-k) in tiles of 16 x 64 nodes with an apron in LDS, chains
+ * shortened in LDS and followed across tiles strictly upward; the peaks numbered by count / scan / emit; the nodes per body
+ * (lanes that share a body first, LDS, 64-bit integer atomics); per level count / scan / emit of (pair, value) records, two stable
+ * radix sorts, a run-length encode, one kernel per run; the merge by an atomic maximum per body over the links' proposals
+ * (saddle << 32 | ~partner: the maximum is rule 4's choice) and a walk up the parents. Integer atomics only, no floating point.
+ * Planes and block counts come from the handle's pool with the first call, the tables grow with their counts, the sort's records
+ * (40 bytes an edge) live for the call.
+ *   lbmdem_network_compute          the compute; map NULL: the handle's; merge: rule 4; max_edges: the most level-0 edges the
+ *                                   caller is prepared to hold records for, 0: no limit below 2^31 - 1. More edges fail with
+ *                                   "lbmdem_network_compute: the ridge has %llu edges, max_edges is %ld" and leave no network
+ *                                   result. counts10. Synchronises; changes nothing a later step reads.
+ *   lbmdem_download_network         body[lx][ly] and group[lx][ly]; either may be NULL, not both
+ *   lbmdem_network_device           the two planes where they lie on the device, node (x, y) at x * *sy + y (for a torch view);
+ *                                   the pad columns ly .. *sy - 1 hold -1; good until the next compute or lbmdem_destroy
+ *   lbmdem_download_network_bodies, lbmdem_download_network_groups, lbmdem_download_network_links (level 0 or 1)   the tables;
+ *                                   sized as lbmdem_download_throats is: cap = 0 reports *count, a short buffer is refused
+ *                                   ("%s: there are %ld bodies (groups, links), the buffer holds %ld") with *count set and
+ *                                   nothing written
+ *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_network_compute has been made for the map as it is now",
+ *   until a compute has been made, after a refused compute, and after anything the clearance readers are refused after.
+ *   lbmdem_write_network_files      host only, no handle, no device. In <dir>: network_bodies%.6i.dat -- "# lx %d ly %d n %d
+ *                                   merge %d\n", "# body node d2 nodes degree parent group\n", then per body "%ld %d %d %ld %d
+ *                                   %d %d\n"; network_links%.6i.dat -- the same first line, "# lo hi edges saddle node\n", then
+ *                                   per link of the table given (lbmdem_write_network gives level 1) "%d %d %d %d %d\n";
+ *                                   network_groups%.6i.dat -- the same first line, "# body bodies nodes d2 node degree\n", then
+ *                                   per group "%d %d %ld %d %d %d\n"; network.data -- one line appended, "%le" of t and " %ld"
+ *                                   of each of the ten counts; when the file is created, first the line "# t fluid_nodes bodies
+ *                                   body_links body_edges groups group_links group_edges isolated_groups largest_group_nodes
+ *                                   narrowest_saddle"; network%.6i.vtk, only when plane != 0 -- lbmdem_write_clearance_files'
+ *                                   layout with the title "lbmdem pore network" and the planes "body" and "group". It checks
+ *                                   fopen ("cannot open"); refused before anything is written: bodies whose nodes, groups whose
+ *                                   bodies and links whose pairs do not ascend; lo >= hi; a body's group, a group's body or a
+ *                                   link's end that is not a root; a negative d2; a plane value outside -1 .. nbodies - 1.
+ *                                   body and group may be NULL when plane == 0, a table when its count is 0.
+ *   lbmdem_write_network            the compute on the handle's map (max_edges 0), the downloads, then that formatter with the
+ *                                   level-1 links and t = nbsteps * dt
+ *   lbmdem_set_network_output       on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_network(dir, nFile, merge, plane)
+ *                                   at every DEM event, behind the clearance files. Off by default; a checkpoint does not
+ *                                   carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL: null arguments; merge < -1; level outside 0 and 1; a side above 32768; max_edges
+ * outside 0 .. 2^31 - 1; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the
+ * single-precision library (the host-only formatter exists there too); a directory that cannot be written. */
+typedef struct lbmdem_net_body {
+  int node, d2;
+  long nodes;
+  int degree, parent, group;
+} lbmdem_net_body;
+typedef struct lbmdem_net_link {
+  int lo, hi, edges, saddle, node;
+} lbmdem_net_link;
+typedef struct lbmdem_net_group {
+  int body, bodies;
+  long nodes;
+  int d2, node, degree;
+} lbmdem_net_group;
+#define LBMDEM_NETWORK_COUNTS 10
+int lbmdem_network_compute(lbmdem_handle* h, const int* map /* NULL: the handle's */, int merge, long max_edges, long* counts10);
+int lbmdem_download_network(lbmdem_handle* h, int* body, int* group);   /* [lx][ly], host layout; either may be NULL, not both */
+int lbmdem_network_device(lbmdem_handle* h, const int** body, const int** group, int* sy);   /* device layout, pitch sy */
+int lbmdem_download_network_bodies(lbmdem_handle* h, lbmdem_net_body* out, long cap, long* count);
+int lbmdem_download_network_groups(lbmdem_handle* h, lbmdem_net_group* out, long cap, long* count);
+int lbmdem_download_network_links(lbmdem_handle* h, int level, lbmdem_net_link* out, long cap, long* count);
+int lbmdem_write_network(lbmdem_handle* h, const char* dir, int nfile, int merge, int plane);
+int lbmdem_set_network_output(lbmdem_handle* h, int on, int merge, int plane);   /* 0: off (default) */
+int lbmdem_write_network_files(const char* dir, int nfile, int lx, int ly, int n, int merge, int plane, const int* body,
+                               const int* group, const lbmdem_net_body* bodies, long nbodies, const lbmdem_net_group* groups,
+                               long ngroups, const lbmdem_net_link* links, long nlinks, const long* counts10, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
