@@ -235,6 +235,17 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_network_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.lbmdem_write_network_files.argtypes = ([C.c_char_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_long, C.c_void_p, C.c_long, C.c_void_p,
                                               C.c_long, C.c_void_p, C.c_double])
+    L.lbmdem_drainage_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p]
+    L.lbmdem_download_drainage.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_drainage_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.lbmdem_download_drainage_bodies.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_drainage_links.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_drainage_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_drainage_rounds.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.lbmdem_write_drainage.argtypes = [C.c_void_p, C.c_char_p] + [C.c_int] * 5
+    L.lbmdem_set_drainage_output.argtypes = [C.c_void_p] + [C.c_int] * 5
+    L.lbmdem_write_drainage_files.argtypes = ([C.c_char_p] + [C.c_int] * 8 + [C.c_void_p] * 2 + [C.c_long, C.c_void_p, C.c_long, C.c_void_p,
+                                               C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -624,6 +635,38 @@ def write_network_files(directory, nFile, lx, ly, n, merge, bodies, groups, link
         os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(merge), 0 if planes is None else 1,
         None if planes is None else _vp(planes[0]), None if planes is None else _vp(planes[1]), _vp(bo) if len(bo) else None, len(bo),
         _vp(gr) if len(gr) else None, len(gr), _vp(li) if len(li) else None, len(li), _vp(cnt), float(t)))
+
+
+# drainage (LbmDem.drainage): the sides of `frm` and `to`, to be or-ed, and the names of the ten counts
+SIDE_B, SIDE_T, SIDE_L, SIDE_R = 1, 2, 4, 8
+DRAINAGE_COUNTERS = ("fluid_nodes", "inlet_nodes", "reached_nodes", "reached_bodies", "access_max", "shielded_nodes", "outlet_nodes",
+                     "critical", "critical_node", "front_links")
+
+
+def write_drainage_files(directory, nFile, lx, ly, n, frm, band, to, bodies, A, hist, clearance_hist, counts, t, access=None,
+                         precision="f64"):
+    """drainage_curve%.6i.dat, drainage_bodies%.6i.dat, one appended line of drainage.data and, with the plane access (lx, ly),
+    drainage%.6i.vtk (include/lbmdem_hip.h spells the four formats out) from the network's body table (NET_BODY_DTYPE), A per body,
+    the access and the clearance histogram, the ten counts (a dict of DRAINAGE_COUNTERS or a sequence) and the time of the line;
+    n: the grain count of the first lines. Host only."""
+    bo = np.ascontiguousarray(bodies, dtype=NET_BODY_DTYPE).reshape(-1)
+    aa = np.ascontiguousarray(A, dtype=np.int32).reshape(-1)
+    hs = np.ascontiguousarray(hist, dtype=np.int64).reshape(-1)
+    ch = np.ascontiguousarray(clearance_hist, dtype=np.int64).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in DRAINAGE_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(DRAINAGE_COUNTERS):
+        raise LbmDemError(-1, "write_drainage_files: ten counts")
+    plane = None
+    if access is not None:
+        plane = np.ascontiguousarray(access, dtype=np.int32)
+        if plane.shape != (int(lx), int(ly)):
+            raise LbmDemError(-1, "write_drainage_files: a plane of shape (lx, ly)")
+    _chk(load_library(precision).lbmdem_write_drainage_files(
+        os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(frm), int(band), int(to), 0 if plane is None else 1,
+        None if plane is None else _vp(plane), _vp(bo) if len(bo) else None, len(bo), _vp(aa) if len(aa) else None, len(aa),
+        _vp(hs) if len(hs) else None, len(hs), _vp(ch) if len(ch) else None, len(ch), _vp(cnt), float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1536,6 +1579,71 @@ class LbmDem:
     def set_network_output(self, on=True, merge=-1, plane=False):
         """run_scene writes the network files at every DEM event, behind the clearance files"""
         _chk(self._L.lbmdem_set_network_output(self._h, 1 if on else 0, int(merge), 1 if plane else 0))
+
+    # drainage: the largest disc that reaches each pore from a chosen side, over the pore network (include/lbmdem_hip.h)
+    def drainage(self, frm, band=1, to=0, map=None, max_edges=0):
+        """the widest path over the clearance map from the fluid nodes within `band` nodes of the sides `frm` (SIDE_B | SIDE_T |
+        SIDE_L | SIDE_R) to every fluid node of the handle's map -- or of `map`, (lx, ly) ints as clearance() takes them --; `to`:
+        the outlet sides the breakthrough size `critical` is taken over, 0: none. Runs network() first where its result is not
+        there (max_edges: its budget) -> dict of DRAINAGE_COUNTERS"""
+        c = np.zeros(len(DRAINAGE_COUNTERS), np.int64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "drainage: a map of shape (lx, ly)")
+        _chk(self._L.lbmdem_drainage_compute(self._h, None if m is None else _vp(m), int(frm), int(band), int(to), int(max_edges), _vp(c)))
+        return dict(zip(DRAINAGE_COUNTERS, (int(v) for v in c)))
+
+    def drainage_plane(self):
+        """access, int32 (lx, ly), of the last drainage(): the squared size of the largest disc that reaches the node from the inlet,
+        0 where none does and off the fluid"""
+        access = np.empty((self.lx, self.ly), np.int32)
+        _chk(self._L.lbmdem_download_drainage(self._h, _vp(access)))
+        return access
+
+    def drainage_tensor(self):
+        """the same plane as a torch.int32 view (lx, sy) of the handle's device memory, sy the device's row pitch: node (x, y) at
+        [x, y], the columns from ly on hold 0. Good until the next drainage()."""
+        import torch
+        p, sy = C.c_void_p(), C.c_int(0)
+        _chk(self._L.lbmdem_drainage_device(self._h, C.byref(p), C.byref(sy)))
+        return torch.as_tensor(_DeviceBlock(p.value, (self.lx, sy.value), "<i4"), device=f"cuda:{self.cfg.device}")
+
+    def _drainage_table(self, call, dtype):
+        n = C.c_long(0)
+        _chk(call(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=dtype)
+        if n.value:
+            _chk(call(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def drainage_bodies(self):
+        """int32 [bodies]: A, the largest access in each body of network_bodies(), 0 where the inlet does not reach"""
+        return self._drainage_table(self._L.lbmdem_download_drainage_bodies, np.int32)
+
+    def drainage_links(self):
+        """int32 [links]: pass, the largest size that crosses each link of network_links(0) coming from the inlet"""
+        return self._drainage_table(self._L.lbmdem_download_drainage_links, np.int32)
+
+    def drainage_hist(self):
+        """int64 [kmax + 1]: the fluid nodes per isqrt(access), entry for entry next to clearance_hist(); [0]: the unreached"""
+        return self._drainage_table(self._L.lbmdem_download_drainage_hist, np.int64)
+
+    def drainage_rounds(self):
+        """the launches the relaxation of the last drainage() took, the quiet last one included"""
+        r = C.c_int(0)
+        _chk(self._L.lbmdem_drainage_rounds(self._h, C.byref(r)))
+        return r.value
+
+    def write_drainage(self, directory=".", nFile=0, frm=SIDE_T, band=1, to=0, plane=False):
+        """drainage_curve%.6i.dat, drainage_bodies%.6i.dat, a line of drainage.data and (plane) drainage%.6i.vtk of the map as it
+        is now"""
+        _chk(self._L.lbmdem_write_drainage(self._h, os.fsencode(directory), int(nFile), int(frm), int(band), int(to), 1 if plane else 0))
+
+    def set_drainage_output(self, on=True, frm=SIDE_T, band=1, to=0, plane=False):
+        """run_scene writes the drainage files at every DEM event, behind the network files"""
+        _chk(self._L.lbmdem_set_drainage_output(self._h, 1 if on else 0, int(frm), int(band), int(to), 1 if plane else 0))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

@@ -651,6 +651,7 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
     return fail(LBMDEM_EINVAL, "lbmdem_network_compute: max_edges must lie in 0 .. %d (%ld)", INT_MAX, max_edges);
   auto& V = h->net;
   V.valid = false;
+  ++V.gen;
   if (map)
     for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
       if (map[k] < -1 || map[k] > n)
@@ -763,6 +764,7 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
   counts10[9] = L1 > 0 ? (long)w[NW_W_NARROWEST] : -1;
   V.nbodies = B; V.ngroups = G; V.nlinks[0] = L0; V.nlinks[1] = L1;
   V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
+  V.own = map == nullptr;
   V.valid = true;
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)

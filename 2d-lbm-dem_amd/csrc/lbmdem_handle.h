@@ -449,7 +449,31 @@ struct lbmdem_handle {
     lbmdem_net_link* links[2] = {nullptr, nullptr};   // [link_cap[level]]
     long link_cap[2] = {0, 0};
     long nbodies = 0, ngroups = 0, nlinks[2] = {0, 0};   // of the last compute
+    bool own = false;                     // the last compute was of the handle's map, not of a caller's (lbm_drainage.hip reuses it then)
+    unsigned long long gen = 0;           // counts the computes: a result made over the tables says which ones (lbm_drainage.hip)
   } net;
+  // Drainage (lbm_drainage.hip): the widest path over clr.d2 from an inlet side -- per fluid node access, per body of the network A,
+  // per level-0 link pass, the histogram of isqrt(access). drn: the plane, the histogram and the words allocated by the first
+  // lbmdem_drainage_compute, A and pass grown with the network's counts, freed with the handle. The kernels read clr.d2, net.body
+  // and net.links[0] and write here only. Valid under the network's guard and while net.gen is the one it was made over.
+  // drainage_*: lbmdem_set_drainage_output.
+  bool drainage_output = false;
+  int drainage_from = 0, drainage_band = 1, drainage_to = 0, drainage_plane = 0;
+  struct DrainageStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    unsigned long long gen = 0;           // net.gen of the network result underneath
+    unsigned long long* words = nullptr;  // [DR_WORDS] the counts and the relaxation's `changed` (null: nothing allocated yet)
+    int* access = nullptr;                // [lx][sy] the result: min(d2, A[body]), 0 off the fluid and in the pad columns
+    unsigned long long* hist = nullptr;   // [clr.hbins] fluid nodes per isqrt(access)
+    int* A = nullptr;                     // [a_cap] per body
+    long a_cap = 0;
+    int* pass = nullptr;                  // [pass_cap] per level-0 link
+    long pass_cap = 0;
+    long nbodies = 0, nlinks = 0;         // of the last compute
+    int kmax = 0;                         // the clearance's at that compute: the histogram has kmax + 1 bins
+    int rounds = 0;                       // launches of the relaxation, the quiet last one included
+  } drn;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

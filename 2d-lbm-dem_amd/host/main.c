@@ -74,6 +74,11 @@
  * within MERGE of the lower summit's radius form (default: no merging) in network_groups%.6i.dat, the links between the groups
  * with their saddles in network_links%.6i.dat, a line of network.data (how many pores? how narrow is the narrowest constriction?)
  * and, with --network-plane, the body and group planes in network%.6i.vtk. Single GPU only.
+ * --drainage FROM [--drainage-to TO] [--drainage-band N] [--drainage-plane]: the drainage analysis of every DEM event
+ * (lbmdem_set_drainage_output): the largest disc that reaches each pore from the sides FROM, letters out of BTLR, through a
+ * reservoir N nodes deep (default 1) -- the intrusion curve next to the pore-size distribution in drainage_curve%.6i.dat, per pore
+ * body the size that reaches it in drainage_bodies%.6i.dat, a line of drainage.data (what passes from FROM to the sides TO, and
+ * through how many candidate throats?) and, with --drainage-plane, the access plane in drainage%.6i.vtk. Single GPU only.
  * --coarse CWxCH: the coarse-grained fields of every DEM event next to its table (lbmdem_set_coarse_output): coarse%.6i.dat, one
  * line per cell of CW x CH lattice nodes with the sums of fluid, grains and contacts over it. Single GPU only.
  * --flow: the flow fields (lbmdem_set_flow_output): flow%.6i.vtk next to every VTK frame -- composite velocity, vorticity, shear
@@ -122,6 +127,8 @@ static double g_voronoi_rcut = 0.;
 static int g_pores = 0, g_pores_conn = 8, g_pores_plane = 0;   /* --pores [4|8], --pores-plane */
 static int g_clearance = 0, g_clearance_plane = 0;   /* --clearance, --clearance-plane */
 static int g_network = 0, g_network_merge = -1, g_network_plane = 0;   /* --network [MERGE], --network-plane */
+static int g_drainage = 0, g_drainage_to = 0, g_drainage_band = 1, g_drainage_plane = 0;   /* --drainage FROM, --drainage-to TO, --drainage-band N, --drainage-plane */
+static int g_drainage_to_set = 0;
 static int g_tracers = 0, g_tracers_nx = 0, g_tracers_ny = 0;   /* --tracers NXxNY */
 static int g_dye = 0, g_dye_box[4] = {0, 0, 0, 0};   /* --dye X0,Y0,X1,Y1 */
 static double g_dye_tau = 0.53;                      /* --dye-tau T */
@@ -137,6 +144,18 @@ static int is_count(const char* s) {
   if (!s || !*s) return 0;
   for (; *s; ++s) if (*s < '0' || *s > '9') return 0;
   return 1;
+}
+/* the sides behind --drainage and --drainage-to: letters out of BTLR -> B 1 | T 2 | L 4 | R 8, 0 for anything else */
+static int side_mask(const char* s) {
+  static const char letters[] = "BTLR";
+  int mask = 0;
+  if (!s || !*s) return 0;
+  for (; *s; ++s) {
+    const char* at = strchr(letters, *s);
+    if (!at) return 0;
+    mask |= 1 << (int)(at - letters);
+  }
+  return mask;
 }
 static int is_number(const char* s, double* v) {   /* the whole of s is one finite number */
   char* end = NULL;
@@ -309,6 +328,16 @@ int main(int argc, char** argv) {
       if (a + 1 < argc && is_count(argv[a + 1])) g_network_merge = atoi(argv[a + 1]);
     }
     if (!strcmp(argv[a], "--network-plane")) g_network_plane = 1;
+    if (!strcmp(argv[a], "--drainage") || !strcmp(argv[a], "--drainage-to")) {
+      const int mask = a + 1 < argc ? side_mask(argv[a + 1]) : 0;
+      if (mask <= 0) { fprintf(stderr, "%s SIDES: letters out of BTLR, at least one\n", argv[a]); return EXIT_FAILURE; }
+      if (!strcmp(argv[a], "--drainage")) g_drainage = mask; else { g_drainage_to = mask; g_drainage_to_set = 1; }
+    }
+    if (!strcmp(argv[a], "--drainage-band")) {
+      if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) < 1) { fprintf(stderr, "--drainage-band N: the depth of the reservoir in nodes, at least 1\n"); return EXIT_FAILURE; }
+      g_drainage_band = atoi(argv[a + 1]);
+    }
+    if (!strcmp(argv[a], "--drainage-plane")) g_drainage_plane = 1;
     if (!strcmp(argv[a], "--structure-bins")) {
       if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) < 1 || atoi(argv[a + 1]) > 4096) { fprintf(stderr, "--structure-bins N: the bins of the pair histogram, 1 .. 4096\n"); return EXIT_FAILURE; }
       g_structure_bins = atoi(argv[a + 1]);
@@ -400,6 +429,9 @@ int main(int argc, char** argv) {
   if (g_network_plane && !g_network) { fprintf(stderr, "--network-plane needs --network\n"); return EXIT_FAILURE; }
   if (g_network && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--network is a single-GPU mode (the pore network analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_network && g_dry) { fprintf(stderr, "--network cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
+  if ((g_drainage_plane || g_drainage_to_set || g_drainage_band != 1) && !g_drainage) { fprintf(stderr, "--drainage-to, --drainage-band and --drainage-plane need --drainage FROM\n"); return EXIT_FAILURE; }
+  if (g_drainage && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--drainage is a single-GPU mode (the drainage analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_drainage && g_dry) { fprintf(stderr, "--drainage cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_tracers && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--tracers is a single-GPU mode (the tracers need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_dye && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dye is a single-GPU mode (the passive scalar needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
@@ -569,6 +601,8 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--clearance-plane")) {}
     else if (!strcmp(argv[a], "--network")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--network-plane")) {}
+    else if ((!strcmp(argv[a], "--drainage") || !strcmp(argv[a], "--drainage-to") || !strcmp(argv[a], "--drainage-band")) && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--drainage-plane")) {}
     else if (!strcmp(argv[a], "--structure-bins") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--structure-shell") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--coarse") && a + 1 < argc) ++a;
@@ -601,7 +635,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -682,6 +716,7 @@ static int run(int argc, char** argv) {
   if (g_pores) DIE(lbmdem_set_pores_output(h, 1, g_pores_conn, g_pores_plane), "set_pores_output");
   if (g_clearance) DIE(lbmdem_set_clearance_output(h, 1, g_clearance_plane), "set_clearance_output");
   if (g_network) DIE(lbmdem_set_network_output(h, 1, g_network_merge, g_network_plane), "set_network_output");
+  if (g_drainage) DIE(lbmdem_set_drainage_output(h, 1, g_drainage, g_drainage_band, g_drainage_to, g_drainage_plane), "set_drainage_output");
   if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");
   if (g_coarse) DIE(lbmdem_set_coarse_output(h, g_coarse_cw, g_coarse_ch), "set_coarse_output");
   if (g_tracers && got_tracers) DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");   /* the loaded set goes on: tracer k stays tracer k */

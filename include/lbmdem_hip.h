@@ -1016,6 +1016,101 @@ int lbmdem_set_network_output(lbmdem_handle* h, int on, int merge, int plane);  
 int lbmdem_write_network_files(const char* dir, int nfile, int lx, int ly, int n, int merge, int plane, const int* body,
                                const int* group, const lbmdem_net_body* bodies, long nbodies, const lbmdem_net_group* groups,
                                long ngroups, const lbmdem_net_link* links, long nlinks, const long* counts10, double t);   /* host only */
+/* Drainage: how large a particle passes through this packing from the free fluid above it to the base, at what capillary pressure
+ * does a non-wetting fluid break through and through which throat, what does a mercury-intrusion curve look like next to the true
+ * pore-size distribution? All three are one object: for every fluid node the (squared) size of the largest disc that can be brought
+ * there from an inlet side without ever overlapping a solid -- the widest-path value over the clearance analysis' d2. It is an
+ * integer and its fixed point is unique whatever the order of evaluation; a numpy restatement over the network and a heap-based
+ * widest path over the grid reproduce everything exactly (tests/drainage_util.py).
+ * Input, as of the call: the map M, validated as lbmdem_clearance_compute validates it -- the handle's or a caller's of that
+ * shape; behind it the clearance's d2 and the pore network's body plane and level-0 link table. Node (x, y) has the index
+ * k = x*ly + y. Adjacency is the network's: 8 neighbours, a diagonal step between two solid corners counts.
+ * Parameters: from and to, side masks with the walls' bit values: B 1 (y low), T 2 (y high), L 4 (x low), R 8 (x high); band, an int
+ * >= 1, each side clamped to the lattice. The REGION of a mask is the set of nodes with y < band (B), y >= ly - band (T), x < band
+ * (L) or x >= lx - band (R), for the bits set. (A band is needed because positions outside the lattice count as wall: every edge
+ * node has d2 == 1, so a reservoir one node deep admits nothing wider.) The inlet set S is the fluid nodes of from's region, the
+ * outlet set T those of to's region. from == 0 is refused; to == 0 is allowed: there is then no outlet.
+ * 1. Access. access[x][y], int: for a fluid node p the maximum, over all paths of adjacent fluid nodes from any node of S to p, of
+ *    the smallest d2 on the path, both ends included; 0 where no such path exists and 0 off the fluid. So access <= d2, and
+ *    access == d2 on S.
+ * 2. Per body. A[b], int: the largest access among the body's nodes, 0 if none is reached. It is the least fixed point of
+ *    A[b] = max(seed[b], max over level-0 links (b, c) of min(A[c], saddle(b, c))), seed[b] the largest d2 among the nodes of S in
+ *    body b, or 0; and access[p] = min(d2[p], A[body[p]]). Why: every node climbs to its peak along non-decreasing d2 and the way
+ *    back down is the same nodes, so a path may always be led over the peaks of the bodies it visits without lowering its smallest
+ *    d2; and the best crossing between two adjacent bodies, peak to peak, has the link's saddle as its smallest d2.
+ * 3. Per level-0 link. pass, int: min(A[lo], A[hi], saddle), the largest size that crosses this link coming from the inlet.
+ * 4. Intrusion curve. hist[k], long, k = 0 .. kmax, kmax the clearance block's: the fluid nodes with isqrt(access) == k; hist[0]
+ *    is the unreached fluid. It lies next to lbmdem_download_clearance_hist's array entry for entry; the shift between the two is
+ *    the ink-bottle effect.
+ * 5. counts10, in order: fluid_nodes; inlet_nodes; reached_nodes (access > 0); reached_bodies (A > 0); access_max;
+ *    shielded_nodes (0 < access < d2); outlet_nodes; critical, the largest access over T, 0 when T is not reached or empty, -1
+ *    when to == 0; critical_node, the smallest index of T with that access and access > 0, otherwise -1; front_links, the level-0
+ *    links with saddle == critical, max(A[lo], A[hi]) > critical and min(A[lo], A[hi]) == critical, counted only when
+ *    critical > 0: the candidate bottleneck throats. An empty S is not an error: everything is then 0 or -1 as stated.
+ * Identities: sum(hist) == fluid_nodes; hist[0] == fluid_nodes - reached_nodes; from == 15 with band >= max(lx, ly) gives
+ * access == d2; the nodes of an 8-connected pore (lbmdem_pore_compute, conn 8) without an inlet node have access 0;
+ * critical <= access_max; swapping from and to gives the same critical whenever both are non-zero.
+ * On the device (lbm_drainage.hip), on the handle's stream: the network first where it is needed -- with map == NULL and a network
+ * result of the handle's map that its guard still calls valid (over a clearance result of which the same holds), the body plane,
+ * the level-0 link table and d2 are reused, whatever merge that result was made with; otherwise lbmdem_network_compute(map, merge
+ * -1, max_edges) runs, and its readers are valid afterwards as if the caller had called it. Then the seed by an atomic maximum
+ * per inlet node; the relaxation over the link table in rounds -- a workgroup sweeps its 256 consecutive links until 32 sweeps in
+ * a row raised nothing, the host reads a `changed` word and stops at the first quiet launch, at most bodies + 1 launches ("the
+ * relaxation did not settle" beyond); no workgroup waits for another; A goes through relaxed agent-scope atomics --; one pass
+ * over the plane for access, the histogram (lanes that share a bin first, LDS, 64-bit integer atomics), the node counts and
+ * critical (an atomic maximum of access << 32 | ~k over the outlet); one lane per body and link for the rest. Integer atomics
+ * only, no floating point. The plane comes from the handle's pool with the first call, the tables grow with their counts.
+ *   lbmdem_drainage_compute         the compute; map NULL: the handle's; max_edges: lbmdem_network_compute's, where that runs.
+ *                                   counts10. A refused compute leaves no drainage result. Synchronises; changes nothing a
+ *                                   later step reads.
+ *   lbmdem_download_drainage        access[lx][ly]
+ *   lbmdem_drainage_device          the plane where it lies on the device, node (x, y) at x * *sy + y (for a torch view); the pad
+ *                                   columns ly .. *sy - 1 hold 0; good until the next compute or lbmdem_destroy
+ *   lbmdem_download_drainage_bodies, lbmdem_download_drainage_links   A and pass, aligned with lbmdem_download_network_bodies
+ *                                   and lbmdem_download_network_links(level 0); lbmdem_download_drainage_hist: kmax + 1 bins. Sized
+ *                                   as lbmdem_download_throats is: cap = 0 reports *count, a short buffer is refused ("%s: there
+ *                                   are %ld bodies (links, bins), the buffer holds %ld") with *count set and nothing written
+ *   lbmdem_drainage_rounds          the launches of the relaxation in the last compute, the quiet last one included; 0 without
+ *                                   a link
+ *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_drainage_compute has been made for the map as it is now",
+ *   until a compute has been made, after a refused compute, after anything the network readers are refused after, and after a
+ *   later lbmdem_network_compute (the tables A and pass are aligned with are gone).
+ *   lbmdem_write_drainage_files     host only, no handle, no device. In <dir>: drainage_curve%.6i.dat -- "# lx %d ly %d n %d from
+ *                                   %d band %d to %d\n", "# k access_nodes clearance_nodes invaded\n", then per k = 0 .. kmax "%ld
+ *                                   %ld %ld %ld\n": k, hist[k], clearance_hist[k] and the nodes with isqrt(access) >= max(k, 1);
+ *                                   drainage_bodies%.6i.dat -- the same first line, "# body node d2 A\n", then per body "%ld %d
+ *                                   %d %d\n"; drainage.data -- one line appended, "%le" of t and " %ld" of each of the ten
+ *                                   counts; when the file is created, first the line "# t fluid_nodes inlet_nodes reached_nodes
+ *                                   reached_bodies access_max shielded_nodes outlet_nodes critical critical_node front_links";
+ *                                   drainage%.6i.vtk, only when plane != 0 -- lbmdem_write_clearance_files' layout with the title
+ *                                   "lbmdem drainage" and the one plane "access". It checks fopen ("cannot open"); refused
+ *                                   before anything is written: nA != nbodies, histograms of different lengths, bodies whose
+ *                                   nodes do not ascend, a negative d2, A, count or plane value, A above the body's d2, from,
+ *                                   band or to outside their ranges. access may be NULL when plane == 0, bodies and A when
+ *                                   their count is 0.
+ *   lbmdem_write_drainage           the compute on the handle's map (max_edges 0), the downloads, then that formatter with
+ *                                   t = nbsteps * dt
+ *   lbmdem_set_drainage_output      on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_drainage(dir, nFile, from, band,
+ *                                   to, plane) at every DEM event, behind the network files. Off by default; a checkpoint does
+ *                                   not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL: null arguments; from outside 1 .. 15; to outside 0 .. 15; band < 1; a side above
+ * 32768; max_edges outside 0 .. 2^31 - 1; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the
+ * setting on); the single-precision library (the host-only formatter exists there too); a directory that cannot be written. */
+#define LBMDEM_DRAINAGE_COUNTS 10
+int lbmdem_drainage_compute(lbmdem_handle* h, const int* map /* NULL: the handle's */, int from, int band, int to, long max_edges,
+                            long* counts10);
+int lbmdem_download_drainage(lbmdem_handle* h, int* access);   /* [lx][ly], host layout */
+int lbmdem_drainage_device(lbmdem_handle* h, const int** access, int* sy);   /* device layout, pitch sy */
+int lbmdem_download_drainage_bodies(lbmdem_handle* h, int* A, long cap, long* count);
+int lbmdem_download_drainage_links(lbmdem_handle* h, int* pass, long cap, long* count);
+int lbmdem_download_drainage_hist(lbmdem_handle* h, long* hist, long cap, long* count);
+int lbmdem_drainage_rounds(lbmdem_handle* h, int* rounds);
+int lbmdem_write_drainage(lbmdem_handle* h, const char* dir, int nfile, int from, int band, int to, int plane);
+int lbmdem_set_drainage_output(lbmdem_handle* h, int on, int from, int band, int to, int plane);   /* 0: off (default) */
+int lbmdem_write_drainage_files(const char* dir, int nfile, int lx, int ly, int n, int from, int band, int to, int plane,
+                                const int* access, const lbmdem_net_body* bodies, long nbodies, const int* A, long nA,
+                                const long* hist, long nhist, const long* clearance_hist, long nclearance_hist,
+                                const long* counts10, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
