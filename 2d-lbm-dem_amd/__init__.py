@@ -246,6 +246,14 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_drainage_output.argtypes = [C.c_void_p] + [C.c_int] * 5
     L.lbmdem_write_drainage_files.argtypes = ([C.c_char_p] + [C.c_int] * 8 + [C.c_void_p] * 2 + [C.c_long, C.c_void_p, C.c_long, C.c_void_p,
                                                C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_double])
+    L.lbmdem_geodesic_compute.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_long, C.c_void_p]
+    L.lbmdem_download_geodesic.argtypes = [C.c_void_p] + [C.c_void_p] * 3
+    L.lbmdem_geodesic_device.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_int)]
+    L.lbmdem_download_geodesic_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_geodesic_rounds.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.lbmdem_write_geodesic.argtypes = [C.c_void_p, C.c_char_p] + [C.c_int] * 7
+    L.lbmdem_set_geodesic_output.argtypes = [C.c_void_p] + [C.c_int] * 7
+    L.lbmdem_write_geodesic_files.argtypes = ([C.c_char_p] + [C.c_int] * 10 + [C.c_void_p] * 4 + [C.c_long, C.c_void_p, C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -667,6 +675,35 @@ def write_drainage_files(directory, nFile, lx, ly, n, frm, band, to, bodies, A, 
         os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(frm), int(band), int(to), 0 if plane is None else 1,
         None if plane is None else _vp(plane), _vp(bo) if len(bo) else None, len(bo), _vp(aa) if len(aa) else None, len(aa),
         _vp(hs) if len(hs) else None, len(hs), _vp(ch) if len(ch) else None, len(ch), _vp(cnt), float(t)))
+
+
+# geodesic (LbmDem.geodesic): the names of the ten counts, struct lbmdem_geo_level (one depth of the profile) and the cost of an
+# axis step (a diagonal one costs 7)
+GEODESIC_COUNTERS = ("fluid_nodes", "passable_nodes", "inlet_nodes", "reached_nodes", "dist_max", "outlet_nodes", "outlet_reached",
+                     "shortest", "shortest_node", "path_nodes")
+GEO_LEVEL_DTYPE = np.dtype([("nodes", np.int64), ("reached", np.int64), ("sum", np.int64), ("dmin", np.int32), ("dmax", np.int32)])
+GEO_UNIT = 5
+
+
+def write_geodesic_files(directory, nFile, lx, ly, n, frm, band, to, conn, min_d2, levels, counts, t, planes=None, precision="f64"):
+    """geodesic_profile%.6i.dat, one appended line of geodesic.data and, with planes = (dist, back, detour), each (lx, ly),
+    geodesic%.6i.vtk (include/lbmdem_hip.h spells the three formats out) from the profile (GEO_LEVEL_DTYPE), the ten counts (a
+    dict of GEODESIC_COUNTERS or a sequence) and the time of the line; n: the grain count of the first line. Host only."""
+    lv = np.ascontiguousarray(levels, dtype=GEO_LEVEL_DTYPE).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in GEODESIC_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(GEODESIC_COUNTERS):
+        raise LbmDemError(-1, "write_geodesic_files: ten counts")
+    pl = None
+    if planes is not None:
+        pl = [np.ascontiguousarray(a, dtype=np.int32) for a in planes]
+        if len(pl) != 3 or any(a.shape != (int(lx), int(ly)) for a in pl):
+            raise LbmDemError(-1, "write_geodesic_files: three planes of shape (lx, ly)")
+    _chk(load_library(precision).lbmdem_write_geodesic_files(
+        os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(frm), int(band), int(to), int(conn), int(min_d2),
+        0 if pl is None else 1, *([None] * 3 if pl is None else [_vp(a) for a in pl]), _vp(lv) if len(lv) else None, len(lv), _vp(cnt),
+        float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1644,6 +1681,65 @@ class LbmDem:
     def set_drainage_output(self, on=True, frm=SIDE_T, band=1, to=0, plane=False):
         """run_scene writes the drainage files at every DEM event, behind the network files"""
         _chk(self._L.lbmdem_set_drainage_output(self._h, 1 if on else 0, int(frm), int(band), int(to), 1 if plane else 0))
+
+    # geodesic: the length of the shortest path through the pore space from a chosen side (include/lbmdem_hip.h)
+    def geodesic(self, frm, band=1, to=0, conn=8, min_d2=0, map=None, max_edges=0):
+        """the shortest path of adjacent passable nodes -- fluid nodes with clearance d2 >= min_d2 -- from those within `band` nodes
+        of the sides `frm` (SIDE_B | SIDE_T | SIDE_L | SIDE_R) to every passable node of the handle's map, or of `map`, (lx, ly)
+        ints as clearance() takes them; an axis step costs GEO_UNIT = 5, a diagonal one (conn 8) 7. `to`: the outlet sides the
+        backward distances, `shortest` and the corridor detour == 0 are taken over, 0: none. With min_d2 > 1 runs clearance()
+        first where its result is not there (max_edges: its budget) -> dict of GEODESIC_COUNTERS"""
+        c = np.zeros(len(GEODESIC_COUNTERS), np.int64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "geodesic: a map of shape (lx, ly)")
+        _chk(self._L.lbmdem_geodesic_compute(self._h, None if m is None else _vp(m), int(frm), int(band), int(to), int(conn), int(min_d2),
+                                             int(max_edges), _vp(c)))
+        return dict(zip(GEODESIC_COUNTERS, (int(v) for v in c)))
+
+    def geodesic_planes(self):
+        """-> dict(dist, back, detour), int32 (lx, ly) each, of the last geodesic(): the distance from the inlet, from the outlet,
+        and dist + back - shortest; -1 where there is none"""
+        out = {k: np.empty((self.lx, self.ly), np.int32) for k in ("dist", "back", "detour")}
+        _chk(self._L.lbmdem_download_geodesic(self._h, _vp(out["dist"]), _vp(out["back"]), _vp(out["detour"])))
+        return out
+
+    def geodesic_tensors(self):
+        """the same planes as torch.int32 views (lx, sy) of the handle's device memory, sy the device's row pitch: node (x, y) at
+        [x, y], the columns from ly on hold -1. Good until the next geodesic()."""
+        import torch
+        p, sy = [C.c_void_p() for _ in range(3)], C.c_int(0)
+        _chk(self._L.lbmdem_geodesic_device(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(sy)))
+        return {k: torch.as_tensor(_DeviceBlock(q.value, (self.lx, sy.value), "<i4"), device=f"cuda:{self.cfg.device}")
+                for k, q in zip(("dist", "back", "detour"), p)}
+
+    def geodesic_profile(self):
+        """structured array of GEO_LEVEL_DTYPE, one record per depth behind the inlet sides: the passable nodes, the reached ones,
+        the sum of their dist, the least and the largest"""
+        n = C.c_long(0)
+        _chk(self._L.lbmdem_download_geodesic_profile(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=GEO_LEVEL_DTYPE)
+        if n.value:
+            _chk(self._L.lbmdem_download_geodesic_profile(self._h, _vp(out), n.value, C.byref(n)))
+        return out
+
+    def geodesic_rounds(self):
+        """(forward, backward): the launches the two relaxations of the last geodesic() took, the quiet last ones included"""
+        f, b = C.c_int(0), C.c_int(0)
+        _chk(self._L.lbmdem_geodesic_rounds(self._h, C.byref(f), C.byref(b)))
+        return f.value, b.value
+
+    def write_geodesic(self, directory=".", nFile=0, frm=SIDE_T, band=1, to=0, conn=8, min_d2=0, plane=False):
+        """geodesic_profile%.6i.dat, a line of geodesic.data and (plane) geodesic%.6i.vtk of the map as it is now"""
+        _chk(self._L.lbmdem_write_geodesic(self._h, os.fsencode(directory), int(nFile), int(frm), int(band), int(to), int(conn),
+                                           int(min_d2), 1 if plane else 0))
+
+    def set_geodesic_output(self, on=True, frm=SIDE_T, band=1, to=0, conn=8, min_d2=0, plane=False):
+        """run_scene writes the geodesic files at every DEM event, behind the drainage files"""
+        _chk(self._L.lbmdem_set_geodesic_output(self._h, 1 if on else 0, int(frm), int(band), int(to), int(conn), int(min_d2),
+                                                1 if plane else 0))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

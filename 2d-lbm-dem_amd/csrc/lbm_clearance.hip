@@ -597,6 +597,7 @@ int lbmdem_clearance_compute(lbmdem_handle* h, const int* map, long max_edges, l
   V.nedges = E; V.nthroats = T; V.kmax = (int)counts10[9];
   V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
   V.own = map == nullptr;
+  V.gen += 1;
   V.valid = true;
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)

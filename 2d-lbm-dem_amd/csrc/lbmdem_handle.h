@@ -423,6 +423,7 @@ struct lbmdem_handle {
     long nedges = 0, nthroats = 0;        // of the last compute
     int kmax = 0;
     bool own = false;                     // the last compute was of the handle's map, not of a caller's (lbm_network.hip reuses d2 then)
+    unsigned long long gen = 0;           // counts the computes: a result made over d2 says which one (lbm_geodesic.hip)
   } clr;
   // The pore network (lbm_network.hip): a watershed of clr.d2 -- per fluid node the body (the local maximum it climbs to) and the
   // group its body merges into, the body and group records and the links of both levels. net: planes and block counts allocated by
@@ -474,6 +475,33 @@ struct lbmdem_handle {
     int kmax = 0;                         // the clearance's at that compute: the histogram has kmax + 1 bins
     int rounds = 0;                       // launches of the relaxation, the quiet last one included
   } drn;
+  // Geodesic (lbm_geodesic.hip): the shortest path through the passable fluid nodes from an inlet region (dist), from an outlet
+  // region (back), the corridor between them (detour) and the profile over the depth behind the inlet. geo: the planes, the tile
+  // lists and the words allocated by the first lbmdem_geodesic_compute, the profile grown with the depths, freed with the handle.
+  // The kernels read the map, or clr.d2 when min_d2 > 1, and write here only. Valid under the pores' guard, and with min_d2 > 1
+  // over the handle's map while clr.gen is the one it was made over. geodesic_*: lbmdem_set_geodesic_output.
+  bool geodesic_output = false;
+  int geodesic_from = 0, geodesic_band = 1, geodesic_to = 0, geodesic_conn = 8, geodesic_min_d2 = 0, geodesic_plane = 0;
+  struct GeodesicStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    bool over_clearance = false;          // made over clr.d2 of the handle's map
+    unsigned long long gen = 0;           // ... clr.gen of that result
+    unsigned long long* words = nullptr;  // [GEO_WORDS] the counts (null: nothing allocated yet)
+    int* dist = nullptr;                  // [lx][sy] the result: the distance from the inlet, -1 where not passable or not reached and in the pad columns
+    int* back = nullptr;                  // [lx][sy] the same from the outlet
+    int* detour = nullptr;                // [lx][sy] dist + back - shortest
+    int* map = nullptr;                   // [lx][sy] a caller's map in device layout (allocated by the first compute that brings one)
+    int* stamp = nullptr;                 // [tiles] the round a tile of the relaxation was last listed for
+    int* list = nullptr;                  // [2][tiles] the active tiles of this round and of the next
+    unsigned* cnt = nullptr;              // [2] their lengths
+    unsigned long long* lev = nullptr;    // [3][depths] per depth: passable nodes, reached ones, the sum of dist
+    long lev_cap = 0;
+    int* lmm = nullptr;                   // [2][depths] per depth: the least and the largest dist
+    long lmm_cap = 0;
+    std::vector<lbmdem_geo_level> levels; // the profile of the last compute, on the host
+    int rounds[2] = {0, 0};               // launches of the forward and the backward relaxation, the quiet last ones included
+  } geo;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -79,6 +79,12 @@
  * reservoir N nodes deep (default 1) -- the intrusion curve next to the pore-size distribution in drainage_curve%.6i.dat, per pore
  * body the size that reaches it in drainage_bodies%.6i.dat, a line of drainage.data (what passes from FROM to the sides TO, and
  * through how many candidate throats?) and, with --drainage-plane, the access plane in drainage%.6i.vtk. Single GPU only.
+ * --geodesic FROM [--geodesic-to TO] [--geodesic-band N] [--geodesic-conn 4|8] [--geodesic-min-d2 D] [--geodesic-plane]: the
+ * geodesic analysis of every DEM event (lbmdem_set_geodesic_output): the length of the shortest path through the fluid nodes with
+ * clearance d2 >= D (default 0: all) from the sides FROM, letters out of BTLR, N nodes deep (default 1), in steps of 5 along an
+ * axis and, with 8 neighbours (the default), 7 along a diagonal -- the profile over the depth behind FROM with the tortuosity in
+ * geodesic_profile%.6i.dat, a line of geodesic.data (how long is the shortest way from FROM to the sides TO?) and, with
+ * --geodesic-plane, the planes dist, back and detour in geodesic%.6i.vtk. Single GPU only.
  * --coarse CWxCH: the coarse-grained fields of every DEM event next to its table (lbmdem_set_coarse_output): coarse%.6i.dat, one
  * line per cell of CW x CH lattice nodes with the sums of fluid, grains and contacts over it. Single GPU only.
  * --flow: the flow fields (lbmdem_set_flow_output): flow%.6i.vtk next to every VTK frame -- composite velocity, vorticity, shear
@@ -129,6 +135,8 @@ static int g_clearance = 0, g_clearance_plane = 0;   /* --clearance, --clearance
 static int g_network = 0, g_network_merge = -1, g_network_plane = 0;   /* --network [MERGE], --network-plane */
 static int g_drainage = 0, g_drainage_to = 0, g_drainage_band = 1, g_drainage_plane = 0;   /* --drainage FROM, --drainage-to TO, --drainage-band N, --drainage-plane */
 static int g_drainage_to_set = 0;
+static int g_geodesic = 0, g_geodesic_to = 0, g_geodesic_band = 1, g_geodesic_conn = 8, g_geodesic_min_d2 = 0, g_geodesic_plane = 0;   /* --geodesic FROM, --geodesic-to TO, --geodesic-band N, --geodesic-conn 4|8, --geodesic-min-d2 D, --geodesic-plane */
+static int g_geodesic_opts = 0;   /* one of the options that need --geodesic FROM has been given */
 static int g_tracers = 0, g_tracers_nx = 0, g_tracers_ny = 0;   /* --tracers NXxNY */
 static int g_dye = 0, g_dye_box[4] = {0, 0, 0, 0};   /* --dye X0,Y0,X1,Y1 */
 static double g_dye_tau = 0.53;                      /* --dye-tau T */
@@ -338,6 +346,24 @@ int main(int argc, char** argv) {
       g_drainage_band = atoi(argv[a + 1]);
     }
     if (!strcmp(argv[a], "--drainage-plane")) g_drainage_plane = 1;
+    if (!strcmp(argv[a], "--geodesic") || !strcmp(argv[a], "--geodesic-to")) {
+      const int mask = a + 1 < argc ? side_mask(argv[a + 1]) : 0;
+      if (mask <= 0) { fprintf(stderr, "%s SIDES: letters out of BTLR, at least one\n", argv[a]); return EXIT_FAILURE; }
+      if (!strcmp(argv[a], "--geodesic")) g_geodesic = mask; else { g_geodesic_to = mask; g_geodesic_opts = 1; }
+    }
+    if (!strcmp(argv[a], "--geodesic-band")) {
+      if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) < 1) { fprintf(stderr, "--geodesic-band N: the depth of the inlet and outlet regions in nodes, at least 1\n"); return EXIT_FAILURE; }
+      g_geodesic_band = atoi(argv[a + 1]); g_geodesic_opts = 1;
+    }
+    if (!strcmp(argv[a], "--geodesic-conn")) {
+      if (a + 1 >= argc || (strcmp(argv[a + 1], "4") && strcmp(argv[a + 1], "8"))) { fprintf(stderr, "--geodesic-conn 4|8: the neighbours a path may step to\n"); return EXIT_FAILURE; }
+      g_geodesic_conn = atoi(argv[a + 1]); g_geodesic_opts = 1;
+    }
+    if (!strcmp(argv[a], "--geodesic-min-d2")) {
+      if (a + 1 >= argc || !is_count(argv[a + 1])) { fprintf(stderr, "--geodesic-min-d2 D: the least squared clearance of a passable node, 0 or more\n"); return EXIT_FAILURE; }
+      g_geodesic_min_d2 = atoi(argv[a + 1]); g_geodesic_opts = 1;
+    }
+    if (!strcmp(argv[a], "--geodesic-plane")) { g_geodesic_plane = 1; g_geodesic_opts = 1; }
     if (!strcmp(argv[a], "--structure-bins")) {
       if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) < 1 || atoi(argv[a + 1]) > 4096) { fprintf(stderr, "--structure-bins N: the bins of the pair histogram, 1 .. 4096\n"); return EXIT_FAILURE; }
       g_structure_bins = atoi(argv[a + 1]);
@@ -432,6 +458,9 @@ int main(int argc, char** argv) {
   if ((g_drainage_plane || g_drainage_to_set || g_drainage_band != 1) && !g_drainage) { fprintf(stderr, "--drainage-to, --drainage-band and --drainage-plane need --drainage FROM\n"); return EXIT_FAILURE; }
   if (g_drainage && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--drainage is a single-GPU mode (the drainage analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_drainage && g_dry) { fprintf(stderr, "--drainage cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
+  if (g_geodesic_opts && !g_geodesic) { fprintf(stderr, "--geodesic-to, --geodesic-band, --geodesic-conn, --geodesic-min-d2 and --geodesic-plane need --geodesic FROM\n"); return EXIT_FAILURE; }
+  if (g_geodesic && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--geodesic is a single-GPU mode (the geodesic analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_geodesic && g_dry) { fprintf(stderr, "--geodesic cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_flow && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--flow is a single-GPU mode (the flow fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_tracers && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--tracers is a single-GPU mode (the tracers need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_dye && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--dye is a single-GPU mode (the passive scalar needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
@@ -603,6 +632,8 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--network-plane")) {}
     else if ((!strcmp(argv[a], "--drainage") || !strcmp(argv[a], "--drainage-to") || !strcmp(argv[a], "--drainage-band")) && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--drainage-plane")) {}
+    else if ((!strcmp(argv[a], "--geodesic") || !strcmp(argv[a], "--geodesic-to") || !strcmp(argv[a], "--geodesic-band") || !strcmp(argv[a], "--geodesic-conn") || !strcmp(argv[a], "--geodesic-min-d2")) && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--geodesic-plane")) {}
     else if (!strcmp(argv[a], "--structure-bins") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--structure-shell") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--coarse") && a + 1 < argc) ++a;
@@ -635,7 +666,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --geodesic FROM --geodesic-to TO --geodesic-band N --geodesic-conn 4|8 --geodesic-min-d2 D --geodesic-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -717,6 +748,7 @@ static int run(int argc, char** argv) {
   if (g_clearance) DIE(lbmdem_set_clearance_output(h, 1, g_clearance_plane), "set_clearance_output");
   if (g_network) DIE(lbmdem_set_network_output(h, 1, g_network_merge, g_network_plane), "set_network_output");
   if (g_drainage) DIE(lbmdem_set_drainage_output(h, 1, g_drainage, g_drainage_band, g_drainage_to, g_drainage_plane), "set_drainage_output");
+  if (g_geodesic) DIE(lbmdem_set_geodesic_output(h, 1, g_geodesic, g_geodesic_band, g_geodesic_to, g_geodesic_conn, g_geodesic_min_d2, g_geodesic_plane), "set_geodesic_output");
   if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");
   if (g_coarse) DIE(lbmdem_set_coarse_output(h, g_coarse_cw, g_coarse_ch), "set_coarse_output");
   if (g_tracers && got_tracers) DIE(lbmdem_set_tracer_output(h, 1), "set_tracer_output");   /* the loaded set goes on: tracer k stays tracer k */

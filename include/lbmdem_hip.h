@@ -1111,6 +1111,110 @@ int lbmdem_write_drainage_files(const char* dir, int nfile, int lx, int ly, int 
                                 const int* access, const lbmdem_net_body* bodies, long nbodies, const int* A, long nA,
                                 const long* hist, long nhist, const long* clearance_hist, long nclearance_hist,
                                 const long* counts10, double t);   /* host only */
+/* Geodesic: how LONG is the way through this packing? Every analysis above says how wide the pore space is; the tortuosity, the
+ * ratio of the shortest path through the pores to the straight distance, is the geometric number Kozeny-Carman needs next to the
+ * porosity and the wetted surface, and it explains a breakthrough time of the dye or the tracers. For every passable fluid node
+ * the length of the shortest path of adjacent passable nodes from an inlet region; on request the same from an outlet region, and
+ * from the two the corridor of shortest paths between them. Integers only, and the result is unique whatever the order of
+ * evaluation; a numpy restatement by Jacobi sweeps and a heap Dijkstra over the grid reproduce everything exactly
+ * (tests/geodesic_util.py).
+ * Input, as of the call: the map M, validated as lbmdem_clearance_compute validates it -- the handle's or a caller's of that
+ * shape. Node (x, y) has the index k = x*ly + y.
+ * Parameters: from and to, side masks as in the drainage block: B 1 (y low), T 2 (y high), L 4 (x low), R 8 (x high); from is
+ * non-zero, to == 0 means no outlet; band, an int >= 1, each side clamped to the lattice; the REGION of a mask and band is the
+ * drainage block's. conn, 4 or 8. min_d2, an int >= 0.
+ * 1. Passable. A fluid node (M == -1) whose clearance d2 (the clearance block's) is >= min_d2. With min_d2 <= 1 this is every
+ *    fluid node; the clearance analysis is then neither needed nor run and its result, if there is one, is not touched. With
+ *    min_d2 > 1 it is the pore space as a particle of that squared radius sees it.
+ * 2. Metric. A step between two passable nodes that differ by 1 in x or in y costs LBMDEM_GEO_UNIT = 5; with conn == 8 a step
+ *    between two passable nodes that differ by 1 in both costs 7, whatever the other two nodes of the square are (as the pores'
+ *    8-connectivity has it): the 5-7 chamfer, 1.4 against sqrt(2). The unit is a fifth of a node spacing in both modes.
+ * 3. dist[x][y], int: 0 on the passable nodes of the region of (from, band); elsewhere the least cost of a path of such steps from
+ *    them; -1 where the node is not passable or not reached.
+ * 4. back[x][y], int: the same from the passable nodes of the region of (to, band); all -1 when to == 0.
+ * 5. shortest: the least dist over the passable nodes of the outlet region, -1 without one (to == 0, an empty outlet, none
+ *    reached). detour[x][y], int: dist + back - shortest where both are >= 0 and shortest >= 0, else -1. detour == 0 marks the
+ *    nodes that lie on some shortest path from the inlet to the outlet; detour is never negative.
+ * 6. Profile. depth(p) is the least offset of p to a side in from: B y, T ly-1-y, L x, R lx-1-x. One lbmdem_geo_level per depth
+ *    0 .. depthmax, depthmax the largest depth on the lattice (a matter of lx, ly and from alone): nodes, the passable nodes of
+ *    that depth; reached, those with dist >= 0; sum, the sum of dist over them; dmin and dmax, the least and the largest dist
+ *    among them, -1 without one. sum / (5 * reached * (depth - band + 1)) is the mean tortuosity at that depth.
+ * 7. counts10, in order: fluid_nodes; passable_nodes; inlet_nodes, the passable nodes of from's region; reached_nodes
+ *    (dist >= 0); dist_max, -1 when nothing is reached; outlet_nodes, the passable nodes of to's region, 0 when to == 0;
+ *    outlet_reached, those with dist >= 0; shortest; shortest_node, the smallest index k among the outlet nodes with
+ *    dist == shortest, -1 without one; path_nodes, the nodes with detour == 0.
+ * Identities: with conn == 4, dist is 5 times the number of steps of a breadth-first search; dist with conn == 8 is at most dist
+ * with conn == 4, node for node; a larger min_d2 never lowers a distance; swapping from and to gives the same shortest; a band
+ * that covers the lattice gives dist == 0 on every passable node; sum over the profile's nodes == passable_nodes.
+ * On the device (lbm_geodesic.hip), on the handle's stream: with min_d2 > 1 the clearance first where it is needed -- with
+ * map == NULL and a clearance result of the handle's map that its guard still calls valid, that result's d2 plane is reused;
+ * otherwise lbmdem_clearance_compute runs on the map with max_edges passed through, and its readers are valid afterwards as if the
+ * caller had called it. The distances are the greatest fixed point below the seed of D[p] = min(D[p], D[q] + cost(p, q)): values
+ * only fall, and only to values a real path realises, so any order of relaxations ends at the same plane. One pass seeds the plane
+ * and counts; then rounds over a list of active tiles of 16 x 64 nodes -- a workgroup holds its tile and an apron of one node in
+ * LDS, sweeps until a sweep lowers nothing (128 sweeps at most), stores what it lowered and lists for the next round every
+ * neighbouring tile that shares a border node it lowered, and itself if it stopped at the bound; the host reads the length of the
+ * next list after every launch and stops at the first launch that lists nothing, after passable_nodes + 2 launches at the latest
+ * ("the relaxation did not settle" beyond); no workgroup waits for another. The backward pass is the same with the outlet region
+ * as seed. One pass for the counts, shortest (an atomic minimum of dist << 32 | k over the outlet) and the profile (LDS bins per
+ * depth, then 64-bit integer atomics), one for detour. Integer atomics only, no floating point. The planes come from the handle's
+ * pool with the first call.
+ *   lbmdem_geodesic_compute         the compute; map NULL: the handle's; max_edges: lbmdem_clearance_compute's, where that runs.
+ *                                   counts10. A refused compute leaves no geodesic result. Synchronises; changes nothing a later
+ *                                   step reads.
+ *   lbmdem_download_geodesic        dist[lx][ly], back[lx][ly], detour[lx][ly]; any pointer may be NULL
+ *   lbmdem_geodesic_device          the three planes where they lie on the device, node (x, y) at x * *sy + y (for a torch view);
+ *                                   the pad columns ly .. *sy - 1 hold -1; good until the next compute or lbmdem_destroy
+ *   lbmdem_download_geodesic_profile   the records; sized as lbmdem_download_throats is: cap = 0 reports *count, a short buffer is
+ *                                   refused ("%s: there are %ld depths, the buffer holds %ld") with *count set and nothing written
+ *   lbmdem_geodesic_rounds          the launches of the forward and of the backward relaxation in the last compute, the quiet
+ *                                   last one included; 0 where the region holds no passable node, *bwd 0 when to == 0
+ *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_geodesic_compute has been made for the map as it is now",
+ *   until a compute has been made, after a refused compute, after anything the pore readers are refused after (a step or
+ *   sub-step, lbmdem_upload_f, lbmdem_upload_kinematics) and, for a result made with min_d2 > 1 over the handle's map, after a
+ *   later lbmdem_clearance_compute (the d2 it was made over is gone).
+ *   lbmdem_write_geodesic_files     host only, no handle, no device. In <dir>: geodesic_profile%.6i.dat -- "# lx %d ly %d n %d
+ *                                   from %d band %d to %d conn %d min_d2 %d\n", "# depth nodes reached sum min max tortuosity\n",
+ *                                   then per depth "%ld %ld %ld %ld %d %d %.6f\n", the last column (double)sum / (double)(5 *
+ *                                   reached * (depth - band + 1)), the product formed in 64-bit integers, followed by one
+ *                                   division; 0.000000 for depth < band or reached == 0; geodesic.data -- one line appended,
+ *                                   "%le" of t and " %ld" of each of the ten counts; when the file is created, first the line
+ *                                   "# t fluid_nodes passable_nodes inlet_nodes reached_nodes dist_max outlet_nodes
+ *                                   outlet_reached shortest shortest_node path_nodes"; geodesic%.6i.vtk, only when plane != 0 --
+ *                                   lbmdem_write_clearance_files' layout with the title "lbmdem geodesic" and the planes "dist",
+ *                                   "back" and "detour". It checks fopen ("cannot open"); refused before anything is written:
+ *                                   no level, a level with reached > nodes, a negative count or sum, dmin and dmax that are not
+ *                                   -1 without a reached node or do not ascend with one, a plane value below -1, from, band, to,
+ *                                   conn or min_d2 outside their ranges. The planes may be NULL when plane == 0.
+ *   lbmdem_write_geodesic           the compute on the handle's map (max_edges 0), the downloads, then that formatter with
+ *                                   t = nbsteps * dt
+ *   lbmdem_set_geodesic_output      on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_geodesic(dir, nFile, from, band,
+ *                                   to, conn, min_d2, plane) at every DEM event, behind the drainage files. Off by default; a
+ *                                   checkpoint does not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL, each with its sentence under the entry point's name: "from must be a mask of sides,
+ * B 1 | T 2 | L 4 | R 8, with at least one (%d)"; "to must be a mask of sides, B 1 | T 2 | L 4 | R 8, or 0 for no outlet (%d)";
+ * "band must be at least 1 node (%d)"; "conn must be 4 or 8 (%d)"; "min_d2 must not be negative (%d)"; "a lattice of %d x %d nodes
+ * has a side above %d or more than %d nodes: a distance is a 32-bit integer" (a side above 32768, or 7 * lx * ly > INT_MAX);
+ * "max_edges must lie in 0 .. %d (%ld)"; "map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor the wall
+ * (%d)". Also: null arguments; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the
+ * single-precision library (the host-only formatter exists there too); a directory that cannot be written. */
+#define LBMDEM_GEO_UNIT 5
+typedef struct lbmdem_geo_level {
+  long nodes, reached, sum;
+  int dmin, dmax;
+} lbmdem_geo_level;
+#define LBMDEM_GEODESIC_COUNTS 10
+int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map /* NULL: the handle's */, int from, int band, int to, int conn,
+                            int min_d2, long max_edges, long* counts10);
+int lbmdem_download_geodesic(lbmdem_handle* h, int* dist, int* back, int* detour);   /* [lx][ly], host layout; any may be NULL */
+int lbmdem_geodesic_device(lbmdem_handle* h, const int** dist, const int** back, const int** detour, int* sy);   /* device layout, pitch sy */
+int lbmdem_download_geodesic_profile(lbmdem_handle* h, lbmdem_geo_level* rec, long cap, long* count);
+int lbmdem_geodesic_rounds(lbmdem_handle* h, int* fwd, int* bwd);
+int lbmdem_write_geodesic(lbmdem_handle* h, const char* dir, int nfile, int from, int band, int to, int conn, int min_d2, int plane);
+int lbmdem_set_geodesic_output(lbmdem_handle* h, int on, int from, int band, int to, int conn, int min_d2, int plane);   /* 0: off (default) */
+int lbmdem_write_geodesic_files(const char* dir, int nfile, int lx, int ly, int n, int from, int band, int to, int conn, int min_d2,
+                                int plane, const int* dist, const int* back, const int* detour, const lbmdem_geo_level* levels,
+                                long nlevels, const long* counts10, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
