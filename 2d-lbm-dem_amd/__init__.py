@@ -254,6 +254,14 @@ def _open_library(LIB_PATH):
     L.lbmdem_write_geodesic.argtypes = [C.c_void_p, C.c_char_p] + [C.c_int] * 7
     L.lbmdem_set_geodesic_output.argtypes = [C.c_void_p] + [C.c_int] * 7
     L.lbmdem_write_geodesic_files.argtypes = ([C.c_char_p] + [C.c_int] * 10 + [C.c_void_p] * 4 + [C.c_long, C.c_void_p, C.c_double])
+    L.lbmdem_netflux_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.lbmdem_download_netflux_links.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_netflux_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_netflux_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lbmdem_write_netflux.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_set_netflux_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.lbmdem_write_netflux_files.argtypes = ([C.c_char_p] + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_long] + [C.c_void_p] * 3 + [C.c_long] +
+                                             [C.c_void_p] * 3 + [C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -704,6 +712,44 @@ def write_geodesic_files(directory, nFile, lx, ly, n, frm, band, to, conn, min_d
         os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(frm), int(band), int(to), int(conn), int(min_d2),
         0 if pl is None else 1, *([None] * 3 if pl is None else [_vp(a) for a in pl]), _vp(lv) if len(lv) else None, len(lv), _vp(cnt),
         float(t)))
+
+
+# pore fluxes (LbmDem.netflux): struct lbmdem_netflux_link and lbmdem_netflux_region, 24 bytes each, aligned with network_links(level)
+# and with network_bodies() (level 0) or network_groups() (level 1); the names of the ten counts
+NETFLUX_LINK_DTYPE = np.dtype([("flux_q32", np.int64), ("exchange_q32", np.int64), ("edges", np.int64)])
+NETFLUX_REGION_DTYPE = np.dtype([("mass_q32", np.int64), ("net_q32", np.int64), ("through_q32", np.int64)])
+NETFLUX_COUNTERS = ("fluid_nodes", "regions", "links", "edges", "ridge_edges", "unaccumulated_edges", "unaccumulated_nodes",
+                    "flowing_links", "strongest_link", "largest_imbalance")
+
+
+def write_netflux_files(directory, nFile, lx, ly, n, merge, level, links, flux, region_body, region_nodes, regions, col, row, counts, t,
+                        precision="f64"):
+    """netflux_links%.6i.dat, netflux_regions%.6i.dat, netflux_profile%.6i.dat and one appended line of netflux.data
+    (include/lbmdem_hip.h spells the four formats out) from the network's links of the level (NET_LINK_DTYPE) and their fluxes
+    (NETFLUX_LINK_DTYPE), per region its (root) body number, its node count and its record (NETFLUX_REGION_DTYPE), the two
+    profiles (lx - 1 and ly - 1 values), the ten counts (a dict of NETFLUX_COUNTERS or a sequence) and the time of the line;
+    n: the grain count of the first lines. Host only."""
+    li = np.ascontiguousarray(links, dtype=NET_LINK_DTYPE).reshape(-1)
+    fx = np.ascontiguousarray(flux, dtype=NETFLUX_LINK_DTYPE).reshape(-1)
+    rb = np.ascontiguousarray(region_body, dtype=np.int32).reshape(-1)
+    rn = np.ascontiguousarray(region_nodes, dtype=np.int64).reshape(-1)
+    rg = np.ascontiguousarray(regions, dtype=NETFLUX_REGION_DTYPE).reshape(-1)
+    co = np.ascontiguousarray(col, dtype=np.int64).reshape(-1)
+    ro = np.ascontiguousarray(row, dtype=np.int64).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in NETFLUX_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(NETFLUX_COUNTERS):
+        raise LbmDemError(-1, "write_netflux_files: ten counts")
+    if len(li) != len(fx) or len(rb) != len(rg) or len(rn) != len(rg):
+        raise LbmDemError(-1, "write_netflux_files: one flux record per link, one body number and one node count per region")
+    if len(co) != max(int(lx) - 1, 0) or len(ro) != max(int(ly) - 1, 0):
+        raise LbmDemError(-1, "write_netflux_files: col has lx - 1 values and row ly - 1")
+    co, ro = (a if len(a) else np.zeros(1, np.int64) for a in (co, ro))
+    _chk(load_library(precision).lbmdem_write_netflux_files(
+        os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(merge), int(level), _vp(li) if len(li) else None,
+        _vp(fx) if len(fx) else None, len(li), _vp(rb) if len(rb) else None, _vp(rn) if len(rn) else None,
+        _vp(rg) if len(rg) else None, len(rg), _vp(co), _vp(ro), _vp(cnt), float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1740,6 +1786,45 @@ class LbmDem:
         """run_scene writes the geodesic files at every DEM event, behind the drainage files"""
         _chk(self._L.lbmdem_set_geodesic_output(self._h, 1 if on else 0, int(frm), int(band), int(to), int(conn), int(min_d2),
                                                 1 if plane else 0))
+
+    # pore fluxes: the mass through every throat of the pore network in the last streaming step (include/lbmdem_hip.h)
+    def netflux(self, merge=-1, level=0, map=None):
+        """the mass that crossed every edge of adjacent fluid nodes of the handle's map -- or of `map`, (lx, ly) ints as
+        clearance() takes them -- in the last streaming step, in units of 2^-32, summed per link and per region of the pore
+        network at `merge` (level 0: the bodies, 1: the groups) and per section of the lattice. Runs network() first where its
+        result at this merge is not there -> dict of NETFLUX_COUNTERS"""
+        c = np.zeros(len(NETFLUX_COUNTERS), np.int64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "netflux: a map of shape (lx, ly)")
+        _chk(self._L.lbmdem_netflux_compute(self._h, None if m is None else _vp(m), int(merge), int(level), _vp(c)))
+        return dict(zip(NETFLUX_COUNTERS, (int(v) for v in c)))
+
+    def netflux_links(self):
+        """structured array of NETFLUX_LINK_DTYPE, entry for entry next to network_links(level) of the last netflux()"""
+        return self._drainage_table(self._L.lbmdem_download_netflux_links, NETFLUX_LINK_DTYPE)
+
+    def netflux_regions(self):
+        """structured array of NETFLUX_REGION_DTYPE, entry for entry next to network_bodies() (level 0) or network_groups() (1)"""
+        return self._drainage_table(self._L.lbmdem_download_netflux_regions, NETFLUX_REGION_DTYPE)
+
+    def netflux_profile(self):
+        """(col, row), int64 [lx - 1] and [ly - 1]: the net mass through the section between rows x and x + 1 towards +x, and
+        between columns y and y + 1 towards +y"""
+        col, row = np.zeros(self.lx, np.int64), np.zeros(self.ly, np.int64)
+        _chk(self._L.lbmdem_download_netflux_profile(self._h, _vp(col), _vp(row)))
+        return col[:self.lx - 1].copy(), row[:self.ly - 1].copy()
+
+    def write_netflux(self, directory=".", nFile=0, merge=-1, level=0):
+        """netflux_links%.6i.dat, netflux_regions%.6i.dat, netflux_profile%.6i.dat and a line of netflux.data of the map and the
+        populations as they are now"""
+        _chk(self._L.lbmdem_write_netflux(self._h, os.fsencode(directory), int(nFile), int(merge), int(level)))
+
+    def set_netflux_output(self, on=True, merge=-1, level=0):
+        """run_scene writes the pore flux files at every DEM event, behind the network files"""
+        _chk(self._L.lbmdem_set_netflux_output(self._h, 1 if on else 0, int(merge), int(level)))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

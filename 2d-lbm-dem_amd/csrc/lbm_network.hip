@@ -765,6 +765,7 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
   V.nbodies = B; V.ngroups = G; V.nlinks[0] = L0; V.nlinks[1] = L1;
   V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
   V.own = map == nullptr;
+  V.merge = merge;
   V.valid = true;
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)

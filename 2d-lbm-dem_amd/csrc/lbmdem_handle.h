@@ -452,6 +452,7 @@ struct lbmdem_handle {
     long nbodies = 0, ngroups = 0, nlinks[2] = {0, 0};   // of the last compute
     bool own = false;                     // the last compute was of the handle's map, not of a caller's (lbm_drainage.hip reuses it then)
     unsigned long long gen = 0;           // counts the computes: a result made over the tables says which ones (lbm_drainage.hip)
+    int merge = -1;                       // of the last compute (lbm_netflux.hip reuses a result of the same merge)
   } net;
   // Drainage (lbm_drainage.hip): the widest path over clr.d2 from an inlet side -- per fluid node access, per body of the network A,
   // per level-0 link pass, the histogram of isqrt(access). drn: the plane, the histogram and the words allocated by the first
@@ -502,6 +503,31 @@ struct lbmdem_handle {
     std::vector<lbmdem_geo_level> levels; // the profile of the last compute, on the host
     int rounds[2] = {0, 0};               // launches of the forward and the backward relaxation, the quiet last ones included
   } geo;
+  // Pore fluxes (lbm_netflux.hip): the mass that crossed every edge of adjacent fluid nodes in the last streaming step, in fixed
+  // point, per link and region of the network's `level` and per section of the lattice. nfx: the profiles and the words allocated
+  // by the first lbmdem_netflux_compute, the tables grown with the network's counts, freed with the handle. The kernels read f,
+  // net.body or net.group and net.links[level] and write here only. Valid under the pores' guard (lattice_seq covers f) and while
+  // net.gen is the one it was made over. netflux_*: lbmdem_set_netflux_output.
+  bool netflux_output = false;
+  int netflux_merge = -1, netflux_level = 0;
+  struct NetfluxStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    unsigned long long gen = 0;           // net.gen of the network result underneath
+    unsigned long long* words = nullptr;  // [NF_WORDS] the counts (null: nothing allocated yet)
+    long* col = nullptr;                  // [lx] the sections towards +x: lx - 1 of them
+    long* row = nullptr;                  // [ly] the sections towards +y: ly - 1 of them
+    int* first = nullptr;                 // [first_cap] per body number the first link with lo >= it
+    long first_cap = 0;
+    unsigned long long* sums = nullptr;   // [3][bodies] mass, net and through by body number
+    long sums_cap = 0;
+    lbmdem_netflux_link* links = nullptr; // [link_cap] aligned with net.links[level]
+    long link_cap = 0;
+    lbmdem_netflux_region* regions = nullptr;   // [region_cap] aligned with net.bodies or net.groups
+    long region_cap = 0;
+    long nlinks = 0, nregions = 0;        // of the last compute
+    int merge = -1, level = 0;
+  } nfx;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -1215,6 +1215,102 @@ int lbmdem_set_geodesic_output(lbmdem_handle* h, int on, int from, int band, int
 int lbmdem_write_geodesic_files(const char* dir, int nfile, int lx, int ly, int n, int from, int band, int to, int conn, int min_d2,
                                 int plane, const int* dist, const int* back, const int* detour, const lbmdem_geo_level* levels,
                                 long nlevels, const long* counts10, double t);   /* host only */
+/* Pore fluxes: where does the fluid actually go? The analyses above are geometry; this one reads the populations. Per throat of the
+ * pore network the mass that crossed it in the last streaming step, per pore whether it fills or drains, its throughput (and so its
+ * residence time), and per section of the lattice the net mass through it -- the Darcy flux. D2Q9 makes the answer exact: the
+ * network's edges are pairs of adjacent fluid nodes p < q with q one of p+1, p+ly-1, p+ly, p+ly+1, which are the four forward
+ * lattice directions 8, 5, 6, 7 (their opposites: 4, 1, 2, 3), and the state a download gives is post-streaming, so between two
+ * fluid nodes f[q][i] is what left p in the last streaming step and f[p][opp(i)] what left q. Their difference is the mass that
+ * crossed the edge, not an interpolated velocity. Every addend is turned into fixed point as the pore table's mass_q32 is, so every
+ * sum is an integer that no order of evaluation changes; a numpy restatement and a node-by-node loop reproduce everything exactly
+ * (tests/netflux_util.py).
+ * Input, as of the call: the map M, validated as lbmdem_clearance_compute validates it -- the handle's (lbmdem_download_obst's) or
+ * a caller's of that shape; f, lbmdem_download_f's [lx][ly][9], always the handle's; behind M the pore network at `merge`: the
+ * body and group planes and the link table of `level`. Node (x, y) has the index k = x*ly + y; fluid means M == -1. level 0: the
+ * regions are the bodies, in the order of lbmdem_download_network_bodies; level 1: the groups, in the order of
+ * lbmdem_download_network_groups. The links are lbmdem_download_network_links(level)'s, entry for entry.
+ * 1. Edge quantum. For adjacent fluid nodes p < q with q = p + e_i, i in 8, 5, 6, 7 (offsets +1, +ly-1, +ly, +ly+1, inside the
+ *    lattice as the network's rule 3 says): phi = f[q][i] - f[p][opp(i)], one IEEE double subtraction, and
+ *    Q(p, q) = (long long) rint(phi * 4294967296.0) when phi is finite and |phi| < 2^20; otherwise Q = 0 and the edge is
+ *    UNACCUMULATED (the pore table's rule for mass_q32). Q(q, p) = -Q(p, q).
+ * 2. Per link, lbmdem_netflux_link, over the link's edges (those whose ends lie in the two regions): flux_q32, Q oriented from
+ *    region lo to region hi, +Q(p, q) when p is in lo and -Q(p, q) when p is in hi; exchange_q32, the sum of |Q| -- against
+ *    |flux_q32| it shows counterflow within one throat --; edges, their number, which equals the network link's edges.
+ * 3. Per region, lbmdem_netflux_region: mass_q32, the sum over the region's nodes of the pore table's rint(rho * 2^32), rho =
+ *    f0 + f1 + ... + f8 in that order, under the same finite / 2^20 rule (a node left out is an UNACCUMULATED NODE); net_q32, the
+ *    inflow through the region's links, +flux where the region is hi and -flux where it is lo; through_q32, the sum of |flux_q32|
+ *    over the region's links: with net == 0 half of it is the throughput and mass / (through / 2) the residence time in fluid
+ *    steps. All are wrapping 64-bit integers, as numpy adds them.
+ * 4. Section profiles, over ALL edges of adjacent fluid nodes, of one region or not. col[x], x = 0 .. lx-2: the sum of Q(p, q)
+ *    over the edges with p in row x and q in row x+1 (three offsets), the net mass through that section towards +x in the last
+ *    streaming step. row[y], y = 0 .. ly-2: the same towards +y between columns y and y+1: +Q from the offsets +1 and +ly+1 with p
+ *    in column y, -Q from the offset +ly-1 with p in column y+1. Divided by 2^32 and by the section's length (ly or lx nodes) it is
+ *    the superficial (Darcy) flux in lattice units, a density times a lattice velocity; times rho_moy * c it is kg / (m^2 s), as the
+ *    flow-fields block converts a velocity by c and a density by rho_moy.
+ * 5. counts10, in order: fluid_nodes; regions; links; edges, all adjacent fluid pairs; ridge_edges, those between different
+ *    regions (the network's body_edges or group_edges); unaccumulated_edges; unaccumulated_nodes; flowing_links, those with
+ *    flux_q32 != 0; strongest_link, the index of the largest |flux_q32|, the smallest among equals, -1 without a link;
+ *    largest_imbalance, the largest |net_q32| over the regions, 0 without one.
+ * Identities: net_q32 summed over the regions is 0; sum(link.edges) == ridge_edges; net_q32[r] equals the node-by-node sum, over
+ * the region's nodes and their 8 neighbours in another region, of Q(q -> p); for every row x the sum over its fluid nodes and
+ * their 8 fluid neighbours of Q(q -> p) equals col[x-1] - col[x], with col[-1] = col[lx-1] = 0, and likewise for row; with every
+ * population of a direction equal across the lattice and to that of the opposite direction (a fluid at rest) every output but
+ * mass_q32 and the counts of nodes and edges is 0.
+ * On the device (lbm_netflux.hip), on the handle's stream, single launches: the network first where it is needed -- with map ==
+ * NULL and a network result of the handle's map, made with the same merge, that its guard still calls valid, the planes and
+ * tables are reused; otherwise lbmdem_network_compute(map, merge, max_edges 0) runs, and its readers are valid afterwards as if
+ * the caller had called it. Then per body number the first link of its run (the table ascends by (lo, hi)); one pass over the
+ * lattice that reads every node's region and, where it is fluid, its nine populations once, 64 lanes along y marching along x
+ * with the row in front in registers; the link of a ridge edge by a binary search of its lo's run; one lane per link and region
+ * for the rest. Integer atomics only. The profiles come from the handle's pool with the first call, the tables grow with the
+ * network's counts.
+ *   lbmdem_netflux_compute          the compute; map NULL: the handle's. counts10. A refused compute leaves no result.
+ *                                   Synchronises; changes nothing a later step reads.
+ *   lbmdem_download_netflux_links, lbmdem_download_netflux_regions   the tables, aligned with lbmdem_download_network_links(level)
+ *                                   and with lbmdem_download_network_bodies (level 0) or _groups (level 1). Sized as
+ *                                   lbmdem_download_throats is: cap = 0 reports *count, a short buffer is refused ("%s: there are
+ *                                   %ld links (regions), the buffer holds %ld") with *count set and nothing written
+ *   lbmdem_download_netflux_profile col[lx - 1] and row[ly - 1]; either may be NULL, not both
+ *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_netflux_compute has been made for the map and populations as
+ *   they are now", until a compute has been made, after a refused compute, after a fluid step, a rasterisation, lbmdem_upload_f or
+ *   a grain upload, and after a later lbmdem_network_compute (the tables the results are aligned with are gone).
+ *   lbmdem_write_netflux_files      host only, no handle, no device. In <dir>: netflux_links%.6i.dat -- "# lx %d ly %d n %d merge
+ *                                   %d level %d\n", "# lo hi edges saddle flux_q32 exchange_q32\n", then per link "%d %d %ld %d %ld
+ *                                   %ld\n"; netflux_regions%.6i.dat -- the same first line, "# region body nodes mass_q32 net_q32
+ *                                   through_q32\n", then per region "%ld %d %ld %ld %ld %ld\n", body the region's (root) body number
+ *                                   and nodes its node count; netflux_profile%.6i.dat -- the same first line, "# axis index
+ *                                   flux_q32\n", then "x %d %ld\n" per col[x] and "y %d %ld\n" per row[y]; netflux.data -- one line
+ *                                   appended, "%le" of t and " %ld" of each of the ten counts; when the file is created, first the
+ *                                   line "# t fluid_nodes regions links edges ridge_edges unaccumulated_edges unaccumulated_nodes
+ *                                   flowing_links strongest_link largest_imbalance". It checks fopen ("cannot open"); refused before
+ *                                   anything is written: merge < -1, level outside 0 and 1, links whose pairs do not ascend, a
+ *                                   link whose edges differ between the two tables, regions whose bodies do not ascend, a
+ *                                   negative node count. The tables may be NULL when their count is 0.
+ *   lbmdem_write_netflux            the compute on the handle's map, the downloads, then that formatter with t = nbsteps * dt
+ *   lbmdem_set_netflux_output       on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_netflux(dir, nFile, merge, level)
+ *                                   at every DEM event, behind the network files. Off by default; a checkpoint does not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL, "<function>: " and: "level must be 0 (between bodies) or 1 (between groups) (%d)";
+ * "merge must be -1 (no merging) or a difference of radii >= 0 (%d)"; "a lattice of %d x %d nodes has a side above %d: the squared
+ * distances of the network underneath are 32-bit integers"; "map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d)
+ * nor the wall (%d)". Also: null arguments; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the
+ * setting on); the single-precision library (the host-only formatter exists there too); a directory that cannot be written. */
+typedef struct lbmdem_netflux_link {
+  long flux_q32, exchange_q32, edges;
+} lbmdem_netflux_link;
+typedef struct lbmdem_netflux_region {
+  long mass_q32, net_q32, through_q32;
+} lbmdem_netflux_region;
+#define LBMDEM_NETFLUX_COUNTS 10
+int lbmdem_netflux_compute(lbmdem_handle* h, const int* map /* NULL: the handle's */, int merge, int level, long* counts10);
+int lbmdem_download_netflux_links(lbmdem_handle* h, lbmdem_netflux_link* out, long cap, long* count);
+int lbmdem_download_netflux_regions(lbmdem_handle* h, lbmdem_netflux_region* out, long cap, long* count);
+int lbmdem_download_netflux_profile(lbmdem_handle* h, long* col /* lx - 1 */, long* row /* ly - 1 */);   /* either may be NULL, not both */
+int lbmdem_write_netflux(lbmdem_handle* h, const char* dir, int nfile, int merge, int level);
+int lbmdem_set_netflux_output(lbmdem_handle* h, int on, int merge, int level);   /* 0: off (default) */
+int lbmdem_write_netflux_files(const char* dir, int nfile, int lx, int ly, int n, int merge, int level, const lbmdem_net_link* links,
+                               const lbmdem_netflux_link* flux, long nlinks, const int* region_body, const long* region_nodes,
+                               const lbmdem_netflux_region* regions, long nregions, const long* col, const long* row,
+                               const long* counts10, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
