@@ -262,6 +262,15 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_netflux_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.lbmdem_write_netflux_files.argtypes = ([C.c_char_p] + [C.c_int] * 6 + [C.c_void_p] * 2 + [C.c_long] + [C.c_void_p] * 3 + [C.c_long] +
                                              [C.c_void_p] * 3 + [C.c_double])
+    L.lbmdem_netsolve_compute.argtypes = ([C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_double, C.c_int, C.c_void_p,
+                                                                                  C.c_void_p])
+    L.lbmdem_download_netsolve_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_download_netsolve_links.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_long)]
+    L.lbmdem_netsolve_rounds.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.lbmdem_write_netsolve.argtypes = [C.c_void_p, C.c_char_p] + [C.c_int] * 6 + [C.c_double, C.c_int]
+    L.lbmdem_set_netsolve_output.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_int]
+    L.lbmdem_write_netsolve_files.argtypes = ([C.c_char_p] + [C.c_int] * 9 + [C.c_void_p, C.c_long] * 4 + [C.c_void_p, C.c_void_p,
+                                                                                                            C.c_double])
     L.lbmdem_coarse_grid.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lbmdem_coarse_fields.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.POINTER(C.c_long), C.c_void_p]
     L.lbmdem_write_coarse.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
@@ -750,6 +759,41 @@ def write_netflux_files(directory, nFile, lx, ly, n, merge, level, links, flux, 
         os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(merge), int(level), _vp(li) if len(li) else None,
         _vp(fx) if len(fx) else None, len(li), _vp(rb) if len(rb) else None, _vp(rn) if len(rn) else None,
         _vp(rg) if len(rg) else None, len(rg), _vp(co), _vp(ro), _vp(cnt), float(t)))
+
+
+# network pressures (LbmDem.netsolve): struct lbmdem_netsolve_region (24 bytes) and lbmdem_netsolve_link (16), aligned with
+# network_bodies() (level 0) or network_groups() (level 1) and with network_links(level); the flag bits; the names of the ten counts
+# and of the four sums
+NETSOLVE_REGION_DTYPE = np.dtype([("p", np.float64), ("net", np.float64), ("flags", np.int32), ("degree", np.int32)])
+NETSOLVE_LINK_DTYPE = np.dtype([("g", np.float64), ("q", np.float64)])
+NETSOLVE_INLET, NETSOLVE_OUTLET, NETSOLVE_SHORTED = 1, 2, 4
+NETSOLVE_COUNTERS = ("regions", "links", "inlet_regions", "outlet_regions", "shorted_regions", "free_regions", "iterations", "status",
+                     "flowing_links", "strongest_link")
+NETSOLVE_SUMS = ("Q_in", "Q_out", "rz0", "rz")
+
+
+def write_netsolve_files(directory, nFile, lx, ly, n, merge, level, frm, band, to, links, solved, region_body, regions, counts, sums, t,
+                         precision="f64"):
+    """netsolve_regions%.6i.dat, netsolve_links%.6i.dat and one appended line of netsolve.data (include/lbmdem_hip.h spells the
+    three formats out) from the network's links of the level (NET_LINK_DTYPE) and their solution (NETSOLVE_LINK_DTYPE), per region
+    its (root) body number and its record (NETSOLVE_REGION_DTYPE), the ten counts and the four sums (dicts of NETSOLVE_COUNTERS
+    and NETSOLVE_SUMS, or sequences) and the time of the line; n: the grain count of the first lines. Host only."""
+    li = np.ascontiguousarray(links, dtype=NET_LINK_DTYPE).reshape(-1)
+    so = np.ascontiguousarray(solved, dtype=NETSOLVE_LINK_DTYPE).reshape(-1)
+    rb = np.ascontiguousarray(region_body, dtype=np.int32).reshape(-1)
+    rg = np.ascontiguousarray(regions, dtype=NETSOLVE_REGION_DTYPE).reshape(-1)
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in NETSOLVE_COUNTERS]
+    if isinstance(sums, dict):
+        sums = [sums[k] for k in NETSOLVE_SUMS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    sm = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+    if len(cnt) != len(NETSOLVE_COUNTERS) or len(sm) != len(NETSOLVE_SUMS):
+        raise LbmDemError(-1, "write_netsolve_files: ten counts and four sums")
+    _chk(load_library(precision).lbmdem_write_netsolve_files(
+        os.fsencode(directory), int(nFile), int(lx), int(ly), int(n), int(merge), int(level), int(frm), int(band), int(to),
+        _vp(li) if len(li) else None, len(li), _vp(so) if len(so) else None, len(so), _vp(rb) if len(rb) else None, len(rb),
+        _vp(rg) if len(rg) else None, len(rg), _vp(cnt), _vp(sm), float(t)))
 
 
 # struct lbmdem_coarse_cell: one cell of the coarse-grained fields (LbmDem.coarse_fields), 25 doubles
@@ -1825,6 +1869,66 @@ class LbmDem:
     def set_netflux_output(self, on=True, merge=-1, level=0):
         """run_scene writes the pore flux files at every DEM event, behind the network files"""
         _chk(self._L.lbmdem_set_netflux_output(self._h, 1 if on else 0, int(merge), int(level)))
+
+    # network pressures: the pore network as a resistor network between an inlet and an outlet side (include/lbmdem_hip.h)
+    def netsolve(self, frm, band, to, merge=-1, level=0, model=0, g=None, rtol=1e-8, max_iter=0, map=None):
+        """pressures and flows of the pore network at `merge` (level 0: the bodies, 1: the groups) of the handle's map -- or of
+        `map`, (lx, ly) ints as clearance() takes them -- with the regions within `band` nodes of the sides `frm` (SIDE_B | SIDE_T |
+        SIDE_L | SIDE_R) held at p = 1 and those of `to` at p = 0: a Jacobi-preconditioned conjugate gradient to the relative
+        residual `rtol`, at most `max_iter` iterations (0: the number of free regions, at most 100 000). model 0: the conductance of
+        a link from its saddle (plane Poiseuille); model 1: `g`, one positive double per link of network_links(level). Runs
+        network() first where its result at this merge is not there -> (dict of NETSOLVE_COUNTERS, dict of NETSOLVE_SUMS)"""
+        c = np.zeros(len(NETSOLVE_COUNTERS), np.int64)
+        sm = np.zeros(len(NETSOLVE_SUMS), np.float64)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, dtype=np.int32)
+            if m.shape != (self.lx, self.ly):
+                raise LbmDemError(-1, "netsolve: a map of shape (lx, ly)")
+        gu = None if g is None else np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+        _chk(self._L.lbmdem_netsolve_compute(self._h, None if m is None else _vp(m), int(merge), int(level), int(frm), int(band), int(to),
+                                             int(model), None if gu is None else _vp(gu), float(rtol), int(max_iter), _vp(c), _vp(sm)))
+        counts = dict(zip(NETSOLVE_COUNTERS, (int(v) for v in c)))
+        sums = dict(zip(NETSOLVE_SUMS, (float(v) for v in sm)))
+        self._netsolve_last = (int(frm), int(to), sums["Q_in"])
+        return counts, sums
+
+    def netsolve_regions(self):
+        """structured array of NETSOLVE_REGION_DTYPE, entry for entry next to network_bodies() (level 0) or network_groups() (1)"""
+        return self._drainage_table(self._L.lbmdem_download_netsolve_regions, NETSOLVE_REGION_DTYPE)
+
+    def netsolve_links(self):
+        """structured array of NETSOLVE_LINK_DTYPE, entry for entry next to network_links(level) of the last netsolve()"""
+        return self._drainage_table(self._L.lbmdem_download_netsolve_links, NETSOLVE_LINK_DTYPE)
+
+    def netsolve_rounds(self):
+        """the launches the iteration of the last netsolve() took: two per iteration enqueued, in whole batches"""
+        r = C.c_int(0)
+        _chk(self._L.lbmdem_netsolve_rounds(self._h, C.byref(r)))
+        return r.value
+
+    def netsolve_permeability(self):
+        """Q_in * L / W of the last netsolve(): L the lattice's extent along the flow, W across it, in nodes; in units of the
+        conductance model (model 0: node spacings squared at unit viscosity). Only for frm / to one pair of opposite sides."""
+        last = getattr(self, "_netsolve_last", None)
+        if last is None:
+            raise ValueError("netsolve_permeability: no netsolve() has been made")
+        frm, to, q_in = last
+        if (frm, to) in ((SIDE_B, SIDE_T), (SIDE_T, SIDE_B)):
+            return q_in * self.ly / self.lx
+        if (frm, to) in ((SIDE_L, SIDE_R), (SIDE_R, SIDE_L)):
+            return q_in * self.lx / self.ly
+        raise ValueError("netsolve_permeability: frm and to must be one pair of opposite sides (%d, %d)" % (frm, to))
+
+    def write_netsolve(self, directory=".", nFile=0, frm=SIDE_T, band=1, to=SIDE_B, merge=-1, level=0, rtol=1e-8, max_iter=0):
+        """netsolve_regions%.6i.dat, netsolve_links%.6i.dat and a line of netsolve.data of the map as it is now (model 0)"""
+        _chk(self._L.lbmdem_write_netsolve(self._h, os.fsencode(directory), int(nFile), int(merge), int(level), int(frm), int(band),
+                                           int(to), float(rtol), int(max_iter)))
+
+    def set_netsolve_output(self, on=True, frm=SIDE_T, band=1, to=SIDE_B, merge=-1, level=0, rtol=1e-8, max_iter=0):
+        """run_scene writes the network pressure files at every DEM event, behind the pore flux files"""
+        _chk(self._L.lbmdem_set_netsolve_output(self._h, 1 if on else 0, int(merge), int(level), int(frm), int(band), int(to),
+                                                float(rtol), int(max_iter)))
 
     # coarse-grained fields: per cell of cw x ch nodes the sums of fluid, grains and contacts (include/lbmdem_hip.h)
     def coarse_fields(self, cw, ch):

@@ -528,6 +528,41 @@ struct lbmdem_handle {
     long nlinks = 0, nregions = 0;        // of the last compute
     int merge = -1, level = 0;
   } nfx;
+  // Network pressures (lbm_netsolve.hip): the pore network of `level` as a resistor network between the regions on an inlet side
+  // (p = 1) and those on an outlet side (p = 0), solved by a Jacobi-preconditioned conjugate gradient whose every operation the
+  // header spells out. nsv: the words allocated by the first lbmdem_netsolve_compute, everything else grown with the network's
+  // counts, freed with the handle. The kernels read net.body or net.group, the tables of the level and write here only. Valid
+  // under the network's guard and while net.gen is the one it was made over. netsolve_*: lbmdem_set_netsolve_output.
+  bool netsolve_output = false;
+  int netsolve_merge = -1, netsolve_level = 0, netsolve_from = 0, netsolve_band = 1, netsolve_to = 0, netsolve_max_iter = 0;
+  double netsolve_rtol = 1e-8;
+  struct NetsolveStage {
+    bool valid = false;
+    long long seq = -1, moved = -1, fluid = -1;
+    unsigned long long gen = 0;           // net.gen of the network result underneath
+    unsigned long long* words = nullptr;  // [NS_WORDS] status, iterations and the counts (null: nothing allocated yet)
+    double* scal = nullptr;               // [NS_SCAL] rz0, the last rz, rz of the iteration (two), Q_in, Q_out
+    int* lints = nullptr;                 // [7][L'] per link: the two regions, the sort's three arrays; the rows' partners (2 L')
+    long lint_cap = 0;
+    double* ldbl = nullptr;               // [4][L'] per link: g; the rows' g (2 L'); the caller's g
+    long ldbl_cap = 0;
+    int* rints = nullptr;                 // [3][R'] per region: the two firsts of its row, its flags
+    long rint_cap = 0;
+    double* rdbl = nullptr;               // [8][R'] per region: diag, b, x, r, z, q and d twice
+    long rdbl_cap = 0;
+    unsigned* bits = nullptr;             // [bits_cap] by body number: an inlet node 1, an outlet node 2
+    long bits_cap = 0;
+    double* parts = nullptr;              // [4][P'] per block of 256 regions: its part of dq, of dot(r, z), of Q_in, of Q_out
+    long part_cap = 0;
+    lbmdem_netsolve_link* links = nullptr;      // [link_cap] aligned with net.links[level]
+    long link_cap = 0;
+    lbmdem_netsolve_region* regions = nullptr;  // [region_cap] aligned with net.bodies or net.groups
+    long region_cap = 0;
+    char* tmp = nullptr;                  // hipcub's scratch: the sort
+    long tmp_bytes = 0;
+    long nlinks = 0, nregions = 0;        // of the last compute
+    int rounds = 0;                       // launches of the iteration in the last compute
+  } nsv;
   // Coarse-grained fields (lbm_coarse.hip). coarse_cw, coarse_ch: lbmdem_set_coarse_output's cell size, 0 x 0 is off. cg: scratch,
   // allocated by the first export, grown when a finer grid needs more, freed with the handle.
   int coarse_cw = 0, coarse_ch = 0;

@@ -207,6 +207,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
       if (!comm && h->clearance_output) RC_TRY(lbmdem_write_clearance(h, dir, nfile, h->clearance_plane));   // lbmdem_set_clearance_output
       if (!comm && h->network_output) RC_TRY(lbmdem_write_network(h, dir, nfile, h->network_merge, h->network_plane));   // lbmdem_set_network_output
       if (!comm && h->netflux_output) RC_TRY(lbmdem_write_netflux(h, dir, nfile, h->netflux_merge, h->netflux_level));   // lbmdem_set_netflux_output
+      if (!comm && h->netsolve_output) RC_TRY(lbmdem_write_netsolve(h, dir, nfile, h->netsolve_merge, h->netsolve_level, h->netsolve_from, h->netsolve_band, h->netsolve_to, h->netsolve_rtol, h->netsolve_max_iter));   // lbmdem_set_netsolve_output
       if (!comm && h->drainage_output) RC_TRY(lbmdem_write_drainage(h, dir, nfile, h->drainage_from, h->drainage_band, h->drainage_to, h->drainage_plane));   // lbmdem_set_drainage_output
       if (!comm && h->geodesic_output) RC_TRY(lbmdem_write_geodesic(h, dir, nfile, h->geodesic_from, h->geodesic_band, h->geodesic_to, h->geodesic_conn, h->geodesic_min_d2, h->geodesic_plane));   // lbmdem_set_geodesic_output
       if (!comm && h->coarse_cw > 0) RC_TRY(lbmdem_write_coarse(h, dir, nfile, h->coarse_cw, h->coarse_ch));   // lbmdem_set_coarse_output

@@ -88,6 +88,7 @@ int lbmdem_dist_enable(lbmdem_handle* h, int margin_rows) try {
   if (h->clearance_output) return fail(LBMDEM_EINVAL, "the pore clearance analysis is not available with distributed grains (lbmdem_set_clearance_output(h, 0, 0) first)");
   if (h->network_output) return fail(LBMDEM_EINVAL, "the pore network analysis is not available with distributed grains (lbmdem_set_network_output(h, 0, 0, 0) first)");
   if (h->netflux_output) return fail(LBMDEM_EINVAL, "the pore flux analysis is not available with distributed grains (lbmdem_set_netflux_output(h, 0, 0, 0) first)");
+  if (h->netsolve_output) return fail(LBMDEM_EINVAL, "the network pressure analysis is not available with distributed grains (lbmdem_set_netsolve_output(h, 0, 0, 0, 0, 0, 0, 0., 0) first)");
   if (h->drainage_output) return fail(LBMDEM_EINVAL, "the drainage analysis is not available with distributed grains (lbmdem_set_drainage_output(h, 0, 0, 0, 0, 0) first)");
   if (h->geodesic_output) return fail(LBMDEM_EINVAL, "the geodesic analysis is not available with distributed grains (lbmdem_set_geodesic_output(h, 0, 0, 0, 0, 0, 0, 0) first)");
   if (h->coarse_cw > 0) return fail(LBMDEM_EINVAL, "the coarse-grained fields export is not available with distributed grains (lbmdem_set_coarse_output(h, 0, 0) first)");

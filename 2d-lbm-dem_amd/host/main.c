@@ -79,6 +79,13 @@
  * within M (LEVEL 1; M default -1, no merging), in netflux_links%.6i.dat, per pore its mass, net inflow and throughput in
  * netflux_regions%.6i.dat, the net mass through every section of the lattice in netflux_profile%.6i.dat and a line of
  * netflux.data. Single GPU only.
+ * --netsolve FROM --netsolve-to TO [--netsolve-band N] [--netsolve-level L] [--netsolve-merge M] [--netsolve-rtol R]
+ * [--netsolve-max-iter K]: the network pressures of every DEM event (lbmdem_set_netsolve_output): the pore network as a resistor
+ * network, the regions within N nodes (default 1) of the sides FROM, letters out of BTLR, at pressure 1 and those of TO at 0, a
+ * link's conductance from its saddle, solved to the relative residual R (default 1e-8) in at most K iterations (default 0: the
+ * number of free regions) between the pore bodies (L 0, the default) or the groups merged within M (L 1; M default -1) -- per
+ * region its pressure and net inflow in netsolve_regions%.6i.dat, per link its conductance and flow in netsolve_links%.6i.dat,
+ * the totals in a line of netsolve.data. Single GPU only.
  * --drainage FROM [--drainage-to TO] [--drainage-band N] [--drainage-plane]: the drainage analysis of every DEM event
  * (lbmdem_set_drainage_output): the largest disc that reaches each pore from the sides FROM, letters out of BTLR, through a
  * reservoir N nodes deep (default 1) -- the intrusion curve next to the pore-size distribution in drainage_curve%.6i.dat, per pore
@@ -139,6 +146,9 @@ static int g_pores = 0, g_pores_conn = 8, g_pores_plane = 0;   /* --pores [4|8],
 static int g_clearance = 0, g_clearance_plane = 0;   /* --clearance, --clearance-plane */
 static int g_network = 0, g_network_merge = -1, g_network_plane = 0;   /* --network [MERGE], --network-plane */
 static int g_netflux = 0, g_netflux_level = 0, g_netflux_merge = -1, g_netflux_merge_set = 0;   /* --netflux [LEVEL], --netflux-merge M */
+static int g_netsolve = 0, g_netsolve_to = 0, g_netsolve_band = 1, g_netsolve_level = 0, g_netsolve_merge = -1, g_netsolve_max_iter = 0;   /* --netsolve FROM, --netsolve-to TO, ... */
+static double g_netsolve_rtol = 1e-8;
+static int g_netsolve_opts = 0;
 static int g_drainage = 0, g_drainage_to = 0, g_drainage_band = 1, g_drainage_plane = 0;   /* --drainage FROM, --drainage-to TO, --drainage-band N, --drainage-plane */
 static int g_drainage_to_set = 0;
 static int g_geodesic = 0, g_geodesic_to = 0, g_geodesic_band = 1, g_geodesic_conn = 8, g_geodesic_min_d2 = 0, g_geodesic_plane = 0;   /* --geodesic FROM, --geodesic-to TO, --geodesic-band N, --geodesic-conn 4|8, --geodesic-min-d2 D, --geodesic-plane */
@@ -351,6 +361,31 @@ int main(int argc, char** argv) {
       if (a + 1 >= argc || (!is_count(argv[a + 1]) && strcmp(argv[a + 1], "-1"))) { fprintf(stderr, "--netflux-merge M: -1 (no merging) or a difference of radii, 0 or more\n"); return EXIT_FAILURE; }
       g_netflux_merge = atoi(argv[a + 1]); g_netflux_merge_set = 1;
     }
+    if (!strcmp(argv[a], "--netsolve") || !strcmp(argv[a], "--netsolve-to")) {
+      const int mask = a + 1 < argc ? side_mask(argv[a + 1]) : 0;
+      if (mask <= 0) { fprintf(stderr, "%s SIDES: letters out of BTLR, at least one\n", argv[a]); return EXIT_FAILURE; }
+      if (!strcmp(argv[a], "--netsolve")) g_netsolve = mask; else { g_netsolve_to = mask; g_netsolve_opts = 1; }
+    }
+    if (!strcmp(argv[a], "--netsolve-band")) {
+      if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) < 1) { fprintf(stderr, "--netsolve-band N: the depth of the inlet and outlet regions in nodes, at least 1\n"); return EXIT_FAILURE; }
+      g_netsolve_band = atoi(argv[a + 1]); g_netsolve_opts = 1;
+    }
+    if (!strcmp(argv[a], "--netsolve-level")) {
+      if (a + 1 >= argc || !is_count(argv[a + 1]) || atoi(argv[a + 1]) > 1) { fprintf(stderr, "--netsolve-level L: 0 between the pore bodies, 1 between the merged groups\n"); return EXIT_FAILURE; }
+      g_netsolve_level = atoi(argv[a + 1]); g_netsolve_opts = 1;
+    }
+    if (!strcmp(argv[a], "--netsolve-merge")) {
+      if (a + 1 >= argc || (!is_count(argv[a + 1]) && strcmp(argv[a + 1], "-1"))) { fprintf(stderr, "--netsolve-merge M: -1 (no merging) or a difference of radii, 0 or more\n"); return EXIT_FAILURE; }
+      g_netsolve_merge = atoi(argv[a + 1]); g_netsolve_opts = 1;
+    }
+    if (!strcmp(argv[a], "--netsolve-rtol")) {
+      if (a + 1 >= argc || !(atof(argv[a + 1]) > 0.) || !(atof(argv[a + 1]) < 1.)) { fprintf(stderr, "--netsolve-rtol R: the relative residual to stop at, strictly between 0 and 1\n"); return EXIT_FAILURE; }
+      g_netsolve_rtol = atof(argv[a + 1]); g_netsolve_opts = 1;
+    }
+    if (!strcmp(argv[a], "--netsolve-max-iter")) {
+      if (a + 1 >= argc || !is_count(argv[a + 1])) { fprintf(stderr, "--netsolve-max-iter K: the most iterations, 0 for the number of free regions\n"); return EXIT_FAILURE; }
+      g_netsolve_max_iter = atoi(argv[a + 1]); g_netsolve_opts = 1;
+    }
     if (!strcmp(argv[a], "--drainage") || !strcmp(argv[a], "--drainage-to")) {
       const int mask = a + 1 < argc ? side_mask(argv[a + 1]) : 0;
       if (mask <= 0) { fprintf(stderr, "%s SIDES: letters out of BTLR, at least one\n", argv[a]); return EXIT_FAILURE; }
@@ -473,6 +508,10 @@ int main(int argc, char** argv) {
   if (g_netflux && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--netflux is a single-GPU mode (the pore flux analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_netflux && g_dry) { fprintf(stderr, "--netflux cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if (g_network && g_dry) { fprintf(stderr, "--network cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
+  if (g_netsolve_opts && !g_netsolve) { fprintf(stderr, "--netsolve-to, --netsolve-band, --netsolve-level, --netsolve-merge, --netsolve-rtol and --netsolve-max-iter need --netsolve FROM\n"); return EXIT_FAILURE; }
+  if (g_netsolve && !g_netsolve_to) { fprintf(stderr, "--netsolve FROM needs --netsolve-to TO\n"); return EXIT_FAILURE; }
+  if (g_netsolve && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--netsolve is a single-GPU mode (the network pressure analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_netsolve && g_dry) { fprintf(stderr, "--netsolve cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
   if ((g_drainage_plane || g_drainage_to_set || g_drainage_band != 1) && !g_drainage) { fprintf(stderr, "--drainage-to, --drainage-band and --drainage-plane need --drainage FROM\n"); return EXIT_FAILURE; }
   if (g_drainage && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--drainage is a single-GPU mode (the drainage analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_drainage && g_dry) { fprintf(stderr, "--drainage cannot be combined with --dry (there is no fluid)\n"); return EXIT_FAILURE; }
@@ -650,6 +689,7 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--network-plane")) {}
     else if (!strcmp(argv[a], "--netflux")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--netflux-merge") && a + 1 < argc) ++a;
+    else if ((!strcmp(argv[a], "--netsolve") || !strcmp(argv[a], "--netsolve-to") || !strcmp(argv[a], "--netsolve-band") || !strcmp(argv[a], "--netsolve-level") || !strcmp(argv[a], "--netsolve-merge") || !strcmp(argv[a], "--netsolve-rtol") || !strcmp(argv[a], "--netsolve-max-iter")) && a + 1 < argc) ++a;
     else if ((!strcmp(argv[a], "--drainage") || !strcmp(argv[a], "--drainage-to") || !strcmp(argv[a], "--drainage-band")) && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--drainage-plane")) {}
     else if ((!strcmp(argv[a], "--geodesic") || !strcmp(argv[a], "--geodesic-to") || !strcmp(argv[a], "--geodesic-band") || !strcmp(argv[a], "--geodesic-conn") || !strcmp(argv[a], "--geodesic-min-d2")) && a + 1 < argc) ++a;
@@ -686,7 +726,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --netflux [LEVEL] --netflux-merge M --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --geodesic FROM --geodesic-to TO --geodesic-band N --geodesic-conn 4|8 --geodesic-min-d2 D --geodesic-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --netflux [LEVEL] --netflux-merge M --netsolve FROM --netsolve-to TO --netsolve-band N --netsolve-level L --netsolve-merge M --netsolve-rtol R --netsolve-max-iter K --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --geodesic FROM --geodesic-to TO --geodesic-band N --geodesic-conn 4|8 --geodesic-min-d2 D --geodesic-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -768,6 +808,7 @@ static int run(int argc, char** argv) {
   if (g_clearance) DIE(lbmdem_set_clearance_output(h, 1, g_clearance_plane), "set_clearance_output");
   if (g_network) DIE(lbmdem_set_network_output(h, 1, g_network_merge, g_network_plane), "set_network_output");
   if (g_netflux) DIE(lbmdem_set_netflux_output(h, 1, g_netflux_merge, g_netflux_level), "set_netflux_output");
+  if (g_netsolve) DIE(lbmdem_set_netsolve_output(h, 1, g_netsolve_merge, g_netsolve_level, g_netsolve, g_netsolve_band, g_netsolve_to, g_netsolve_rtol, g_netsolve_max_iter), "set_netsolve_output");
   if (g_drainage) DIE(lbmdem_set_drainage_output(h, 1, g_drainage, g_drainage_band, g_drainage_to, g_drainage_plane), "set_drainage_output");
   if (g_geodesic) DIE(lbmdem_set_geodesic_output(h, 1, g_geodesic, g_geodesic_band, g_geodesic_to, g_geodesic_conn, g_geodesic_min_d2, g_geodesic_plane), "set_geodesic_output");
   if (g_flow) DIE(lbmdem_set_flow_output(h, 1), "set_flow_output");

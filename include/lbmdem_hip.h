@@ -1311,6 +1311,117 @@ int lbmdem_write_netflux_files(const char* dir, int nfile, int lx, int ly, int n
                                const lbmdem_netflux_link* flux, long nlinks, const int* region_body, const long* region_nodes,
                                const lbmdem_netflux_region* regions, long nregions, const long* col, const long* row,
                                const long* counts10, double t);   /* host only */
+/* Network pressures: what does the pore network predict for pressures and flows when a pressure difference is applied across it?
+ * Every link gets a conductance from its width, the regions on an inlet side are held at p = 1, those on an outlet side at p = 0,
+ * Kirchhoff's equations are solved for the others, and the flow per link and the total are read off: the permeability of the
+ * packing from its geometry alone, and per link the prediction that sits next to the pore fluxes' measured flux_q32. The solver is
+ * iterative and in floating point, so the contract is the arithmetic itself: every operation below is one IEEE double operation,
+ * rounded before the next (the build has -ffp-contract=off), in the order stated; a numpy restatement reproduces every double on
+ * the bits (tests/netsolve_util.py), and nothing depends on the order anything happens in or on how the host batches launches.
+ * Input, as of the call: the map M, validated as lbmdem_clearance_compute validates it -- the handle's or a caller's of that
+ * shape; behind it the pore network at `merge`: the regions of `level` (0: the bodies, in the order of
+ * lbmdem_download_network_bodies; 1: the groups, in the order of lbmdem_download_network_groups) and the link table of that level,
+ * lbmdem_download_network_links(level)'s, entry for entry. R regions, Lk links; a link's lo and hi below are the places of its two
+ * regions in that order (at level 1 the ranks of its two root bodies).
+ * Parameters: from, band, to: the drainage block's side masks and REGION rule, from and to both in 1 .. 15, band >= 1; model, 0 or
+ * 1; g_user, Lk doubles when model == 1, else NULL; rtol, a double in (0, 1); max_iter >= 0, 0 meaning the number of free regions,
+ * at most 100 000 (the number of free regions is CG's bound in exact arithmetic).
+ * 1. Fixed regions. A region that holds a fluid node of from's REGION is an INLET, flags 1, p = 1.0; one that holds a fluid node of
+ *    to's REGION and no inlet node is an OUTLET, flags 2, p = 0.0; one with both is an inlet and carries 4 as well (SHORTED, flags
+ *    5); all others are FREE, flags 0.
+ * 2. Conductance g[l], double. Model 0, plane Poiseuille at unit viscosity: w = 2.0 * sqrt((double)saddle); len =
+ *    sqrt((double)(dx*dx + dy*dy)) with dx, dy the integer differences of the two regions' peak nodes (node / ly, node % ly: the
+ *    node of the body or group record); g = ((w*w)*w) / (12.0*len). Model 1: g[l] = g_user[l], refused unless every value is
+ *    finite and > 0 ("g_user[%ld] = %g: a conductance is finite and > 0" names the first offender).
+ * 3. Rows. The row of region a is its incident links in ascending link index -- ascending partner number, because the table
+ *    ascends by (lo, hi). diag[a]: the chain from +0.0 of g over the row. apply(v)[a] for a free a: diag[a]*v[a] - s, s the chain
+ *    from +0.0 over the row of g*v[partner]; apply(v) is 0 at fixed regions, and every vector below is exactly 0 there. b[a] for a
+ *    free a: the chain from +0.0 over the row of g where the partner is an inlet; 0 at fixed regions.
+ * 4. dot(u, v). t[a] = u[a]*v[a], padded with +0.0 to a multiple of 256; in every block of 256 consecutive entries, for s = 128, 64,
+ *    .., 1: t[i] = t[i] + t[i+s] for i < s, the block's value being t[0]; the block values, padded and reduced the same way, until
+ *    one value remains (0.0 without a region). At most 256^3 regions: three levels.
+ * 5. Jacobi-preconditioned CG from x = 0. r = b; z = r/diag where a is free and diag[a] > 0, else 0; d = z; rz0 = rz = dot(r, z);
+ *    tol2 = rtol*rtol. If rz0 == 0: no iteration, status 0. Iteration k = 1, 2, ..: q = apply(d); dq = dot(d, q); if dq is not
+ *    finite or <= 0: status 2, stop, x as it was (k - 1 iterations); alpha = rz/dq; x = x + alpha*d; r = r - alpha*q; z as above;
+ *    rzn = dot(r, z); if rzn <= tol2*rz0: status 0, stop; if k == max_iter: status 1, stop; beta = rzn/rz; d = z + beta*d;
+ *    rz = rzn. (With every g > 0 the matrix of the free regions is symmetric and diagonally dominant with a positive diagonal, and
+ *    d is non-zero while rz is: status 2 needs a rounding accident and has not been seen.)
+ * 6. Outputs. Per region lbmdem_netsolve_region: p, 1.0, 0.0 or x; net, the chain from +0.0 over the row of the flow INTO the
+ *    region, g*(p[partner] - p[a]); flags; degree, the length of the row. Per link lbmdem_netsolve_link: g, and q = g*(p[lo] -
+ *    p[hi]). sums4, doubles: Q_in, rule 4's reduction of -net over the inlets, +0.0 elsewhere; Q_out, the same of +net over the
+ *    outlets; rz0; the last dot(r, z) formed (rz0 without an iteration). counts10, in order: regions; links; inlet_regions;
+ *    outlet_regions; shorted_regions; free_regions; iterations; status; flowing_links (q != 0); strongest_link, the index of the
+ *    largest |q|, the smallest among equals, -1 without a link.
+ * Identities: fixed regions hold exactly 1.0 or 0.0; a region whose connected component of the network holds no inlet keeps
+ * p == 0.0 and its links q == 0.0 exactly -- b, r, z, d and q never leave 0 there; an empty inlet set is not an error: rz0 == 0,
+ * everything 0; from == to makes every fixed region a shorted inlet; Q_in and Q_out agree as far as the residual allows.
+ * Q_in * L / W, L and W the lattice's extents along and across the flow, is the permeability in units of the conductance model.
+ * On the device (lbm_netsolve.hip), on the handle's stream: the network first where it is needed -- the pore fluxes' rule: with
+ * map == NULL and a network result of the handle's map, made with the same merge, that its guard still calls valid, it is reused;
+ * otherwise lbmdem_network_compute(map, merge, max_edges 0) runs, and its readers are valid afterwards as if the caller had called
+ * it. Once per compute: per link its two regions and g; the rows by a stable radix sort of (hi, link) for the partners below a
+ * region and the table's own run for those above, every entry placed by two binary searches, no atomics; the flags by an integer
+ * atomic OR per node of the two REGIONs; diag and b by one lane per region, serial over its row. An iteration is two launches: in
+ * A every workgroup reduces the blocks' parts of rzn by rule 4 itself, makes the stop tests, forms d = z + beta*d for its own
+ * regions and on the fly for its rows' partners, q and its part of dq; in B every workgroup reduces the parts of dq, updates x, r,
+ * z and leaves its part of rzn. Every workgroup decides from the same bits; lane 0 of workgroup 0 publishes the status, behind
+ * which both kernels return at once; the host enqueues 16 iterations and then reads the status word. No workgroup waits for
+ * another, no floating-point atomics, no grid-wide barrier. Everything grows with the network's counts in the handle's pool.
+ *   lbmdem_netsolve_compute         the compute; map NULL: the handle's. counts10, sums4. A refused compute leaves no result.
+ *                                   Synchronises; changes nothing a later step reads.
+ *   lbmdem_download_netsolve_regions, lbmdem_download_netsolve_links   the tables, aligned with lbmdem_download_network_bodies
+ *                                   (level 0) or _groups (level 1) and with lbmdem_download_network_links(level). Sized as
+ *                                   lbmdem_download_throats is: cap = 0 reports *count, a short buffer is refused ("%s: there are
+ *                                   %ld regions (links), the buffer holds %ld") with *count set and nothing written
+ *   lbmdem_netsolve_rounds          the launches of the iteration in the last compute: two per iteration enqueued, whole batches
+ *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_netsolve_compute has been made for the map as it is now",
+ *   until a compute has been made, after a refused compute, after anything the network readers are refused after, and after a
+ *   later lbmdem_network_compute (the tables the results are aligned with are gone).
+ *   lbmdem_write_netsolve_files     host only, no handle, no device. In <dir>: netsolve_regions%.6i.dat -- "# lx %d ly %d n %d merge
+ *                                   %d level %d from %d band %d to %d\n", "# region body flags degree p net\n", then per region "%ld
+ *                                   %d %d %d %.17g %.17g\n", body the region's (root) body number; netsolve_links%.6i.dat -- the
+ *                                   same first line, "# lo hi saddle g q\n", then per link "%d %d %d %.17g %.17g\n", lo and hi as
+ *                                   the network's table has them; netsolve.data -- one line appended, "%le" of t, " %ld" of each
+ *                                   of the ten counts and " %.17g" of each of the four sums; when the file is created, first the
+ *                                   line "# t regions links inlet_regions outlet_regions shorted_regions free_regions iterations
+ *                                   status flowing_links strongest_link Q_in Q_out rz0 rz". It checks fopen ("cannot open");
+ *                                   refused before anything is written: merge, level, from, band or to outside their ranges,
+ *                                   tables whose lengths disagree, links whose pairs do not ascend, regions whose bodies do not
+ *                                   ascend, flags outside 0 .. 7. The tables may be NULL when their count is 0.
+ *   lbmdem_write_netsolve           the compute on the handle's map with model 0, the downloads, then that formatter with
+ *                                   t = nbsteps * dt
+ *   lbmdem_set_netsolve_output      on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_netsolve(dir, nFile, merge, level,
+ *                                   from, band, to, rtol, max_iter) at every DEM event, behind the pore flux files. Off by
+ *                                   default; a checkpoint does not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL, "<function>: " and: the pore fluxes' sentences for level, merge, the lattice's side
+ * and the map; the drainage block's for from and band; "to must be a mask of sides, B 1 | T 2 | L 4 | R 8, with at least one
+ * (%d)"; "model must be 0 (plane Poiseuille from the saddle) or 1 (the caller's g) (%d)"; "model 1 needs g_user, one conductance
+ * per link"; "g_user must be NULL with model 0"; "rtol must lie strictly between 0 and 1 (%g)"; "max_iter must not be negative, 0:
+ * the number of free regions (%d)"; more than 256^3 regions. Also: null arguments; a strip of a decomposition or distributed
+ * grains (and lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); a
+ * directory that cannot be written. */
+typedef struct lbmdem_netsolve_region {
+  double p, net;
+  int flags, degree;
+} lbmdem_netsolve_region;
+typedef struct lbmdem_netsolve_link {
+  double g, q;
+} lbmdem_netsolve_link;
+#define LBMDEM_NETSOLVE_COUNTS 10
+#define LBMDEM_NETSOLVE_SUMS 4
+int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map /* NULL: the handle's */, int merge, int level, int from, int band,
+                            int to, int model, const double* g_user, double rtol, int max_iter, long* counts10, double* sums4);
+int lbmdem_download_netsolve_regions(lbmdem_handle* h, lbmdem_netsolve_region* out, long cap, long* count);
+int lbmdem_download_netsolve_links(lbmdem_handle* h, lbmdem_netsolve_link* out, long cap, long* count);
+int lbmdem_netsolve_rounds(lbmdem_handle* h, int* rounds);
+int lbmdem_write_netsolve(lbmdem_handle* h, const char* dir, int nfile, int merge, int level, int from, int band, int to, double rtol,
+                          int max_iter);
+int lbmdem_set_netsolve_output(lbmdem_handle* h, int on, int merge, int level, int from, int band, int to, double rtol,
+                               int max_iter);   /* 0: off (default) */
+int lbmdem_write_netsolve_files(const char* dir, int nfile, int lx, int ly, int n, int merge, int level, int from, int band, int to,
+                                const lbmdem_net_link* links, long nlinks, const lbmdem_netsolve_link* solved, long nsolved,
+                                const int* region_body, long nbodies, const lbmdem_netsolve_region* regions, long nregions,
+                                const long* counts10, const double* sums4, double t);   /* host only */
 /* Coarse-grained fields: per cell of cw x ch lattice nodes the sums people plot -- solid fraction, grain momentum, kinetic energy,
  * coordination and moment tensor next to the fluid's mass, momentum and pore pressure over the SAME cells. The reference adds z, the
  * kinetic-energy terms and M11..M22 over the whole packing only (write_DEM, main.c:373-421); it has no routine for this, so the
