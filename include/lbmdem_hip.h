@@ -1272,8 +1272,10 @@ int lbmdem_write_geodesic_files(const char* dir, int nfile, int lx, int ly, int 
  *                                   %ld links (regions), the buffer holds %ld") with *count set and nothing written
  *   lbmdem_download_netflux_profile col[lx - 1] and row[ly - 1]; either may be NULL, not both
  *   These readers are refused, with LBMDEM_EINVAL and "%s: no lbmdem_netflux_compute has been made for the map and populations as
- *   they are now", until a compute has been made, after a refused compute, after a fluid step, a rasterisation, lbmdem_upload_f or
- *   a grain upload, and after a later lbmdem_network_compute (the tables the results are aligned with are gone).
+ *   they are now", until a compute has been made, after a refused compute, after anything the network readers are refused after
+ *   (any kind of step or sub-step -- a DEM sub-step alone included, as for every stage above, although it changes neither the map
+ *   nor f --, lbmdem_upload_f or a grain upload), and after a later lbmdem_network_compute, the caller's or one that another
+ *   stage's compute ran (the tables the results are aligned with are gone).
  *   lbmdem_write_netflux_files      host only, no handle, no device. In <dir>: netflux_links%.6i.dat -- "# lx %d ly %d n %d merge
  *                                   %d level %d\n", "# lo hi edges saddle flux_q32 exchange_q32\n", then per link "%d %d %ld %d %ld
  *                                   %ld\n"; netflux_regions%.6i.dat -- the same first line, "# region body nodes mass_q32 net_q32
