@@ -309,7 +309,7 @@ int cluster_words(lbmdem_handle* h, unsigned long long* w2) {
 
 int clusters_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
-  if (!h->contacts_valid || !h->cl.valid || h->cl.seq != h->substep_seq)
+  if (!h->contacts_valid || h->contacts_walls != h->walls_moved || !h->cl.valid || h->cl.seq != h->substep_seq)
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_cluster_compute has been made for the last table sub-step", who);
   return LBMDEM_OK;
 }

@@ -5,7 +5,8 @@
 // The per-contact values of a sub-step exist only in the registers of the sub-step kernels. They are re-derived here, with the
 // same device functions (dem_laws.h), from the state the LAST sub-step started from -- the other half of the kinematics ping-pong,
 // kin[1 - kcur] -- with that sub-step's pair list, wall flags, law and parameters (lbmdem_handle::contacts_P, kept when it was
-// launched). Nothing here is on the step path: the kernels only read the handle's state.
+// launched). A wall moved by hand since (lbmdem_move_walls) makes the export refuse: the handle's walls are then not the ones of
+// the records (lbmdem_handle::walls_moved). Nothing here is on the step path: the kernels only read the handle's state.
 //
 // Three steps on the handle's stream, the order fixed without atomics:
 //   k_contacts_count  one lane per entry of the symmetric list; a workgroup owns CT_GRAINS consecutive grains and therefore a
@@ -196,6 +197,10 @@ int contacts_job(lbmdem_handle* h, const char* who, ContactsJob* J) {
   if (!h->contacts_valid || !h->verlet_ok)
     return fail(LBMDEM_EINVAL, "%s: the last sub-step was no table sub-step, or the state it started from has been replaced since "
                                "(lbmdem_set_diagnostics(h, 1), or the sub-step that reaches a multiple of 4000)", who);
+  if (h->contacts_walls != h->walls_moved)
+    return fail(LBMDEM_EINVAL, "%s: a wall has been moved since the last table sub-step (lbmdem_move_walls): its records belong to "
+                               "walls the handle no longer has, and the next table sub-step (lbmdem_set_diagnostics(h, 1)) makes "
+                               "new ones", who);
   if (*h->ovf_host) return fail(LBMDEM_ENOMEM, "Verlet list overflow (more than %ld symmetric entries)", h->V.cap);
   *J = ContactsJob{};
   J->K = h->kin[1 - h->kcur];

@@ -278,7 +278,7 @@ int vo_rcut_of(double rc2, double* rcut) {
 int voronoi_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
   const auto& V = h->vo;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved)
+  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.walls != h->walls_moved)
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_voronoi_compute has been made for the grains where they are now", who);
   return LBMDEM_OK;
 }
@@ -392,7 +392,7 @@ int lbmdem_voronoi_compute(lbmdem_handle* h, long* counts8) try {
   }
   for (int k = 0; k < 8; ++k) counts8[k] = (long)w[k];
   V.nfaces = nfaces; V.rcut = rcut;
-  V.seq = h->substep_seq; V.moved = h->grains_moved;
+  V.seq = h->substep_seq; V.moved = h->grains_moved; V.walls = h->walls_moved;
   V.valid = true;
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)

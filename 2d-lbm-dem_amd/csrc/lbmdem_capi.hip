@@ -789,7 +789,9 @@ int lbmdem_lbm_step(lbmdem_handle* h) {
 int lbmdem_verlet_rebuild(lbmdem_handle* h) {
   CHECK_H(h);
   // VerletWall moves the right/top DEM walls: main.c:1555-1561
+  const WallBits before = wall_bits(h->cfg);
   verlet_wall_reset(h->cfg, h->nbsteps);
+  note_walls(h, before);
   return lbmdem_verlet_build_lists(h);
 }
 
@@ -868,7 +870,7 @@ int lbmdem_dem_substep(lbmdem_handle* h) {
   h->diag_valid = want_table;
   // the contact network export re-derives this sub-step's contacts from the state it started from: what it was launched with
   h->contacts_valid = want_table;
-  if (want_table) { h->contacts_film = film; h->contacts_P = P; }
+  if (want_table) { h->contacts_film = film; h->contacts_P = P; h->contacts_walls = h->walls_moved; }
   HIP_TRY(hipGetLastError());
   h->kcur = 1 - h->kcur;
   h->nbsteps++;
@@ -1169,6 +1171,7 @@ static ChainSnap chain_snapshot(const lbmdem_handle* h) {
 }
 
 static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
+  const WallBits before = wall_bits(h->cfg);
   h->fcur = s.fcur; h->ocur = s.ocur; h->kcur = s.kcur;
   for (int b = 0; b < 2; ++b) { h->snap_cur[b] = s.snap_cur[b]; h->snap_ok[b] = s.snap_ok[b]; h->chg_state[b] = s.chg_state[b]; }
   h->list_generation = s.list_generation;
@@ -1179,6 +1182,8 @@ static void chain_restore(lbmdem_handle* h, const ChainSnap& s) {
   h->fs.gathered = s.gathered; h->fs.gathered_next = s.gathered_next;
   h->nbsteps = s.nbsteps; h->cfg.Mdx = s.Mdx; h->cfg.Mhy = s.Mhy;
   h->cfg.Mgx = s.Mgx; h->cfg.phys.t = s.t; h->L.Mgx = (real)s.Mgx;
+  note_walls(h, before);   // (what was made before the snapshot is stale by substep_seq already, once the replay has run; the count
+                           // is raised all the same, so that a wall's value never changes outside a sub-step without it)
   // the samples issued behind the failed launch found the stop word: the ring holds what it held (chain_settle_impl sets its
   // device counters to match), and the fluid steps since are counted again when they are repeated
   h->probe.seen = s.probe_seen; h->probe.issued = s.probe_issued;
@@ -1388,7 +1393,9 @@ int lbmdem_vibration(lbmdem_handle* h) { return h ? (h->vib ? 1 : 0) : LBMDEM_EI
 int lbmdem_move_walls(lbmdem_handle* h) {
   CHECK_H(h);
   if (!h->vib) return fail(LBMDEM_EINVAL, "lbmdem_move_walls: the walls do not vibrate (lbmdem_set_vibration)");
+  const WallBits before = wall_bits(h->cfg);
   vib_advance(h);
+  note_walls(h, before);
   return LBMDEM_OK;
 }
 

@@ -285,6 +285,13 @@ struct lbmdem_handle {
   bool contacts_valid = false;
   int contacts_film = 0;
   DemParams contacts_P{};
+  // walls_moved: raised whenever Mgx, Mdx, Mby or Mhy takes another value OUTSIDE a sub-step (lbmdem_move_walls,
+  // lbmdem_verlet_rebuild, a recovery that puts them back: note_walls below). What was made for the walls as they were is stale
+  // then, although no grain has moved: contacts_walls is the count the last table sub-step found (the export and the clusters ask
+  // for contacts_walls == walls_moved: walls() no longer describes the walls of their records otherwise), vo.walls the Voronoi
+  // compute's. Wall motion inside a run comes with sub-steps, which substep_seq counts.
+  long long walls_moved = 0;
+  long long contacts_walls = -1;
   bool contacts_output = false;   // lbmdem_set_contacts_output: lbmdem_run_scene writes the contact files at every DEM event
   struct ContactStage {
     int nwg = 0;                          // workgroups of the two kernels (0: nothing allocated yet)
@@ -348,12 +355,14 @@ struct lbmdem_handle {
   } st;
   // Voronoi cells (lbm_voronoi.hip): the radical tessellation on top of st's neighbour list. vo: scratch and results, allocated by
   // the first lbmdem_voronoi_compute, the face arrays grown with the faces, freed with the handle. The kernels read st and the
-  // kinematics and write here only. seq, moved: as st's, and the readers ask the same of them. voronoi_*: lbmdem_set_voronoi_output.
+  // kinematics and write here only. seq, moved: as st's, and the readers ask the same of them; walls: the handle's walls_moved at the
+  // compute, which clipped every cell with the four walls (the readers ask for walls == walls_moved). voronoi_*:
+  // lbmdem_set_voronoi_output.
   bool voronoi_output = false;
   double voronoi_rcut = 0.;
   struct VoronoiStage {
     bool valid = false;
-    long long seq = -1, moved = -1;
+    long long seq = -1, moved = -1, walls = -1;
     unsigned long long* words = nullptr;  // [VO_WORDS] the census (null: nothing allocated yet)
     double* dbl = nullptr;                // [4][n] area, perimeter, phi, R2
     int* ints = nullptr;                  // [4][n] faces, walls, nverts, flags; then nf [n + 1] and foff [n + 1]
@@ -790,6 +799,20 @@ static inline void verlet_wall_reset(lbmdem_config& c, long nbsteps) {
     c.Mdx = 1.e-3 * c.lx;
     c.Mhy = 1.e-3 * c.ly;
   }
+}
+// The four walls, to be compared on the bits, and what every entry point that moves a wall outside a sub-step does afterwards:
+// a wall that has taken another value makes stale what was computed with the walls as they were (lbmdem_handle::walls_moved);
+// walls that are where they were leave everything readable.
+struct WallBits { unsigned long long w[4]; };
+static inline WallBits wall_bits(const lbmdem_config& c) {
+  const double v[4] = {c.Mgx, c.Mdx, c.Mby, c.Mhy};
+  WallBits b;
+  memcpy(b.w, v, sizeof v);
+  return b;
+}
+static inline void note_walls(lbmdem_handle* h, const WallBits& before) {
+  const WallBits now = wall_bits(h->cfg);
+  if (memcmp(now.w, before.w, sizeof now.w) != 0) h->walls_moved++;
 }
 // the walls a sub-step sees, as dem_params() hands them to the kernels
 static inline VibWall vib_wall(const lbmdem_config& c) {

@@ -125,7 +125,9 @@ int lbmdem_path_info(lbmdem_handle* h, int* info4);
 int lbmdem_fused_work_order(lbmdem_handle* h, int* info12);
 
 /* initVerlet + VerletWall, main.c:1519-1594 (same pair set; uniform grid + radix sort instead of
- * the O(N^2) scan). Also moves the right/top DEM walls as VerletWall does (main.c:1555-1561). */
+ * the O(N^2) scan). Also moves the right/top DEM walls as VerletWall does (main.c:1555-1561). A wall that takes another value
+ * here invalidates what was computed with the walls as they were: the Voronoi readers and the cluster readers are refused until
+ * their next compute, the contact export until the next table sub-step; walls that keep their values leave them readable. */
 int lbmdem_verlet_rebuild(lbmdem_handle* h);
 
 /* One DEM sub-step = main.c:1733-1764: drift + half kick, acceleration_grains (1336-1516, film
@@ -259,7 +261,9 @@ int lbmdem_set_lid(lbmdem_handle* h, double uw_h);
 int lbmdem_set_vibration(lbmdem_handle* h, int on);
 int lbmdem_vibration(lbmdem_handle* h);   /* 1 when on, 0 when off */
 /* renderScene's first statement alone (main.c:1700-1705), for callers that run the phases themselves (lbmdem_lbm_step,
- * lbmdem_verlet_rebuild, lbmdem_dem_substep) instead of lbmdem_run: once per sub-step, before its fluid step */
+ * lbmdem_verlet_rebuild, lbmdem_dem_substep) instead of lbmdem_run: once per sub-step, before its fluid step. A wall that
+ * changes value (amp != 0) invalidates what was computed with the walls as they were: the Voronoi readers are refused until the
+ * next lbmdem_voronoi_compute, the contact export, lbmdem_cluster_compute and the cluster readers until the next table sub-step. */
 int lbmdem_move_walls(lbmdem_handle* h);
 /* walls5 = t, Mgx, Mdx, Mby, Mhy as the next sub-step finds them (before its renderScene moves them) */
 int lbmdem_get_walls(lbmdem_handle* h, double* walls5);
@@ -484,7 +488,10 @@ int lbmdem_write_obst_files(const char* dir, int lx, int ly, const int* obst, co
  *                                  nFile. Off by default; a checkpoint does not carry it.
  * LBMDEM_EINVAL: a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the
  * single-precision library (the host-only formatter exists there too); null buffers; a directory that cannot be written.
- * Vibrating and probing handles have the export. */
+ * Vibrating and probing handles have the export. A wall that lbmdem_move_walls gives another value invalidates the records: the
+ * three calls are refused (LBMDEM_EINVAL, "a wall has been moved since the last table sub-step") until the next table sub-step,
+ * since the handle's walls are no longer the ones that sub-step saw. lbmdem_verlet_rebuild invalidates them whether a wall moves
+ * or not (the list that sub-step walked is gone), with the sentence of a handle without a table sub-step. */
 #define LBMDEM_WALL_B (-1)   /* bottom, force_WallB main.c:809 */
 #define LBMDEM_WALL_T (-2)   /* top */
 #define LBMDEM_WALL_L (-3)   /* left */
@@ -561,7 +568,9 @@ int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double*
  *                                   carry it.
  * LBMDEM_EINVAL: fmin negative or not finite, zmin outside 0 .. 6; a strip of a decomposition or distributed grains (and
  * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers; a
- * directory that cannot be written ("cannot open"). */
+ * directory that cannot be written ("cannot open"). What invalidates the contact records invalidates the clusters made of them: a
+ * wall that lbmdem_move_walls gives another value, and every lbmdem_verlet_rebuild; compute and readers are refused until the next
+ * table sub-step. */
 typedef struct lbmdem_cluster { int label, size; long contacts; int walls, core; double xmin, xmax, ymin, ymax; } lbmdem_cluster;
 #define LBMDEM_CLUSTER_COUNTS 10
 int lbmdem_cluster_compute(lbmdem_handle* h, double fmin, int relative, int zmin, long* counts10, double* thr);
@@ -726,7 +735,9 @@ int lbmdem_write_structure_files(const char* dir, int nfile, int n, const int* n
  *                                   DEM event, behind the structure files. Off by default; a checkpoint does not carry it.
  * Single-domain fp64 handles. LBMDEM_EINVAL: rcut not finite and > 0; a strip of a decomposition or distributed grains (and
  * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers;
- * a directory that cannot be written ("cannot open"). */
+ * a directory that cannot be written ("cannot open"). The cells are clipped with Mgx, Mdx, Mby, Mhy as the compute finds them: a
+ * wall that changes value afterwards without a sub-step (lbmdem_move_walls, lbmdem_verlet_rebuild) invalidates them, and the
+ * readers are refused as after a move of the grains until the next lbmdem_voronoi_compute (the neighbour list stays good). */
 #define LBMDEM_VORONOI_COUNTS 8
 #define LBMDEM_VOR_MAXV 32
 #define LBMDEM_VOR_COMPLETE 1
