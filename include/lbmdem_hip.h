@@ -491,7 +491,13 @@ int lbmdem_write_obst_files(const char* dir, int lx, int ly, const int* obst, co
  * Vibrating and probing handles have the export. A wall that lbmdem_move_walls gives another value invalidates the records: the
  * three calls are refused (LBMDEM_EINVAL, "a wall has been moved since the last table sub-step") until the next table sub-step,
  * since the handle's walls are no longer the ones that sub-step saw. lbmdem_verlet_rebuild invalidates them whether a wall moves
- * or not (the list that sub-step walked is gone), with the sentence of a handle without a table sub-step. */
+ * or not (the list that sub-step walked is gone), with the sentence of a handle without a table sub-step. A fluid step alone
+ * (lbmdem_lbm_step), lbmdem_upload_f, the coarse-grained and the flow fields move no grain and no wall: the contact export, the
+ * clusters, the structure and the Voronoi readers go on answering (a fluid step raises no sub-step count; the coarse and the flow
+ * fields, which read the populations, change with it). Every call counts the records anew; one that has room for all of them
+ * (lbmdem_write_contacts, and lbmdem_cluster_compute for itself) also emits them into the export's own buffer: the same records, in
+ * the same order, as often as it is asked. lbmdem_contact_stats and a download with too little room or with room 0 count only and
+ * leave the buffer as the last emit wrote it. */
 #define LBMDEM_WALL_B (-1)   /* bottom, force_WallB main.c:809 */
 #define LBMDEM_WALL_T (-2)   /* top */
 #define LBMDEM_WALL_L (-3)   /* left */
@@ -570,7 +576,11 @@ int lbmdem_write_contacts_files(const char* dir, int nfile, int n, const double*
  * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers; a
  * directory that cannot be written ("cannot open"). What invalidates the contact records invalidates the clusters made of them: a
  * wall that lbmdem_move_walls gives another value, and every lbmdem_verlet_rebuild; compute and readers are refused until the next
- * table sub-step. */
+ * table sub-step. A compute that is refused for fmin or zmin changes nothing: an earlier result stays readable; one that is refused
+ * because the contact records are not valid finds the readers refused already. The kernels read the records in the contact export's
+ * buffer, which the compute fills itself; the per-grain planes and the table are the cluster stage's own. No call of the contact
+ * export (lbmdem_contact_stats, lbmdem_download_contacts with any room, lbmdem_write_contacts) changes a cluster result, and
+ * lbmdem_write_clusters downloads the records of its own compute, right behind it, for DEM%.6i_clusters.ps. */
 typedef struct lbmdem_cluster { int label, size; long contacts; int walls, core; double xmin, xmax, ymin, ymax; } lbmdem_cluster;
 #define LBMDEM_CLUSTER_COUNTS 10
 int lbmdem_cluster_compute(lbmdem_handle* h, double fmin, int relative, int zmin, long* counts10, double* thr);
@@ -653,7 +663,12 @@ int lbmdem_write_clusters_files(const char* dir, int nfile, int n, const double*
  *                                         does not carry it.
  * Single-domain fp64 handles; vibrating, probing, lid, tracer, scalar and mean handles included. LBMDEM_EINVAL: a parameter outside
  * its range; a strip of a decomposition or distributed grains (and lbmdem_dist_enable with the setting on); the single-precision
- * library (the two host-only functions exist there too); null buffers; a directory that cannot be written ("cannot open"). */
+ * library (the two host-only functions exist there too); null buffers; a directory that cannot be written ("cannot open"). A later
+ * compute replaces the result whole -- list, histogram, sums, rcut, nbins and whether there is a list --; one that is refused for a
+ * parameter changes nothing, one whose list exceeds max_entries leaves no result. lbmdem_write_structure and lbmdem_write_voronoi
+ * make computes of their own: after lbmdem_write_voronoi(rcut) the readers describe lbmdem_structure_compute(rcut, 1, 1.0), and
+ * so they do after a DEM event of lbmdem_run_scene with both outputs on, where the structure files, written first, are those of
+ * lbmdem_set_structure_output's parameters and the Voronoi files those of lbmdem_set_voronoi_output's rcut. */
 #define LBMDEM_STRUCTURE_COUNTS 8
 int lbmdem_structure_edges(double rcut, int nbins, double* e2);   /* host only */
 int lbmdem_structure_compute(lbmdem_handle* h, double rcut, int nbins, double shell, long max_entries, long* counts8);
@@ -737,7 +752,12 @@ int lbmdem_write_structure_files(const char* dir, int nfile, int n, const int* n
  * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers;
  * a directory that cannot be written ("cannot open"). The cells are clipped with Mgx, Mdx, Mby, Mhy as the compute finds them: a
  * wall that changes value afterwards without a sub-step (lbmdem_move_walls, lbmdem_verlet_rebuild) invalidates them, and the
- * readers are refused as after a move of the grains until the next lbmdem_voronoi_compute (the neighbour list stays good). */
+ * readers are refused as after a move of the grains until the next lbmdem_voronoi_compute (the neighbour list stays good). The cells
+ * are the Voronoi stage's own: a later lbmdem_structure_compute (another rcut or nbins, counts only, refused) leaves the readers
+ * answering with the cells of the list and the rcut they were made with, until a grain or a wall moves. A refused
+ * lbmdem_voronoi_compute (no valid list, a counts-only list) discards an earlier result: the readers are refused until the next
+ * compute that succeeds. lbmdem_write_voronoi writes its own argument as "# rcut"; its lbmdem_structure_compute(rcut, 1, 1.0,
+ * 2^31 - 1) replaces the structure result. Afterwards the structure readers describe that compute, not an earlier one. */
 #define LBMDEM_VORONOI_COUNTS 8
 #define LBMDEM_VOR_MAXV 32
 #define LBMDEM_VOR_COMPLETE 1
