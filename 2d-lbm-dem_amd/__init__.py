@@ -204,6 +204,17 @@ def _open_library(LIB_PATH):
     L.lbmdem_set_voronoi_output.argtypes = [C.c_void_p, C.c_int, C.c_double]
     L.lbmdem_write_voronoi_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_double, C.c_void_p] +
                                              [C.c_double] * 3)
+    L.lbmdem_strain_mark.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    L.lbmdem_strain_clear.argtypes = [C.c_void_p]
+    L.lbmdem_strain_compute.argtypes = [C.c_void_p, C.c_void_p]
+    L.lbmdem_download_strain_grains.argtypes = [C.c_void_p] + [C.c_void_p] * 11
+    L.lbmdem_strain_grains_device.argtypes = [C.c_void_p] + [C.POINTER(C.c_void_p)] * 11
+    L.lbmdem_download_strain_reference.argtypes = ([C.c_void_p] + [C.c_void_p] * 5 + [C.c_long, C.POINTER(C.c_long),
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_long)])
+    L.lbmdem_write_strain.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_int]
+    L.lbmdem_set_strain_output.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int]
+    L.lbmdem_write_strain_files.argtypes = ([C.c_char_p, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_double, C.c_void_p] +
+                                            [C.c_double] * 2)
     L.lbmdem_pore_compute.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.lbmdem_download_pore_labels.argtypes = [C.c_void_p, C.c_void_p]
     L.lbmdem_pore_labels_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
@@ -558,6 +569,29 @@ def write_voronoi_files(directory, nFile, grains, rcut, counts, t, W, H, precisi
         raise LbmDemError(-1, "write_voronoi_files: counts must have eight values")
     _chk(load_library(precision).lbmdem_write_voronoi_files(
         os.fsencode(directory), int(nFile), len(g), *(_vp(a) for a in cols), float(rcut), _vp(cnt), float(t), float(W), float(H)))
+
+
+# the per-grain results of LbmDem.strain() (LbmDem.strain_grains), the names of its eight counts, and the bits of `flags`
+STRAIN_DTYPE = np.dtype([("ux", np.float64), ("uy", np.float64), ("drot", np.float64), ("Fxx", np.float64), ("Fxy", np.float64),
+                         ("Fyx", np.float64), ("Fyy", np.float64), ("d2min", np.float64), ("used", np.int32), ("lost", np.int32),
+                         ("flags", np.int32)])
+STRAIN_COUNTERS = ("fitted", "few", "degenerate", "nonfinite_grains", "entries", "used", "lost", "worst_grain")
+STRAIN_NONFINITE, STRAIN_FEW, STRAIN_DEGENERATE = 1, 2, 4
+
+
+def write_strain_files(directory, nFile, grains, rc2, counts, t, t_mark, precision="f64"):
+    """strain%.6i.dat and one appended line of strain.data (include/lbmdem_hip.h spells the two formats out) from the per-grain
+    results (STRAIN_DTYPE), the square of the mark's cutoff, the eight counts (a dict of STRAIN_COUNTERS or a sequence), the time
+    of the line and the time of the mark. Host only."""
+    g = np.ascontiguousarray(grains, dtype=STRAIN_DTYPE).reshape(-1)
+    cols = [np.ascontiguousarray(g[k]) for k in STRAIN_DTYPE.names]
+    if isinstance(counts, dict):
+        counts = [counts[k] for k in STRAIN_COUNTERS]
+    cnt = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(cnt) != len(STRAIN_COUNTERS):
+        raise LbmDemError(-1, "write_strain_files: counts must have eight values")
+    _chk(load_library(precision).lbmdem_write_strain_files(
+        os.fsencode(directory), int(nFile), len(g), *(_vp(a) for a in cols), float(rc2), _vp(cnt), float(t), float(t_mark)))
 
 
 # struct lbmdem_pore: one connected component of the fluid phase (LbmDem.pore_table), 56 bytes; the names of the ten counts of
@@ -1515,6 +1549,64 @@ class LbmDem:
     def set_voronoi_output(self, on=True, rcut=0.0):
         """run_scene writes the Voronoi files at every DEM event, behind the structure files"""
         _chk(self._L.lbmdem_set_voronoi_output(self._h, 1 if on else 0, float(rcut)))
+
+    # strain fields: the grains where they are now against a marked reference state (include/lbmdem_hip.h)
+    def strain_mark(self):
+        """marks the grains where they are now, with the neighbour list of the last structure(), as the reference state ->
+        the list entries copied"""
+        cnt = C.c_long(0)
+        _chk(self._L.lbmdem_strain_mark(self._h, C.byref(cnt)))
+        return cnt.value
+
+    def strain_clear(self):
+        """no mark and no result any more"""
+        _chk(self._L.lbmdem_strain_clear(self._h))
+
+    def strain(self):
+        """displacement, the fitted deformation gradient, D2min and the lost neighbours of every grain since the mark -> dict of
+        STRAIN_COUNTERS"""
+        c = np.zeros(len(STRAIN_COUNTERS), np.int64)
+        _chk(self._L.lbmdem_strain_compute(self._h, _vp(c)))
+        return dict(zip(STRAIN_COUNTERS, (int(v) for v in c)))
+
+    def strain_grains(self):
+        """structured array [n] of STRAIN_DTYPE of the last strain(): ux, uy, drot, the four entries of F, the unnormalised D2min,
+        the marked neighbours used and lost, and flags (STRAIN_NONFINITE, STRAIN_FEW, STRAIN_DEGENERATE)"""
+        cols = {k: np.zeros(self.n, STRAIN_DTYPE[k]) for k in STRAIN_DTYPE.names}
+        _chk(self._L.lbmdem_download_strain_grains(self._h, *(_vp(cols[k]) for k in STRAIN_DTYPE.names)))
+        out = np.zeros(self.n, STRAIN_DTYPE)
+        for k in STRAIN_DTYPE.names:
+            out[k] = cols[k]
+        return out
+
+    def strain_tensors(self):
+        """the same eleven as torch views (float64, int32) of the handle's device memory, good until the next strain()"""
+        import torch
+        p = [C.c_void_p() for _ in range(11)]
+        _chk(self._L.lbmdem_strain_grains_device(self._h, *(C.byref(q) for q in p)))
+        dev = f"cuda:{self.cfg.device}"
+        return {k: torch.as_tensor(_DeviceBlock(q.value, (self.n,), "<i4" if STRAIN_DTYPE[k] == np.int32 else "<f8"), device=dev)
+                for k, q in zip(STRAIN_DTYPE.names, p)}
+
+    def strain_reference(self):
+        """the mark -> dict: x0, y0, th0 float64 [n], offsets int32 [n + 1], nbr int32 [entries], rc2, nbsteps"""
+        cnt, rc2, nbs = C.c_long(0), C.c_double(0.), C.c_long(0)
+        _chk(self._L.lbmdem_download_strain_reference(self._h, None, None, None, None, None, 0, C.byref(cnt), C.byref(rc2),
+                                                      C.byref(nbs)))
+        x0, y0, th0 = (np.zeros(self.n, np.float64) for _ in range(3))
+        off, nbr = np.zeros(self.n + 1, np.int32), np.zeros(cnt.value, np.int32)
+        _chk(self._L.lbmdem_download_strain_reference(self._h, _vp(x0), _vp(y0), _vp(th0), _vp(off), _vp(nbr) if cnt.value else None,
+                                                      cnt.value, C.byref(cnt), C.byref(rc2), C.byref(nbs)))
+        return {"x0": x0, "y0": y0, "th0": th0, "offsets": off, "nbr": nbr, "rc2": rc2.value, "nbsteps": nbs.value}
+
+    def write_strain(self, directory=".", nFile=0, rcut=0.0, incremental=False):
+        """strain%.6i.dat and a line of strain.data of the grains where they are now against the mark (made first, where there is
+        none); incremental: a new mark afterwards"""
+        _chk(self._L.lbmdem_write_strain(self._h, os.fsencode(directory), int(nFile), float(rcut), 1 if incremental else 0))
+
+    def set_strain_output(self, on=True, rcut=0.0, incremental=False):
+        """run_scene writes the strain files at every DEM event, behind the Voronoi files"""
+        _chk(self._L.lbmdem_set_strain_output(self._h, 1 if on else 0, float(rcut), 1 if incremental else 0))
 
     # pore space: the connected components of the fluid phase of the map as it is now (include/lbmdem_hip.h)
     def pores(self, conn=8, map=None):

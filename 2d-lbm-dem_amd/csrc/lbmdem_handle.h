@@ -376,6 +376,30 @@ struct lbmdem_handle {
     long nfaces = 0;                      // of the last compute
     double rcut = 0.;                     // the structure compute's, as the last compute recovered it
   } vo;
+  // Strain fields (lbm_strain.hip): the grains where they are now against a marked reference state. sn: the mark -- a copy of the
+  // centres, the angles and st's list, which nothing st or vo do later changes -- and the compute's scratch and results, allocated
+  // by the first lbmdem_strain_mark, the list grown with the entries, freed with the handle. The kernels read the mark and the
+  // kinematics and write here only. marked: from a successful mark to the next one, lbmdem_strain_clear or the handle's end (steps,
+  // uploads and wall moves do not end it; a checkpoint does not carry it); mark_gen counts the marks. The result describes mark
+  // `of_mark` and the centres as of sub-step `seq` and upload `moved`: the readers ask for of_mark == mark_gen, seq == substep_seq
+  // and moved == grains_moved (walls do not enter). strain_*: lbmdem_set_strain_output.
+  bool strain_output = false, strain_incremental = false;
+  double strain_rcut = 0.;
+  struct StrainStage {
+    bool marked = false, valid = false;
+    long long mark_gen = 0, of_mark = -1, seq = -1, moved = -1;
+    unsigned long long* words = nullptr;  // [SN_WORDS] the census and the argmax (null: nothing allocated yet)
+    double* ref = nullptr;                // [3][n] the mark: x1, x2, x3
+    int* off = nullptr;                   // [n + 1] the mark: st's offsets
+    int* nbr = nullptr;                   // [nbr_cap] the mark: st's list, ascending
+    double* rec = nullptr;                // [n][4] the compute's packed records {X0, Y0, x, y}
+    double* dbl = nullptr;                // [8][n] ux, uy, drot, Fxx, Fxy, Fyx, Fyy, d2min
+    int* ints = nullptr;                  // [3][n] used, lost, flags
+    long ref_cap = 0, off_cap = 0, nbr_cap = 0, rec_cap = 0, dbl_cap = 0, ints_cap = 0;
+    long entries = 0;                     // of the mark
+    double rc2 = 0.;                      // the marked structure compute's rcut*rcut
+    long nbsteps = 0;                     // the handle's at the mark
+  } sn;
   // The pore space (lbm_pores.hip): the fluid phase labelled into connected components. po: scratch and results, allocated by the
   // first lbmdem_pore_compute, the table grown with the components, freed with the handle. The kernels read the map and f and
   // write here only. The results describe the map and f as of sub-step `seq`, upload `moved` and lattice change `fluid`: the

@@ -203,6 +203,7 @@ static int run_scene_loop(lbmdem_handle* h, lbmdem_comm* comm, long n, const lbm
       if (!comm && h->clusters_output) RC_TRY(lbmdem_write_clusters(h, dir, nfile, h->clusters_fmin, h->clusters_relative, h->clusters_zmin));   // lbmdem_set_clusters_output
       if (!comm && h->structure_output) RC_TRY(lbmdem_write_structure(h, dir, nfile, h->structure_rcut, h->structure_nbins, h->structure_shell));   // lbmdem_set_structure_output
       if (!comm && h->voronoi_output) RC_TRY(lbmdem_write_voronoi(h, dir, nfile, h->voronoi_rcut));   // lbmdem_set_voronoi_output
+      if (!comm && h->strain_output) RC_TRY(lbmdem_write_strain(h, dir, nfile, h->strain_rcut, h->strain_incremental));   // lbmdem_set_strain_output
       if (!comm && h->pores_output) RC_TRY(lbmdem_write_pores(h, dir, nfile, h->pores_conn, h->pores_plane));   // lbmdem_set_pores_output
       if (!comm && h->clearance_output) RC_TRY(lbmdem_write_clearance(h, dir, nfile, h->clearance_plane));   // lbmdem_set_clearance_output
       if (!comm && h->network_output) RC_TRY(lbmdem_write_network(h, dir, nfile, h->network_merge, h->network_plane));   // lbmdem_set_network_output

@@ -84,6 +84,7 @@ int lbmdem_dist_enable(lbmdem_handle* h, int margin_rows) try {
   if (h->clusters_output) return fail(LBMDEM_EINVAL, "the cluster analysis is not available with distributed grains (lbmdem_set_clusters_output(h, 0, 0., 0, 0) first)");
   if (h->structure_output) return fail(LBMDEM_EINVAL, "the packing structure analysis is not available with distributed grains (lbmdem_set_structure_output(h, 0, 0., 0, 0.) first)");
   if (h->voronoi_output) return fail(LBMDEM_EINVAL, "the Voronoi analysis is not available with distributed grains (lbmdem_set_voronoi_output(h, 0, 0.) first)");
+  if (h->strain_output) return fail(LBMDEM_EINVAL, "the strain analysis is not available with distributed grains (lbmdem_set_strain_output(h, 0, 0., 0) first)");
   if (h->pores_output) return fail(LBMDEM_EINVAL, "the pore space analysis is not available with distributed grains (lbmdem_set_pores_output(h, 0, 0, 0) first)");
   if (h->clearance_output) return fail(LBMDEM_EINVAL, "the pore clearance analysis is not available with distributed grains (lbmdem_set_clearance_output(h, 0, 0) first)");
   if (h->network_output) return fail(LBMDEM_EINVAL, "the pore network analysis is not available with distributed grains (lbmdem_set_network_output(h, 0, 0, 0) first)");

@@ -60,6 +60,11 @@
  * --voronoi RCUT: the Voronoi cells of every DEM event (lbmdem_set_voronoi_output): the radical tessellation of the discs inside the
  * walls from the neighbours within RCUT metres -- per grain the cell's area, perimeter, local solid fraction and topological
  * neighbour count in voronoi%.6i.dat, and a line of voronoi.data. Single GPU only.
+ * --strain RCUT [--strain-incremental]: the strain fields of every DEM event (lbmdem_set_strain_output): the first event marks the
+ * grains where they are, with their neighbours within RCUT metres, as the reference state; every event writes per grain the
+ * displacement since the mark, the strain of its neighbourhood (a least-squares fit over the marked neighbours), D2min and the
+ * neighbours lost in strain%.6i.dat, and a line of strain.data. --strain-incremental marks anew after every event: the files then
+ * describe the motion between two events. Single GPU only.
  * --pores [4|8] [--pores-plane]: the pore space of every DEM event (lbmdem_set_pores_output): the fluid phase of the obstacle map
  * labelled into components joined along 4 or 8 (the default) directions -- per component its nodes, extent, walls, wetted links and
  * fluid mass in pore_table%.6i.dat, per grain the pores it borders in pore_grains%.6i.dat, a line of pores.data (is the pore space
@@ -142,6 +147,9 @@ static int g_structure = 0, g_structure_bins = 64;   /* --structure RCUT, --stru
 static double g_structure_rcut = 0., g_structure_shell = 1.2;
 static int g_voronoi = 0;        /* --voronoi RCUT */
 static double g_voronoi_rcut = 0.;
+static int g_strain = 0;         /* --strain RCUT */
+static double g_strain_rcut = 0.;
+static int g_strain_incremental = 0;   /* --strain-incremental */
 static int g_pores = 0, g_pores_conn = 8, g_pores_plane = 0;   /* --pores [4|8], --pores-plane */
 static int g_clearance = 0, g_clearance_plane = 0;   /* --clearance, --clearance-plane */
 static int g_network = 0, g_network_merge = -1, g_network_plane = 0;   /* --network [MERGE], --network-plane */
@@ -337,6 +345,11 @@ int main(int argc, char** argv) {
       if (a + 1 >= argc || !is_number(argv[a + 1], &g_voronoi_rcut) || !(g_voronoi_rcut > 0)) { fprintf(stderr, "--voronoi RCUT: the neighbours' cutoff in metres, above 0\n"); return EXIT_FAILURE; }
       g_voronoi = 1;
     }
+    if (!strcmp(argv[a], "--strain")) {
+      if (a + 1 >= argc || !is_number(argv[a + 1], &g_strain_rcut) || !(g_strain_rcut > 0)) { fprintf(stderr, "--strain RCUT: the neighbours' cutoff in metres, above 0\n"); return EXIT_FAILURE; }
+      g_strain = 1;
+    }
+    if (!strcmp(argv[a], "--strain-incremental")) g_strain_incremental = 1;
     if (!strcmp(argv[a], "--pores")) {
       g_pores = 1;
       if (a + 1 < argc && is_count(argv[a + 1])) {
@@ -495,6 +508,8 @@ int main(int argc, char** argv) {
   if (g_coarse && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--coarse is a single-GPU mode (the coarse-grained fields need the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_clusters && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--clusters is a single-GPU mode (the cluster analysis needs all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_structure && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--structure is a single-GPU mode (the packing structure analysis needs all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_strain && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--strain is a single-GPU mode (the strain analysis needs all grains on one handle)\n"); return EXIT_FAILURE; }
+  if (g_strain_incremental && !g_strain) { fprintf(stderr, "--strain-incremental goes with --strain RCUT\n"); return EXIT_FAILURE; }
   if (g_voronoi && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--voronoi is a single-GPU mode (the Voronoi analysis needs all grains on one handle)\n"); return EXIT_FAILURE; }
   if (g_pores_plane && !g_pores) { fprintf(stderr, "--pores-plane needs --pores\n"); return EXIT_FAILURE; }
   if (g_pores && (gpus > 1 || g_use_comm)) { fprintf(stderr, "--pores is a single-GPU mode (the pore space analysis needs the whole lattice and all grains on one handle)\n"); return EXIT_FAILURE; }
@@ -681,6 +696,8 @@ static int run(int argc, char** argv) {
     else if (!strcmp(argv[a], "--clusters-zmin") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--structure") && a + 1 < argc) ++a;
     else if (!strcmp(argv[a], "--voronoi") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--strain") && a + 1 < argc) ++a;
+    else if (!strcmp(argv[a], "--strain-incremental")) {}
     else if (!strcmp(argv[a], "--pores")) { if (a + 1 < argc && is_count(argv[a + 1])) ++a; }
     else if (!strcmp(argv[a], "--pores-plane")) {}
     else if (!strcmp(argv[a], "--clearance")) {}
@@ -726,7 +743,7 @@ static int run(int argc, char** argv) {
     else { sample = NULL; break; }
   }
   if (!sample) {
-    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --netflux [LEVEL] --netflux-merge M --netsolve FROM --netsolve-to TO --netsolve-band N --netsolve-level L --netsolve-merge M --netsolve-rtol R --netsolve-max-iter K --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --geodesic FROM --geodesic-to TO --geodesic-band N --geodesic-conn 4|8 --geodesic-min-d2 D --geodesic-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
+    SAY("usage: usage %s <filename> [--lx N --ly N --scale S --duration T --steps N --device K --gpus N --devices a,b,.. --comm-timeout S --dry --vib --vib-freq F --vib-amp A --run-stats --async-output [N] --async-dem [N] --checkpoint FILE --restart FILE --checkpoint-every N --checkpoint-state --async-checkpoint [N] --verify-checkpoint FILE --probes FILE --probe-every K --probe-row Y --probe-point X,Y --dump-geometry DIR --densities DIR --contacts --clusters [K] --clusters-abs F --clusters-zmin Z --structure RCUT --structure-bins N --structure-shell S --voronoi RCUT --strain RCUT --strain-incremental --pores [4|8] --pores-plane --clearance --clearance-plane --network [MERGE] --network-plane --netflux [LEVEL] --netflux-merge M --netsolve FROM --netsolve-to TO --netsolve-band N --netsolve-level L --netsolve-merge M --netsolve-rtol R --netsolve-max-iter K --drainage FROM --drainage-to TO --drainage-band N --drainage-plane --geodesic FROM --geodesic-to TO --geodesic-band N --geodesic-conn 4|8 --geodesic-min-d2 D --geodesic-plane --coarse CWxCH --flow --tracers NXxNY --dye X0,Y0,X1,Y1 --dye-tau T --mean [EVERY]]\n", argv[0]);
     exit(EXIT_FAILURE);
   }
   if (g_ckpt_every > 0 && !ckpt_out) { fprintf(stderr, "--checkpoint-every needs --checkpoint FILE\n"); return EXIT_FAILURE; }
@@ -804,6 +821,7 @@ static int run(int argc, char** argv) {
   if (g_clusters) DIE(lbmdem_set_clusters_output(h, 1, g_clusters_fmin, g_clusters_rel, g_clusters_zmin), "set_clusters_output");
   if (g_structure) DIE(lbmdem_set_structure_output(h, 1, g_structure_rcut, g_structure_bins, g_structure_shell), "set_structure_output");
   if (g_voronoi) DIE(lbmdem_set_voronoi_output(h, 1, g_voronoi_rcut), "set_voronoi_output");
+  if (g_strain) DIE(lbmdem_set_strain_output(h, 1, g_strain_rcut, g_strain_incremental), "set_strain_output");
   if (g_pores) DIE(lbmdem_set_pores_output(h, 1, g_pores_conn, g_pores_plane), "set_pores_output");
   if (g_clearance) DIE(lbmdem_set_clearance_output(h, 1, g_clearance_plane), "set_clearance_output");
   if (g_network) DIE(lbmdem_set_network_output(h, 1, g_network_merge, g_network_plane), "set_network_output");

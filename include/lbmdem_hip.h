@@ -775,6 +775,104 @@ int lbmdem_set_voronoi_output(lbmdem_handle* h, int on, double rcut);   /* 0: of
 int lbmdem_write_voronoi_files(const char* dir, int nfile, int n, const double* area, const double* perimeter, const double* phi,
                                const int* faces, const int* walls, const int* nverts, const int* flags, double rcut,
                                const long* counts8, double t, double W, double H);   /* host only */
+/* Strain fields: what has happened to the packing since a reference state -- per grain the displacement, the deformation gradient F
+ * of its neighbourhood (a least-squares fit over the neighbours it had at the reference state), Falk and Langer's D2min (the part of
+ * the neighbours' motion that F does not explain: the marker of plastic rearrangements) and the neighbours it has lost. Every
+ * floating-point result is a chain of IEEE double operations in the order stated here, which a numpy restatement reproduces on the
+ * bits (tests/strain_util.py).
+ * The mark (the reference configuration). lbmdem_strain_mark copies into scratch of the stage's own: the current x1, x2, x3 of the
+ * n grains (columns 0, 1, 2 of lbmdem_download_grain_table); offsets[n + 1], nbr[] (each grain's neighbours ascending) and
+ * rc2 = rcut*rcut of the most recent lbmdem_structure_compute, which must still be valid for the grains where they are and must
+ * have made a list; nbsteps. It makes no structure compute of its own. It is a copy: nothing the structure or the Voronoi analysis
+ * do later changes it. A mark lives until the next successful mark, lbmdem_strain_clear or lbmdem_destroy; steps,
+ * lbmdem_upload_kinematics and wall moves do not end it; a checkpoint does not carry it and a loaded handle has none. A new mark
+ * and a clear discard the compute's result; a refused mark leaves the earlier mark and its result as they were.
+ * The compute. X0, Y0, T0: the marked x1, x2, x3; x, y, th: the current ones. All arithmetic is IEEE double without contraction,
+ * the operations in the order written here. Per grain i:
+ * 1. LBMDEM_STRAIN_NONFINITE iff any of x_i, y_i, X0_i, Y0_i is not finite. Then flags = 1, used = lost = 0, every double output
+ *    of i is +0.0 and 2 to 4 are skipped. Otherwise ux = x_i - X0_i, uy = y_i - Y0_i, drot = th_i - T0_i.
+ * 2. Pass 1 over i's marked neighbours j in list order, the seven sums from +0.0: d0x = X0_j - X0_i, d0y = Y0_j - Y0_i,
+ *    dx = x_j - x_i, dy = y_j - y_i. j is skipped unless dx and dy are finite. Otherwise used += 1, and lost += 1 where
+ *    dx*dx + dy*dy > rc2; Xxx += dx*d0x; Xxy += dx*d0y; Xyx += dy*d0x; Xyy += dy*d0y; Yxx += d0x*d0x; Yxy += d0x*d0y;
+ *    Yyy += d0y*d0y.
+ * 3. Fit. det = Yxx*Yyy - Yxy*Yxy. LBMDEM_STRAIN_FEW iff used < 2; LBMDEM_STRAIN_DEGENERATE iff not FEW and not
+ *    det > 0x1p-40*(Yxx*Yyy) (collinear neighbours; a NaN too). With either flag Fxx, Fxy, Fyx, Fyy and d2min are +0.0 and 4 is
+ *    skipped. Otherwise Ixx = Yyy/det; Ixy = (-Yxy)/det; Iyy = Yxx/det; Fxx = Xxx*Ixx + Xxy*Ixy; Fxy = Xxx*Ixy + Xxy*Iyy;
+ *    Fyx = Xyx*Ixx + Xyy*Ixy; Fyy = Xyx*Ixy + Xyy*Iyy. A grain without a flag is "fitted".
+ * 4. Pass 2 over the same neighbours with the same skip rule, d2min from +0.0: rx = dx - (Fxx*d0x + Fxy*d0y);
+ *    ry = dy - (Fyx*d0x + Fyy*d0y); d2min += rx*rx + ry*ry. Unnormalised: dividing by used is the caller's.
+ * 5. counts8, in order: fitted grains (flags == 0); FEW; DEGENERATE; NONFINITE; marked list entries; entries used (the sum of used);
+ *    entries lost (the sum of lost); the index of the fitted grain with the largest d2min, the smallest index among equals, -1
+ *    without a fitted grain. "Largest" is by the key of d2min: its bit pattern as an unsigned 64-bit integer where d2min >= +0.0
+ *    -- the order of the values --, and 0 otherwise (a NaN counts as +0.0).
+ * On the device, on the handle's stream: a packing pass writes one 32-byte record {X0, Y0, x, y} per grain, so that a neighbour
+ * costs two 16-byte loads; one lane per grain walks its segment of the marked list twice, serially; the census is integer
+ * atomics, the argmax an integer atomicMax over the keys and an atomicMin over the indices that carry the maximum. No
+ * floating-point atomic, no workgroup waits for another, every loop is bounded by the segment length. Scratch comes from the
+ * handle's pool with the first mark.
+ *   lbmdem_strain_mark                the mark; *entries (may be NULL): the list entries copied. Synchronises; changes nothing a later
+ *                                     step reads. Refused with a sentence that names lbmdem_structure_compute when no such compute
+ *                                     describes the grains where they are now, or when the last one had max_entries == 0.
+ *   lbmdem_strain_clear               no mark and no result any more (the scratch stays with the handle)
+ *   lbmdem_strain_compute             the compute; counts8. Synchronises; changes nothing a later step reads. Without a mark it is
+ *                                     refused with a sentence that names lbmdem_strain_mark, and an earlier result is discarded.
+ *   lbmdem_download_strain_grains     ux, uy, drot, Fxx, Fxy, Fyx, Fyy, d2min, [n] doubles; used, lost, flags, [n] ints; any pointer
+ *                                     may be NULL
+ *   lbmdem_strain_grains_device       the same eleven as device pointers into the handle's scratch (for a torch view), good until
+ *                                     the next compute or lbmdem_destroy; any pointer may be NULL
+ *   These two readers are refused, with LBMDEM_EINVAL and a sentence that names lbmdem_strain_compute, until a compute has been
+ *   made, and again after anything that moves grains (a sub-step, lbmdem_upload_kinematics), after a new mark and after a clear.
+ *   A wall that moves without a sub-step does not invalidate the result: walls do not enter.
+ *   lbmdem_download_strain_reference  the mark: x0, y0, th0, [n] doubles, offsets[n + 1] (any of the four may be NULL) and nbr[];
+ *                                     *rc2 and *nbsteps (either may be NULL); cap = 0 leaves nbr alone and reports *count, the
+ *                                     entries; a buffer of fewer than *count entries is refused with *count set. Good whenever a
+ *                                     mark exists, compute or not; refused with a sentence that names lbmdem_strain_mark otherwise.
+ *   lbmdem_write_strain_files         host only, no handle, no device. Two files in <dir>: strain%.6i.dat -- "# rc2 %le t_mark
+ *                                     %le\n", "# i ux uy drot exx eyy exy omega vol dev d2min used lost flags\n", then n lines
+ *                                     "%d %le %le %le %le %le %le %le %le %le %le %d %d %d\n". For a fitted grain exx = Fxx - 1.,
+ *                                     eyy = Fyy - 1., exy = 0.5*(Fxy + Fyx), omega = 0.5*(Fyx - Fxy), vol = exx + eyy,
+ *                                     h = 0.5*(exx - eyy), dev = sqrt(h*h + exy*exy); otherwise all six are 0.
+ *                                     strain.data -- one line appended: "%le" of t, " %ld" of each of the eight counts,
+ *                                     " %le %le %le\n" of the mean squared displacement (ux*ux + uy*uy added from +0.0 by index
+ *                                     over the grains without NONFINITE, divided by their number; 0 without one), the mean of
+ *                                     d2min/used over the fitted grains (added and divided alike) and the largest d2min of a
+ *                                     fitted grain (from 0., by index, replaced where d2min is greater). When the file is
+ *                                     created, first the line "# t fitted few degenerate nonfinite_grains entries used lost
+ *                                     worst_grain msd mean_d2min max_d2min". It checks fopen; used outside [0, n), lost outside
+ *                                     [0, used] and flags outside 0 .. 7 are refused before anything is written.
+ *   lbmdem_write_strain               without a mark, first lbmdem_structure_compute(rcut, 1, 1.0, 2^31 - 1) and the mark (the
+ *                                     files then describe the mark against itself); the compute, the downloads, then that
+ *                                     formatter with the mark's rc2, t = nbsteps * dt and t_mark = the mark's nbsteps * dt; with
+ *                                     incremental != 0, afterwards the same structure compute and a new mark, so that the next
+ *                                     call describes the motion since this one
+ *   lbmdem_set_strain_output          on != 0: lbmdem_run_scene (comm == NULL) calls lbmdem_write_strain(dir, nFile, rcut,
+ *                                     incremental) at every DEM event, behind the Voronoi files. Off by default; nothing is
+ *                                     allocated or launched while it is off; a checkpoint does not carry it.
+ * Single-domain fp64 handles. LBMDEM_EINVAL: rcut not finite and > 0; a strip of a decomposition or distributed grains (and
+ * lbmdem_dist_enable with the setting on); the single-precision library (the host-only formatter exists there too); null buffers;
+ * a directory that cannot be written ("cannot open"). lbmdem_write_strain's lbmdem_structure_compute(rcut, 1, 1.0, 2^31 - 1) --
+ * made when there is no mark, and again with incremental != 0 -- replaces the structure result. Afterwards the structure readers
+ * describe that compute, not an earlier one; with a mark and incremental == 0 the structure result is left alone. */
+#define LBMDEM_STRAIN_COUNTS 8
+#define LBMDEM_STRAIN_NONFINITE 1
+#define LBMDEM_STRAIN_FEW 2
+#define LBMDEM_STRAIN_DEGENERATE 4
+int lbmdem_strain_mark(lbmdem_handle* h, long* entries);
+int lbmdem_strain_clear(lbmdem_handle* h);
+int lbmdem_strain_compute(lbmdem_handle* h, long* counts8);
+int lbmdem_download_strain_grains(lbmdem_handle* h, double* ux, double* uy, double* drot, double* Fxx, double* Fxy, double* Fyx,
+                                  double* Fyy, double* d2min, int* used, int* lost, int* flags);
+int lbmdem_strain_grains_device(lbmdem_handle* h, const double** ux, const double** uy, const double** drot, const double** Fxx,
+                                const double** Fxy, const double** Fyx, const double** Fyy, const double** d2min, const int** used,
+                                const int** lost, const int** flags);
+int lbmdem_download_strain_reference(lbmdem_handle* h, double* x0, double* y0, double* th0, int* offsets, int* nbr, long cap,
+                                     long* count, double* rc2, long* nbsteps);
+int lbmdem_write_strain(lbmdem_handle* h, const char* dir, int nfile, double rcut, int incremental);
+int lbmdem_set_strain_output(lbmdem_handle* h, int on, double rcut, int incremental);   /* 0: off (default) */
+int lbmdem_write_strain_files(const char* dir, int nfile, int n, const double* ux, const double* uy, const double* drot,
+                              const double* Fxx, const double* Fxy, const double* Fyx, const double* Fyy, const double* d2min,
+                              const int* used, const int* lost, const int* flags, double rc2, const long* counts8, double t,
+                              double t_mark);   /* host only */
 /* Pore space: is the fluid connected? In two dimensions touching discs close the gaps between them, and whether a reductionR, a
  * lattice resolution and a packing leave one percolating pore space or a set of sealed pockets decides whether the pore pressures
  * mean anything. The fluid phase of the obstacle map is labelled into connected components on the device; per component its size,
