@@ -31,9 +31,10 @@
 // loop has the bound its comment states.
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
 // both. Front end, as every export's: whole_handle(), SP_REFUSE() and reader_obst() (lbmdem_handle.h), MemPool (lbm_mem.h) for the
-// scratch kept on the handle, OutFile (lbm_outfile.h) for the files.
+// scratch kept on the handle, OutFile (lbm_outfile.h) for the files; what the pore stages share, lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 
@@ -349,8 +350,6 @@ __global__ __launch_bounds__(CE_THREADS) void k_ce_census(const CeJob J) {
   }
 }
 
-long ce_blocks(long items, int per) { return (items + per - 1) / per; }
-int ce_bits(unsigned long long v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }   // bits that hold 0 .. v
 long ce_isqrt_host(long v) { long r = 0; for (long b = 1L << 15; b; b >>= 1) if ((r | b) * (r | b) <= v) r |= b; return r; }
 
 // what depends on the lattice and on n, once
@@ -358,7 +357,7 @@ int clearance_stage(lbmdem_handle* h) {
   auto& V = h->clr;
   if (V.words) return LBMDEM_OK;
   const size_t N = (size_t)h->L.lx * h->L.sy;
-  const long nb = ce_blocks((long)N, CE_THREADS);
+  const long nb = stage_blocks((long)N, CE_THREADS);
   const int side = h->L.lx < h->L.ly ? h->L.lx : h->L.ly;
   V.hbins = (side + 1) / 2 + 2;   // isqrt(d2) <= (min(lx, ly) + 1) / 2
   HIP_TRY(h->mem.dev(&V.key, N));
@@ -375,14 +374,11 @@ int clearance_stage(lbmdem_handle* h) {
 
 int clearance_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
-  const auto& V = h->clr;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq)
+  if (!h->clr.at.current(h))
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_clearance_compute has been made for the map as it is now", who);
   return LBMDEM_OK;
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
-
-unsigned ce_be(int v) { return __builtin_bswap32((unsigned)v); }
 
 }  // namespace
 
@@ -432,33 +428,13 @@ int lbmdem_write_clearance_files(const char* dir, int nfile, int lx, int ly, int
   for (int i = 0; i <= n; ++i) fprintf(fp, "%d %ld %d\n", i, owned[i], d2max[i]);
   RC_TRY(F.close());
   if (plane) {
-    std::vector<unsigned> image((size_t)cnt);
-    const float pas = (float)(1. / lx);   // (lbmdem_vtk_put_mesh's)
-    RC_TRY(F.open("w+", dir, "clearance%.6i.vtk", nfile));
-    fp = F.fp;
-    fprintf(fp, "# vtk DataFile Version 2.0\nlbmdem pore clearance\nBINARY\nDATASET STRUCTURED_POINTS\n");
-    fprintf(fp, "DIMENSIONS %d %d 1\nORIGIN 0 0 0\nSPACING %.9g %.9g 1\n", lx, ly, (double)pas, (double)pas);
-    fprintf(fp, "POINT_DATA %ld\n", cnt);
-    bool short_write = false;
     const int* const planes[2] = {d2, owner};
     const char* const names[2] = {"d2", "owner"};
-    for (int k = 0; k < 2; ++k) {
-      for (int y = 0; y < ly; ++y)
-        for (int x = 0; x < lx; ++x) image[(size_t)y * lx + x] = ce_be(planes[k][(size_t)x * ly + y]);
-      fprintf(fp, "SCALARS %s int 1\nLOOKUP_TABLE default\n", names[k]);
-      short_write = short_write || fwrite(image.data(), 4, (size_t)cnt, fp) != (size_t)cnt;
-      fprintf(fp, "\n");
-    }
-    RC_TRY(F.close(short_write));
+    RC_TRY(stage_write_int_planes(F, dir, nfile, "clearance%.6i.vtk", "lbmdem pore clearance", lx, ly, names, planes, 2));
   }
-  RC_TRY(F.open("a", dir, "clearance.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t fluid_nodes d2_max d2_max_node sum_d2 ridge_edges throats grain_throats narrowest_c ownerless_grains kmax\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_CLEARANCE_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  return stage_append_row(F, dir, "clearance.data",
+                          "# t fluid_nodes d2_max d2_max_node sum_d2 ridge_edges throats grain_throats narrowest_c ownerless_grains kmax",
+                          t, counts10, LBMDEM_CLEARANCE_COUNTS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -485,24 +461,17 @@ int lbmdem_clearance_compute(lbmdem_handle* h, const int* map, long max_edges, l
   if (lx > CE_SIDE_MAX || ly > CE_SIDE_MAX)
     return fail(LBMDEM_EINVAL, "lbmdem_clearance_compute: a lattice of %d x %d nodes has a side above %d: the squared distances are "
                                "32-bit integers", lx, ly, CE_SIDE_MAX);
-  if (max_edges < 0 || max_edges > (long)INT_MAX)
-    return fail(LBMDEM_EINVAL, "lbmdem_clearance_compute: max_edges must lie in 0 .. %d (%ld)", INT_MAX, max_edges);
+  RC_TRY(stage_check_max_edges("lbmdem_clearance_compute", max_edges));
   auto& V = h->clr;
-  V.valid = false;
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_clearance_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  V.at.valid = false;
+  RC_TRY(stage_check_map("lbmdem_clearance_compute", map, lx, ly, n));
   RC_TRY(clearance_stage(h));
   const hipStream_t st = h->stream;
   const long N = (long)lx * sy;
   CeJob J{};
   J.M = reader_obst(h);
   if (map) {
-    if (!V.map) HIP_TRY(h->mem.dev(&V.map, (size_t)N));
-    // host rows of ly into device rows of sy; the pad columns are never read
-    HIP_TRY(hipMemcpy2DAsync(V.map, sizeof(int) * sy, map, sizeof(int) * ly, sizeof(int) * ly, lx, hipMemcpyHostToDevice, st));
+    RC_TRY(stage_upload_map(h, &V.map, map));
     J.M = V.map;
   }
   J.lx = lx; J.ly = ly; J.sy = sy; J.n = n;
@@ -511,13 +480,13 @@ int lbmdem_clearance_compute(lbmdem_handle* h, const int* map, long max_edges, l
   J.hist = V.hist; J.hbins = V.hbins;
   J.owned = V.owned; J.d2max = V.d2max;
   J.words = V.words;
-  J.nblocks = ce_blocks(N, CE_THREADS);
+  J.nblocks = stage_blocks(N, CE_THREADS);
   J.cnt = V.cnt; J.off = V.cnt + J.nblocks + 1;
-  J.pbits = ce_bits((unsigned long long)((long)lx * ly - 1));
+  J.pbits = stage_bits((unsigned long long)((long)lx * ly - 1));
   const int need = V.hbins > n + 1 ? V.hbins : n + 1;
-  hipLaunchKernelGGL(k_ce_init, dim3((unsigned)ce_blocks(need > CE_WORDS ? need : CE_WORDS, CE_THREADS)), dim3(CE_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_ce_row, dim3((unsigned)ce_blocks(lx, CE_THREADS / 64)), dim3(CE_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_ce_col, dim3((unsigned)ce_blocks(sy, CE_THREADS), (unsigned)ce_blocks(lx, CE_ROWS)), dim3(CE_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_ce_init, dim3((unsigned)stage_blocks(need > CE_WORDS ? need : CE_WORDS, CE_THREADS)), dim3(CE_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_ce_row, dim3((unsigned)stage_blocks(lx, CE_THREADS / 64)), dim3(CE_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_ce_col, dim3((unsigned)stage_blocks(sy, CE_THREADS), (unsigned)stage_blocks(lx, CE_ROWS)), dim3(CE_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_ce_count, dim3((unsigned)J.nblocks), dim3(CE_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   size_t b = 0;
@@ -553,8 +522,8 @@ int lbmdem_clearance_compute(lbmdem_handle* h, const int* map, long max_edges, l
     HIP_TRY(hipGetLastError());
     const int side = lx < ly ? lx : ly;
     const long dtop = (long)((side + 1) / 2 + 1) * ((side + 1) / 2 + 1);
-    const int vbits = J.pbits + ce_bits((unsigned long long)dtop);
-    const int kbits = ce_bits((unsigned long long)(n + 1) * (unsigned long long)(n + 1));
+    const int vbits = J.pbits + stage_bits((unsigned long long)dtop);
+    const int kbits = stage_bits((unsigned long long)(n + 1) * (unsigned long long)(n + 1));
     size_t b1 = 0, b2 = 0, b3 = 0, b4 = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, rv0, rv1, rk0, rk1, E, 0, vbits, st));
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, rk1, rk0, rv1, rv0, E, 0, kbits, st));
@@ -575,10 +544,10 @@ int lbmdem_clearance_compute(lbmdem_handle* h, const int* map, long max_edges, l
     HIP_TRY(h->mem.grow(&V.table, &V.table_cap, (long)T + T / 4 + 64));
     J.uniq = V.uniq; J.runs = runs; J.offs = offs;
     J.table = V.table; J.nthroats = T;
-    hipLaunchKernelGGL(k_ce_throats, dim3((unsigned)ce_blocks(T, CE_THREADS)), dim3(CE_THREADS), 0, st, J);
+    hipLaunchKernelGGL(k_ce_throats, dim3((unsigned)stage_blocks(T, CE_THREADS)), dim3(CE_THREADS), 0, st, J);
   }
   J.table = V.table; J.nthroats = T;
-  hipLaunchKernelGGL(k_ce_census, dim3((unsigned)ce_blocks(T > n ? T : n, CE_THREADS)), dim3(CE_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_ce_census, dim3((unsigned)stage_blocks(T > n ? T : n, CE_THREADS)), dim3(CE_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned long long w[CE_WORDS] = {};
   HIP_TRY(hipMemcpyAsync(w, V.words, sizeof w, hipMemcpyDeviceToHost, st));
@@ -595,10 +564,9 @@ int lbmdem_clearance_compute(lbmdem_handle* h, const int* map, long max_edges, l
   counts10[8] = (long)w[CE_W_OWNERLESS];
   counts10[9] = ce_isqrt_host(d2_max);
   V.nedges = E; V.nthroats = T; V.kmax = (int)counts10[9];
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
   V.own = map == nullptr;
   V.gen += 1;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -608,9 +576,8 @@ int lbmdem_download_clearance(lbmdem_handle* h, int* d2, int* owner) try {
   CHECK_H(h);
   if (!d2 && !owner) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(clearance_ready(h, "lbmdem_download_clearance"));
-  const LatticeView& L = h->L;
-  if (d2) HIP_TRY(hipMemcpy2DAsync(d2, sizeof(int) * L.ly, h->clr.d2, sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx, hipMemcpyDeviceToHost, h->stream));
-  if (owner) HIP_TRY(hipMemcpy2DAsync(owner, sizeof(int) * L.ly, h->clr.owner, sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx, hipMemcpyDeviceToHost, h->stream));
+  if (d2) RC_TRY(stage_download_plane(h, d2, h->clr.d2));
+  if (owner) RC_TRY(stage_download_plane(h, owner, h->clr.owner));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -633,14 +600,7 @@ int lbmdem_download_clearance_hist(lbmdem_handle* h, long* hist, long cap, long*
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !hist)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(clearance_ready(h, "lbmdem_download_clearance_hist"));
-  const auto& V = h->clr;
-  const long bins = (long)V.kmax + 1;
-  *count = bins;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < bins) return fail(LBMDEM_EINVAL, "lbmdem_download_clearance_hist: there are %ld bins, the buffer holds %ld", bins, cap);
-  HIP_TRY(hipMemcpyAsync(hist, V.hist, sizeof(long) * (size_t)bins, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return LBMDEM_OK;
+  return stage_table(h, "lbmdem_download_clearance_hist", "bins", h->clr.hist, sizeof *hist, (long)h->clr.kmax + 1, hist, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -648,7 +608,7 @@ int lbmdem_download_clearance_hist(lbmdem_handle* h, long* hist, long cap, long*
 int lbmdem_download_clearance_owners(lbmdem_handle* h, long* owned, int* d2max) try {
   CHECK_H(h);
   RC_TRY(clearance_ready(h, "lbmdem_download_clearance_owners"));
-  const size_t m = (size_t)h->n + 1;
+  const size_t m = (size_t)h->n + 1;   // (a fixed length and no cap: not a stage_table)
   if (owned) HIP_TRY(hipMemcpyAsync(owned, h->clr.owned, sizeof(long) * m, hipMemcpyDeviceToHost, h->stream));
   if (d2max) HIP_TRY(hipMemcpyAsync(d2max, h->clr.d2max, sizeof(int) * m, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -671,16 +631,7 @@ int lbmdem_download_throats(lbmdem_handle* h, lbmdem_throat* out, long cap, long
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(clearance_ready(h, "lbmdem_download_throats"));
-  const auto& V = h->clr;
-  *count = V.nthroats;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < V.nthroats)
-    return fail(LBMDEM_EINVAL, "lbmdem_download_throats: there are %ld throats, the buffer holds %ld", V.nthroats, cap);
-  if (V.nthroats > 0) {
-    HIP_TRY(hipMemcpyAsync(out, V.table, sizeof(lbmdem_throat) * (size_t)V.nthroats, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return LBMDEM_OK;
+  return stage_table(h, "lbmdem_download_throats", "throats", h->clr.table, sizeof *out, h->clr.nthroats, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }

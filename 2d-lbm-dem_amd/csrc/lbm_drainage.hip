@@ -24,9 +24,11 @@
 //   k_dr_tables   one lane per body and link: the reached bodies, pass, the front links (critical is there by now).
 // Integer atomics only, no floating point anywhere. Every loop has the bound its comment states.
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
-// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h).
+// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h),
+// lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 
@@ -226,8 +228,6 @@ __global__ __launch_bounds__(DR_THREADS) void k_dr_tables(const DrJob J) {
   }
 }
 
-long dr_blocks(long items, int per) { return (items + per - 1) / per; }
-
 // what depends on the lattice, once (the clearance stage, whose bin count this one shares, is there: a network compute has run)
 int drainage_stage(lbmdem_handle* h) {
   auto& V = h->drn;
@@ -244,34 +244,12 @@ int drainage_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
   const auto& V = h->drn;
   const auto& W = h->net;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq || !W.valid || W.gen != V.gen)
+  if (!V.at.current(h) || !W.at.valid || W.gen != V.gen)
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_drainage_compute has been made for the map as it is now", who);
   return LBMDEM_OK;
 }
 
-// the tables are sized alike: cap = 0 reports *count, a short buffer is refused with *count set and nothing written
-int drainage_table(lbmdem_handle* h, const char* who, const char* what, const void* src, size_t each, long have, void* out, long cap,
-                   long* count) {
-  *count = have;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < have) return fail(LBMDEM_EINVAL, "%s: there are %ld %s, the buffer holds %ld", who, have, what, cap);
-  if (have > 0) {
-    HIP_TRY(hipMemcpyAsync(out, src, each * (size_t)have, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return LBMDEM_OK;
-}
-
-int drainage_sides(const char* who, int from, int band, int to) {
-  if (from < 1 || from > 15)
-    return fail(LBMDEM_EINVAL, "%s: from must be a mask of sides, B 1 | T 2 | L 4 | R 8, with at least one (%d)", who, from);
-  if (to < 0 || to > 15) return fail(LBMDEM_EINVAL, "%s: to must be a mask of sides, B 1 | T 2 | L 4 | R 8, or 0 for no outlet (%d)", who, to);
-  if (band < 1) return fail(LBMDEM_EINVAL, "%s: band must be at least 1 node (%d)", who, band);
-  return LBMDEM_OK;
-}
 #endif   // !LBMDEM_SINGLE_PRECISION
-
-unsigned dr_be(int v) { return __builtin_bswap32((unsigned)v); }
 
 }  // namespace
 
@@ -328,29 +306,12 @@ int lbmdem_write_drainage_files(const char* dir, int nfile, int lx, int ly, int 
   for (long k = 0; k < nbodies; ++k) fprintf(fp, "%ld %d %d %d\n", k, bodies[k].node, bodies[k].d2, A[k]);
   RC_TRY(F.close());
   if (plane) {
-    std::vector<unsigned> image((size_t)cnt);
-    const float pas = (float)(1. / lx);   // (lbmdem_vtk_put_mesh's)
-    RC_TRY(F.open("w+", dir, "drainage%.6i.vtk", nfile));
-    fp = F.fp;
-    fprintf(fp, "# vtk DataFile Version 2.0\nlbmdem drainage\nBINARY\nDATASET STRUCTURED_POINTS\n");
-    fprintf(fp, "DIMENSIONS %d %d 1\nORIGIN 0 0 0\nSPACING %.9g %.9g 1\n", lx, ly, (double)pas, (double)pas);
-    fprintf(fp, "POINT_DATA %ld\n", cnt);
-    for (int y = 0; y < ly; ++y)
-      for (int x = 0; x < lx; ++x) image[(size_t)y * lx + x] = dr_be(access[(size_t)x * ly + y]);
-    fprintf(fp, "SCALARS access int 1\nLOOKUP_TABLE default\n");
-    const bool short_write = fwrite(image.data(), 4, (size_t)cnt, fp) != (size_t)cnt;
-    fprintf(fp, "\n");
-    RC_TRY(F.close(short_write));
+    const char* const names[1] = {"access"};
+    RC_TRY(stage_write_int_planes(F, dir, nfile, "drainage%.6i.vtk", "lbmdem drainage", lx, ly, names, &access, 1));
   }
-  RC_TRY(F.open("a", dir, "drainage.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t fluid_nodes inlet_nodes reached_nodes reached_bodies access_max shielded_nodes outlet_nodes critical critical_node "
-                "front_links\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_DRAINAGE_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  return stage_append_row(F, dir, "drainage.data",
+                          "# t fluid_nodes inlet_nodes reached_nodes reached_bodies access_max shielded_nodes outlet_nodes critical "
+                          "critical_node front_links", t, counts10, LBMDEM_DRAINAGE_COUNTS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -375,24 +336,17 @@ int lbmdem_drainage_compute(lbmdem_handle* h, const int* map, int from, int band
   const LatticeView& L = h->L;
   const int lx = L.lx, ly = L.ly, sy = L.sy, n = h->n;
   auto& V = h->drn;
-  V.valid = false;
+  V.at.valid = false;
   if (lx > DR_SIDE_MAX || ly > DR_SIDE_MAX)
     return fail(LBMDEM_EINVAL, "lbmdem_drainage_compute: a lattice of %d x %d nodes has a side above %d: the squared distances are "
                                "32-bit integers", lx, ly, DR_SIDE_MAX);
-  RC_TRY(drainage_sides("lbmdem_drainage_compute", from, band, to));
-  if (max_edges < 0 || max_edges > (long)INT_MAX)
-    return fail(LBMDEM_EINVAL, "lbmdem_drainage_compute: max_edges must lie in 0 .. %d (%ld)", INT_MAX, max_edges);
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_drainage_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  RC_TRY(stage_check_sides("lbmdem_drainage_compute", from, band, to));
+  RC_TRY(stage_check_max_edges("lbmdem_drainage_compute", max_edges));
+  RC_TRY(stage_check_map("lbmdem_drainage_compute", map, lx, ly, n));
   // the network first: the result of the handle's map is reused while its guard calls it valid and the d2 it was made over is there
   const auto& Q = h->clr;
   const auto& W = h->net;
-  const bool clearance_there = Q.valid && Q.own && Q.seq == h->substep_seq && Q.moved == h->grains_moved && Q.fluid == h->lattice_seq;
-  const bool network_there = W.valid && W.own && W.seq == h->substep_seq && W.moved == h->grains_moved && W.fluid == h->lattice_seq;
-  if (map || !clearance_there || !network_there) {
+  if (map || !(Q.at.current(h) && Q.own) || !(W.at.current(h) && W.own)) {
     long nc[LBMDEM_NETWORK_COUNTS];
     RC_TRY(lbmdem_network_compute(h, map, -1, max_edges, nc));
   }
@@ -416,14 +370,14 @@ int lbmdem_drainage_compute(lbmdem_handle* h, const int* map, int from, int band
   HIP_TRY(hipMemsetAsync(V.words, 0, sizeof(dr_u64) * DR_WORDS, st));
   HIP_TRY(hipMemsetAsync(V.hist, 0, sizeof(dr_u64) * (size_t)Q.hbins, st));
   HIP_TRY(hipMemsetAsync(V.A, 0, sizeof(int) * (size_t)(B > 0 ? B : 1), st));
-  if (B > 0) hipLaunchKernelGGL(k_dr_seed, dim3((unsigned)dr_blocks(J.N, DR_THREADS)), dim3(DR_THREADS), 0, st, J);
+  if (B > 0) hipLaunchKernelGGL(k_dr_seed, dim3((unsigned)stage_blocks(J.N, DR_THREADS)), dim3(DR_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   // the relaxation: until a launch raises nothing
   V.rounds = 0;
   for (long round = 1; nl > 0; ++round) {
     if (round > B + 1) return fail(LBMDEM_EINVAL, "lbmdem_drainage_compute: the relaxation did not settle in %ld rounds", B + 1);
     HIP_TRY(hipMemsetAsync(V.words + DR_W_CHANGED, 0, sizeof(dr_u64), st));
-    hipLaunchKernelGGL(k_dr_relax, dim3((unsigned)dr_blocks(nl, DR_CHUNK)), dim3(DR_THREADS), 0, st, J);
+    hipLaunchKernelGGL(k_dr_relax, dim3((unsigned)stage_blocks(nl, DR_CHUNK)), dim3(DR_THREADS), 0, st, J);
     HIP_TRY(hipGetLastError());
     unsigned long long changed = 0;
     HIP_TRY(hipMemcpyAsync(&changed, V.words + DR_W_CHANGED, sizeof changed, hipMemcpyDeviceToHost, st));
@@ -431,9 +385,9 @@ int lbmdem_drainage_compute(lbmdem_handle* h, const int* map, int from, int band
     V.rounds = (int)round;
     if (!changed) break;
   }
-  hipLaunchKernelGGL(k_dr_plane, dim3((unsigned)dr_blocks(sy, DR_THREADS), (unsigned)dr_blocks(lx, DR_ROWS)), dim3(DR_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_dr_plane, dim3((unsigned)stage_blocks(sy, DR_THREADS), (unsigned)stage_blocks(lx, DR_ROWS)), dim3(DR_THREADS), 0, st, J);
   const long items = B > nl ? B : nl;
-  if (items > 0) hipLaunchKernelGGL(k_dr_tables, dim3((unsigned)dr_blocks(items, DR_THREADS)), dim3(DR_THREADS), 0, st, J);
+  if (items > 0) hipLaunchKernelGGL(k_dr_tables, dim3((unsigned)stage_blocks(items, DR_THREADS)), dim3(DR_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned long long w[DR_WORDS] = {};
   HIP_TRY(hipMemcpyAsync(w, V.words, sizeof w, hipMemcpyDeviceToHost, st));
@@ -450,8 +404,7 @@ int lbmdem_drainage_compute(lbmdem_handle* h, const int* map, int from, int band
   counts10[9] = (long)w[DR_W_FRONT];
   V.nbodies = B; V.nlinks = nl; V.kmax = Q.kmax;
   V.gen = W.gen;
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -461,8 +414,7 @@ int lbmdem_download_drainage(lbmdem_handle* h, int* access) try {
   CHECK_H(h);
   if (!access) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(drainage_ready(h, "lbmdem_download_drainage"));
-  const LatticeView& L = h->L;
-  HIP_TRY(hipMemcpy2DAsync(access, sizeof(int) * L.ly, h->drn.access, sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx, hipMemcpyDeviceToHost, h->stream));
+  RC_TRY(stage_download_plane(h, access, h->drn.access));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -484,7 +436,7 @@ int lbmdem_download_drainage_bodies(lbmdem_handle* h, int* A, long cap, long* co
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !A)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(drainage_ready(h, "lbmdem_download_drainage_bodies"));
-  return drainage_table(h, "lbmdem_download_drainage_bodies", "bodies", h->drn.A, sizeof *A, h->drn.nbodies, A, cap, count);
+  return stage_table(h, "lbmdem_download_drainage_bodies", "bodies", h->drn.A, sizeof *A, h->drn.nbodies, A, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -493,7 +445,7 @@ int lbmdem_download_drainage_links(lbmdem_handle* h, int* pass, long cap, long* 
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !pass)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(drainage_ready(h, "lbmdem_download_drainage_links"));
-  return drainage_table(h, "lbmdem_download_drainage_links", "links", h->drn.pass, sizeof *pass, h->drn.nlinks, pass, cap, count);
+  return stage_table(h, "lbmdem_download_drainage_links", "links", h->drn.pass, sizeof *pass, h->drn.nlinks, pass, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -502,7 +454,7 @@ int lbmdem_download_drainage_hist(lbmdem_handle* h, long* hist, long cap, long* 
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !hist)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(drainage_ready(h, "lbmdem_download_drainage_hist"));
-  return drainage_table(h, "lbmdem_download_drainage_hist", "bins", h->drn.hist, sizeof *hist, (long)h->drn.kmax + 1, hist, cap, count);
+  return stage_table(h, "lbmdem_download_drainage_hist", "bins", h->drn.hist, sizeof *hist, (long)h->drn.kmax + 1, hist, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -550,7 +502,7 @@ int lbmdem_set_drainage_output(lbmdem_handle* h, int on, int from, int band, int
   if (!h) return fail(LBMDEM_EINVAL, "null handle");
   if (on) {
     RC_TRY(whole_handle(h, "lbmdem_set_drainage_output"));
-    RC_TRY(drainage_sides("lbmdem_set_drainage_output", from, band, to));
+    RC_TRY(stage_check_sides("lbmdem_set_drainage_output", from, band, to));
     h->drainage_from = from; h->drainage_band = band; h->drainage_to = to;
     h->drainage_plane = plane != 0;
   }

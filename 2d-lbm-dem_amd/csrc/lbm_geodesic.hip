@@ -26,9 +26,11 @@
 //   k_geo_detour   one lane per node: detour (shortest is there by now) and path_nodes.
 // Integer atomics only, no floating point in a kernel.
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
-// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h).
+// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h),
+// lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 
@@ -363,8 +365,6 @@ __global__ __launch_bounds__(GEO_THREADS) void k_geo_detour(const GeoJob J) {
   if ((threadIdx.x & 63) == 0 && n) atomicAdd(&J.words[GEO_W_PATH], n);
 }
 
-long geo_blocks(long items, int per) { return (items + per - 1) / per; }
-
 // the largest depth on the lattice: depth = min(along y, along x), and the two vary independently
 int geo_depthmax(int lx, int ly, int from) {
   int dy = INT_MAX, dx = INT_MAX;
@@ -378,7 +378,7 @@ int geodesic_stage(lbmdem_handle* h) {
   auto& V = h->geo;
   if (V.words) return LBMDEM_OK;
   const size_t N = (size_t)h->L.lx * h->L.sy;
-  const size_t tiles = (size_t)geo_blocks(h->L.lx, GEO_TX) * (size_t)geo_blocks(h->L.ly, GEO_TY);
+  const size_t tiles = (size_t)stage_blocks(h->L.lx, GEO_TX) * (size_t)stage_blocks(h->L.ly, GEO_TY);
   HIP_TRY(h->mem.dev(&V.dist, N));
   HIP_TRY(h->mem.dev(&V.back, N));
   HIP_TRY(h->mem.dev(&V.detour, N));
@@ -398,7 +398,7 @@ int geodesic_pass(lbmdem_handle* h, GeoJob J, int* plane, int mask, int wbase, i
   HIP_TRY(hipMemsetAsync(V.stamp, 0, sizeof(int) * (size_t)tiles, st));
   HIP_TRY(hipMemsetAsync(V.cnt, 0, sizeof(unsigned) * 2, st));
   J.next = 1; J.list_in = nullptr; J.list_out = V.list; J.cnt_out = V.cnt;
-  hipLaunchKernelGGL(k_geo_seed, dim3((unsigned)geo_blocks(J.sy, GEO_THREADS), (unsigned)geo_blocks(J.lx, GEO_ROWS)), dim3(GEO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_geo_seed, dim3((unsigned)stage_blocks(J.sy, GEO_THREADS), (unsigned)stage_blocks(J.lx, GEO_ROWS)), dim3(GEO_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned listed = 0;
   unsigned long long passable = 0;
@@ -429,24 +429,18 @@ int geodesic_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
   const auto& V = h->geo;
   const auto& Q = h->clr;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq ||
-      (V.over_clearance && (!Q.valid || Q.gen != V.gen)))
+  if (!V.at.current(h) || (V.over_clearance && (!Q.at.valid || Q.gen != V.gen)))
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_geodesic_compute has been made for the map as it is now", who);
   return LBMDEM_OK;
 }
 
 int geodesic_args(const char* who, int from, int band, int to, int conn, int min_d2) {
-  if (from < 1 || from > 15)
-    return fail(LBMDEM_EINVAL, "%s: from must be a mask of sides, B 1 | T 2 | L 4 | R 8, with at least one (%d)", who, from);
-  if (to < 0 || to > 15) return fail(LBMDEM_EINVAL, "%s: to must be a mask of sides, B 1 | T 2 | L 4 | R 8, or 0 for no outlet (%d)", who, to);
-  if (band < 1) return fail(LBMDEM_EINVAL, "%s: band must be at least 1 node (%d)", who, band);
+  RC_TRY(stage_check_sides(who, from, band, to));
   if (conn != 4 && conn != 8) return fail(LBMDEM_EINVAL, "%s: conn must be 4 or 8 (%d)", who, conn);
   if (min_d2 < 0) return fail(LBMDEM_EINVAL, "%s: min_d2 must not be negative (%d)", who, min_d2);
   return LBMDEM_OK;
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
-
-unsigned geo_be(int v) { return __builtin_bswap32((unsigned)v); }
 
 }  // namespace
 
@@ -472,14 +466,13 @@ int lbmdem_write_geodesic_files(const char* dir, int nfile, int lx, int ly, int 
                                  "nodes", k, e.dmin, e.dmax, e.reached);
   }
   const long cnt = (long)lx * ly;
-  if (plane) {
-    const int* const planes[3] = {dist, back, detour};
-    const char* const names[3] = {"dist", "back", "detour"};
+  const int* const planes[3] = {dist, back, detour};
+  const char* const names[3] = {"dist", "back", "detour"};
+  if (plane)
     for (int i = 0; i < 3; ++i)
       for (long k = 0; k < cnt; ++k)
         if (planes[i][k] < -1)
           return fail(LBMDEM_EINVAL, "lbmdem_write_geodesic_files: %s[%ld][%ld] = %d is below -1", names[i], k / ly, k % ly, planes[i][k]);
-  }
   OutFile F;
   RC_TRY(F.open("w", dir, "geodesic_profile%.6i.dat", nfile));
   FILE* fp = F.fp;
@@ -492,35 +485,10 @@ int lbmdem_write_geodesic_files(const char* dir, int nfile, int lx, int ly, int 
     fprintf(fp, "%ld %ld %ld %ld %d %d %.6f\n", k, e.nodes, e.reached, e.sum, e.dmin, e.dmax, tau);
   }
   RC_TRY(F.close());
-  if (plane) {
-    std::vector<unsigned> image((size_t)cnt);
-    const float pas = (float)(1. / lx);   // (lbmdem_vtk_put_mesh's)
-    RC_TRY(F.open("w+", dir, "geodesic%.6i.vtk", nfile));
-    fp = F.fp;
-    fprintf(fp, "# vtk DataFile Version 2.0\nlbmdem geodesic\nBINARY\nDATASET STRUCTURED_POINTS\n");
-    fprintf(fp, "DIMENSIONS %d %d 1\nORIGIN 0 0 0\nSPACING %.9g %.9g 1\n", lx, ly, (double)pas, (double)pas);
-    fprintf(fp, "POINT_DATA %ld\n", cnt);
-    bool short_write = false;
-    const int* const planes[3] = {dist, back, detour};
-    const char* const names[3] = {"dist", "back", "detour"};
-    for (int k = 0; k < 3; ++k) {
-      for (int y = 0; y < ly; ++y)
-        for (int x = 0; x < lx; ++x) image[(size_t)y * lx + x] = geo_be(planes[k][(size_t)x * ly + y]);
-      fprintf(fp, "SCALARS %s int 1\nLOOKUP_TABLE default\n", names[k]);
-      short_write = short_write || fwrite(image.data(), 4, (size_t)cnt, fp) != (size_t)cnt;
-      fprintf(fp, "\n");
-    }
-    RC_TRY(F.close(short_write));
-  }
-  RC_TRY(F.open("a", dir, "geodesic.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t fluid_nodes passable_nodes inlet_nodes reached_nodes dist_max outlet_nodes outlet_reached shortest shortest_node "
-                "path_nodes\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_GEODESIC_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  if (plane) RC_TRY(stage_write_int_planes(F, dir, nfile, "geodesic%.6i.vtk", "lbmdem geodesic", lx, ly, names, planes, 3));
+  return stage_append_row(F, dir, "geodesic.data",
+                          "# t fluid_nodes passable_nodes inlet_nodes reached_nodes dist_max outlet_nodes outlet_reached shortest "
+                          "shortest_node path_nodes", t, counts10, LBMDEM_GEODESIC_COUNTS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -544,27 +512,19 @@ int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map, int from, int band
   const LatticeView& L = h->L;
   const int lx = L.lx, ly = L.ly, sy = L.sy, n = h->n;
   auto& V = h->geo;
-  V.valid = false;
+  V.at.valid = false;
   RC_TRY(geodesic_args("lbmdem_geodesic_compute", from, band, to, conn, min_d2));
   if (lx > GEO_SIDE_MAX || ly > GEO_SIDE_MAX || 7 * (long)lx * ly > (long)INT_MAX)
     return fail(LBMDEM_EINVAL, "lbmdem_geodesic_compute: a lattice of %d x %d nodes has a side above %d or more than %d nodes: a "
                                "distance is a 32-bit integer", lx, ly, GEO_SIDE_MAX, INT_MAX / 7);
-  if (max_edges < 0 || max_edges > (long)INT_MAX)
-    return fail(LBMDEM_EINVAL, "lbmdem_geodesic_compute: max_edges must lie in 0 .. %d (%ld)", INT_MAX, max_edges);
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_geodesic_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  RC_TRY(stage_check_max_edges("lbmdem_geodesic_compute", max_edges));
+  RC_TRY(stage_check_map("lbmdem_geodesic_compute", map, lx, ly, n));
   // min_d2 > 1: the clearance first; the result of the handle's map is reused while its guard calls it valid
   const auto& Q = h->clr;
   const bool narrow = min_d2 > 1;
-  if (narrow) {
-    const bool there = Q.valid && Q.own && Q.seq == h->substep_seq && Q.moved == h->grains_moved && Q.fluid == h->lattice_seq;
-    if (map || !there) {
-      long cc[LBMDEM_CLEARANCE_COUNTS];
-      RC_TRY(lbmdem_clearance_compute(h, map, max_edges, cc));
-    }
+  if (narrow && (map || !(Q.at.current(h) && Q.own))) {
+    long cc[LBMDEM_CLEARANCE_COUNTS];
+    RC_TRY(lbmdem_clearance_compute(h, map, max_edges, cc));
   }
   RC_TRY(geodesic_stage(h));
   const hipStream_t st = h->stream;
@@ -572,9 +532,7 @@ int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map, int from, int band
   GeoJob J{};
   if (narrow) J.d2 = Q.d2;
   else if (map) {
-    if (!V.map) HIP_TRY(h->mem.dev(&V.map, (size_t)N));
-    // host rows of ly into device rows of sy; the pad columns are never read
-    HIP_TRY(hipMemcpy2DAsync(V.map, sizeof(int) * sy, map, sizeof(int) * ly, sizeof(int) * ly, lx, hipMemcpyHostToDevice, st));
+    RC_TRY(stage_upload_map(h, &V.map, map));
     J.M = V.map;
   } else J.M = reader_obst(h);
   J.min_d2 = min_d2;
@@ -582,7 +540,7 @@ int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map, int from, int band
   J.band = band < GEO_SIDE_MAX ? band : GEO_SIDE_MAX;   // (the sides are clamped to the lattice)
   J.from = from; J.to = to;
   J.N = N;
-  J.ntx = (int)geo_blocks(lx, GEO_TX); J.nty = (int)geo_blocks(ly, GEO_TY);
+  J.ntx = (int)stage_blocks(lx, GEO_TX); J.nty = (int)stage_blocks(ly, GEO_TY);
   J.dist = V.dist; J.back = V.back; J.detour = V.detour;
   J.stamp = V.stamp;
   J.words = V.words;
@@ -599,8 +557,8 @@ int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map, int from, int band
   RC_TRY(geodesic_pass(h, J, V.dist, from, GEO_W_FLUID, &V.rounds[0]));   // (synchronises: the caller's map has been read)
   if (to) RC_TRY(geodesic_pass(h, J, V.back, to, GEO_W_BACK0, &V.rounds[1]));
   else HIP_TRY(hipMemsetAsync(V.back, 0xFF, sizeof(int) * (size_t)N, st));
-  hipLaunchKernelGGL(k_geo_finish, dim3((unsigned)geo_blocks(sy, GEO_THREADS), (unsigned)geo_blocks(lx, GEO_ROWS)), dim3(GEO_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_geo_detour, dim3((unsigned)geo_blocks(N, GEO_THREADS)), dim3(GEO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_geo_finish, dim3((unsigned)stage_blocks(sy, GEO_THREADS), (unsigned)stage_blocks(lx, GEO_ROWS)), dim3(GEO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_geo_detour, dim3((unsigned)stage_blocks(N, GEO_THREADS)), dim3(GEO_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned long long w[GEO_WORDS] = {};
   std::vector<unsigned long long> lev(3 * (size_t)nd);
@@ -629,8 +587,7 @@ int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map, int from, int band
   }
   V.over_clearance = narrow && !map;
   V.gen = Q.gen;
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -639,12 +596,10 @@ int lbmdem_geodesic_compute(lbmdem_handle* h, const int* map, int from, int band
 int lbmdem_download_geodesic(lbmdem_handle* h, int* dist, int* back, int* detour) try {
   CHECK_H(h);
   RC_TRY(geodesic_ready(h, "lbmdem_download_geodesic"));
-  const LatticeView& L = h->L;
   int* const out[3] = {dist, back, detour};
   const int* const src[3] = {h->geo.dist, h->geo.back, h->geo.detour};
   for (int k = 0; k < 3; ++k)
-    if (out[k])
-      HIP_TRY(hipMemcpy2DAsync(out[k], sizeof(int) * L.ly, src[k], sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx, hipMemcpyDeviceToHost, h->stream));
+    if (out[k]) RC_TRY(stage_download_plane(h, out[k], src[k]));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -668,7 +623,7 @@ int lbmdem_download_geodesic_profile(lbmdem_handle* h, lbmdem_geo_level* rec, lo
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !rec)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(geodesic_ready(h, "lbmdem_download_geodesic_profile"));
-  const auto& lv = h->geo.levels;
+  const auto& lv = h->geo.levels;   // (on the host already: not a stage_table)
   const long have = (long)lv.size();
   *count = have;
   if (cap == 0) return LBMDEM_OK;   // (how many there are)

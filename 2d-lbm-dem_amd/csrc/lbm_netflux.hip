@@ -24,9 +24,11 @@
 // is needed: k_nf_regions reads the place's body from the group table. Integer atomics only. Every loop has the bound its comment
 // states.
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
-// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h).
+// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h),
+// lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 
@@ -302,8 +304,6 @@ __global__ __launch_bounds__(NF_THREADS) void k_nf_regions(const NfJob J) {
   }
 }
 
-long nf_blocks(long items, int per) { return (items + per - 1) / per; }
-
 // what depends on the lattice, once
 int netflux_stage(lbmdem_handle* h) {
   auto& V = h->nfx;
@@ -319,21 +319,8 @@ int netflux_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
   const auto& V = h->nfx;
   const auto& W = h->net;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq || !W.valid || W.gen != V.gen)
+  if (!V.at.current(h) || !W.at.valid || W.gen != V.gen)
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_netflux_compute has been made for the map and populations as they are now", who);
-  return LBMDEM_OK;
-}
-
-// the tables are sized alike: cap = 0 reports *count, a short buffer is refused with *count set and nothing written
-int netflux_table(lbmdem_handle* h, const char* who, const char* what, const void* src, size_t each, long have, void* out, long cap,
-                  long* count) {
-  *count = have;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < have) return fail(LBMDEM_EINVAL, "%s: there are %ld %s, the buffer holds %ld", who, have, what, cap);
-  if (have > 0) {
-    HIP_TRY(hipMemcpyAsync(out, src, each * (size_t)have, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
   return LBMDEM_OK;
 }
 
@@ -397,15 +384,9 @@ int lbmdem_write_netflux_files(const char* dir, int nfile, int lx, int ly, int n
   for (int x = 0; x < lx - 1; ++x) fprintf(fp, "x %d %ld\n", x, col[x]);
   for (int y = 0; y < ly - 1; ++y) fprintf(fp, "y %d %ld\n", y, row[y]);
   RC_TRY(F.close());
-  RC_TRY(F.open("a", dir, "netflux.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t fluid_nodes regions links edges ridge_edges unaccumulated_edges unaccumulated_nodes flowing_links strongest_link "
-                "largest_imbalance\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_NETFLUX_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  return stage_append_row(F, dir, "netflux.data",
+                          "# t fluid_nodes regions links edges ridge_edges unaccumulated_edges unaccumulated_nodes flowing_links "
+                          "strongest_link largest_imbalance", t, counts10, LBMDEM_NETFLUX_COUNTS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -427,21 +408,15 @@ int lbmdem_netflux_compute(lbmdem_handle* h, const int* map, int merge, int leve
   const LatticeView& L = h->L;
   const int lx = L.lx, ly = L.ly, sy = L.sy, n = h->n;
   auto& V = h->nfx;
-  V.valid = false;
+  V.at.valid = false;
   if (lx > NF_SIDE_MAX || ly > NF_SIDE_MAX)
     return fail(LBMDEM_EINVAL, "lbmdem_netflux_compute: a lattice of %d x %d nodes has a side above %d: the squared distances of the "
                                "network underneath are 32-bit integers", lx, ly, NF_SIDE_MAX);
   RC_TRY(netflux_params("lbmdem_netflux_compute", merge, level));
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_netflux_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  RC_TRY(stage_check_map("lbmdem_netflux_compute", map, lx, ly, n));
   // the network first: the result of the handle's map is reused while its guard calls it valid and it was made with this merge
   const auto& W = h->net;
-  const bool network_there = W.valid && W.own && W.merge == merge && W.seq == h->substep_seq && W.moved == h->grains_moved &&
-                             W.fluid == h->lattice_seq;
-  if (map || !network_there) {
+  if (map || !(W.at.current(h) && W.own && W.merge == merge)) {
     long nc[LBMDEM_NETWORK_COUNTS];
     RC_TRY(lbmdem_network_compute(h, map, merge, 0, nc));
   }
@@ -471,11 +446,11 @@ int lbmdem_netflux_compute(lbmdem_handle* h, const int* map, int merge, int leve
   HIP_TRY(hipMemsetAsync(V.row, 0, sizeof(long) * (size_t)ly, st));
   HIP_TRY(hipMemsetAsync(V.sums, 0, sizeof(nf_u64) * 3 * (size_t)(B > 0 ? B : 1), st));
   HIP_TRY(hipMemsetAsync(V.links, 0, sizeof(lbmdem_netflux_link) * (size_t)(nl > 0 ? nl : 1), st));
-  hipLaunchKernelGGL(k_nf_first, dim3((unsigned)nf_blocks(B + 1, NF_THREADS)), dim3(NF_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_nf_plane, dim3((unsigned)nf_blocks(sy, NF_THREADS), (unsigned)nf_blocks(lx, NF_ROWS)), dim3(NF_THREADS), 0, st, J);
-  if (nl > 0) hipLaunchKernelGGL(k_nf_tables, dim3((unsigned)nf_blocks(nl, NF_THREADS)), dim3(NF_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_nf_first, dim3((unsigned)stage_blocks(B + 1, NF_THREADS)), dim3(NF_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_nf_plane, dim3((unsigned)stage_blocks(sy, NF_THREADS), (unsigned)stage_blocks(lx, NF_ROWS)), dim3(NF_THREADS), 0, st, J);
+  if (nl > 0) hipLaunchKernelGGL(k_nf_tables, dim3((unsigned)stage_blocks(nl, NF_THREADS)), dim3(NF_THREADS), 0, st, J);
   const long items = nl > R ? nl : R;
-  if (items > 0) hipLaunchKernelGGL(k_nf_regions, dim3((unsigned)nf_blocks(items, NF_THREADS)), dim3(NF_THREADS), 0, st, J);
+  if (items > 0) hipLaunchKernelGGL(k_nf_regions, dim3((unsigned)stage_blocks(items, NF_THREADS)), dim3(NF_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned long long w[NF_WORDS] = {};
   HIP_TRY(hipMemcpyAsync(w, V.words, sizeof w, hipMemcpyDeviceToHost, st));
@@ -493,8 +468,7 @@ int lbmdem_netflux_compute(lbmdem_handle* h, const int* map, int merge, int leve
   V.nlinks = nl; V.nregions = R;
   V.merge = merge; V.level = level;
   V.gen = W.gen;
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -504,7 +478,7 @@ int lbmdem_download_netflux_links(lbmdem_handle* h, lbmdem_netflux_link* out, lo
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(netflux_ready(h, "lbmdem_download_netflux_links"));
-  return netflux_table(h, "lbmdem_download_netflux_links", "links", h->nfx.links, sizeof *out, h->nfx.nlinks, out, cap, count);
+  return stage_table(h, "lbmdem_download_netflux_links", "links", h->nfx.links, sizeof *out, h->nfx.nlinks, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -513,7 +487,7 @@ int lbmdem_download_netflux_regions(lbmdem_handle* h, lbmdem_netflux_region* out
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(netflux_ready(h, "lbmdem_download_netflux_regions"));
-  return netflux_table(h, "lbmdem_download_netflux_regions", "regions", h->nfx.regions, sizeof *out, h->nfx.nregions, out, cap, count);
+  return stage_table(h, "lbmdem_download_netflux_regions", "regions", h->nfx.regions, sizeof *out, h->nfx.nregions, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }

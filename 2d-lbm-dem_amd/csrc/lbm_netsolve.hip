@@ -30,9 +30,11 @@
 // No workgroup waits for another, no floating-point atomics, no grid-wide barrier; integer atomics for the bits and the counts.
 // Every loop has the bound its comment states.
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
-// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h).
+// both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h), OutFile (lbm_outfile.h),
+// lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 #include <math.h>
@@ -386,38 +388,20 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_last(const NsJob J) {
   }
 }
 
-long ns_blocks(long items, int per) { return (items + per - 1) / per; }
-
 // the network's own guard, and that the network result is the one this result was made over
 int netsolve_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
   const auto& V = h->nsv;
   const auto& W = h->net;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq || !W.valid || W.gen != V.gen)
+  if (!V.at.current(h) || !W.at.valid || W.gen != V.gen)
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_netsolve_compute has been made for the map as it is now", who);
-  return LBMDEM_OK;
-}
-
-// the tables are sized alike: cap = 0 reports *count, a short buffer is refused with *count set and nothing written
-int netsolve_table(lbmdem_handle* h, const char* who, const char* what, const void* src, size_t each, long have, void* out, long cap,
-                   long* count) {
-  *count = have;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < have) return fail(LBMDEM_EINVAL, "%s: there are %ld %s, the buffer holds %ld", who, have, what, cap);
-  if (have > 0) {
-    HIP_TRY(hipMemcpyAsync(out, src, each * (size_t)have, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
   return LBMDEM_OK;
 }
 
 int netsolve_params(const char* who, int merge, int level, int from, int band, int to, double rtol, int max_iter) {
   if (level != 0 && level != 1) return fail(LBMDEM_EINVAL, "%s: level must be 0 (between bodies) or 1 (between groups) (%d)", who, level);
   if (merge < -1) return fail(LBMDEM_EINVAL, "%s: merge must be -1 (no merging) or a difference of radii >= 0 (%d)", who, merge);
-  if (from < 1 || from > 15)
-    return fail(LBMDEM_EINVAL, "%s: from must be a mask of sides, B 1 | T 2 | L 4 | R 8, with at least one (%d)", who, from);
-  if (to < 1 || to > 15) return fail(LBMDEM_EINVAL, "%s: to must be a mask of sides, B 1 | T 2 | L 4 | R 8, with at least one (%d)", who, to);
-  if (band < 1) return fail(LBMDEM_EINVAL, "%s: band must be at least 1 node (%d)", who, band);
+  RC_TRY(stage_check_sides(who, from, band, to, true));   // (an outlet there must be)
   if (!(rtol > 0. && rtol < 1.)) return fail(LBMDEM_EINVAL, "%s: rtol must lie strictly between 0 and 1 (%g)", who, rtol);
   if (max_iter < 0) return fail(LBMDEM_EINVAL, "%s: max_iter must not be negative, 0: the number of free regions (%d)", who, max_iter);
   return LBMDEM_OK;
@@ -470,16 +454,9 @@ int lbmdem_write_netsolve_files(const char* dir, int nfile, int lx, int ly, int 
   fprintf(fp, "# lo hi saddle g q\n");
   for (long k = 0; k < nlinks; ++k) fprintf(fp, "%d %d %d %.17g %.17g\n", links[k].lo, links[k].hi, links[k].saddle, solved[k].g, solved[k].q);
   RC_TRY(F.close());
-  RC_TRY(F.open("a", dir, "netsolve.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t regions links inlet_regions outlet_regions shorted_regions free_regions iterations status flowing_links "
-                "strongest_link Q_in Q_out rz0 rz\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_NETSOLVE_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  for (int k = 0; k < LBMDEM_NETSOLVE_SUMS; ++k) fprintf(fp, " %.17g", sums4[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  return stage_append_row(F, dir, "netsolve.data",
+                          "# t regions links inlet_regions outlet_regions shorted_regions free_regions iterations status flowing_links "
+                          "strongest_link Q_in Q_out rz0 rz", t, counts10, LBMDEM_NETSOLVE_COUNTS, sums4, LBMDEM_NETSOLVE_SUMS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -504,7 +481,7 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
   const LatticeView& L = h->L;
   const int lx = L.lx, ly = L.ly, sy = L.sy, n = h->n;
   auto& V = h->nsv;
-  V.valid = false;
+  V.at.valid = false;
   if (lx > NS_SIDE_MAX || ly > NS_SIDE_MAX)
     return fail(LBMDEM_EINVAL, "lbmdem_netsolve_compute: a lattice of %d x %d nodes has a side above %d: the squared distances of the "
                                "network underneath are 32-bit integers", lx, ly, NS_SIDE_MAX);
@@ -513,16 +490,10 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
     return fail(LBMDEM_EINVAL, "lbmdem_netsolve_compute: model must be 0 (plane Poiseuille from the saddle) or 1 (the caller's g) (%d)", model);
   if (model == 1 && !g_user) return fail(LBMDEM_EINVAL, "lbmdem_netsolve_compute: model 1 needs g_user, one conductance per link");
   if (model == 0 && g_user) return fail(LBMDEM_EINVAL, "lbmdem_netsolve_compute: g_user must be NULL with model 0");
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_netsolve_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  RC_TRY(stage_check_map("lbmdem_netsolve_compute", map, lx, ly, n));
   // the network first: the result of the handle's map is reused while its guard calls it valid and it was made with this merge
   const auto& W = h->net;
-  const bool network_there = W.valid && W.own && W.merge == merge && W.seq == h->substep_seq && W.moved == h->grains_moved &&
-                             W.fluid == h->lattice_seq;
-  if (map || !network_there) {
+  if (map || !(W.at.current(h) && W.own && W.merge == merge)) {
     long nc[LBMDEM_NETWORK_COUNTS];
     RC_TRY(lbmdem_network_compute(h, map, merge, 0, nc));
   }
@@ -535,7 +506,7 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
     for (long k = 0; k < nl; ++k)
       if (!(g_user[k] > 0. && g_user[k] < INFINITY))
         return fail(LBMDEM_EINVAL, "lbmdem_netsolve_compute: g_user[%ld] = %g: a conductance is finite and > 0", k, g_user[k]);
-  const int nblk = (int)ns_blocks(R, NS_THREADS);
+  const int nblk = (int)stage_blocks(R, NS_THREADS);
   const long Rc = R + R / 4 + 64, Lc = nl + nl / 4 + 64, Bc = B + B / 4 + 64, Pc = nblk + nblk / 4 + 64;
   if (!V.words) {
     HIP_TRY(h->mem.dev(&V.scal, (size_t)NS_SCAL));
@@ -582,7 +553,7 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
   if (R > 0) {
     if (nl > 0) {
       if (model == 1) HIP_TRY(hipMemcpyAsync(V.ldbl + 3 * Lc, g_user, sizeof(double) * (size_t)nl, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_ns_ends, dim3((unsigned)ns_blocks(nl, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
+      hipLaunchKernelGGL(k_ns_ends, dim3((unsigned)stage_blocks(nl, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
       HIP_TRY(hipGetLastError());
       int bits = 1;
       while (bits < 31 && (1L << bits) < R) ++bits;
@@ -592,9 +563,9 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
       need = (size_t)V.tmp_bytes;
       HIP_TRY(hipcub::DeviceRadixSort::SortPairs(V.tmp, need, J.eb, J.skey, J.iota, J.sval, (int)nl, 0, bits, st));   // stable
     }
-    hipLaunchKernelGGL(k_ns_first, dim3((unsigned)ns_blocks(R + 1, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
-    if (nl > 0) hipLaunchKernelGGL(k_ns_emit, dim3((unsigned)ns_blocks(nl, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
-    if (B > 0) hipLaunchKernelGGL(k_ns_band, dim3((unsigned)ns_blocks(J.N, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
+    hipLaunchKernelGGL(k_ns_first, dim3((unsigned)stage_blocks(R + 1, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
+    if (nl > 0) hipLaunchKernelGGL(k_ns_emit, dim3((unsigned)stage_blocks(nl, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
+    if (B > 0) hipLaunchKernelGGL(k_ns_band, dim3((unsigned)stage_blocks(J.N, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
     hipLaunchKernelGGL(k_ns_flags, dim3((unsigned)nblk), dim3(NS_THREADS), 0, st, J);
     hipLaunchKernelGGL(k_ns_rows, dim3((unsigned)nblk), dim3(NS_THREADS), 0, st, J);
     HIP_TRY(hipGetLastError());
@@ -615,8 +586,8 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
       HIP_TRY(hipStreamSynchronize(st));
     }
     const long items = nl > R ? nl : R;
-    hipLaunchKernelGGL(k_ns_out, dim3((unsigned)ns_blocks(items, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
-    hipLaunchKernelGGL(k_ns_last, dim3((unsigned)ns_blocks(items, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
+    hipLaunchKernelGGL(k_ns_out, dim3((unsigned)stage_blocks(items, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
+    hipLaunchKernelGGL(k_ns_last, dim3((unsigned)stage_blocks(items, NS_THREADS)), dim3(NS_THREADS), 0, st, J);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(w, V.words, sizeof w, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(s, V.scal, sizeof s, hipMemcpyDeviceToHost, st));
@@ -638,8 +609,7 @@ int lbmdem_netsolve_compute(lbmdem_handle* h, const int* map, int merge, int lev
   sums4[0] = s[NS_S_QIN]; sums4[1] = s[NS_S_QOUT]; sums4[2] = s[NS_S_RZ0]; sums4[3] = s[NS_S_LAST];
   V.nlinks = nl; V.nregions = R;
   V.gen = W.gen;
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -649,7 +619,7 @@ int lbmdem_download_netsolve_regions(lbmdem_handle* h, lbmdem_netsolve_region* o
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(netsolve_ready(h, "lbmdem_download_netsolve_regions"));
-  return netsolve_table(h, "lbmdem_download_netsolve_regions", "regions", h->nsv.regions, sizeof *out, h->nsv.nregions, out, cap, count);
+  return stage_table(h, "lbmdem_download_netsolve_regions", "regions", h->nsv.regions, sizeof *out, h->nsv.nregions, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -658,7 +628,7 @@ int lbmdem_download_netsolve_links(lbmdem_handle* h, lbmdem_netsolve_link* out, 
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(netsolve_ready(h, "lbmdem_download_netsolve_links"));
-  return netsolve_table(h, "lbmdem_download_netsolve_links", "links", h->nsv.links, sizeof *out, h->nsv.nlinks, out, cap, count);
+  return stage_table(h, "lbmdem_download_netsolve_links", "links", h->nsv.links, sizeof *out, h->nsv.nlinks, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }

@@ -31,9 +31,10 @@
 // loop has the bound its comment states.
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
 // both. Front end, as every export's: whole_handle(), SP_REFUSE() (lbmdem_handle.h), MemPool (lbm_mem.h) for what is kept on the
-// handle and for a call's sort records, OutFile (lbm_outfile.h) for the files.
+// handle and for a call's sort records, OutFile (lbm_outfile.h) for the files; what the pore stages share, lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 
@@ -426,15 +427,12 @@ __global__ __launch_bounds__(NW_THREADS) void k_nw_census(const NwJob J) {
   }
 }
 
-long nw_blocks(long items, int per) { return (items + per - 1) / per; }
-int nw_bits(unsigned long long v) { int b = 1; while (b < 64 && (v >> b)) ++b; return b; }   // bits that hold 0 .. v
-
 // what depends on the lattice, once
 int network_stage(lbmdem_handle* h) {
   auto& V = h->net;
   if (V.words) return LBMDEM_OK;
   const size_t N = (size_t)h->L.lx * h->L.sy;
-  const long nb = nw_blocks((long)N, NW_THREADS);
+  const long nb = stage_blocks((long)N, NW_THREADS);
   HIP_TRY(h->mem.dev(&V.par, N));
   HIP_TRY(h->mem.dev(&V.body, N));
   HIP_TRY(h->mem.dev(&V.group, N));
@@ -446,8 +444,7 @@ int network_stage(lbmdem_handle* h) {
 
 int network_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
-  const auto& V = h->net;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq)
+  if (!h->net.at.current(h))
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_network_compute has been made for the map as it is now", who);
   return LBMDEM_OK;
 }
@@ -484,8 +481,8 @@ int network_links(lbmdem_handle* h, NwJob& J, int level, long max_edges, long* n
     J.rk = rk0; J.rv = rv0;
     hipLaunchKernelGGL(k_nw_emit, dim3((unsigned)J.nblocks), dim3(NW_THREADS), 0, st, J);
     HIP_TRY(hipGetLastError());
-    const int vbits = J.pbits + nw_bits((unsigned long long)J.dtop);
-    const int kbits = nw_bits((unsigned long long)J.B * (unsigned long long)J.B);
+    const int vbits = J.pbits + stage_bits((unsigned long long)J.dtop);
+    const int kbits = stage_bits((unsigned long long)J.B * (unsigned long long)J.B);
     size_t b1 = 0, b2 = 0, b3 = 0, b4 = 0;
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, rv0, rv1, rk0, rk1, E, 0, vbits, st));
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, rk1, rk0, rv1, rv0, E, 0, kbits, st));
@@ -507,7 +504,7 @@ int network_links(lbmdem_handle* h, NwJob& J, int level, long max_edges, long* n
     HIP_TRY(h->mem.grow(&V.links[level], &V.link_cap[level], (long)T + T / 4 + 64));
     J.uniq = uniq; J.runs = runs; J.offs = offs;
     J.table = V.links[level]; J.nlinks = T;
-    hipLaunchKernelGGL(k_nw_links, dim3((unsigned)nw_blocks(T, NW_THREADS)), dim3(NW_THREADS), 0, st, J);
+    hipLaunchKernelGGL(k_nw_links, dim3((unsigned)stage_blocks(T, NW_THREADS)), dim3(NW_THREADS), 0, st, J);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));   // (the records go with `scratch`)
   }
@@ -516,8 +513,6 @@ int network_links(lbmdem_handle* h, NwJob& J, int level, long max_edges, long* n
   return LBMDEM_OK;
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
-
-unsigned nw_be(int v) { return __builtin_bswap32((unsigned)v); }
 
 }  // namespace
 
@@ -593,34 +588,13 @@ int lbmdem_write_network_files(const char* dir, int nfile, int lx, int ly, int n
   }
   RC_TRY(F.close());
   if (plane) {
-    std::vector<unsigned> image((size_t)cnt);
-    const float pas = (float)(1. / lx);   // (lbmdem_vtk_put_mesh's)
-    RC_TRY(F.open("w+", dir, "network%.6i.vtk", nfile));
-    fp = F.fp;
-    fprintf(fp, "# vtk DataFile Version 2.0\nlbmdem pore network\nBINARY\nDATASET STRUCTURED_POINTS\n");
-    fprintf(fp, "DIMENSIONS %d %d 1\nORIGIN 0 0 0\nSPACING %.9g %.9g 1\n", lx, ly, (double)pas, (double)pas);
-    fprintf(fp, "POINT_DATA %ld\n", cnt);
-    bool short_write = false;
     const int* const planes[2] = {body, group};
     const char* const names[2] = {"body", "group"};
-    for (int k = 0; k < 2; ++k) {
-      for (int y = 0; y < ly; ++y)
-        for (int x = 0; x < lx; ++x) image[(size_t)y * lx + x] = nw_be(planes[k][(size_t)x * ly + y]);
-      fprintf(fp, "SCALARS %s int 1\nLOOKUP_TABLE default\n", names[k]);
-      short_write = short_write || fwrite(image.data(), 4, (size_t)cnt, fp) != (size_t)cnt;
-      fprintf(fp, "\n");
-    }
-    RC_TRY(F.close(short_write));
+    RC_TRY(stage_write_int_planes(F, dir, nfile, "network%.6i.vtk", "lbmdem pore network", lx, ly, names, planes, 2));
   }
-  RC_TRY(F.open("a", dir, "network.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t fluid_nodes bodies body_links body_edges groups group_links group_edges isolated_groups largest_group_nodes "
-                "narrowest_saddle\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_NETWORK_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  return stage_append_row(F, dir, "network.data",
+                          "# t fluid_nodes bodies body_links body_edges groups group_links group_edges isolated_groups "
+                          "largest_group_nodes narrowest_saddle", t, counts10, LBMDEM_NETWORK_COUNTS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -647,19 +621,14 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
     return fail(LBMDEM_EINVAL, "lbmdem_network_compute: a lattice of %d x %d nodes has a side above %d: the squared distances are "
                                "32-bit integers", lx, ly, NW_SIDE_MAX);
   if (merge < -1) return fail(LBMDEM_EINVAL, "lbmdem_network_compute: merge must be -1 (no merging) or a difference of radii >= 0 (%d)", merge);
-  if (max_edges < 0 || max_edges > (long)INT_MAX)
-    return fail(LBMDEM_EINVAL, "lbmdem_network_compute: max_edges must lie in 0 .. %d (%ld)", INT_MAX, max_edges);
+  RC_TRY(stage_check_max_edges("lbmdem_network_compute", max_edges));
   auto& V = h->net;
-  V.valid = false;
+  V.at.valid = false;
   ++V.gen;
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_network_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  RC_TRY(stage_check_map("lbmdem_network_compute", map, lx, ly, n));
   // the clearance first: its d2 of the handle's map is reused while its guard calls it valid
   const auto& Q = h->clr;
-  if (map || !Q.valid || !Q.own || Q.seq != h->substep_seq || Q.moved != h->grains_moved || Q.fluid != h->lattice_seq) {
+  if (map || !(Q.at.current(h) && Q.own)) {
     long cc[LBMDEM_CLEARANCE_COUNTS];
     RC_TRY(lbmdem_clearance_compute(h, map, 0, cc));
   }
@@ -672,15 +641,15 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
   J.N = N; J.Nh = (long)lx * ly;
   J.par = V.par; J.body = V.body; J.group = V.group;
   J.words = V.words;
-  J.nblocks = nw_blocks(N, NW_THREADS);
+  J.nblocks = stage_blocks(N, NW_THREADS);
   J.cnt = V.cnt; J.off = V.cnt + J.nblocks + 1;
   J.merge = merge;
-  J.pbits = nw_bits((unsigned long long)(J.Nh - 1));
+  J.pbits = stage_bits((unsigned long long)(J.Nh - 1));
   const int side = lx < ly ? lx : ly;
   J.dtop = (long)((side + 1) / 2 + 1) * ((side + 1) / 2 + 1);
   HIP_TRY(hipMemsetAsync(V.words, 0, sizeof(nw_u64) * NW_WORDS, st));
   HIP_TRY(hipMemsetAsync(V.words + NW_W_NARROWEST, 0xFF, sizeof(nw_u64), st));   // (a minimum)
-  hipLaunchKernelGGL(k_nw_ascent, dim3((unsigned)nw_blocks(sy, NW_TY), (unsigned)nw_blocks(lx, NW_TX)), dim3(NW_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_nw_ascent, dim3((unsigned)stage_blocks(sy, NW_TY), (unsigned)stage_blocks(lx, NW_TX)), dim3(NW_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_nw_find, dim3((unsigned)J.nblocks), dim3(NW_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_nw_peaks, dim3((unsigned)J.nblocks), dim3(NW_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
@@ -720,10 +689,10 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
   hipLaunchKernelGGL(k_nw_label, dim3((unsigned)J.nblocks), dim3(NW_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   long E0 = 0, L0 = 0, E1 = 0, L1 = 0, G = 0;
-  const unsigned bblocks = (unsigned)nw_blocks(B + 1, NW_THREADS);
+  const unsigned bblocks = (unsigned)stage_blocks(B + 1, NW_THREADS);
   J.lab = V.body; J.deg = deg0;
   RC_TRY(network_links(h, J, 0, max_edges, &E0, &L0));
-  if (merge >= 0 && L0 > 0) hipLaunchKernelGGL(k_nw_propose, dim3((unsigned)nw_blocks(L0, NW_THREADS)), dim3(NW_THREADS), 0, st, J);
+  if (merge >= 0 && L0 > 0) hipLaunchKernelGGL(k_nw_propose, dim3((unsigned)stage_blocks(L0, NW_THREADS)), dim3(NW_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_nw_parent, dim3(bblocks), dim3(NW_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_nw_root, dim3(bblocks), dim3(NW_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_nw_group, dim3((unsigned)J.nblocks), dim3(NW_THREADS), 0, st, J);
@@ -747,7 +716,7 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
   J.groups = V.groups; J.G = G;
   hipLaunchKernelGGL(k_nw_groups, dim3(bblocks), dim3(NW_THREADS), 0, st, J);
   hipLaunchKernelGGL(k_nw_gather, dim3(bblocks), dim3(NW_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_nw_census, dim3((unsigned)nw_blocks((G > L1 ? G : L1) + 1, NW_THREADS)), dim3(NW_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_nw_census, dim3((unsigned)stage_blocks((G > L1 ? G : L1) + 1, NW_THREADS)), dim3(NW_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned long long w[NW_WORDS] = {};
   HIP_TRY(hipMemcpyAsync(w, V.words, sizeof w, hipMemcpyDeviceToHost, st));
@@ -763,10 +732,9 @@ int lbmdem_network_compute(lbmdem_handle* h, const int* map, int merge, long max
   counts10[8] = (long)w[NW_W_LARGEST];
   counts10[9] = L1 > 0 ? (long)w[NW_W_NARROWEST] : -1;
   V.nbodies = B; V.ngroups = G; V.nlinks[0] = L0; V.nlinks[1] = L1;
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
   V.own = map == nullptr;
   V.merge = merge;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -776,9 +744,8 @@ int lbmdem_download_network(lbmdem_handle* h, int* body, int* group) try {
   CHECK_H(h);
   if (!body && !group) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(network_ready(h, "lbmdem_download_network"));
-  const LatticeView& L = h->L;
-  if (body) HIP_TRY(hipMemcpy2DAsync(body, sizeof(int) * L.ly, h->net.body, sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx, hipMemcpyDeviceToHost, h->stream));
-  if (group) HIP_TRY(hipMemcpy2DAsync(group, sizeof(int) * L.ly, h->net.group, sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx, hipMemcpyDeviceToHost, h->stream));
+  if (body) RC_TRY(stage_download_plane(h, body, h->net.body));
+  if (group) RC_TRY(stage_download_plane(h, group, h->net.group));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -797,24 +764,11 @@ int lbmdem_network_device(lbmdem_handle* h, const int** body, const int** group,
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
 
-// the three tables are sized alike: cap = 0 reports *count, a short buffer is refused with *count set and nothing written
-static int network_table(lbmdem_handle* h, const char* who, const char* what, const void* src, size_t each, long have, void* out,
-                         long cap, long* count) {
-  *count = have;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < have) return fail(LBMDEM_EINVAL, "%s: there are %ld %s, the buffer holds %ld", who, have, what, cap);
-  if (have > 0) {
-    HIP_TRY(hipMemcpyAsync(out, src, each * (size_t)have, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return LBMDEM_OK;
-}
-
 int lbmdem_download_network_bodies(lbmdem_handle* h, lbmdem_net_body* out, long cap, long* count) try {
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(network_ready(h, "lbmdem_download_network_bodies"));
-  return network_table(h, "lbmdem_download_network_bodies", "bodies", h->net.bodies, sizeof *out, h->net.nbodies, out, cap, count);
+  return stage_table(h, "lbmdem_download_network_bodies", "bodies", h->net.bodies, sizeof *out, h->net.nbodies, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -823,7 +777,7 @@ int lbmdem_download_network_groups(lbmdem_handle* h, lbmdem_net_group* out, long
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(network_ready(h, "lbmdem_download_network_groups"));
-  return network_table(h, "lbmdem_download_network_groups", "groups", h->net.groups, sizeof *out, h->net.ngroups, out, cap, count);
+  return stage_table(h, "lbmdem_download_network_groups", "groups", h->net.groups, sizeof *out, h->net.ngroups, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -834,7 +788,7 @@ int lbmdem_download_network_links(lbmdem_handle* h, int level, lbmdem_net_link* 
   if (level != 0 && level != 1)
     return fail(LBMDEM_EINVAL, "lbmdem_download_network_links: level must be 0 (between bodies) or 1 (between groups) (%d)", level);
   RC_TRY(network_ready(h, "lbmdem_download_network_links"));
-  return network_table(h, "lbmdem_download_network_links", "links", h->net.links[level], sizeof *out, h->net.nlinks[level], out, cap, count);
+  return stage_table(h, "lbmdem_download_network_links", "links", h->net.links[level], sizeof *out, h->net.nlinks[level], out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }

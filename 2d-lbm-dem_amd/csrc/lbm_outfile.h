@@ -1,5 +1,5 @@
 // lbm_outfile.h -- one checked output file for the writers that report through fail(): the text and VTK files of the exports
-// (lbm_links.hip, lbm_densities.hip, lbm_contacts.hip, lbm_clusters.hip: clusters.data too, lbm_structure.hip: structure.data too, lbm_voronoi.hip: voronoi.data too, lbm_strain.hip: strain.data too, lbm_pores.hip: pores.data too, lbm_clearance.hip: clearance.data too, lbm_network.hip: network.data too, lbm_netflux.hip: netflux.data too, lbm_netsolve.hip: netsolve.data too, lbm_drainage.hip: drainage.data too, lbm_geodesic.hip: geodesic.data too, lbm_coarse.hip, lbm_flow.hip, lbm_tracers.hip, lbm_scalar.hip: scalar.data too, lbm_mean.hip) and flow.data (lbmdem_scene.hip). Host only.
+// (lbm_links.hip, lbm_densities.hip, lbm_contacts.hip, lbm_clusters.hip: clusters.data too, lbm_structure.hip: structure.data too, lbm_voronoi.hip: voronoi.data too, lbm_strain.hip: strain.data too, the seven map-reading analyses of lbm_stage.h, whose VTK planes and <stage>.data rows that header writes, lbm_coarse.hip, lbm_flow.hip, lbm_tracers.hip, lbm_scalar.hip: scalar.data too, lbm_mean.hip) and flow.data (lbmdem_scene.hip). Host only.
 // The writers of lbmdem_output.hip are not meant: they report into a buffer for the writer thread and say why a write failed.
 #pragma once
 

@@ -32,9 +32,10 @@
 // Double-precision library only: the entry points that take a handle refuse in the float build; the host-only formatter exists in
 // both.
 // Front end, as every export's: whole_handle(), SP_REFUSE() and reader_obst() (lbmdem_handle.h), MemPool (lbm_mem.h) for the
-// scratch kept on the handle, OutFile (lbm_outfile.h) for the files.
+// scratch kept on the handle, OutFile (lbm_outfile.h) for the files; what the pore stages share, lbm_stage.h.
 #include "lbm_device.h"
 #include "lbm_outfile.h"
+#include "lbm_stage.h"
 
 #include <limits.h>
 
@@ -449,14 +450,12 @@ __global__ __launch_bounds__(PO_THREADS) void k_po_grains(const PoJob J) {
   }
 }
 
-int po_blocks(long items, int per) { return (int)((items + per - 1) / per); }
-
 // what depends on the lattice and on n, once
 int pore_stage(lbmdem_handle* h) {
   auto& V = h->po;
   if (V.words) return LBMDEM_OK;
   const size_t N = (size_t)h->L.lx * h->L.sy;
-  const int nb = po_blocks((long)N, PO_BLOCK_NODES);
+  const int nb = (int)stage_blocks((long)N, PO_BLOCK_NODES);
   HIP_TRY(h->mem.dev(&V.parent, N));
   HIP_TRY(h->mem.dev(&V.label, N));
   HIP_TRY(h->mem.dev(&V.rank, N));
@@ -471,14 +470,11 @@ int pore_stage(lbmdem_handle* h) {
 
 int pores_ready(const lbmdem_handle* h, const char* who) {
   RC_TRY(whole_handle(h, who));
-  const auto& V = h->po;
-  if (!V.valid || V.seq != h->substep_seq || V.moved != h->grains_moved || V.fluid != h->lattice_seq)
+  if (!h->po.at.current(h))
     return fail(LBMDEM_EINVAL, "%s: no lbmdem_pore_compute has been made for the map and the populations as they are now", who);
   return LBMDEM_OK;
 }
 #endif   // !LBMDEM_SINGLE_PRECISION
-
-unsigned po_be(int v) { return __builtin_bswap32((unsigned)v); }
 
 }  // namespace
 
@@ -520,27 +516,13 @@ int lbmdem_write_pore_files(const char* dir, int nfile, int conn, int lx, int ly
   for (int i = 0; i < n; ++i) fprintf(fp, "%d %d %d %d\n", i, wet[i], pore_min[i], pore_max[i]);
   RC_TRY(F.close());
   if (plane) {
-    std::vector<unsigned> image((size_t)cnt);
-    for (int y = 0; y < ly; ++y)
-      for (int x = 0; x < lx; ++x) image[(size_t)y * lx + x] = po_be(label[(size_t)x * ly + y]);
-    const float pas = (float)(1. / lx);   // (lbmdem_vtk_put_mesh's)
-    RC_TRY(F.open("w+", dir, "pores%.6i.vtk", nfile));
-    fp = F.fp;
-    fprintf(fp, "# vtk DataFile Version 2.0\nlbmdem pore labels\nBINARY\nDATASET STRUCTURED_POINTS\n");
-    fprintf(fp, "DIMENSIONS %d %d 1\nORIGIN 0 0 0\nSPACING %.9g %.9g 1\n", lx, ly, (double)pas, (double)pas);
-    fprintf(fp, "POINT_DATA %ld\nSCALARS pore int 1\nLOOKUP_TABLE default\n", cnt);
-    const bool short_write = fwrite(image.data(), 4, (size_t)cnt, fp) != (size_t)cnt;
-    RC_TRY(F.close(short_write));
+    const char* const names[1] = {"pore"};
+    // (this file alone ends with its plane's last byte, no line feed behind it)
+    RC_TRY(stage_write_int_planes(F, dir, nfile, "pores%.6i.vtk", "lbmdem pore labels", lx, ly, names, &label, 1, false));
   }
-  RC_TRY(F.open("a", dir, "pores.data"));
-  fp = F.fp;
-  if (fseek(fp, 0, SEEK_END) == 0 && ftell(fp) == 0)
-    fprintf(fp, "# t fluid_nodes components largest_nodes largest_label trapped_nodes single_nodes spanning throat_grains dry_grains "
-                "unaccumulated\n");
-  fprintf(fp, "%le", t);
-  for (int k = 0; k < LBMDEM_PORE_COUNTS; ++k) fprintf(fp, " %ld", counts10[k]);
-  fprintf(fp, "\n");
-  return F.close();
+  return stage_append_row(F, dir, "pores.data",
+                          "# t fluid_nodes components largest_nodes largest_label trapped_nodes single_nodes spanning throat_grains "
+                          "dry_grains unaccumulated", t, counts10, LBMDEM_PORE_COUNTS);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }
@@ -568,38 +550,32 @@ int lbmdem_pore_compute(lbmdem_handle* h, int conn, const int* map, long* counts
     return fail(LBMDEM_EINVAL, "lbmdem_pore_compute: a lattice of %d x %d nodes (row pitch %d) has 2^31 nodes or more: the labels "
                                "are 32-bit integers", lx, ly, sy);
   auto& V = h->po;
-  V.valid = false;
-  if (map)
-    for (long k = 0, cnt = (long)lx * ly; k < cnt; ++k)
-      if (map[k] < -1 || map[k] > n)
-        return fail(LBMDEM_EINVAL, "lbmdem_pore_compute: map[%ld] = %d (node %ld, %ld) is neither -1 (fluid), a grain (0 .. %d) nor "
-                                   "the wall (%d)", k, map[k], k / ly, k % ly, n - 1, n);
+  V.at.valid = false;
+  RC_TRY(stage_check_map("lbmdem_pore_compute", map, lx, ly, n));
   RC_TRY(pore_stage(h));
   const hipStream_t st = h->stream;
   const long N = (long)lx * sy;
   PoJob J{};
   J.M = reader_obst(h);
   if (map) {
-    if (!V.map) HIP_TRY(h->mem.dev(&V.map, (size_t)N));
-    // host rows of ly into device rows of sy; the pad columns are never read
-    HIP_TRY(hipMemcpy2DAsync(V.map, sizeof(int) * sy, map, sizeof(int) * ly, sizeof(int) * ly, lx, hipMemcpyHostToDevice, st));
+    RC_TRY(stage_upload_map(h, &V.map, map));
     J.M = V.map;
   }
   J.f = h->f[h->fcur];
   J.lx = lx; J.ly = ly; J.sy = sy; J.n = n; J.conn = conn;
   J.N = N;
   J.parent = V.parent; J.label = V.label; J.rank = V.rank;
-  J.nblocks = po_blocks(N, PO_BLOCK_NODES);
+  J.nblocks = (int)stage_blocks(N, PO_BLOCK_NODES);
   J.cnt = V.cnt; J.off = V.cnt + J.nblocks + 1;
   J.wet = V.grains; J.pmin = V.grains + n; J.pmax = V.grains + 2 * (size_t)n;
   J.words = V.words;
   const int need = n > PO_WORDS ? n : PO_WORDS;
-  hipLaunchKernelGGL(k_po_init, dim3(po_blocks(need, PO_THREADS)), dim3(PO_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_po_local, dim3(po_blocks(ly, PO_TY), po_blocks(lx, PO_TX)), dim3(PO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_po_init, dim3((unsigned)stage_blocks(need, PO_THREADS)), dim3(PO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_po_local, dim3((unsigned)stage_blocks(ly, PO_TY), (unsigned)stage_blocks(lx, PO_TX)), dim3(PO_THREADS), 0, st, J);
   if (lx > PO_TX)
-    hipLaunchKernelGGL(k_po_seam, dim3(po_blocks(ly, PO_THREADS), (lx - 1) / PO_TX), dim3(PO_THREADS), 0, st, J, 0);
+    hipLaunchKernelGGL(k_po_seam, dim3((unsigned)stage_blocks(ly, PO_THREADS), (lx - 1) / PO_TX), dim3(PO_THREADS), 0, st, J, 0);
   if (ly > PO_TY)
-    hipLaunchKernelGGL(k_po_seam, dim3(po_blocks(lx, PO_THREADS), 2 * ((ly - 1) / PO_TY)), dim3(PO_THREADS), 0, st, J, 1);
+    hipLaunchKernelGGL(k_po_seam, dim3((unsigned)stage_blocks(lx, PO_THREADS), 2 * ((ly - 1) / PO_TY)), dim3(PO_THREADS), 0, st, J, 1);
   hipLaunchKernelGGL(k_po_flatten, dim3(J.nblocks), dim3(PO_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   size_t bytes = (size_t)V.tmp_bytes;
@@ -612,9 +588,9 @@ int lbmdem_pore_compute(lbmdem_handle* h, int conn, const int* map, long* counts
   if (ncomp > 0) {
     hipLaunchKernelGGL(k_po_emit, dim3(J.nblocks), dim3(PO_THREADS), 0, st, J);
   }
-  hipLaunchKernelGGL(k_po_table, dim3(po_blocks(sy, PO_THREADS), po_blocks(lx, PO_ROWS)), dim3(PO_THREADS), 0, st, J);
-  if (ncomp > 0) hipLaunchKernelGGL(k_po_census, dim3(po_blocks(ncomp, PO_THREADS)), dim3(PO_THREADS), 0, st, J);
-  hipLaunchKernelGGL(k_po_grains, dim3(po_blocks(n, PO_THREADS)), dim3(PO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_po_table, dim3((unsigned)stage_blocks(sy, PO_THREADS), (unsigned)stage_blocks(lx, PO_ROWS)), dim3(PO_THREADS), 0, st, J);
+  if (ncomp > 0) hipLaunchKernelGGL(k_po_census, dim3((unsigned)stage_blocks(ncomp, PO_THREADS)), dim3(PO_THREADS), 0, st, J);
+  hipLaunchKernelGGL(k_po_grains, dim3((unsigned)stage_blocks(n, PO_THREADS)), dim3(PO_THREADS), 0, st, J);
   HIP_TRY(hipGetLastError());
   unsigned long long w[PO_WORDS] = {};
   HIP_TRY(hipMemcpyAsync(w, V.words, sizeof w, hipMemcpyDeviceToHost, st));
@@ -631,8 +607,7 @@ int lbmdem_pore_compute(lbmdem_handle* h, int conn, const int* map, long* counts
   counts10[8] = (long)w[PO_W_DRY];
   counts10[9] = (long)w[PO_W_SKIPPED];
   V.ncomp = ncomp;
-  V.seq = h->substep_seq; V.moved = h->grains_moved; V.fluid = h->lattice_seq;
-  V.valid = true;
+  V.at.set(h);
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {   // (CHECK_H may replay logged runs)
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
@@ -642,9 +617,7 @@ int lbmdem_download_pore_labels(lbmdem_handle* h, int* label) try {
   CHECK_H(h);
   if (!label) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(pores_ready(h, "lbmdem_download_pore_labels"));
-  const LatticeView& L = h->L;
-  HIP_TRY(hipMemcpy2DAsync(label, sizeof(int) * L.ly, h->po.label, sizeof(int) * L.sy, sizeof(int) * L.ly, L.lx,
-                           hipMemcpyDeviceToHost, h->stream));
+  RC_TRY(stage_download_plane(h, label, h->po.label));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LBMDEM_OK;
 } catch (const std::bad_alloc&) {
@@ -666,16 +639,7 @@ int lbmdem_download_pores(lbmdem_handle* h, lbmdem_pore* out, long cap, long* co
   CHECK_H(h);
   if (!count || cap < 0 || (cap > 0 && !out)) return fail(LBMDEM_EINVAL, "null buffer");
   RC_TRY(pores_ready(h, "lbmdem_download_pores"));
-  const auto& V = h->po;
-  *count = V.ncomp;
-  if (cap == 0) return LBMDEM_OK;   // (how many there are)
-  if (cap < V.ncomp)
-    return fail(LBMDEM_EINVAL, "lbmdem_download_pores: there are %ld components, the buffer holds %ld", V.ncomp, cap);
-  if (V.ncomp > 0) {
-    HIP_TRY(hipMemcpyAsync(out, V.table, sizeof(lbmdem_pore) * (size_t)V.ncomp, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-  }
-  return LBMDEM_OK;
+  return stage_table(h, "lbmdem_download_pores", "components", h->po.table, sizeof *out, h->po.ncomp, out, cap, count);
 } catch (const std::bad_alloc&) {
   return fail(LBMDEM_ENOMEM, "host memory allocation failed");
 }

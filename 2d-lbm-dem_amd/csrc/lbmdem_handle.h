@@ -213,6 +213,17 @@ struct AsyncOut {
   char err_msg[4400];
 };
 
+// Which map and populations a result of the map-reading analyses (pores to netsolve) describes: those of sub-step `seq`, upload
+// `moved` and lattice change `fluid`. set() takes the three from the handle and raises `valid`; current() asks for `valid`,
+// seq == substep_seq, moved == grains_moved and fluid == lattice_seq (a rasterisation, a fluid step and lbmdem_upload_f raise the
+// last). Both are defined in lbm_stage.h, with the rest of what those analyses share.
+struct MapStamp {
+  bool valid = false;
+  long long seq = -1, moved = -1, fluid = -1;
+  void set(const lbmdem_handle* h);
+  bool current(const lbmdem_handle* h) const;
+};
+
 struct lbmdem_handle {
   lbmdem_config cfg;
   LatticeView L;
@@ -402,15 +413,13 @@ struct lbmdem_handle {
   } sn;
   // The pore space (lbm_pores.hip): the fluid phase labelled into connected components. po: scratch and results, allocated by the
   // first lbmdem_pore_compute, the table grown with the components, freed with the handle. The kernels read the map and f and
-  // write here only. The results describe the map and f as of sub-step `seq`, upload `moved` and lattice change `fluid`: the
-  // readers ask for seq == substep_seq, moved == grains_moved and fluid == lattice_seq (a rasterisation, a fluid step and
-  // lbmdem_upload_f raise the last). pores_*: lbmdem_set_pores_output.
+  // write here only. The results describe the map and f of po.at (MapStamp), and the readers ask for po.at.current(): lattice_seq
+  // is raised by a rasterisation, a fluid step and lbmdem_upload_f. pores_*: lbmdem_set_pores_output.
   long long lattice_seq = 0;
   bool pores_output = false;
   int pores_conn = 8, pores_plane = 0;
   struct PoreStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     unsigned long long* words = nullptr;  // [PO_WORDS] the census (null: nothing allocated yet)
     int* parent = nullptr;                // [lx][sy] the union-find: a fluid node's parent, a device node no larger than itself; else -1
     int* label = nullptr;                 // [lx][sy] the result: the smallest host index of the node's component, else -1
@@ -427,13 +436,11 @@ struct lbmdem_handle {
   // The pore clearance (lbm_clearance.hip): the exact squared distance from every fluid node to the nearest position that is not
   // fluid, that position's owner, the histogram, the owners' table and the throats. clr: scratch and results, allocated by the
   // first lbmdem_clearance_compute, the ridge records and the throat table grown with their counts, freed with the handle. The
-  // kernels read the map and write here only. Valid under the pores' guard: seq, moved and fluid as in PoreStage.
-  // clearance_*: lbmdem_set_clearance_output.
+  // kernels read the map and write here only. Valid while clr.at (MapStamp) is current. clearance_*: lbmdem_set_clearance_output.
   bool clearance_output = false;
   int clearance_plane = 0;
   struct ClearanceStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     unsigned long long* words = nullptr;  // [CE_WORDS] the census (null: nothing allocated yet)
     unsigned long long* key = nullptr;    // [lx][sy] the row pass: (distance along y)^2 << 32 | owner
     int* d2 = nullptr;                    // [lx][sy] the result: the squared distance, 0 off the fluid and in the pad columns
@@ -466,8 +473,7 @@ struct lbmdem_handle {
   bool network_output = false;
   int network_merge = -1, network_plane = 0;
   struct NetworkStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     unsigned long long* words = nullptr;  // [NW_WORDS] the census (null: nothing allocated yet)
     int* par = nullptr;                   // [lx][sy] the ascent: a higher node of the same basin, in the end the peak; -1 off the fluid
     int* body = nullptr;                  // [lx][sy] the result: the body's number, -1 off the fluid and in the pad columns
@@ -495,8 +501,7 @@ struct lbmdem_handle {
   bool drainage_output = false;
   int drainage_from = 0, drainage_band = 1, drainage_to = 0, drainage_plane = 0;
   struct DrainageStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     unsigned long long gen = 0;           // net.gen of the network result underneath
     unsigned long long* words = nullptr;  // [DR_WORDS] the counts and the relaxation's `changed` (null: nothing allocated yet)
     int* access = nullptr;                // [lx][sy] the result: min(d2, A[body]), 0 off the fluid and in the pad columns
@@ -517,8 +522,7 @@ struct lbmdem_handle {
   bool geodesic_output = false;
   int geodesic_from = 0, geodesic_band = 1, geodesic_to = 0, geodesic_conn = 8, geodesic_min_d2 = 0, geodesic_plane = 0;
   struct GeodesicStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     bool over_clearance = false;          // made over clr.d2 of the handle's map
     unsigned long long gen = 0;           // ... clr.gen of that result
     unsigned long long* words = nullptr;  // [GEO_WORDS] the counts (null: nothing allocated yet)
@@ -544,8 +548,7 @@ struct lbmdem_handle {
   bool netflux_output = false;
   int netflux_merge = -1, netflux_level = 0;
   struct NetfluxStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     unsigned long long gen = 0;           // net.gen of the network result underneath
     unsigned long long* words = nullptr;  // [NF_WORDS] the counts (null: nothing allocated yet)
     long* col = nullptr;                  // [lx] the sections towards +x: lx - 1 of them
@@ -570,8 +573,7 @@ struct lbmdem_handle {
   int netsolve_merge = -1, netsolve_level = 0, netsolve_from = 0, netsolve_band = 1, netsolve_to = 0, netsolve_max_iter = 0;
   double netsolve_rtol = 1e-8;
   struct NetsolveStage {
-    bool valid = false;
-    long long seq = -1, moved = -1, fluid = -1;
+    MapStamp at;                          // the map and populations the last compute was made for
     unsigned long long gen = 0;           // net.gen of the network result underneath
     unsigned long long* words = nullptr;  // [NS_WORDS] status, iterations and the counts (null: nothing allocated yet)
     double* scal = nullptr;               // [NS_SCAL] rz0, the last rz, rz of the iteration (two), Q_in, Q_out
